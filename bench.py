@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- Azul env steps/sec, random-agent self-play (BASELINE.json metric), on N MI355X of one node.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--games G] [--chunk T]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--games G] [--chunk T] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 Started as a plain command with --gpus N > 1 (no WORLD_SIZE in the environment) it launches the N ranks ITSELF: fresh child
@@ -55,7 +55,12 @@ def parse():
     ap.add_argument("--sustained", type=int, default=1000, help="launches of the `sustained` object after the timed region (0 = skip)")
     ap.add_argument("--gather-c1", action="store_true", help="N>1, secondary line configs[4]: also all-gather every window's full C1 records "
                                                              "(184 B per agent step; opt-in, the collective north_star names)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed launches, write what the last one computed (rank 0's trajectory "
+                                                          "arrays) as DIR/<name>.npy, float32 / float64, at most 64 MB in all (dump_outputs)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def _host_cores():
@@ -118,6 +123,34 @@ def parity_gate(env, games, seed_base, moves_done, budget=6000000, move_limit=0)
         if s.rng_state()[1] != env.get_rng(g)[1]:
             return "RNG position MISMATCH in game %d after %d moves" % (g, moves_done)
     return "ok (%d games x %d moves bit-exact vs oracle, %d episodes each)" % (k, moves_done, int(s.episodes.value))
+
+
+DUMP_LIMIT_BYTES = 64 << 20        # --dump-outputs: .npy bytes in all, headers included
+DUMP_SAMPLE_SEED = 0
+
+
+def dump_outputs(out_dir, traj, limit=DUMP_LIMIT_BYTES):
+    """Write the trajectory arrays one launch handed its caller ([T][G] action / reward / done / packed, [T][G][180] mask) as
+    out_dir/<name>.npy: float32, but `packed` (action | done << 8 | reward << 16, int32) in float64, which holds every int32 exactly.  When
+    all G games do not fit in `limit` bytes, every array keeps the same seeded sample of games, in ascending order; `games.npy` lists the
+    game ids kept.  The inputs and the sample depend only on the arguments, so two builds run alike write comparable files.  `maskbits`
+    (--gather-masks) is `mask` bit-packed into int64 words, which float64 cannot hold exactly: it is not written."""
+    import numpy as np
+    import torch
+    kinds = {"action": np.float32, "reward": np.float32, "done": np.float32, "packed": np.float64, "mask": np.float32}
+    arrays = {k: traj[k] for k in kinds if k in traj}
+    G = arrays["action"].shape[1]
+    per_game = 8 + sum(a[:, 0].numel() * np.dtype(kinds[k]).itemsize for k, a in arrays.items())      # + its id in games.npy
+    n = min(G, (limit - 128 * (len(arrays) + 1)) // per_game)                                         # (a .npy header is 128 bytes)
+    if n < 1:
+        raise ValueError("one game's trajectory (%d bytes) exceeds the %d-byte dump limit: use a smaller --chunk" % (per_game, limit))
+    games = np.arange(G) if n == G else np.sort(np.random.RandomState(DUMP_SAMPLE_SEED).permutation(G)[:n])   # (a stream numpy keeps fixed)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "games.npy"), games.astype(np.float64))
+    for k, a in arrays.items():
+        idx = torch.as_tensor(games, device=a.device)
+        np.save(os.path.join(out_dir, k + ".npy"), a.index_select(1, idx).cpu().numpy().astype(kinds[k]))
+    return {"dir": out_dir, "games": int(n), "arrays": sorted(arrays) + ["games"]}
 
 
 F32_MFMA_PEAK_TFLOPS = 157.3       # MI355X_MICROARCH.md: dense f32 matrix peak
@@ -835,6 +868,8 @@ def main():
     cnt = env.counters()
     stuck = int(cnt["stuck"].sum()) - stuck0
     gate_end = parity_gate(env, G, base, gate_moves + K * T, move_limit=args.move_limit) if rank == 0 else None      # ... and the state the timed region left
+    # the last timed launch wrote bufs[(K - 1) & 1]; the sustained launches below reuse both buffers
+    dumped = dump_outputs(args.dump_outputs, bufs[(K - 1) & 1]) if args.dump_outputs and rank == 0 else None
     el = torch.tensor([elapsed], dtype=torch.float64, device=dev)
     moves = torch.tensor([float(G * K * T - stuck)], dtype=torch.float64, device=dev)
     coll_.all_reduce(el, dist.ReduceOp.MAX, "all-reduce (max) of the ranks' elapsed time")
@@ -1060,6 +1095,8 @@ def main():
             "episodes_finished": int(cnt["episodes"].sum()), "stuck_resets": stuck,
             "sustained": sustained,
         }
+        if dumped:
+            out["dump_outputs"] = dumped
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(G, args.seed_base)
     if not args.no_extras:

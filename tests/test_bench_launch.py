@@ -12,6 +12,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 import torch
 
@@ -118,6 +119,75 @@ def test_single_gpu_line_keeps_its_shape():
     assert out["value_sustained"] > 0 and len(out["sustained"]["blocks"]) == 10 and "never_ending_games" in out["sustained"]
     vs = out["extra"]["policy_vs_policy"]
     assert vs["value"] > 0 and vs["roofline"]["bound"] == "mfma" and 0.5 < vs["opponent_moves_per_agent_step"] < 2.0
+
+
+DUMPED = ("action", "done", "mask", "packed", "reward")
+
+
+def test_dump_outputs_writes_one_seeded_sample_of_games_within_the_limit(tmp_path):
+    """--dump-outputs: float32 / float64 .npy files, at most `limit` bytes in all, the same seeded games in every array and from call to
+    call, the values exact (`packed` in float64: reward << 16 leaves float32's 24 bits); the whole batch, in order, when it fits."""
+    sys.path.insert(0, ROOT)
+    import bench
+    T, G = 16, 96
+    gen = torch.Generator().manual_seed(5)
+    traj = {"action": torch.randint(0, 180, (T, G), dtype=torch.int32, generator=gen),
+            "reward": torch.randint(-300, 300, (T, G), dtype=torch.int32, generator=gen),
+            "done": torch.randint(0, 2, (T, G), dtype=torch.uint8, generator=gen),
+            "mask": torch.randint(0, 2, (T, G, 192), dtype=torch.uint8, generator=gen)[:, :, :180],      # alloc_trajectory(mask_pitch=192)
+            "maskbits": torch.zeros((T, G, 3), dtype=torch.int64)}
+    traj["packed"] = traj["action"] | (traj["done"].int() << 8) | (traj["reward"] << 16)
+    limit = 40 * (8 + T * (4 + 4 + 4 + 8 + 180 * 4)) + 1024
+    info = bench.dump_outputs(str(tmp_path / "a"), traj, limit=limit)
+    bench.dump_outputs(str(tmp_path / "b"), traj, limit=limit)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == sorted(n + ".npy" for n in DUMPED + ("games",))
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= limit
+    games = np.load(tmp_path / "a" / "games.npy")
+    assert info["games"] == len(games) == 40 and np.all(np.diff(games) > 0) and games[-1] < G
+    for f in files:
+        a = np.load(tmp_path / "a" / f)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, np.load(tmp_path / "b" / f)), f
+    gi = games.astype(np.int64)
+    for k in DUMPED:
+        assert np.array_equal(np.load(tmp_path / "a" / (k + ".npy")), traj[k].numpy()[:, gi].astype(np.float64)), k
+    assert np.load(tmp_path / "a" / "packed.npy").dtype == np.float64
+    bench.dump_outputs(str(tmp_path / "c"), traj)
+    assert np.array_equal(np.load(tmp_path / "c" / "games.npy"), np.arange(G))
+    assert np.array_equal(np.load(tmp_path / "c" / "mask.npy"), traj["mask"].numpy())
+
+
+def test_steps_below_one_are_refused(monkeypatch):
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit) as ei:
+        bench.parse()
+    assert ei.value.code == 2
+
+
+@pytest.mark.gpu
+def test_dump_outputs_hold_the_last_timed_launch(tmp_path):
+    """The dumped arrays are what the LAST of the K timed launches wrote: game for game, the moves the oracle plays there."""
+    from oracle import oracle as oz
+    d, W, K, T, G, seed = tmp_path / "dump", 1, 3, 64, 128, 7
+    r = subprocess.run([sys.executable, BENCH, "--steps", str(K), "--warmup", str(W), "--games", str(G), "--chunk", str(T), "--seed-base", str(seed),
+                        "--no-cpu-baseline", "--no-extras", "--sustained", "0", "--dump-outputs", str(d)],
+                       env=_env(), capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    out = json.loads(lines[0])
+    assert out["steps"] == K and out["ms_per_step"] > 0 and out["dump_outputs"]["games"] == G
+    assert np.array_equal(np.load(d / "games.npy"), np.arange(G))
+    got = {k: np.load(d / (k + ".npy")) for k in DUMPED}
+    assert got["mask"].shape == (T, G, 180) and got["action"].shape == (T, G)
+    first = 128 + (W + K - 1) * T                # moves before the last timed launch: bench.py's 128-move parity gate, then W + K launches
+    for g in range(G):
+        o = oz.Stream(seed + g).advance(first + T, want_records=False)
+        for k in ("action", "reward", "done", "mask"):
+            assert np.array_equal(got[k][:, g], o[k][first:]), (k, g)
+    assert np.array_equal(got["packed"], got["reward"].astype(np.float64) * 65536 + got["done"] * 256 + got["action"])
 
 
 def test_watchdog_prints_the_headline_and_exits_non_zero(capsys):
