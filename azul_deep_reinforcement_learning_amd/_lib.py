@@ -111,6 +111,13 @@ SIGNATURES = {
     "azul_discounted_returns_ring": (_i, [_vp, _vp, _vp, C.c_float, _i, C.c_int64, _i, _i, _vp]),
     "azul_batch_sample_mask": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "azul_batch_score_preview": (_i, [_vp, _vp, _vp]),
+    "azul_batch_mp_runner_init": (_i, [_vp, _vp, _vp, _vp]),
+    "azul_batch_mp_runner_reset": (_i, [_vp, _vp, _vp, _vp]),
+    "azul_batch_mp_runner_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "azul_batch_mp_agent_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    "azul_batch_mp_policy_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    "azul_batch_mp_score_preview": (_i, [_vp, _vp, _vp]),
+    "azul_policy_head_n": (_i, [_vp, _vp, _u64, _u64, _vp, _i, _i, _u32, _vp, _vp, _vp, _vp]),
     "azul_game_call": (_i, [_vp, C.POINTER(AzulCall), _vp]),
     "azul_batch_selfplay": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "azul_batch_selfplay_strided": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -63,6 +63,16 @@ __global__ void __launch_bounds__(64) azul_x_selfplay_kernel(azx::XBatchDev b, a
     azx::selfplay_body_x<P, D, OUT, PAD, BITS>(b, t, wave_id, mt_lds, mtt_lds, tab_lds);
 }
 
+// GameRunner for P seats on the wide record (azul_batch_mp_* entries; azx::runner_body_x in azul_rules_x.hpp): one runner call per game, two games per wavefront
+// (azx::runner_body_x), the game in VGPRs from the agent's move through the replies, the reset and the observation.
+template <u32 P, u32 D>
+__global__ void __launch_bounds__(64) azul_x_runner_kernel(azx::XBatchDev b, azx::XRun a)
+{
+    __shared__ u32 mt_lds[2][624];
+    __shared__ double2 tab_lds[azx::Dim<D>::TROWS * T_STRIDE];
+    azx::runner_body_x<P, D>(b, a, blockIdx.x, mt_lds, tab_lds);
+}
+
 #include "azul_policy.hpp"
 #include "azul_rollout2.hpp"
 #include "azul_learner.hpp"
@@ -880,6 +890,116 @@ int azul_batch_score_preview(azul_batch_t *b, int32_t *potential_dev, void *stre
     if (!potential_dev) return fail(AZUL_ERR_INVALID, "potential_dev is NULL");
     OpArgs a = op_args(OP_QUERY); a.potential = potential_dev;
     return launch_op(b, a, stream);
+}
+
+// ---- GameRunner for P seats (azul_rules_x.hpp: runner_body_x): the azul_batch_mp_* entries ------------------------------------------------------
+// One launch over the whole batch, no host synchronisation, no allocation: capturable in a HIP graph.  Wide batches only; a two-player
+// reference batch is refused with the name of its own entry (`twin`).
+static int launch_runner_x(azul_batch_t *b, const azx::XRun &a0, const char *who, const char *twin, void *stream)
+{
+    if (!b) return fail(AZUL_ERR_INVALID, "batch is NULL");
+    if (!b->x)
+        return fail(AZUL_ERR_INVALID, (std::string(who) + ": a two-player batch of 128-byte records: use " + twin).c_str());
+    if (b->d.move_limit) return fail(AZUL_ERR_INVALID, (std::string(who) + ": no move limit for wide batches").c_str());
+    azx::XRun a = a0;
+    a.count = b->d.n;
+    const dim3 grid((a.count + 1u) / 2u), block(64);
+    const azx::XBatchDev xb = xdev(b);
+    AZ_X_DISPATCH(b, hipLaunchKernelGGL((azul_x_runner_kernel<PP, DD>), grid, block, 0, (hipStream_t)stream, xb, a));
+    HIP_TRY(hipGetLastError());
+    return AZUL_SUCCESS;
+}
+
+static azx::XRun run_args(int op)
+{
+    azx::XRun a;
+    memset(&a, 0, sizeof(a));
+    a.op = op;
+    return a;
+}
+
+int azul_batch_mp_runner_init(azul_batch_t *b, const uint8_t *active_dev, uint8_t *status_dev, void *stream)
+{
+    BATCH_GUARD(b, stream);
+    azx::XRun a = run_args(azx::XRUN_INIT); a.active = active_dev; a.status = status_dev;
+    return launch_runner_x(b, a, __func__, "azul_batch_runner_init", stream);
+}
+
+int azul_batch_mp_runner_reset(azul_batch_t *b, const uint8_t *active_dev, uint8_t *status_dev, void *stream)
+{
+    BATCH_GUARD(b, stream);
+    azx::XRun a = run_args(azx::XRUN_RESET); a.active = active_dev; a.status = status_dev;
+    return launch_runner_x(b, a, __func__, "azul_batch_runner_reset", stream);
+}
+
+int azul_batch_mp_runner_step(azul_batch_t *b, const int32_t *actions_dev, const uint8_t *active_dev, int32_t *reward_dev,
+                              uint8_t *done_dev, uint8_t *status_dev, void *stream)
+{
+    BATCH_GUARD(b, stream);
+    if (!actions_dev) return fail(AZUL_ERR_INVALID, "actions_dev is NULL");
+    azx::XRun a = run_args(azx::XRUN_STEP);
+    a.actions = actions_dev; a.active = active_dev; a.reward = reward_dev; a.done = done_dev; a.status = status_dev;
+    return launch_runner_x(b, a, __func__, "azul_batch_runner_step", stream);
+}
+
+static int mp_step(azul_batch_t *b, int op, const int32_t *actions_dev, const uint8_t *active_dev, int32_t *reward_dev, uint8_t *done_dev,
+                   uint8_t *status_dev, int perspective, float *obs_next_dev, uint8_t *mask_next_dev, uint8_t *player_next_dev,
+                   const char *who, const char *twin, void *stream)
+{
+    if (!b) return fail(AZUL_ERR_INVALID, "batch is NULL");
+    if (!actions_dev || (b->x && !persp_ok(b, perspective))) return fail(AZUL_ERR_INVALID, (std::string(who) + ": bad arguments").c_str());
+    azx::XRun a = run_args(op);
+    a.actions = actions_dev; a.active = active_dev; a.reward = reward_dev; a.done = done_dev; a.status = status_dev;
+    a.persp = perspective; a.obs = obs_next_dev; a.mask = mask_next_dev; a.player = player_next_dev;
+    return launch_runner_x(b, a, who, twin, stream);
+}
+
+int azul_batch_mp_agent_step(azul_batch_t *b, const int32_t *actions_dev, const uint8_t *active_dev, int32_t *reward_dev,
+                             uint8_t *done_dev, uint8_t *status_dev, int perspective, float *obs_next_dev,
+                             uint8_t *mask_next_dev, uint8_t *player_next_dev, void *stream)
+{
+    BATCH_GUARD(b, stream);
+    return mp_step(b, azx::XRUN_AGENT_STEP, actions_dev, active_dev, reward_dev, done_dev, status_dev, perspective, obs_next_dev, mask_next_dev,
+                   player_next_dev, __func__, "azul_batch_agent_step", stream);
+}
+
+int azul_batch_mp_policy_step(azul_batch_t *b, const int32_t *actions_dev, const uint8_t *active_dev, int32_t *reward_dev,
+                              uint8_t *done_dev, uint8_t *status_dev, int perspective, float *obs_next_dev,
+                              uint8_t *mask_next_dev, uint8_t *player_next_dev, void *stream)
+{
+    BATCH_GUARD(b, stream);
+    return mp_step(b, azx::XRUN_POLICY_STEP, actions_dev, active_dev, reward_dev, done_dev, status_dev, perspective, obs_next_dev, mask_next_dev,
+                   player_next_dev, __func__, "azul_batch_policy_step", stream);
+}
+
+int azul_batch_mp_score_preview(azul_batch_t *b, int32_t *potential_dev, void *stream)
+{
+    BATCH_GUARD(b, stream);
+    if (!potential_dev) return fail(AZUL_ERR_INVALID, "potential_dev is NULL");
+    azx::XRun a = run_args(azx::XRUN_PREVIEW); a.potential = potential_dev;
+    return launch_runner_x(b, a, __func__, "azul_batch_score_preview", stream);
+}
+
+int azul_policy_head_n(const float *logits_dev, const uint8_t *mask_dev, uint64_t seed, uint64_t counter, const uint64_t *counter_dev,
+                       int n_games, int num_actions, uint32_t game_id_base, int32_t *action_dev, float *logp_dev, float *entropy_dev, void *stream)
+{
+    if (!logits_dev || !mask_dev || !action_dev || !logp_dev || !entropy_dev || n_games <= 0) return fail(AZUL_ERR_INVALID, "azul_policy_head_n: bad arguments");
+    if (num_actions != 180 && num_actions != 240 && num_actions != 300)
+        return fail(AZUL_ERR_INVALID, "azul_policy_head_n: num_actions must be 180, 240 or 300 (azul_batch_num_actions)");
+    STREAM_GUARD(stream);
+    const dim3 grid(((u32)n_games + 3u) / 4u), block(64);
+    const hipStream_t st = (hipStream_t)stream;
+    if (num_actions == 180)
+        hipLaunchKernelGGL((azul_policy_head_n_kernel<180, 12>), grid, block, 0, st, logits_dev, mask_dev, (u64)seed, (u64)counter,
+                           (const u64 *)counter_dev, (u32)n_games, action_dev, logp_dev, entropy_dev, (u32)game_id_base);
+    else if (num_actions == 240)
+        hipLaunchKernelGGL((azul_policy_head_n_kernel<240, 15>), grid, block, 0, st, logits_dev, mask_dev, (u64)seed, (u64)counter,
+                           (const u64 *)counter_dev, (u32)n_games, action_dev, logp_dev, entropy_dev, (u32)game_id_base);
+    else
+        hipLaunchKernelGGL((azul_policy_head_n_kernel<300, 19>), grid, block, 0, st, logits_dev, mask_dev, (u64)seed, (u64)counter,
+                           (const u64 *)counter_dev, (u32)n_games, action_dev, logp_dev, entropy_dev, (u32)game_id_base);
+    HIP_TRY(hipGetLastError());
+    return AZUL_SUCCESS;
 }
 
 // ---- azul_game_call: one method call of the single-game API in one submission + one synchronisation ---------------------------

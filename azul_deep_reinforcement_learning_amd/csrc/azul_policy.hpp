@@ -78,14 +78,16 @@ __device__ __forceinline__ u32 row_sum_u(u32 v)
 
 constexpr int HEAD_PER_LANE = 12;
 
-// x[j]: the lane's 12 logits; row: the game's 180 logits (LDS or global: the chosen action's logit is read back from there); okbits: bit
-// j set when action 12c+j is legal; g: the lane's game (uniform inside a 16-lane row).
+// x[j]: the lane's NPL logits (12 for the reference's 180 actions; azul_policy_head_n_kernel: 15 / 19 for 240 / 300); row: the game's
+// logits (LDS or global: the chosen action's logit is read back from there); okbits: bit j set when action NPL c + j is legal; g: the
+// lane's game (uniform inside a 16-lane row).
 // Lane c == 0 of every row whose `store` is true writes the three results of its game.
 // The per-lane loops are BRANCH-FREE (round 3): the first version's `if (ok && pick < 0 && target < cum)` became twelve divergent
 // regions per lane (26 exec-mask saves, 58 register copies in 670 instructions).  Now the twelve crossing tests are the sign bits of
 // target - cum_j collected into a bit mask, the pick is its lowest bit among the legal ones, and the chosen action's logit is read
 // back from `row` instead of being tracked through the loop.  Same additions in the same order: the same numbers as before.
-__device__ __forceinline__ void policy_head_rows(const float (&x)[HEAD_PER_LANE], const float *row, u32 okbits, u64 seed, u64 counter, u32 g, u32 l,
+template <int NPL>
+__device__ __forceinline__ void policy_head_rows(const float (&x)[NPL], const float *row, u32 okbits, u64 seed, u64 counter, u32 g, u32 l,
                                                  bool store, i32 *action, float *logp, float *entropy, u32 id_base, i32 *lds_action = nullptr,
                                                  const float *u_ready = nullptr /* the game's uniform, when the caller drew it ahead of time */)
 {
@@ -93,13 +95,13 @@ __device__ __forceinline__ void policy_head_rows(const float (&x)[HEAD_PER_LANE]
     const float NEG = -3.0e38f;
     float m = NEG;
 #pragma unroll
-    for (int j = 0; j < HEAD_PER_LANE; j++) m = fmaxf(m, ((okbits >> j) & 1u) ? x[j] : NEG);
+    for (int j = 0; j < NPL; j++) m = fmaxf(m, ((okbits >> j) & 1u) ? x[j] : NEG);
     m = row_max(m);
     const u32 cnt = row_sum_u((u32)__popc(okbits));
-    float e[HEAD_PER_LANE];
+    float e[NPL];
     float mine = 0.f, zs = 0.f;
 #pragma unroll
-    for (int j = 0; j < HEAD_PER_LANE; j++) {
+    for (int j = 0; j < NPL; j++) {
         const bool ok = (okbits >> j) & 1u;
         const float z = ok ? x[j] - m : 0.f;
         e[j] = ok ? __expf(z) : 0.f;
@@ -120,10 +122,10 @@ __device__ __forceinline__ void policy_head_rows(const float (&x)[HEAD_PER_LANE]
     u32 cross = 0;                                       // bit j: target < cum_j (sampling) / x_j == m (argmax)
     if (argmax) {                                        // (wave-uniform)
 #pragma unroll
-        for (int j = 0; j < HEAD_PER_LANE; j++) cross |= (x[j] == m ? 1u : 0u) << j;
+        for (int j = 0; j < NPL; j++) cross |= (x[j] == m ? 1u : 0u) << j;
     } else {
 #pragma unroll
-        for (int j = 0; j < HEAD_PER_LANE; j++) {
+        for (int j = 0; j < NPL; j++) {
             cum += e[j];
             cross |= (__builtin_bit_cast(u32, target - cum) >> 31) << j;      // the sign of target - cum_j (no NaNs: finite logits)
         }
@@ -138,7 +140,7 @@ __device__ __forceinline__ void policy_head_rows(const float (&x)[HEAD_PER_LANE]
     const int jmine = hit16 ? pick : lastok;
     const int src = (int)((16u * grp + lane_sel) << 2);
     const int jsel = __builtin_amdgcn_ds_bpermute(src, jmine);
-    const i32 chosen = cnt == 0u ? -1 : (i32)(HEAD_PER_LANE * lane_sel) + jsel;     // no legal action (stuck game): the rollout sends -1
+    const i32 chosen = cnt == 0u ? -1 : (i32)(NPL * lane_sel) + jsel;     // no legal action (stuck game): the rollout sends -1
     if (lds_action && c == 0u) lds_action[grp] = chosen;
     if (store && c == 0u) {
         const float zsel = row[chosen < 0 ? 0 : chosen] - m;                         // log-softmax numerator of the chosen action
@@ -172,6 +174,33 @@ __global__ void __launch_bounds__(64) azul_policy_head_kernel(const float *logit
     for (int j = 0; j < HEAD_PER_LANE; j++) x[j] = lg[j];
     u32 okbits = head_mask_bits(mask + (size_t)gc * AZUL_NUM_ACTIONS, c);
     policy_head_rows(x, logits + (size_t)gc * AZUL_NUM_ACTIONS, okbits, seed, counter, gc, l, g < n, action, logp, entropy, id_base);
+}
+
+// The same head for the action spaces of every batch shape (azul_batch_num_actions: 180 / 240 / 300 for 5 / 7 / 9 displays): 16 lanes per
+// game as above, lane c owning actions NPL c .. NPL c + NPL - 1 (NPL = 12 / 15 / 19); rows of NA logits / mask bytes.  At NA = 180 every
+// lane sees what azul_policy_head_kernel's lane sees where it matters (lane 15 owns no action there: its logits are never read), so the
+// results are the same bits.
+template <u32 NA, int NPL>
+__global__ void __launch_bounds__(64) azul_policy_head_n_kernel(const float *logits, const uint8_t *mask, u64 seed, u64 counter,
+                                                                const u64 *counter_dev, u32 n, i32 *action, float *logp, float *entropy, u32 id_base)
+{
+    static_assert(16 * NPL >= (int)NA && 16 * (NPL - 1) < (int)NA && NPL <= 32, "NPL = ceil(NA / 16): 16 lanes per game");
+    const u32 l = threadIdx.x, c = l & 15u;
+    const u32 g = blockIdx.x * 4u + (l >> 4);
+    const u32 gc = g < n ? g : n - 1u;
+    if (counter_dev) counter += *counter_dev;
+    const float *row = logits + (size_t)gc * NA;
+    const uint8_t *mk = mask + (size_t)gc * NA;
+    float x[NPL];
+    u32 okbits = 0;
+#pragma unroll
+    for (int j = 0; j < NPL; j++) {
+        const u32 i = (u32)NPL * c + (u32)j;
+        const bool in = i < NA;
+        x[j] = in ? row[i] : 0.f;
+        okbits |= ((in && mk[in ? i : 0u] != 0) ? 1u : 0u) << j;
+    }
+    policy_head_rows(x, row, okbits, seed, counter, gc, l, g < n, action, logp, entropy, id_base);
 }
 
 // ---- fused ActorCritic forward + head ------------------------------------------------------------------------------

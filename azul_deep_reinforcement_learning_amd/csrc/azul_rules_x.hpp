@@ -1094,4 +1094,277 @@ AZ_FN void selfplay_body_x(const XBatchDev &b, const XTraj &t, u32 wave_id, u32 
     counters2_close(cnt, l);
 }
 
+// ---- GameRunner for P = 2, 3, 4 players on D = 5 or 2 P + 1 displays, TWO GAMES PER 64-LANE WAVEFRONT, on top of the rules above
+// (state in VGPRs, one game per 32-lane half).  runner_body_x is the body of azul_x_runner_kernel; tests/hostcheck/simt_runner_x.cpp runs it,
+// unmodified, under the lockstep 64-lane emulation against a model composed from the oracle's primitives (tests/mp_runner_model.py).
+//
+// What it is: GameRunner.__init__ / step / reset of the reference (azulnet/game_runner.py:23-36, 43-55, 76-85) statement for statement on an
+// Azul(players = P), the agent in seat 0 ("player 1"), every other seat replying with its own RandomAgent draw (:87-97) from the game's
+// stream; plus agent_step2 / policy_step2 of azul_env2.hpp generalised to P seats.  The reference's code is P-generic in every one of these
+// lines except the shaped reward, score[0] - score[1] (:50).  BEYOND THE REFERENCE for P > 2: the potential is
+//     phi = s[0] - max_{j = 1 .. P-1} s[j]      (s: the scores after count_score() on a copy of the game, :48-49)
+// -- the agent's margin over the best opponent; at P = 2 it is the reference's line exactly.
+//
+// Runner state per game (GameRunner.player_score / move_counter, :35-36) lives in the wide record's tail: bytes 228..229 i16 phi_stored,
+// 230..231 u16 move counter (include/azul_hip.h).  No other entry reads or writes them.
+enum { XRUN_INIT = 0, XRUN_RESET, XRUN_STEP, XRUN_AGENT_STEP, XRUN_POLICY_STEP, XRUN_PREVIEW };
+
+struct XRun {
+    int op;                  // XRUN_*
+    const i32 *actions;      // [count] in  (STEP / AGENT_STEP / POLICY_STEP)
+    const uint8_t *active;   // [count] in, optional
+    i32 *reward;             // [count] out, optional
+    uint8_t *done;           // [count] out, optional
+    uint8_t *status;         // [count] out, optional
+    i32 *potential;          // [count] out (PREVIEW)
+    uint8_t *mask;           // [count][NA] out, optional: the legal mask after the op
+    float *obs;              // [count][obs_size] out, optional: get_state after the op
+    int persp;               // 0 .. P-1, or >= P: the player to move
+    uint8_t *player;         // [count] out, optional: current_player after the op
+    u32 count;               // the launch covers games 0 .. count - 1
+};
+
+struct RunX {
+    i32 phi;                 // GameRunner.player_score (:35): the potential stored by the last step
+    u32 moves;               // GameRunner.move_counter (:36)
+};
+
+AZ_FN void runx_load(RunX &s, const uint8_t *rec)
+{
+    const u32 t = *(const u32 *)(rec + 228);
+    s.phi = (i32)(int16_t)(t & 0xffffu);
+    s.moves = t >> 16;
+}
+
+AZ_FN void runx_store(const RunX &s, uint8_t *rec, u32 l)
+{
+    if (l == 0u) *(u32 *)(rec + 228) = ((u32)s.phi & 0xffffu) | ((s.moves & 0xffffu) << 16);
+}
+
+template <u32 D>
+AZ_FN u32 mask_count_x(const MaskX<D> &m)
+{
+    u32 c = 0;
+#pragma unroll
+    for (u32 r = 0; r < 6u; r++) c += row_count<D>(m, r);
+    return c;
+}
+
+// game_runner.py:48-50 for P seats: count_score() on a REGISTER copy of the game (only the scores are read: the rest of the copy is dead code)
+template <u32 P, u32 D>
+AZ_FN i32 potential_x(const GX<P, D> &g, const RulesX &rules, const KX<D> &K)
+{
+    GX<P, D> c = g;
+    count_score_x(c, false, rules.end_bonus != 0u, K);
+    i32 best = c.score[1];
+#pragma unroll
+    for (u32 p = 2; p < P; p++) best = c.score[p] > best ? c.score[p] : best;
+    return c.score[0] - best;
+}
+
+// a fresh Azul(players = P, rules) + new_round(), player_score = move_counter = 0 (game_runner.py:23-36 / :79-82)
+template <u32 P, u32 D>
+AZ_FN u32 runner_restart_x(GX<P, D> &g, RunX &s, const RulesX &rules, Rng2 &r, u64 margin, const KX<D> &K)
+{
+    s.phi = 0;
+    s.moves = 0;
+    return restart_x(g, rules, r, margin, K);
+}
+
+// the opponents' RandomAgent moves: GameRunner.step's loop (:46-47, `opening` false) or reset's (:84-85, `opening` true).  ST_STUCK when the
+// seat to move has no legal action (random.choices raises in the reference) or after the 4096-move guard of az2::opponent_loop2.
+template <u32 P, u32 D>
+AZ_FN u32 opponent_loop_x(GX<P, D> &g, RunX &s, const RulesX &rules, const KX<D> &K, Rng2 &r, const Tab2 &T, u64 margin, bool opening)
+{
+    const bool tracked = rules.pool != (u32)XPOOL_RANDOM;
+#pragma unroll 1
+    for (u32 guard = 0; guard < 4096u; guard++) {
+        MaskX<D> m;
+        legal_mask_x(g, K, m);
+        const u32 L = mask_count_x<D>(m);
+        const bool keep = opening ? (g.cur != 1u) : ((g.cur != 1u || L < 2u) && !g.over);
+        if (!keep) return ST_OK;
+        if (L == 0u) return ST_STUCK;                                  // RandomAgent: random.choices on all-zero weights raises
+        if (g.eog) return ST_GAME_ENDED;                               // azul.py:298-299
+        const i32 a = random_agent_x<D>(m, r, T, K.k);                 // :97
+        const u32 row = (u32)a / Dim<D>::Q, q = (u32)a - row * Dim<D>::Q, c = q / Dim<D>::S, src = q - c * Dim<D>::S;
+        do_move_x(g, src, c, row, tracked, K);                         // Azul.step on a legal action (azul.py:304-313)
+        sources_x(g);
+        const u32 st = after_move_x(g, rules, r, margin, K);
+        if (st) return st;
+        s.moves += 1u;                                                 // :42
+    }
+    return ST_STUCK;
+}
+
+// GameRunner.step (game_runner.py:43-55): the agent's move, the replies, the shaped reward, done.  No reset.
+template <u32 P, u32 D>
+AZ_FN u32 runner_step_x(GX<P, D> &g, RunX &s, i32 av, const RulesX &rules, const KX<D> &K, Rng2 &r, const Tab2 &T, u64 margin, i32 &rew, u32 &dn)
+{
+    rew = 0;
+    dn = g.over ? 1u : 0u;
+    u32 st = checked_step_x(g, rules, K, r, margin, av);               // :44
+    if (!st) {
+        s.moves += 1u;                                                 // :45
+        st = opponent_loop_x(g, s, rules, K, r, T, margin, false);     // :46-47
+        if (!st) {
+            const i32 phi = potential_x(g, rules, K);                  // :48-50 (beyond the reference for P > 2: margin over the best opponent)
+            rew = phi - s.phi;                                         // :51
+            s.phi = phi;                                               // :52
+            dn = g.over ? 1u : 0u;                                     // :55
+        }
+    }
+    return st;
+}
+
+template <u32 P, u32 D>
+AZ_FN void episode_stats_x(const GX<P, D> &g, Counters2 &cnt, u32 l)
+{
+    double fsum = 0.0;
+#pragma unroll
+    for (u32 p = 0; p < P; p++) fsum += (double)g.fps[p];              // first_player_stats.sum(): left to right
+    counters2_episode(cnt, stat_lane(l, g.score[0], g.score[1], g.turn, (double)g.fps[0] / fsum * 100, g.fpen[0], g.mc[0], g.cl[0]));
+}
+
+// One AGENT step of NNRunner.run_episode (nn_runner.py:24-29) = az2::agent_step2 for P seats: GameRunner.step, and when the episode ends its
+// statistics and the GameRunner.reset() that opens the next one (incl. the opening replies).  done 2: nobody could move (slot restarted).
+template <u32 P, u32 D>
+AZ_FN u32 agent_step_x(GX<P, D> &g, RunX &s, i32 av, const RulesX &rules, const KX<D> &K, Rng2 &r, const Tab2 &T, u64 margin, Counters2 &cnt,
+                       i32 &rew, u32 &dn)
+{
+    u32 st = runner_step_x(g, s, av, rules, K, r, T, margin, rew, dn);
+    const bool dirty = !(st == ST_ILLEGAL_MOVE || st == ST_BAD_ACTION);
+    if (st == ST_STUCK) { cnt.stuck_add += 1u; dn = 2u; rew = 0; }
+    else if (st == ST_GAME_ENDED) dn = 1u;
+    else if (st == ST_OK && dn) episode_stats_x(g, cnt, K.k.l);
+    if (dirty && dn) {
+        u32 st2 = runner_restart_x(g, s, rules, r, margin, K);         // game_runner.py:79-82
+        if (!st2) st2 = opponent_loop_x(g, s, rules, K, r, T, margin, true);      // :84-85
+        if (st == ST_OK) st = st2;
+    }
+    return st;
+}
+
+// One env move of policy-driven self-play (the policy plays every seat) = az2::policy_step2 for P seats: Azul.step for the current player,
+// the per-move shaped reward (seat-0-centric, as above), done, statistics and the auto-reset (a fresh game, no opening replies).
+template <u32 P, u32 D>
+AZ_FN u32 policy_step_x(GX<P, D> &g, RunX &s, i32 av, const RulesX &rules, const KX<D> &K, Rng2 &r, u64 margin, Counters2 &cnt, i32 &rew, u32 &dn)
+{
+    rew = 0; dn = 0;
+    bool stuck = false;
+    if (AZ_UNLIKELY(wave_any(av < 0))) {                               // "no action" is legitimate only when nothing is legal (hazard H3)
+        MaskX<D> m;
+        legal_mask_x(g, K, m);
+        stuck = (av < 0) & (g.eog == 0u) & (mask_count_x<D>(m) == 0u);
+    }
+    u32 st = ST_OK;
+    bool restart = false;
+    if (!stuck) {
+        st = checked_step_x(g, rules, K, r, margin, av);
+        const bool dirty = !(st == ST_ILLEGAL_MOVE || st == ST_GAME_ENDED || st == ST_BAD_ACTION);
+        if (dirty) {
+            s.moves += 1u;
+            const i32 phi = potential_x(g, rules, K);
+            rew = phi - s.phi;
+            s.phi = phi;
+            dn = g.over ? 1u : 0u;
+            restart = dn && st == ST_OK;
+        } else if (st == ST_GAME_ENDED) {                              // a finished game handed in: restart the slot, report done
+            dn = 1u;
+            restart = true;
+        }
+    }
+    if (AZ_UNLIKELY(wave_any(stuck | restart))) {
+        if (stuck | restart) {
+            if (stuck) { cnt.stuck_add += 1u; dn = 2u; }
+            else if (st == ST_OK) episode_stats_x(g, cnt, K.k.l);
+            const u32 st0 = runner_restart_x(g, s, rules, r, margin, K);
+            st = stuck ? (st0 ? st0 : (u32)ST_STUCK) : st0;
+        }
+    }
+    return st;
+}
+
+// One runner call on games 2 pair, 2 pair + 1 of the batch: the op, the record / tail / stream / counters written back, then the queries
+template <u32 P, u32 D>
+AZ_FN void runner_body_x(const XBatchDev &b, const XRun &a, u32 pair, u32 (*mt_lds)[624], double2 *tab_lds)
+{
+    const u32 lane = wv::lane(), l = lane & 31u, half = lane >> 5;
+    stage_tab_x<D>(b.tab, tab_lds, lane);
+    const u32 gi = 2u * pair + half;
+    if (gi >= a.count) return;                                         // odd batch: the last wave serves one game
+    const bool act = a.active ? (a.active[gi] != 0) : true;
+    uint8_t *rec = b.state + (size_t)gi * AZUL_RECORD_BYTES_WIDE;
+    KX<D> K;
+    kx_init(K);
+    const Tab2 tab = {tab_lds};
+    GX<P, D> g;
+    gx_load(g, rec, l);
+    prime_x(g, K);
+    RunX s;
+    runx_load(s, rec);
+    const bool steps = a.op == XRUN_STEP || a.op == XRUN_AGENT_STEP || a.op == XRUN_POLICY_STEP;
+    if (act && a.op != XRUN_PREVIEW) {
+        Rng2 r;
+        u32 *gmt = b.mt + (size_t)gi * 624u;
+        rng2_open(r, gmt, mt_lds[half], b.mtpos[gi], l);
+        Counters2 cnt;
+        counters2_open(cnt, b.episodes + gi, b.stuck + gi, b.stat_sum + (size_t)gi * 10, l);
+        u32 st = ST_OK;
+        i32 rew = 0;
+        u32 dn = 0;
+        const i32 av = steps ? a.actions[gi] : -1;
+        switch (a.op) {
+        case XRUN_INIT:
+            st = runner_restart_x(g, s, b.rules, r, b.draw_margin, K);
+            break;
+        case XRUN_RESET:
+            st = runner_restart_x(g, s, b.rules, r, b.draw_margin, K);
+            if (!st) st = opponent_loop_x(g, s, b.rules, K, r, tab, b.draw_margin, true);
+            break;
+        case XRUN_STEP:
+            st = runner_step_x(g, s, av, b.rules, K, r, tab, b.draw_margin, rew, dn);
+            if (!st && dn) episode_stats_x(g, cnt, l);
+            if (st == ST_STUCK) cnt.stuck_add += 1u;
+            break;
+        case XRUN_AGENT_STEP:
+            st = agent_step_x(g, s, av, b.rules, K, r, tab, b.draw_margin, cnt, rew, dn);
+            break;
+        default:
+            st = policy_step_x(g, s, av, b.rules, K, r, b.draw_margin, cnt, rew, dn);
+            break;
+        }
+        // an illegal / out-of-range action (and, for the plain step, a finished game) leaves the game untouched
+        const bool dirty = !(st == ST_ILLEGAL_MOVE || st == ST_BAD_ACTION || (a.op == XRUN_STEP && st == ST_GAME_ENDED));
+        if (dirty) {
+            gx_store(g, rec, l);
+            runx_store(s, rec, l);
+        }
+        rng2_close(r, gmt, b.mtpos + gi, l);
+        counters2_close(cnt, l);
+        if (l == 0u) {
+            if (steps && a.reward) a.reward[gi] = rew;
+            if (steps && a.done) a.done[gi] = (uint8_t)dn;
+            if (a.status) a.status[gi] = (uint8_t)st;
+        }
+    }
+    if (a.op == XRUN_PREVIEW) {
+        const i32 phi = potential_x(g, b.rules, K);                    // (cross-lane: every lane of the half computes it)
+        if (l == 0u) a.potential[gi] = phi;
+    }
+    // queries on the state after the op: the next decision's observation, legal mask and player to move
+    if (a.mask) {
+        MaskX<D> m;
+        legal_mask_x(g, K, m);
+        uint8_t *row = a.mask + (size_t)gi * Dim<D>::NA + l;
+#pragma unroll
+        for (u32 rr = 0; rr < 6u; rr++) {
+            if (l < (Dim<D>::Q < 32u ? Dim<D>::Q : 32u)) row[Dim<D>::Q * rr] = (uint8_t)m.bit[rr][0];
+            if (Dim<D>::NW > 1) { if (l < Dim<D>::Q - 32u) row[Dim<D>::Q * rr + 32u] = (uint8_t)m.bit[rr][Dim<D>::NW - 1]; }
+        }
+    }
+    if (a.obs) observe_x(g, (u32)a.persp < P ? (u32)a.persp : mex(g), a.obs + (size_t)gi * obs_size<P, D>(), l);
+    if (a.player && l == 0u) a.player[gi] = (uint8_t)g.cur;
+}
+
 } // namespace azx

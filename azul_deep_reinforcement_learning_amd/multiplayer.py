@@ -1,0 +1,72 @@
+"""MultiplayerAzul: GameRunner for batches of three / four players and extended-rule batches (wide records) on one MI355X.
+
+The reference's GameRunner (azulnet/game_runner.py:23-97) on an Azul(players=P): the agent is seat 0 ("player 1"), every other seat
+replies with its own RandomAgent draw from the game's stream.  Each method is one launch of azul_x_runner_kernel through the
+azul_batch_mp_* entries of the C ABI (include/azul_hip.h).  The shaped reward is the one departure from the reference, BEYOND THE
+REFERENCE for P > 2: phi = s[0] - max_{j>0} s[j] after count_score() on a copy of the game (game_runner.py:48-50), reward = phi - phi_stored;
+at P = 2 it is the reference's score[0] - score[1].  Plain BatchedAzul keeps refusing these calls for wide batches.
+"""
+import torch
+
+from . import _lib as L
+from .batch import BatchedAzul, _ptr
+from .records import runner_tail
+
+
+class MultiplayerAzul(BatchedAzul):
+    def __init__(self, n_games, rules={"first_player": "Random", "tile_pool": "Lid"}, device=None, seed=None, players=3, ext_rules=None):
+        super().__init__(n_games, rules=rules, device=device, seed=seed, players=players, ext_rules=ext_rules)
+        if not self.wide:
+            raise ValueError("MultiplayerAzul is for batches of three / four players or extended rules: BatchedAzul runs the two-player GameRunner")
+
+    def _status(self):
+        return torch.zeros(self.n, dtype=torch.uint8, device=self.device)
+
+    def runner_init(self, active=None):
+        """GameRunner.__init__ (game_runner.py:23-36): Azul(players=P, rules) + new_round(), player_score = move_counter = 0."""
+        st = self._status()
+        L.check(L.lib.azul_batch_mp_runner_init(self._h, _ptr(self._dev(active, torch.uint8)), _ptr(st), self._stream()))
+        return st
+
+    def reset(self, active=None):
+        """GameRunner.reset (game_runner.py:76-85): a fresh game, then the other seats move while current_player != 1."""
+        st = self._status()
+        L.check(L.lib.azul_batch_mp_runner_reset(self._h, _ptr(self._dev(active, torch.uint8)), _ptr(st), self._stream()))
+        return st
+
+    def step(self, actions, active=None):
+        """GameRunner.step (game_runner.py:43-55) for every game -> (reward int32[N], done bool[N], status uint8[N])."""
+        a = self._dev(actions, torch.int32)
+        reward = torch.zeros(self.n, dtype=torch.int32, device=self.device)
+        done = torch.zeros(self.n, dtype=torch.uint8, device=self.device)
+        st = self._status()
+        L.check(L.lib.azul_batch_mp_runner_step(self._h, _ptr(a), _ptr(self._dev(active, torch.uint8)), _ptr(reward), _ptr(done), _ptr(st),
+                                                self._stream()))
+        return reward, done.bool(), st
+
+    def score_preview(self):
+        """phi of the current state for every game (int32[N])."""
+        p = self._new((self.n,), torch.int32)
+        L.check(L.lib.azul_batch_mp_score_preview(self._h, _ptr(p), self._stream()))
+        return p
+
+    def observe_all(self, perspective=L.PERSP_MOVER, obs=None, mask=None, player=None):
+        return super().observe_all(perspective, obs, mask, player)
+
+    def policy_step(self, actions, reward, done, status, obs_next, mask_next, player_next, perspective=L.PERSP_MOVER, active=None):
+        """One env move for the player to move with caller-chosen actions (the policy plays every seat): per-move reward (delta of the
+        seat-0 potential), done, statistics and auto-reset, then the next observation (from the mover), mask and player."""
+        L.check(L.lib.azul_batch_mp_policy_step(self._h, _ptr(actions), _ptr(self._dev(active, torch.uint8)), _ptr(reward), _ptr(done),
+                                                _ptr(status), int(perspective), _ptr(obs_next), _ptr(mask_next), _ptr(player_next),
+                                                self._stream()))
+
+    def agent_step(self, actions, reward, done, status, obs_next, mask_next, player_next=None, perspective=0, active=None):
+        """One AGENT step of NNRunner.run_episode: GameRunner.step incl. the replies, at the end of an episode its statistics and
+        GameRunner.reset() with the opening replies, then the next decision's observation / mask / player (preallocated tensors)."""
+        L.check(L.lib.azul_batch_mp_agent_step(self._h, _ptr(actions), _ptr(self._dev(active, torch.uint8)), _ptr(reward), _ptr(done),
+                                               _ptr(status), int(perspective), _ptr(obs_next), _ptr(mask_next), _ptr(player_next),
+                                               self._stream()))
+
+    def runner_counters(self, first=0, count=None):
+        """GameRunner.player_score (the stored potential) and move_counter of every game: (int16[N], uint16[N]) read from the records."""
+        return runner_tail(self.get_records(first, count))

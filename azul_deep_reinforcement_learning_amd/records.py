@@ -49,6 +49,15 @@ RECORD_NP_DTYPE = np.dtype([
 ])
 assert RECORD_NP_DTYPE.itemsize == 256
 
+
+def runner_tail(records):
+    """GameRunner's counters of the P-player runner (azul_batch_mp_* entries) from wide records: bytes 228..229 of the `reserved` tail are
+    player_score (int16, the stored potential), 230..231 move_counter (uint16) -> (player_score int16[N], move_counter uint16[N])."""
+    raw = np.ascontiguousarray(records).view(np.uint8).reshape(-1, RECORD_NP_DTYPE.itemsize)
+    tail = np.ascontiguousarray(raw[:, 228:232])
+    return tail[:, 0:2].copy().view("<i2").reshape(-1), tail[:, 2:4].copy().view("<u2").reshape(-1)
+
+
 _WALL_SHIFTS = np.arange(25, dtype=np.uint32)
 
 

@@ -24,7 +24,8 @@ import ctypes as C
 import torch
 
 from . import _lib as L
-from .batch import BatchedAzul
+from .batch import BatchedAzul, parse_ext_rules
+from .multiplayer import MultiplayerAzul
 
 
 def _p(t):
@@ -35,7 +36,7 @@ class PolicyRollout:
     def __init__(self, policy, n_games=4096, parts=1, rules={"first_player": "Random", "tile_pool": "Lid"}, seed_base=0,
                  device=None, window=32, use_graph=True, fused_head=True, sample_seed=0x5EED, opponent=None, fused_mlp=True, persistent=False,
                  action_selection="Distribution", kweights=None, game_id_base=None, ring=1, opponent_selection="Distribution",
-                 opponent_seed=None, opponent_trace=0, move_limit=0):
+                 opponent_seed=None, opponent_trace=0, move_limit=0, players=2):
         """opponent=None: the policy moves for both players (flat self-play, one record per env move).
         opponent="random": the reference's training setup -- the policy is player 1 of GameRunner, the opponent a RandomAgent
         inside the env step (game_runner.py:43-47); one record per AGENT step, observations from the agent's perspective.
@@ -55,8 +56,19 @@ class PolicyRollout:
         `ring` (persistent=True only): the trajectory buffers hold the last `ring` windows (a ring of ring * window time slots);
         run_window fills the next window of the ring and re-chains the discounted returns backwards through the older windows, so
         that the opening steps of an episode that ends in a LATER window get their exact Monte-Carlo return too
-        (A2CLearner.update_from_rollout trains every step of every episode exactly once, like NNRunner.train)."""
+        (A2CLearner.update_from_rollout trains every step of every episode exactly once, like NNRunner.train).
+        `players` = 3 / 4, or extended-rule keys in `rules` (the wide records): the games are MultiplayerAzul parts (GameRunner for P seats,
+        azul_batch_mp_*; the shaped reward is the margin over the best opponent, beyond the reference for P > 2), the network runs as
+        PyTorch GEMMs + azul_policy_head_n on env.num_actions logits, trajectory buffers are env.obs_size / env.num_actions wide;
+        opponent=None | "random" with both action_selection modes, HIP graphs and parts as on the two-player PyTorch path."""
         assert n_games % parts == 0
+        self.players = int(players)
+        self.wide = self.players != 2 or parse_ext_rules(rules, self.players) != 0
+        if self.wide and opponent is not None and not isinstance(opponent, str):
+            raise ValueError("a network opponent is compiled for the two-player game (ActorCritic(136, 180, 180)): batches of %d players / "
+                             "extended rules support opponent=None or \"random\"" % self.players)
+        if self.wide and move_limit:
+            raise ValueError("no move limit for batches of three / four players or extended rules")
         self.opp_policy = None
         if opponent is not None and not isinstance(opponent, str):
             self.opp_policy, opponent = opponent, "net"
@@ -67,7 +79,7 @@ class PolicyRollout:
         self.n, self.parts, self.h, self.T = n_games, parts, n_games // parts, window
         self.fused_head = fused_head
         # the one-launch forward (azul_policy_forward) is compiled for the reference's ActorCritic(136, 180, hidden 180)
-        self.fused_mlp = bool(fused_mlp and fused_head and policy.critic_linear1.in_features == L.OBS_SIZE and
+        self.fused_mlp = bool(fused_mlp and fused_head and not self.wide and policy.critic_linear1.in_features == L.OBS_SIZE and
                               policy.critic_linear1.out_features == 180 and policy.actor_linear2.out_features == L.NUM_ACTIONS)
         # persistent=True: the whole window runs in ONE launch per part (azul_batch_policy_rollout); same results
         self.persistent = bool(persistent and self.fused_mlp)
@@ -86,6 +98,8 @@ class PolicyRollout:
         self.envs, self.streams, self.work, self.traj, self.graphs = [], [], [], [], []
         # kweights: k-major weight tensors owned by someone else (A2CLearner.kweights(): views of its flat master copy, kept current
         # by the optimiser kernel) -- then nothing is copied here and refresh_weights() has nothing to do
+        if self.wide:
+            kweights = None                                # (the 136-shaped flat copy belongs to the two-player kernels)
         self._external_kweights = kweights is not None
         if kweights is not None:
             self.H = policy.critic_linear1.out_features
@@ -98,7 +112,7 @@ class PolicyRollout:
             self.set_opponent(self.opp_policy)
         d, h, T = self.device, self.h, window
         for p in range(parts):
-            env = BatchedAzul(h, rules=rules, device=d)
+            env = MultiplayerAzul(h, rules=rules, device=d, players=self.players) if self.wide else BatchedAzul(h, rules=rules, device=d)
             env.seed(seed_base + p * h)                            # seeds follow the global game id
             env.set_id_base(self.game_id_base + p * h)             # ... and so does the sampler's Philox key
             if move_limit:
@@ -113,7 +127,8 @@ class PolicyRollout:
             self.envs.append(env)
             self.streams.append(torch.cuda.Stream(device=d))
             R = self.ring * T
-            rg = {"obs": torch.zeros(R + 1, h, L.OBS_SIZE, device=d), "mask": torch.zeros(R + 1, h, L.NUM_ACTIONS, dtype=torch.uint8, device=d),
+            self.obs_size, self.num_actions = env.obs_size, env.num_actions
+            rg = {"obs": torch.zeros(R + 1, h, env.obs_size, device=d), "mask": torch.zeros(R + 1, h, env.num_actions, dtype=torch.uint8, device=d),
                   "player": torch.zeros(R + 1, h, dtype=torch.uint8, device=d),
                   "action": torch.zeros(R, h, dtype=torch.int32, device=d), "reward": torch.zeros(R, h, dtype=torch.int32, device=d),
                   "done": torch.zeros(R, h, dtype=torch.uint8, device=d),
@@ -127,7 +142,7 @@ class PolicyRollout:
             self.rings = getattr(self, "rings", [])
             self.rings.append(rg)
             t = self._window_views(rg, self.ring - 1)             # the "previous" window: its slot T seeds the first window
-            w = {"hidden": torch.zeros(h, 2 * self.H, device=d), "logits": torch.zeros(h, L.NUM_ACTIONS, device=d),
+            w = {"hidden": torch.zeros(h, 2 * self.H, device=d), "logits": torch.zeros(h, env.num_actions, device=d),
                  "status": torch.zeros(h, dtype=torch.uint8, device=d),
                  "counter": torch.tensor([0, 0], dtype=torch.int64, device=d)}     # [0] Philox step counter, [1] launch ticket
             if self.opponent == "net":
@@ -241,7 +256,12 @@ class PolicyRollout:
             w["hidden"].relu_()
             torch.addmm(pol.critic_linear2.bias, w["hidden"][:, :H], self.w2c_t, out=tr["value"][t])          # agent.py:66
             torch.addmm(pol.actor_linear2.bias, w["hidden"][:, H:], self.w2a_t, out=w["logits"])               # agent.py:67
-            if self.fused_head:
+            if self.fused_head and self.wide:
+                L.check(L.lib.azul_policy_head_n(_p(w["logits"]), _p(mask), self.sample_seed, 0, _p(w["counter"]), self.h, self.num_actions,
+                                                 self.game_id_base + p * self.h, _p(tr["action"][t]), _p(tr["log_prob"][t]), _p(tr["entropy"][t]),
+                                                 C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+                w["counter"][:1].add_(1)
+            elif self.fused_head:
                 L.check(L.lib.azul_policy_head(_p(w["logits"]), _p(mask), self.sample_seed, 0, _p(w["counter"]), self.h, self.game_id_base + p * self.h,
                                                _p(tr["action"][t]), _p(tr["log_prob"][t]), _p(tr["entropy"][t]),
                                                C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))

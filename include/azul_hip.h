@@ -64,7 +64,10 @@
  *   205   1  u8  n_displays                0 = the reference's five (a five-display record is byte for byte what it was); else 7 / 9
  *   206   2  u8  reserved0                 zero
  *   208  20  u8  xdisplays[4][5]           factory displays 5 .. 8, beyond the reference's five (AZUL_RULE_DISPLAYS_2P1); zero otherwise
- *   228  28      reserved (zero)
+ *   228   2  i16 player_score              GameRunner.player_score (game_runner.py:35) of the azul_batch_mp_* entries: the stored
+ *                                          potential phi (beyond the reference for P > 2, see azul_batch_mp_runner_step); zero otherwise
+ *   230   2  u16 move_counter              GameRunner.move_counter (game_runner.py:36) of the azul_batch_mp_* entries; zero otherwise
+ *   232  24      reserved (zero)
  *
  * Random numbers: every game owns a CPython-exact MT19937 stream (624 words + index), i.e. what the
  * reference consumes through the process-global `random` module (azul.py:37,78,87; game_runner.py:97).
@@ -146,7 +149,8 @@ int azul_batch_create_players(azul_batch_t **out, int n_games, int players, int 
  * _legal_mask / _next_player / _flags / _count_score / _step / _statistics), azul_batch_random_action / _sample_mask, azul_batch_observe
  * (get_state for P players, game_runner.py:56-72), the state and RNG I/O and azul_batch_selfplay; mask rows are azul_batch_num_actions
  * bytes, observations azul_batch_obs_size floats.  The entries that mirror GameRunner.step / reset and the policy entries (compiled for
- * 180 actions / 136 observations) return AZUL_ERR_INVALID for them.  AZUL_RULE_FINITE_BAG with AZUL_POOL_LID: AZUL_ERR_RULE. */
+ * 180 actions / 136 observations) return AZUL_ERR_INVALID for them: GameRunner for these batches is azul_batch_mp_*, the sampling head
+ * azul_policy_head_n.  AZUL_RULE_FINITE_BAG with AZUL_POOL_LID: AZUL_ERR_RULE. */
 int azul_batch_create_rules(azul_batch_t **out, int n_games, int players, int first_player, int tile_pool, unsigned rule_flags);
 int azul_batch_players(const azul_batch_t *b);
 int azul_batch_displays(const azul_batch_t *b);            /* 5, or 2 * players + 1 */
@@ -197,6 +201,35 @@ int azul_batch_random_action(azul_batch_t *b, const uint8_t *active_dev, int32_t
 int azul_batch_sample_mask(azul_batch_t *b, const uint8_t *mask_dev /*[N][180]*/, const uint8_t *active_dev,
                            int32_t *actions_dev, void *stream);
 int azul_batch_score_preview(azul_batch_t *b, int32_t *potential_dev /*[N]*/, void *stream);   /* deepcopy+count_score, score[0]-score[1]  game_runner.py:48-50 */
+
+/* ---- GameRunner for P players: batches of 3 / 4 players and extended-rule batches (wide records) ------------------------------
+ * The reference's GameRunner (game_runner.py:23-97) on an Azul(players = P): the agent is seat 0 ("player 1"), every other seat answers
+ * with its own RandomAgent draw (:87-97) from the game's stream.  Argument order as the two-player entries; a two-player batch of
+ * 128-byte records is refused (AZUL_ERR_INVALID, the message names its entry).  One launch each, no host synchronisation, no
+ * allocation: capturable in a HIP graph.  Runner state (player_score, move_counter) lives in bytes 228..231 of the wide record.
+ * Reward -- BEYOND THE REFERENCE for P > 2: phi = s[0] - max_{j=1..P-1} s[j] with s the scores after count_score() on a copy of the game
+ * (:48-50), reward = phi - player_score, player_score = phi (:51-52); at P = 2 this is the reference's score[0] - score[1]. */
+int azul_batch_mp_runner_init(azul_batch_t *b, const uint8_t *active_dev, uint8_t *status_dev, void *stream);   /* GameRunner.__init__ game_runner.py:23-36 */
+int azul_batch_mp_runner_reset(azul_batch_t *b, const uint8_t *active_dev, uint8_t *status_dev, void *stream);  /* reset (+ opening replies) :76-85 */
+/* GameRunner.step (game_runner.py:43-55): the agent's move, the other seats' replies while (current_player != 1 or the agent has fewer
+ * than two legal moves) and the game is not over (:46-47), the shaped reward, done.  status STUCK when a seat to move has no legal move. */
+int azul_batch_mp_runner_step(azul_batch_t *b, const int32_t *actions_dev, const uint8_t *active_dev, int32_t *reward_dev,
+                              uint8_t *done_dev, uint8_t *status_dev, void *stream);
+/* azul_batch_agent_step for P seats (nn_runner.py:24-29): GameRunner.step, at the end of an episode its statistics (azul.py:314-315, into
+ * azul_batch_counters) and GameRunner.reset() with the opening replies (game_runner.py:76-85), then the next decision's observation from
+ * `perspective` (get_state, :56-72; azul_batch_obs_size floats), legal mask (azul_batch_num_actions bytes) and player to move.  done: 1 game
+ * over, 2 stuck (nobody could move, or more than 4096 replies: slot restarted, reward 0); an illegal action leaves the game untouched
+ * (status AZUL_ILLEGAL_MOVE, reward 0). */
+int azul_batch_mp_agent_step(azul_batch_t *b, const int32_t *actions_dev, const uint8_t *active_dev, int32_t *reward_dev,
+                             uint8_t *done_dev, uint8_t *status_dev, int perspective, float *obs_next_dev,
+                             uint8_t *mask_next_dev, uint8_t *player_next_dev, void *stream);
+/* azul_batch_policy_step for P seats (the policy plays every seat): Azul.step for the current player (azul.py:296-313), the per-move
+ * reward (delta of the seat-0 potential above), done, statistics + auto-reset (a fresh game, no replies), then the next observation
+ * (perspective AZUL_PERSP_MOVER: the player to move), mask and player. */
+int azul_batch_mp_policy_step(azul_batch_t *b, const int32_t *actions_dev, const uint8_t *active_dev, int32_t *reward_dev,
+                              uint8_t *done_dev, uint8_t *status_dev, int perspective, float *obs_next_dev,
+                              uint8_t *mask_next_dev, uint8_t *player_next_dev, void *stream);
+int azul_batch_mp_score_preview(azul_batch_t *b, int32_t *potential_dev /*[N]*/, void *stream);   /* phi of the current state, game_runner.py:48-50 */
 
 /* ---- one method call of the reference's SINGLE-GAME API on one game of a batch -------------------
  * What the Python facade (Azul / GameRunner / RandomAgent of this package, i.e. BASELINE configs[0]: tests/test_azul.py,
@@ -287,6 +320,10 @@ int azul_batch_observe_all(azul_batch_t *b, int perspective, float *obs_dev, uin
  * draws the same numbers however the batch is sharded over GPUs or split into parts.  Rows without a legal action give -1. */
 int azul_policy_head(const float *logits_dev, const uint8_t *mask_dev, uint64_t seed, uint64_t counter, const uint64_t *counter_dev,
                      int n_games, uint32_t game_id_base, int32_t *action_dev, float *logp_dev, float *entropy_dev, void *stream);
+/* the same head for rows of num_actions = 180 / 240 / 300 logits and mask bytes (azul_batch_num_actions of any batch): the same Philox
+ * keys, argmax rule and outputs (agent.py:64-72, nn_runner.py:32-40); at 180 its results are azul_policy_head's, bit for bit. */
+int azul_policy_head_n(const float *logits_dev, const uint8_t *mask_dev, uint64_t seed, uint64_t counter, const uint64_t *counter_dev,
+                       int n_games, int num_actions, uint32_t game_id_base, int32_t *action_dev, float *logp_dev, float *entropy_dev, void *stream);
 /* The whole ActorCritic forward (model.py:12-41) + the head above in ONE launch, 16 games per workgroup on the f32 matrix cores
  * (exact f32):  hidden = relu(obs @ w1t + b1), value = hidden[:, :H] . w2c + b2c, logits = hidden[:, H:] @ w2a_t + b2a, then
  * azul_policy_head's sampling on the logits.  Weight layouts (k-major, i.e. nn.Linear.weight transposed):

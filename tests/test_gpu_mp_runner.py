@@ -1,0 +1,214 @@
+"""GPU: the P-player GameRunner entries (azul_batch_mp_*, azul_x_runner_kernel) through the C ABI against the model composed from the oracle
+(tests/mp_runner_model.py, pinned to the reference by tests/test_mp_runner_model.py) -- every instantiation, a full 4096-game window, the
+fused agent step against its parts, a graph-captured replay against eager calls, and the refusal of two-player 128-byte batches."""
+import ctypes as C
+import random
+
+import numpy as np
+import pytest
+import torch
+
+from oracle import oracle as oz
+
+pytestmark = pytest.mark.gpu
+
+SHAPES = [  # (players, rules): every instantiation of azul_x_runner_kernel (P, D)
+    (2, {"first_player": "Random", "tile_pool": "Lid", "bonuses": "end"}),                                # (2, 5)
+    (3, {"first_player": "Random", "tile_pool": "Lid"}),                                                  # (3, 5)
+    (3, {"first_player": 2, "tile_pool": "Random", "displays": "2P+1", "finite_bag": True}),              # (3, 7)
+    (4, {"first_player": "Random", "tile_pool": "Random"}),                                               # (4, 5)
+    (4, {"first_player": "Random", "tile_pool": "Lid", "displays": "2P+1", "short_deal": True, "bonuses": "end"}),   # (4, 9)
+]
+
+
+def models_for(env, seed_base):
+    from azul_deep_reinforcement_learning_amd import _lib as L
+    from azul_deep_reinforcement_learning_amd.batch import parse_rules
+    from tests.mp_runner_model import MPRunner
+    first, pool = parse_rules(env.rules, env.players)
+    return [MPRunner(env.players, first, pool, env.ext, seed=seed_base + g) for g in range(env.n)]
+
+
+def check_records(env, models):
+    recs = env.get_records().view(np.uint8).reshape(env.n, 256)
+    mt, pos = env.get_rng_range()
+    for g, m in enumerate(models):
+        assert np.array_equal(recs[g], m.record()), g
+        mm, pp = m.rng_state()
+        assert pos[g] == pp and np.array_equal(mt[g], mm), g
+    c = env.counters()
+    assert np.array_equal(c["episodes"], [m.episodes for m in models])
+    assert np.array_equal(c["stuck"], [m.stuck for m in models])
+    assert np.array_equal(c["stat_sums"], np.stack([m.stat_sum for m in models]))
+
+
+def bufs(env):
+    d, n = env.device, env.n
+    return {"reward": torch.zeros(n, dtype=torch.int32, device=d), "done": torch.zeros(n, dtype=torch.uint8, device=d),
+            "status": torch.zeros(n, dtype=torch.uint8, device=d), "obs": torch.zeros(n, env.obs_size, device=d),
+            "mask": torch.zeros(n, env.num_actions, dtype=torch.uint8, device=d), "player": torch.zeros(n, dtype=torch.uint8, device=d)}
+
+
+def play_agent_steps(env, models, steps, rnd, compare_every=1):
+    b = bufs(env)
+    obs, mask, player = env.observe_all(0)
+    mask_h = mask.cpu().numpy()
+    for t in range(steps):
+        acts = np.array([int(rnd.choice(list(np.flatnonzero(mask_h[g])))) if mask_h[g].any() else -1 for g in range(env.n)], np.int32)
+        a = torch.from_numpy(acts).to(env.device)
+        env.agent_step(a, b["reward"], b["done"], b["status"], b["obs"], b["mask"], b["player"], perspective=0)
+        exp = [m.agent_step(int(x)) for m, x in zip(models, acts)]
+        out = {k: v.cpu().numpy() for k, v in b.items()}
+        assert np.array_equal(out["status"], [e[0] for e in exp]), t
+        assert np.array_equal(out["reward"], [e[1] for e in exp]), t
+        assert np.array_equal(out["done"], [e[2] for e in exp]), t
+        if t % compare_every == 0 or t == steps - 1:
+            for g, m in enumerate(models):
+                assert np.array_equal(out["obs"][g], m.obs(0).astype(np.float32)), (t, g)
+                assert np.array_equal(out["mask"][g], m.mask()), (t, g)
+                assert out["player"][g] == m.g.current_player, (t, g)
+        mask_h = out["mask"]
+
+
+@pytest.mark.parametrize("players,rules", SHAPES)
+def test_mp_entries_replay_the_model(players, rules):
+    from azul_deep_reinforcement_learning_amd import MultiplayerAzul
+    env = MultiplayerAzul(256, rules=rules, players=players, device="cuda:0")
+    env.seed(4000)
+    models = models_for(env, 4000)
+    st = env.runner_init().cpu().numpy()
+    assert np.array_equal(st, [m.runner_init() for m in models])
+    pv = env.score_preview().cpu().numpy()
+    assert np.array_equal(pv, [m.potential() for m in models])
+    st = env.reset().cpu().numpy()
+    assert np.array_equal(st, [m.reset() for m in models])
+    check_records(env, models)
+    play_agent_steps(env, models, 60, random.Random(players))
+    check_records(env, models)
+    # GameRunner.step alone, then the flat self-play step (the policy plays every seat)
+    rnd = random.Random(7)
+    for t in range(10):
+        mask = env.get_valid_moves().cpu().numpy()
+        acts = np.array([int(rnd.choice(list(np.flatnonzero(mask[g])))) if mask[g].any() else -1 for g in range(env.n)], np.int32)
+        rew, done, st = env.step(torch.from_numpy(acts).to(env.device))
+        exp = [m.runner_step(int(a)) for m, a in zip(models, acts)]
+        assert np.array_equal(st.cpu().numpy(), [e[0] for e in exp]) and np.array_equal(rew.cpu().numpy(), [e[1] for e in exp])
+        assert np.array_equal(done.cpu().numpy().astype(int), [e[2] for e in exp])
+        if done.any():
+            ad = done.to(torch.uint8)
+            env.reset(active=ad)
+            for g in np.flatnonzero(done.cpu().numpy()):
+                models[g].reset()
+    check_records(env, models)
+    b = bufs(env)
+    _, mask, _ = env.observe_all()
+    mask_h = mask.cpu().numpy()
+    for t in range(30):
+        acts = np.array([int(rnd.choice(list(np.flatnonzero(mask_h[g])))) if mask_h[g].any() else -1 for g in range(env.n)], np.int32)
+        env.policy_step(torch.from_numpy(acts).to(env.device), b["reward"], b["done"], b["status"], b["obs"], b["mask"], b["player"])
+        exp = [m.policy_step(int(a)) for m, a in zip(models, acts)]
+        out = {k: v.cpu().numpy() for k, v in b.items()}
+        assert np.array_equal(out["reward"], [e[1] for e in exp]) and np.array_equal(out["done"], [e[2] for e in exp]), t
+        for g, m in enumerate(models):
+            assert np.array_equal(out["obs"][g], m.obs(m.g.current_player - 1).astype(np.float32)), (t, g)
+        mask_h = out["mask"]
+    check_records(env, models)
+    ps, mc = env.runner_counters()
+    assert np.array_equal(ps, [m.phi for m in models]) and np.array_equal(mc, [m.moves & 0xFFFF for m in models])
+
+
+def test_full_window_of_4096_three_player_games():
+    from azul_deep_reinforcement_learning_amd import MultiplayerAzul
+    env = MultiplayerAzul(4096, rules={"first_player": "Random", "tile_pool": "Lid"}, players=3, device="cuda:0")
+    env.seed(90000)
+    models = models_for(env, 90000)
+    env.runner_init()
+    env.reset()
+    for m in models:
+        m.runner_init()
+        m.reset()
+    play_agent_steps(env, models, 32, random.Random(5), compare_every=8)
+    check_records(env, models)
+
+
+def test_agent_step_equals_step_reset_observe():
+    from azul_deep_reinforcement_learning_amd import MultiplayerAzul
+    envs = [MultiplayerAzul(512, rules={"first_player": "Random", "tile_pool": "Lid"}, players=4, device="cuda:0", seed=321) for _ in range(2)]
+    for e in envs:
+        e.runner_init()
+        e.reset()
+    fused, parts = envs
+    b = bufs(fused)
+    rnd = random.Random(3)
+    mask = fused.get_valid_moves().cpu().numpy()
+    for t in range(80):
+        acts = torch.from_numpy(np.array([int(rnd.choice(list(np.flatnonzero(mask[g])))) for g in range(fused.n)], np.int32)).cuda()
+        fused.agent_step(acts, b["reward"], b["done"], b["status"], b["obs"], b["mask"], b["player"])
+        rew, done, st = parts.step(acts)
+        assert st.eq(0).all()
+        if done.any():
+            parts.reset(active=done.to(torch.uint8))
+        obs, m2, pl = parts.observe_all(0)
+        assert torch.equal(rew, b["reward"]) and torch.equal(done.to(torch.uint8), b["done"])
+        assert torch.equal(obs, b["obs"]) and torch.equal(m2, b["mask"]) and torch.equal(pl, b["player"])
+        mask = m2.cpu().numpy()
+    assert np.array_equal(fused.get_records().view(np.uint8), parts.get_records().view(np.uint8))
+
+
+def test_graph_captured_agent_steps_equal_eager_calls():
+    from azul_deep_reinforcement_learning_amd import MultiplayerAzul
+    rules = {"first_player": "Random", "tile_pool": "Lid", "displays": "2P+1"}
+    envs = [MultiplayerAzul(256, rules=rules, players=3, device="cuda:0", seed=77) for _ in range(2)]
+    outs = []
+    for k, env in enumerate(envs):
+        env.runner_init()
+        env.reset()
+        b = bufs(env)
+        _, m, _ = env.observe_all(0)
+        b["mask"].copy_(m)
+        act = torch.zeros(env.n, dtype=torch.int32, device=env.device)
+
+        def window():
+            for _ in range(8):
+                act.copy_(b["mask"].float().argmax(dim=1).to(torch.int32))          # the first legal action
+                env.agent_step(act, b["reward"], b["done"], b["status"], b["obs"], b["mask"], b["player"])
+        s = torch.cuda.Stream()
+        s.wait_stream(torch.cuda.current_stream())
+        if k == 0:
+            with torch.cuda.stream(s):
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g, stream=s):
+                    window()
+            for _ in range(4):
+                g.replay()
+        else:
+            for _ in range(4):
+                window()
+        torch.cuda.synchronize()
+        outs.append(({k2: v.clone() for k2, v in b.items()}, env.get_records().view(np.uint8).copy(), env.get_rng_range()))
+    (b0, r0, (mt0, p0)), (b1, r1, (mt1, p1)) = outs
+    for k in b0:
+        assert torch.equal(b0[k], b1[k]), k
+    assert np.array_equal(r0, r1) and np.array_equal(mt0, mt1) and np.array_equal(p0, p1)
+
+
+def test_two_player_batches_are_refused_with_the_name_of_their_entry():
+    from azul_deep_reinforcement_learning_amd import BatchedAzul, MultiplayerAzul
+    from azul_deep_reinforcement_learning_amd import _lib as L
+    env = BatchedAzul(8, device="cuda:0", seed=1)
+    one = torch.zeros(8, dtype=torch.int32, device="cuda:0")
+    u8 = torch.zeros(8, dtype=torch.uint8, device="cuda:0")
+    h, p = env._h, lambda t: C.c_void_p(t.data_ptr())
+    calls = {"azul_batch_runner_init": lambda: L.lib.azul_batch_mp_runner_init(h, None, p(u8), None),
+             "azul_batch_runner_reset": lambda: L.lib.azul_batch_mp_runner_reset(h, None, p(u8), None),
+             "azul_batch_runner_step": lambda: L.lib.azul_batch_mp_runner_step(h, p(one), None, p(one), p(u8), p(u8), None),
+             "azul_batch_agent_step": lambda: L.lib.azul_batch_mp_agent_step(h, p(one), None, p(one), p(u8), p(u8), 0, None, None, None, None),
+             "azul_batch_policy_step": lambda: L.lib.azul_batch_mp_policy_step(h, p(one), None, p(one), p(u8), p(u8), 0, None, None, None, None),
+             "azul_batch_score_preview": lambda: L.lib.azul_batch_mp_score_preview(h, p(one), None)}
+    for name, fn in calls.items():
+        assert fn() == L.ERR_INVALID
+        assert name in L.lib.azul_last_error_string().decode()
+    with pytest.raises(ValueError):
+        MultiplayerAzul(8, players=2, device="cuda:0")
+    with pytest.raises(L.AzulHipError):                    # ... and the two-player entries keep refusing wide batches
+        BatchedAzul(8, players=3, device="cuda:0", seed=1).reset()

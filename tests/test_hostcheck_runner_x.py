@@ -1,0 +1,192 @@
+"""The P-player GameRunner kernel body on CPU: azx::runner_body_x (csrc/azul_rules_x.hpp, the body of azul_x_runner_kernel) compiled UNMODIFIED
+by g++ and run under the lockstep 64-lane emulation of tests/hostcheck/simt, against the model composed from the oracle
+(tests/mp_runner_model.py, itself pinned to the reference by tests/test_mp_runner_model.py).  Every output of every call is compared: status,
+reward, done, observation, mask, player, the 256-byte records INCLUDING the runner's tail (bytes 228..231), all 624 MT19937 words and the
+index, and the episode / stuck / statistics counters.
+
+  * (2, 5) with every rule switch off pins P = 2 to the reference's GameRunner (the model equals oz_runner_step there);
+  * (3, 5) and (4, 5): the reference's Azul(players=P) under GameRunner, phi = s[0] - max_j>0 s[j] (beyond the reference for P > 2);
+  * (3, 7) and (4, 9) with each extended rule (beyond the reference, "parity unpinned");
+  * crafted states in which nobody can move give done = 2."""
+import ctypes as C
+import os
+import random
+import subprocess
+
+import numpy as np
+import pytest
+
+from oracle import oracle as oz
+from tests.mp_runner_model import MPRunner
+
+HERE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "hostcheck")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+LIB = os.path.join(HERE, "libsimt_runner_x.so")
+# tests/hostcheck/Makefile's SIMT_FLAGS, restated (-O0: the emulation's reconvergence rule relies on code addresses following source order)
+SIMT_FLAGS = ["-O0", "-g", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fno-omit-frame-pointer", "-fno-optimize-sibling-calls", "-Wall",
+              "-Wno-unused-function", "-Wno-unknown-pragmas", "-Wno-attributes", "-Wno-unused-variable", "-Wno-unused-but-set-variable"]
+XRUN = {"init": 0, "reset": 1, "step": 2, "agent_step": 3, "policy_step": 4, "preview": 5}
+PERSP_MOVER = 7
+
+
+def load():
+    src = os.path.join(HERE, "simt_runner_x.cpp")
+    csrc = os.path.join(ROOT, "azul_deep_reinforcement_learning_amd", "csrc")
+    deps = [src, os.path.join(csrc, "azul_rules_x.hpp"), os.path.join(csrc, "azul_selfplay2.hpp"), os.path.join(csrc, "azul_common.hpp"),
+            os.path.join(HERE, "simt", "simt.hpp"), os.path.join(ROOT, "include", "azul_hip.h")]
+    if not os.path.exists(LIB) or os.path.getmtime(LIB) < max(os.path.getmtime(d) for d in deps):
+        tmp = LIB + ".%d.tmp" % os.getpid()
+        subprocess.check_call([os.environ.get("CXX", "g++")] + SIMT_FLAGS + ["-I", os.path.join(HERE, "simt"), "-I", csrc, "-I",
+                                                                            os.path.join(ROOT, "include"), "-o", tmp, src])
+        os.replace(tmp, LIB)
+    L = C.CDLL(LIB)
+    L.shx_runner.restype = C.c_longlong
+    L.shx_runner.argtypes = [C.c_int] * 3 + [C.c_void_p] * 6 + [C.c_int] * 5 + [C.c_void_p] * 6 + [C.c_int] + [C.c_void_p] * 3
+    return L
+
+
+def ptr(a):
+    return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+class Emu:
+    """n games of one batch shape on the emulated kernel body, next to n models."""
+
+    def __init__(self, L, P, first, pool, ext, n, seed0):
+        self.L, self.P, self.n = L, P, n
+        self.D = 2 * P + 1 if ext & oz.EXT_DISPLAYS_2P1 else 5
+        self.NA, self.OBS = (self.D + 1) * 30, 5 * self.D + 6 + 52 * P + 1
+        self.models = [MPRunner(P, first, pool, ext, seed=seed0 + g) for g in range(n)]
+        self.state = np.zeros((n, 256), np.uint8)
+        self.state[:, 204] = P
+        self.state[:, 205] = 0 if self.D == 5 else self.D
+        self.mt = np.stack([m.rng_state()[0] for m in self.models]).astype(np.uint32)
+        self.pos = np.array([m.rng_state()[1] for m in self.models], np.uint32)
+        self.ep, self.stuck, self.ss = np.zeros(n, np.uint64), np.zeros(n, np.uint32), np.zeros((n, 10))
+        self.first = first
+        self.xpool = 2 if ext & oz.EXT_FINITE_BAG else (1 if pool == oz.POOL_LID else 0)
+        self.eb, self.sd = int(bool(ext & oz.EXT_END_BONUS)), int(bool(ext & oz.EXT_SHORT_DEAL))
+
+    def call(self, op, actions=None, persp=0):
+        n = self.n
+        out = {"reward": np.full(n, -77, np.int32), "done": np.full(n, 9, np.uint8), "status": np.full(n, 99, np.uint8),
+               "potential": np.full(n, -77, np.int32), "obs": np.full((n, self.OBS), -5, np.float32), "mask": np.full((n, self.NA), 7, np.uint8),
+               "player": np.full(n, 9, np.uint8)}
+        acts = None if actions is None else np.ascontiguousarray(actions, np.int32)
+        ops = self.L.shx_runner(n, self.P, self.D, ptr(self.state), ptr(self.mt), ptr(self.pos), ptr(self.ep), ptr(self.stuck), ptr(self.ss),
+                                self.first, self.xpool, self.eb, self.sd, XRUN[op], ptr(acts), None, ptr(out["reward"]), ptr(out["done"]),
+                                ptr(out["status"]), ptr(out["potential"]), persp, ptr(out["obs"]), ptr(out["mask"]), ptr(out["player"]))
+        assert ops > 0
+        return out
+
+    def check(self, op, out, expect, persp=0):
+        for g, m in enumerate(self.models):
+            if op in ("step", "agent_step", "policy_step"):
+                st, rew, dn = expect[g]
+                assert (out["status"][g], out["reward"][g], out["done"][g]) == (st, rew, dn), (op, g, expect[g])
+            elif op == "preview":
+                assert out["potential"][g] == m.potential(), g
+            else:
+                assert out["status"][g] == expect[g], (op, g)
+            assert np.array_equal(self.state[g], m.record()), (op, g, np.flatnonzero(self.state[g] != m.record()))
+            mt, pos = m.rng_state()
+            assert self.pos[g] == pos and np.array_equal(self.mt[g], mt), (op, g)
+            assert (self.ep[g], self.stuck[g]) == (m.episodes, m.stuck), (op, g)
+            assert np.array_equal(self.ss[g], m.stat_sum), (op, g)
+            p = (m.g.current_player - 1) if persp == PERSP_MOVER else persp
+            assert np.array_equal(out["obs"][g], m.obs(p).astype(np.float32)), (op, g)
+            assert np.array_equal(out["mask"][g], m.mask()), (op, g)
+            assert out["player"][g] == m.g.current_player, (op, g)
+
+    def run(self, op, actions=None, persp=0):
+        out = self.call(op, actions, persp)
+        if op == "init":
+            expect = [m.runner_init() for m in self.models]
+        elif op == "reset":
+            expect = [m.reset() for m in self.models]
+        elif op == "preview":
+            expect = None
+        else:
+            fn = {"step": "runner_step", "agent_step": "agent_step", "policy_step": "policy_step"}[op]
+            expect = [getattr(m, fn)(int(a)) for m, a in zip(self.models, actions)]
+        self.check(op, out, expect, persp)
+        return out
+
+
+def pick_actions(emu, rnd, illegal_rate=0.03):
+    acts = []
+    for m in emu.models:
+        legal = np.flatnonzero(m.mask())
+        if rnd.random() < illegal_rate or len(legal) == 0:
+            acts.append(rnd.choice([-1, emu.NA, int(np.flatnonzero(m.mask() == 0)[0])]))
+        else:
+            acts.append(int(rnd.choice(list(legal))))
+    return acts
+
+
+CASES = [  # (P, first, pool, ext)
+    (2, oz.FIRST_RANDOM, oz.POOL_LID, 0), (2, 1, oz.POOL_RANDOM, 0),
+    (3, oz.FIRST_RANDOM, oz.POOL_LID, 0), (3, 3, oz.POOL_RANDOM, 0), (4, oz.FIRST_RANDOM, oz.POOL_RANDOM, 0), (4, 1, oz.POOL_LID, 0),
+    (3, oz.FIRST_RANDOM, oz.POOL_LID, oz.EXT_DISPLAYS_2P1), (4, 2, oz.POOL_RANDOM, oz.EXT_DISPLAYS_2P1),
+    (3, oz.FIRST_RANDOM, oz.POOL_LID, oz.EXT_DISPLAYS_2P1 | oz.EXT_END_BONUS),
+    (4, oz.FIRST_RANDOM, oz.POOL_LID, oz.EXT_DISPLAYS_2P1 | oz.EXT_SHORT_DEAL),
+    (3, oz.FIRST_RANDOM, oz.POOL_RANDOM, oz.EXT_DISPLAYS_2P1 | oz.EXT_FINITE_BAG | oz.EXT_SHORT_DEAL),
+    (4, 4, oz.POOL_RANDOM, oz.EXT_DISPLAYS_2P1 | oz.EXT_END_BONUS | oz.EXT_FINITE_BAG | oz.EXT_SHORT_DEAL),
+]
+
+
+@pytest.mark.parametrize("P,first,pool,ext", CASES)
+def test_runner_body_matches_the_model(P, first, pool, ext):
+    L = load()
+    emu = Emu(L, P, first, pool, ext, 4, 7000 + 31 * P + ext)
+    rnd = random.Random(P * 100 + ext)
+    emu.run("init")
+    emu.run("preview")
+    emu.run("reset")
+    for t in range(90):
+        emu.run("agent_step", pick_actions(emu, rnd), persp=0)
+    for t in range(20):
+        emu.run("step", pick_actions(emu, rnd))
+        emu.run("preview")
+    emu.run("reset")
+    for t in range(60):
+        emu.run("policy_step", pick_actions(emu, rnd), persp=PERSP_MOVER)
+    assert emu.ep.sum() >= 1 or P == 2
+
+
+def _craft(m, token_only):
+    """Player 1 to move; every source empty except (token_only False) one tile of colour 2 on display 0; the first-player token in the centre:
+    the round is not over (the token counts, azul.py:182-183), yet after that tile nobody can move (hazard H3)."""
+    g = m.g
+    for d in range(5):
+        for c in range(5):
+            g.displays[d][c] = 0
+    for c in range(6):
+        g.center[c] = 0
+    g.center[5] = 1
+    if not token_only:
+        g.displays[0][2] = 1
+    g.current_player = 1
+
+
+@pytest.mark.parametrize("P", [3, 4])
+def test_nobody_can_move_gives_done_2(P):
+    L = load()
+    # agent_step: the agent takes the last tile, the next seat has no legal move -> stuck, the slot restarts with its opening replies
+    emu = Emu(L, P, oz.FIRST_RANDOM, oz.POOL_LID, 0, 2, 9100 + P)
+    emu.run("init")
+    for m in emu.models:
+        _craft(m, token_only=False)
+    emu.state[:] = np.stack([m.record() for m in emu.models])
+    a = int(np.flatnonzero(emu.models[0].mask())[0])
+    out = emu.run("agent_step", [a, a], persp=0)
+    assert list(out["done"]) == [2, 2] and list(out["reward"]) == [0, 0] and emu.stuck.sum() == 2
+    # policy_step: the mover has no legal move and sends -1 -> stuck, restarted
+    emu = Emu(L, P, 1, oz.POOL_RANDOM, 0, 2, 9200 + P)
+    emu.run("init")
+    for m in emu.models:
+        _craft(m, token_only=True)
+    emu.state[:] = np.stack([m.record() for m in emu.models])
+    assert emu.models[0].mask().sum() == 0
+    out = emu.run("policy_step", [-1, -1], persp=PERSP_MOVER)
+    assert list(out["done"]) == [2, 2] and emu.stuck.sum() == 2

@@ -1,0 +1,81 @@
+"""Agent steps/s of PolicyRollout(players=3 / 4) (PyTorch-GEMM network + azul_policy_head_n + azul_batch_mp_agent_step, HIP graph per window)
+and the launch time of azul_batch_mp_agent_step alone at 4096 games.  One JSON line per configuration.
+
+Usage: python tools/mp_rollout_bench.py [--games 4096] [--window 32] [--windows 20] [--hidden 180]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import torch  # noqa: E402
+
+from azul_deep_reinforcement_learning_amd import BatchedActorCritic, MultiplayerAzul, PolicyRollout  # noqa: E402
+
+CONFIGS = [
+    ("p3_d5", 3, {"first_player": "Random", "tile_pool": "Lid"}),
+    ("p4_d5", 4, {"first_player": "Random", "tile_pool": "Lid"}),
+    ("p3_d7", 3, {"first_player": "Random", "tile_pool": "Lid", "displays": "2P+1"}),
+    ("p4_d9", 4, {"first_player": "Random", "tile_pool": "Lid", "displays": "2P+1"}),
+]
+
+
+def rollout_rate(players, rules, args):
+    probe = MultiplayerAzul(2, rules=rules, players=players)
+    pol = BatchedActorCritic(probe.obs_size, probe.num_actions, args.hidden)
+    ro = PolicyRollout(pol, n_games=args.games, rules=rules, window=args.window, opponent="random", players=players)
+    for _ in range(3):
+        ro.run_window()
+    ro.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(args.windows):
+        ro.run_window()
+    ro.synchronize()
+    dt = time.perf_counter() - t0
+    return args.games * args.window * args.windows / dt, ro.use_graph
+
+
+def launch_ms(players, rules, args):
+    env = MultiplayerAzul(args.games, rules=rules, players=players, seed=1)
+    env.runner_init()
+    env.reset()
+    d, n = env.device, env.n
+    b = [torch.zeros(n, dtype=torch.int32, device=d), torch.zeros(n, dtype=torch.uint8, device=d), torch.zeros(n, dtype=torch.uint8, device=d),
+         torch.zeros(n, env.obs_size, device=d), torch.zeros(n, env.num_actions, dtype=torch.uint8, device=d), torch.zeros(n, dtype=torch.uint8, device=d)]
+    _, mask, _ = env.observe_all(0)
+    b[4].copy_(mask)
+    act = torch.zeros(n, dtype=torch.int32, device=d)
+    times = []
+    for i in range(60):
+        act.copy_(b[4].float().argmax(dim=1).to(torch.int32))
+        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        s.record()
+        env.agent_step(act, *b)
+        e.record()
+        e.synchronize()
+        if i >= 10:
+            times.append(s.elapsed_time(e))
+    times.sort()
+    return times[len(times) // 2]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--games", type=int, default=4096)
+    ap.add_argument("--window", type=int, default=32)
+    ap.add_argument("--windows", type=int, default=20)
+    ap.add_argument("--hidden", type=int, default=180)
+    args = ap.parse_args()
+    for name, players, rules in CONFIGS:
+        rate, graph = rollout_rate(players, rules, args)
+        ms = launch_ms(players, rules, args)
+        print(json.dumps({"config": name, "games": args.games, "window": args.window, "hidden": args.hidden, "graph": graph,
+                          "agent_steps_per_s": round(rate), "mp_agent_step_launch_ms_median": round(ms, 4)}), flush=True)
+
+
+if __name__ == "__main__":
+    main()
