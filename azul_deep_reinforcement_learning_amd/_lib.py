@@ -117,6 +117,9 @@ SIGNATURES = {
     "azul_batch_mp_agent_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     "azul_batch_mp_policy_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     "azul_batch_mp_score_preview": (_i, [_vp, _vp, _vp]),
+    "azul_batch_mp_net_step_begin": (_i, [_vp] * 11),
+    "azul_batch_mp_net_step_reply": (_i, [_vp] * 11),
+    "azul_batch_mp_net_reset_begin": (_i, [_vp] * 8),
     "azul_policy_head_n": (_i, [_vp, _vp, _u64, _u64, _vp, _i, _i, _u32, _vp, _vp, _vp, _vp]),
     "azul_game_call": (_i, [_vp, C.POINTER(AzulCall), _vp]),
     "azul_batch_selfplay": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

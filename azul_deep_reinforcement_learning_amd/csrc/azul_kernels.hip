@@ -73,6 +73,16 @@ __global__ void __launch_bounds__(64) azul_x_runner_kernel(azx::XBatchDev b, azx
     azx::runner_body_x<P, D>(b, a, blockIdx.x, mt_lds, tab_lds);
 }
 
+// The same GameRunner with an EXTERNAL opponent (azul_batch_mp_net_* entries; azx::net_body_x): one cut of the protocol per launch -- the
+// agent's move, one opponent_move() of every game that owes one, or the fresh game -- and what the opponent is handed.  A kernel of its own:
+// azul_x_runner_kernel's register budget stays as it is.
+template <u32 P, u32 D>
+__global__ void __launch_bounds__(64) azul_x_net_kernel(azx::XBatchDev b, azx::XNet a)
+{
+    __shared__ u32 mt_lds[2][624];
+    azx::net_body_x<P, D>(b, a, blockIdx.x, mt_lds);
+}
+
 #include "azul_policy.hpp"
 #include "azul_rollout2.hpp"
 #include "azul_learner.hpp"
@@ -978,6 +988,52 @@ int azul_batch_mp_score_preview(azul_batch_t *b, int32_t *potential_dev, void *s
     if (!potential_dev) return fail(AZUL_ERR_INVALID, "potential_dev is NULL");
     azx::XRun a = run_args(azx::XRUN_PREVIEW); a.potential = potential_dev;
     return launch_runner_x(b, a, __func__, "azul_batch_score_preview", stream);
+}
+
+// GameRunner with an external opponent for P seats, cut at its opponent_move() calls (azx::net_body_x): azul_batch_net_*'s protocol on wide batches
+static int mp_net(azul_batch_t *b, int op, const int32_t *actions_dev, const uint8_t *active_dev, uint8_t *pending_dev, uint8_t *replies_dev,
+                  int32_t *reward_dev, uint8_t *done_dev, uint8_t *status_dev, float *obs_opp_dev, uint8_t *mask_opp_dev, uint32_t *owing_dev,
+                  const char *who, const char *twin, void *stream)
+{
+    if (!b) return fail(AZUL_ERR_INVALID, "batch is NULL");
+    if (!b->x) return fail(AZUL_ERR_INVALID, (std::string(who) + ": a two-player batch of 128-byte records: use " + twin).c_str());
+    if (!pending_dev || (op != azx::XNET_RESET && !actions_dev)) return fail(AZUL_ERR_INVALID, (std::string(who) + ": bad arguments").c_str());
+    if (b->d.move_limit) return fail(AZUL_ERR_INVALID, (std::string(who) + ": no move limit for wide batches").c_str());
+    azx::XNet a;
+    memset(&a, 0, sizeof(a));
+    a.op = op; a.actions = actions_dev; a.active = active_dev; a.pending = pending_dev; a.replies = replies_dev; a.reward = reward_dev;
+    a.done = done_dev; a.status = status_dev; a.obs = obs_opp_dev; a.mask = mask_opp_dev; a.owing = owing_dev;
+    a.count = b->d.n;
+    if (owing_dev) HIP_TRY(hipMemsetAsync(owing_dev, 0, sizeof(uint32_t), (hipStream_t)stream));
+    const dim3 grid((a.count + 1u) / 2u), block(64);
+    const azx::XBatchDev xb = xdev(b);
+    AZ_X_DISPATCH(b, hipLaunchKernelGGL((azul_x_net_kernel<PP, DD>), grid, block, 0, (hipStream_t)stream, xb, a));
+    HIP_TRY(hipGetLastError());
+    return AZUL_SUCCESS;
+}
+
+int azul_batch_mp_net_step_begin(azul_batch_t *b, const int32_t *actions_dev, uint8_t *pending_dev, uint8_t *replies_dev, int32_t *reward_dev,
+                                 uint8_t *done_dev, uint8_t *status_dev, float *obs_opp_dev, uint8_t *mask_opp_dev, uint32_t *owing_dev, void *stream)
+{
+    BATCH_GUARD(b, stream);
+    return mp_net(b, azx::XNET_BEGIN, actions_dev, nullptr, pending_dev, replies_dev, reward_dev, done_dev, status_dev, obs_opp_dev, mask_opp_dev,
+                  owing_dev, __func__, "azul_batch_net_step_begin", stream);
+}
+
+int azul_batch_mp_net_step_reply(azul_batch_t *b, const int32_t *opp_actions_dev, uint8_t *pending_dev, uint8_t *replies_dev, int32_t *reward_dev,
+                                 uint8_t *done_dev, uint8_t *status_dev, float *obs_opp_dev, uint8_t *mask_opp_dev, uint32_t *owing_dev, void *stream)
+{
+    BATCH_GUARD(b, stream);
+    return mp_net(b, azx::XNET_REPLY, opp_actions_dev, nullptr, pending_dev, replies_dev, reward_dev, done_dev, status_dev, obs_opp_dev, mask_opp_dev,
+                  owing_dev, __func__, "azul_batch_net_step_reply", stream);
+}
+
+int azul_batch_mp_net_reset_begin(azul_batch_t *b, const uint8_t *active_dev, uint8_t *pending_dev, uint8_t *status_dev, float *obs_opp_dev,
+                                  uint8_t *mask_opp_dev, uint32_t *owing_dev, void *stream)
+{
+    BATCH_GUARD(b, stream);
+    return mp_net(b, azx::XNET_RESET, nullptr, active_dev, pending_dev, nullptr, nullptr, nullptr, status_dev, obs_opp_dev, mask_opp_dev, owing_dev,
+                  __func__, "azul_batch_net_reset_begin", stream);
 }
 
 int azul_policy_head_n(const float *logits_dev, const uint8_t *mask_dev, uint64_t seed, uint64_t counter, const uint64_t *counter_dev,

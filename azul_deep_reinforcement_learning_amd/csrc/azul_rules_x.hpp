@@ -32,6 +32,7 @@
 // RandomAgent game_runner.py:87-97, check_all_valid :113-117, get_state :56-72.
 #pragma once
 #include "azul_selfplay2.hpp"
+#include "azul_env2.hpp"      // NetStep / NET_*: the external-opponent protocol, shared with the P-seat version below
 
 namespace azx {
 using namespace az;
@@ -1365,6 +1366,177 @@ AZ_FN void runner_body_x(const XBatchDev &b, const XRun &a, u32 pair, u32 (*mt_l
     }
     if (a.obs) observe_x(g, (u32)a.persp < P ? (u32)a.persp : mex(g), a.obs + (size_t)gi * obs_size<P, D>(), l);
     if (a.player && l == 0u) a.player[gi] = (uint8_t)g.cur;
+}
+
+// ---- GameRunner for P seats with an EXTERNAL opponent (game_runner.py:27-30, 37-47, 84-85): az2::net_settle2 / net_move2 / net_reset2 of
+// azul_env2.hpp generalised to P seats, statement for statement, on the wide record.  Every seat other than the agent's is the opponent: each
+// opponent_move() -- the other seats' replies, the agent's FORCED moves (:46) and the opening moves of reset() (:84-85) -- is answered
+// outside the rule code (PolicyRollout's PyTorch GEMMs + azul_policy_head_n on the mover-perspective observation) and handed back by the next
+// launch.  The loop conditions are opponent_loop_x's, the potential is potential_x's, restarts and statistics are runner_restart_x /
+// episode_stats_x, and the runner's tail (phi, move counter: bytes 228..231) is kept as runner_body_x keeps it.  No move limit (wide batches
+// have none), no reply guard: the host bounds its reply rounds.  net_body_x is the body of azul_x_net_kernel; tests/hostcheck/simt_net_x.cpp
+// runs it, unmodified, under the lockstep emulation against tests/mp_net_model.py.
+template <u32 P, u32 D>
+AZ_FN void net_settle_x(GX<P, D> &g, RunX &s, NetStep &ns, MaskX<D> &m, const RulesX &rules, const KX<D> &K, Rng2 &r, u64 margin, Counters2 &cnt)
+{
+#pragma unroll 1
+    for (u32 pass = 0; pass < 4u; pass++) {
+        if (ns.pending == NET_RESET) {                                          // the next run_episode: nn_runner.py:20 -> game_runner.py:76-82
+            const u32 st2 = runner_restart_x(g, s, rules, r, margin, K);
+            if (!ns.st) ns.st = st2;
+            ns.pending = st2 ? (u32)NET_READY : (u32)NET_OPENING;
+            continue;
+        }
+        legal_mask_x(g, K, m);
+        if (ns.pending == NET_READY) break;
+        const u32 legal = mask_count_x<D>(m);
+        if (ns.pending == NET_REPLY) {
+            const bool keep = (g.cur != 1u || legal < 2u) && !g.over;          // game_runner.py:46
+            if (keep && legal) break;                                           // :47 -- an opponent_move() is owed
+            ns.closed = true;
+            if (keep) {                                                         // nobody can move (hazard H3)
+                cnt.stuck_add += 1u; ns.dn = 2u; ns.rew = 0;
+                if (!ns.st) ns.st = ST_STUCK;
+            } else {
+                const i32 phi = potential_x(g, rules, K);                      // :48-50 (beyond the reference for P > 2: margin over the best opponent)
+                ns.rew = phi - s.phi;                                          // :51
+                s.phi = phi;                                                   // :52
+                ns.dn = g.over ? 1u : 0u;                                      // :55
+                if (ns.dn) episode_stats_x(g, cnt, K.k.l);                     // :53-54
+            }
+            ns.pending = ns.dn ? (u32)NET_RESET : (u32)NET_READY;
+            if (!ns.dn) break;                                                  // (`m` is the mask of this state: the agent's next decision)
+        } else {                                                                // NET_OPENING
+            if (g.cur != 1u && legal) break;                                    // game_runner.py:84-85 -- an opponent_move() is owed
+            if (g.cur != 1u && !ns.st) ns.st = ST_STUCK;
+            ns.pending = NET_READY;
+            break;
+        }
+    }
+}
+
+// The agent's action of GameRunner.step (:44-45; `agent`) or one opponent_move() (:37-42), then the loop conditions; `m` out: the legal mask
+// of the state left behind.  Returns the status of the move itself: an answer that is not legal (ST_ILLEGAL_MOVE / ST_BAD_ACTION) leaves
+// the game and the debt as they are.
+template <u32 P, u32 D>
+AZ_FN u32 net_move_x(GX<P, D> &g, RunX &s, i32 av, bool agent, MaskX<D> &m, const RulesX &rules, const KX<D> &K, Rng2 &r, u64 margin,
+                     Counters2 &cnt, NetStep &ns)
+{
+    if (agent) { ns.pending = NET_READY; ns.replies = 0; ns.rew = 0; ns.dn = g.over ? 1u : 0u; ns.closed = false; ns.st = ST_OK; }
+    const u32 st = checked_step_x(g, rules, K, r, margin, av);                 // :44 / :41
+    if (st == ST_OK) {
+        s.moves += 1u;                                                          // :45 / :42
+        if (agent) ns.pending = NET_REPLY; else ns.replies += 1u;
+    } else {
+        if (!ns.st) ns.st = st;
+        if (st == ST_ILLEGAL_MOVE || st == ST_BAD_ACTION) {                     // state untouched
+            if (agent) ns.closed = true;
+            legal_mask_x(g, K, m);
+            return st;
+        }
+        const bool in_step = agent || ns.pending == NET_REPLY;                  // (runner_step_x returning a status: reward 0, done only for GAME_ENDED)
+        ns.pending = NET_READY;
+        if (in_step) {
+            ns.closed = true; ns.rew = 0;
+            ns.dn = st == ST_GAME_ENDED ? 1u : (agent ? ns.dn : 0u);
+            if (ns.dn) ns.pending = NET_RESET;
+        }
+    }
+    net_settle_x(g, s, ns, m, rules, K, r, margin, cnt);
+    return st;
+}
+
+// GameRunner.reset() with an external opponent (game_runner.py:76-85): the fresh game, then the opening loop's condition
+template <u32 P, u32 D>
+AZ_FN void net_reset_x(GX<P, D> &g, RunX &s, MaskX<D> &m, const RulesX &rules, const KX<D> &K, Rng2 &r, u64 margin, Counters2 &cnt, NetStep &ns)
+{
+    ns.pending = NET_RESET; ns.replies = 0; ns.rew = 0; ns.dn = 0; ns.closed = false; ns.st = ST_OK;
+    net_settle_x(g, s, ns, m, rules, K, r, margin, cnt);
+}
+
+enum { XNET_BEGIN = 0, XNET_REPLY, XNET_RESET };
+
+struct XNet {
+    int op;                  // XNET_*
+    const i32 *actions;      // [count] in: the agent's actions (BEGIN) or the opponent's answers (REPLY)
+    const uint8_t *active;   // [count] in, optional (RESET)
+    uint8_t *pending;        // [count] in / out: NET_READY / NET_REPLY / NET_OPENING -- does the game owe an opponent_move()?
+    uint8_t *replies;        // [count] in / out, optional: opponent moves played since the agent's action
+    i32 *reward;             // [count] out, optional: written by the launch that closes the agent step
+    uint8_t *done;           // [count] out, optional: likewise
+    uint8_t *status;         // [count] in / out, optional: the step's first status that was not ST_OK
+    float *obs;              // [count][obs_size] out, optional: get_state(perspective = mover) of the games that owe an opponent_move()
+    uint8_t *mask;           // [count][NA] out, optional: their legal mask
+    u32 *owing;              // [1] optional: += the games of this launch that still owe an opponent_move()
+    u32 count;
+};
+
+// One cut of the protocol on games 2 pair, 2 pair + 1: begin (the agent's move), reply (one opponent_move() of a game that owes one) or reset;
+// the record / tail / stream / counters written back; then, for the games that still owe an opponent_move(), what the opponent is handed.
+template <u32 P, u32 D>
+AZ_FN void net_body_x(const XBatchDev &b, const XNet &a, u32 pair, u32 (*mt_lds)[624])
+{
+    const u32 lane = wv::lane(), l = lane & 31u, half = lane >> 5;
+    const u32 gi = 2u * pair + half;
+    if (gi >= a.count) return;                                         // odd batch: the last wave serves one game
+    const bool reset = a.op == XNET_RESET, agent = a.op == XNET_BEGIN;
+    const bool act = (reset && a.active) ? (a.active[gi] != 0) : true;
+    const u32 pend = a.op == XNET_REPLY ? (u32)a.pending[gi] : (u32)NET_READY;
+    uint8_t *rec = b.state + (size_t)gi * AZUL_RECORD_BYTES_WIDE;
+    KX<D> K;
+    kx_init(K);
+    GX<P, D> g;
+    gx_load(g, rec, l);
+    prime_x(g, K);
+    RunX s;
+    runx_load(s, rec);
+    MaskX<D> m;
+    bool owes = false;
+    if (act && (reset || agent || pend != NET_READY)) {                // (a reply round leaves the games that owe nothing alone)
+        Rng2 r;
+        u32 *gmt = b.mt + (size_t)gi * 624u;
+        rng2_open(r, gmt, mt_lds[half], b.mtpos[gi], l);
+        Counters2 cnt;
+        counters2_open(cnt, b.episodes + gi, b.stuck + gi, b.stat_sum + (size_t)gi * 10, l);
+        NetStep ns;
+        u32 st = ST_OK;
+        if (reset) {
+            net_reset_x(g, s, m, b.rules, K, r, b.draw_margin, cnt, ns);
+        } else {
+            ns.pending = pend;
+            ns.replies = a.replies ? a.replies[gi] : 0u; ns.rew = 0; ns.dn = 0; ns.closed = false;
+            ns.st = a.status ? a.status[gi] : 0u;                              // the step's status is its FIRST status that was not OK
+            st = net_move_x(g, s, a.actions[gi], agent, m, b.rules, K, r, b.draw_margin, cnt, ns);
+        }
+        if (!(st == ST_ILLEGAL_MOVE || st == ST_BAD_ACTION)) {
+            gx_store(g, rec, l);
+            runx_store(s, rec, l);
+        }
+        rng2_close(r, gmt, b.mtpos + gi, l);
+        counters2_close(cnt, l);
+        if (l == 0u) {
+            a.pending[gi] = (uint8_t)ns.pending;
+            if (a.replies) a.replies[gi] = (uint8_t)(ns.replies < 255u ? ns.replies : 255u);
+            if (ns.closed && a.reward) a.reward[gi] = ns.rew;
+            if (ns.closed && a.done) a.done[gi] = (uint8_t)ns.dn;
+            if (a.status) a.status[gi] = (uint8_t)ns.st;
+        }
+        owes = ns.pending != NET_READY;
+    }
+    // what the opponent is handed: the state and legal mask (left in `m` by net_settle_x) from the mover's perspective (game_runner.py:38-39)
+    if (owes) {
+        if (a.mask) {
+            uint8_t *row = a.mask + (size_t)gi * Dim<D>::NA + l;
+#pragma unroll
+            for (u32 rr = 0; rr < 6u; rr++) {
+                if (l < (Dim<D>::Q < 32u ? Dim<D>::Q : 32u)) row[Dim<D>::Q * rr] = (uint8_t)m.bit[rr][0];
+                if (Dim<D>::NW > 1) { if (l < Dim<D>::Q - 32u) row[Dim<D>::Q * rr + 32u] = (uint8_t)m.bit[rr][Dim<D>::NW - 1]; }
+            }
+        }
+        if (a.obs) observe_x(g, mex(g), a.obs + (size_t)gi * obs_size<P, D>(), l);
+    }
+    const u64 who = __builtin_amdgcn_ballot_w64(owes && l == 0u);      // one atomic per wave
+    if (a.owing && who != 0ull && lane == (u32)__builtin_ctzll(who)) atomicAdd(a.owing, (u32)__builtin_popcountll(who));
 }
 
 } // namespace azx

@@ -2,7 +2,9 @@
 
 The reference's GameRunner (azulnet/game_runner.py:23-97) on an Azul(players=P): the agent is seat 0 ("player 1"), every other seat
 replies with its own RandomAgent draw from the game's stream.  Each method is one launch of azul_x_runner_kernel through the
-azul_batch_mp_* entries of the C ABI (include/azul_hip.h).  The shaped reward is the one departure from the reference, BEYOND THE
+azul_batch_mp_* entries of the C ABI (include/azul_hip.h).  With a network opponent (GameRunner(opponent=Agent(...)), game_runner.py:27-30)
+the net_step_begin / net_step_reply / net_reset_begin cuts (azul_x_net_kernel, azul_batch_mp_net_*) hand every opponent_move() of every
+other seat to the caller: PolicyRollout(players=P, opponent=<module>) answers them with the opponent's forward.  The shaped reward is the one departure from the reference, BEYOND THE
 REFERENCE for P > 2: phi = s[0] - max_{j>0} s[j] after count_score() on a copy of the game (game_runner.py:48-50), reward = phi - phi_stored;
 at P = 2 it is the reference's score[0] - score[1].  Plain BatchedAzul keeps refusing these calls for wide batches.
 """
@@ -66,6 +68,25 @@ class MultiplayerAzul(BatchedAzul):
         L.check(L.lib.azul_batch_mp_agent_step(self._h, _ptr(actions), _ptr(self._dev(active, torch.uint8)), _ptr(reward), _ptr(done),
                                                _ptr(status), int(perspective), _ptr(obs_next), _ptr(mask_next), _ptr(player_next),
                                                self._stream()))
+
+    # -- GameRunner(opponent=<network>) for P seats, cut at its opponent_move() calls (game_runner.py:27-30, 37-47, 84-85): the protocol of
+    # BatchedAzul.net_* on azul_batch_mp_net_*; net_state() sizes obs / mask by obs_size / num_actions.  Every seat other than seat 0 is the
+    # opponent; what it is handed is the mover-perspective observation and the legal mask, written for the games that owe a move.
+    def net_step_begin(self, actions, net, reward, done, status):
+        """The agent's move of GameRunner.step (game_runner.py:44-45) for every game, then the loop condition (:46)."""
+        L.check(L.lib.azul_batch_mp_net_step_begin(self._h, _ptr(actions), _ptr(net["pending"]), _ptr(net["replies"]), _ptr(reward), _ptr(done),
+                                                   _ptr(status), _ptr(net["obs"]), _ptr(net["mask"]), _ptr(net["owing"]), self._stream()))
+
+    def net_step_reply(self, opp_actions, net, reward, done, status):
+        """One opponent_move() (game_runner.py:37-42) with `opp_actions` for every game that owes one, then the loop condition again."""
+        L.check(L.lib.azul_batch_mp_net_step_reply(self._h, _ptr(opp_actions), _ptr(net["pending"]), _ptr(net["replies"]), _ptr(reward),
+                                                   _ptr(done), _ptr(status), _ptr(net["obs"]), _ptr(net["mask"]), _ptr(net["owing"]),
+                                                   self._stream()))
+
+    def net_reset_begin(self, net, status, active=None):
+        """GameRunner.reset() (game_runner.py:76-85) up to its first opponent_move()."""
+        L.check(L.lib.azul_batch_mp_net_reset_begin(self._h, _ptr(self._dev(active, torch.uint8)), _ptr(net["pending"]), _ptr(status),
+                                                    _ptr(net["obs"]), _ptr(net["mask"]), _ptr(net["owing"]), self._stream()))
 
     def runner_counters(self, first=0, count=None):
         """GameRunner.player_score (the stored potential) and move_counter of every game: (int16[N], uint16[N]) read from the records."""

@@ -33,6 +33,10 @@ def _p(t):
 
 
 class PolicyRollout:
+    # reply rounds per agent step / opening on the wide path before the loop gives up: a legal opponent ends a step within about two rounds
+    # of the game (at most ~45 moves each for four players on nine displays); an opponent that keeps answering illegally would spin
+    MAX_REPLY_ROUNDS = 512
+
     def __init__(self, policy, n_games=4096, parts=1, rules={"first_player": "Random", "tile_pool": "Lid"}, seed_base=0,
                  device=None, window=32, use_graph=True, fused_head=True, sample_seed=0x5EED, opponent=None, fused_mlp=True, persistent=False,
                  action_selection="Distribution", kweights=None, game_id_base=None, ring=1, opponent_selection="Distribution",
@@ -60,13 +64,22 @@ class PolicyRollout:
         `players` = 3 / 4, or extended-rule keys in `rules` (the wide records): the games are MultiplayerAzul parts (GameRunner for P seats,
         azul_batch_mp_*; the shaped reward is the margin over the best opponent, beyond the reference for P > 2), the network runs as
         PyTorch GEMMs + azul_policy_head_n on env.num_actions logits, trajectory buffers are env.obs_size / env.num_actions wide;
-        opponent=None | "random" with both action_selection modes, HIP graphs and parts as on the two-player PyTorch path."""
+        opponent=None | "random" with both action_selection modes, HIP graphs and parts as on the two-player PyTorch path; opponent=<module>
+        when its shape matches the batch (ActorCritic(env.obs_size, env.num_actions), any hidden size: anything else raises ValueError):
+        every other seat's opponent_move() goes through MultiplayerAzul.net_* (azul_batch_mp_net_*), answered by the module's actor half as
+        PyTorch GEMMs + azul_policy_head_n with the two-player path's Philox keys; no HIP graph, and at most MAX_REPLY_ROUNDS reply rounds
+        per step or opening -- an opponent that keeps answering with moves that are not legal raises RuntimeError."""
         assert n_games % parts == 0
         self.players = int(players)
         self.wide = self.players != 2 or parse_ext_rules(rules, self.players) != 0
         if self.wide and opponent is not None and not isinstance(opponent, str):
-            raise ValueError("a network opponent is compiled for the two-player game (ActorCritic(136, 180, 180)): batches of %d players / "
-                             "extended rules support opponent=None or \"random\"" % self.players)
+            D = 2 * self.players + 1 if parse_ext_rules(rules, self.players) & L.RULE_DISPLAYS_2P1 else 5
+            n_obs, n_act = 5 * D + 6 + 52 * self.players + 1, (D + 1) * 30       # azul_batch_obs_size / azul_batch_num_actions
+            shape = (opponent.critic_linear1.in_features, opponent.actor_linear1.in_features, opponent.actor_linear2.out_features)
+            if shape != (n_obs, n_obs, n_act):
+                raise ValueError("a network opponent for batches of %d players / extended rules must take the batch's observation and give its "
+                                 "actions: ActorCritic(%d, %d, any hidden size), got inputs %d / %d and %d actions"
+                                 % (self.players, n_obs, n_act, shape[0], shape[1], shape[2]))
         if self.wide and move_limit:
             raise ValueError("no move limit for batches of three / four players or extended rules")
         self.opp_policy = None
@@ -107,7 +120,7 @@ class PolicyRollout:
             self.w2c_t = self.w2c.view(-1, 1)
         self.refresh_weights()
         if self.opponent == "net":
-            assert self.fused_mlp, "the network opponent runs on the library's forward (ActorCritic(136, 180, hidden 180))"
+            assert self.fused_mlp or self.wide, "the network opponent runs on the library's forward (ActorCritic(136, 180, hidden 180))"
             self.opp_policy = self.opp_policy.to(self.device).eval()
             self.set_opponent(self.opp_policy)
         d, h, T = self.device, self.h, window
@@ -148,6 +161,9 @@ class PolicyRollout:
             if self.opponent == "net":
                 w["net"] = env.net_state()
                 w["scratch_f"] = torch.zeros(3, h, device=d)       # the opponent forward's value / entropy (not recorded) and untraced log-prob
+                if self.wide:                                      # the opponent's actor half as PyTorch GEMMs (its own hidden size)
+                    w["opp_hidden"] = torch.zeros(h, self.ob1.numel() // 2, device=d)
+                    w["opp_logits"] = torch.zeros(h, env.num_actions, device=d)
             self.traj.append(t)
             self.work.append(w)
             with torch.cuda.stream(self.streams[p]):
@@ -199,6 +215,21 @@ class PolicyRollout:
         w = self.work[p]
         net, sc = w["net"], w["scratch_f"]
         key = self.opponent_seed if self.opponent_seed == L.POLICY_ARGMAX else (self.opponent_seed + j) & 0xFFFFFFFFFFFFFFFF
+        if self.wide:
+            # forward_actor (model.py:28-41) on the mover-perspective observations net_step_* left; the head samples at the same counter as
+            # the two-player path (counter_dev - 1: the value the agent's draw of this step used; before the first step, 2^64 - 1)
+            Ho = w["opp_hidden"].shape[1]
+            with torch.no_grad():
+                torch.addmm(self.ob1[Ho:], net["obs"], self.ow1t[:, Ho:], out=w["opp_hidden"])
+                w["opp_hidden"].relu_()
+                torch.addmm(self.ob2a, w["opp_hidden"], self.ow2a_t, out=w["opp_logits"])
+            L.check(L.lib.azul_policy_head_n(_p(w["opp_logits"]), _p(net["mask"]), key, 0xFFFFFFFFFFFFFFFF, _p(w["counter"]), self.h, self.num_actions,
+                                             self.game_id_base + p * self.h, _p(net["action"]), _p(logp_out), _p(sc[1]),
+                                             C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+            # a forward that is not finite has no distribution to sample (np.random.choice raises on NaN probabilities, agent.py:76):
+            # its answer is -1, which the env refuses -- the game keeps owing the move and the bounded reply loop reports it
+            net["action"].masked_fill_(~torch.isfinite(w["opp_logits"].sum(dim=1)), -1)
+            return
         L.check(L.lib.azul_policy_forward(_p(net["obs"]), _p(net["mask"]), _p(self.ow1t), _p(self.ob1), _p(self.ow2c), _p(self.ob2c), _p(self.ow2a_t),
                                           _p(self.ob2a), L.OBS_SIZE, self.H, L.NUM_ACTIONS, key, 0xFFFFFFFFFFFFFFFF, _p(w["counter"]), 0, self.h,
                                           self.game_id_base + p * self.h, _p(sc[0]), _p(net["action"]), _p(logp_out), _p(sc[1]), None,
@@ -211,9 +242,20 @@ class PolicyRollout:
         env.net_reset_begin(w["net"], w["status"])
         j = 0
         while int(w["net"]["owing"].item()) > 0:
+            if self.wide and j >= self.MAX_REPLY_ROUNDS:
+                self._reply_loop_failed(p, j, "the opening of reset()")
             self._opp_forward(p, j, w["scratch_f"][2])
             env.net_step_reply(w["net"]["action"], w["net"], None, None, w["status"])
             j += 1
+
+    def _reply_loop_failed(self, p, rounds, where):
+        net = self.work[p]["net"]
+        owing = torch.nonzero(net["pending"]).flatten().cpu().tolist()
+        st = self.work[p]["status"].cpu()
+        ids = [self.game_id_base + p * self.h + i for i in owing]
+        raise RuntimeError("network opponent: games %s (global ids) still owe an opponent_move() after %d reply rounds of %s (round %d); "
+                           "statuses %s -- the opponent keeps answering with moves that are not legal (a forward that is not finite answers -1)"
+                           % (ids[:16], rounds, where, rounds, [int(st[i]) for i in owing[:16]]))
 
     def refresh_weights(self):
         """(Re)build the fused first-layer weights from the policy's parameters -- call after every optimiser step.  The
@@ -287,6 +329,8 @@ class PolicyRollout:
             env.net_step_begin(tr["action"][t], net, tr["reward"][t], tr["done"][t], w["status"])
             j = 0
             while int(net["owing"].item()) > 0:
+                if self.wide and j >= self.MAX_REPLY_ROUNDS:
+                    self._reply_loop_failed(p, j, "agent step %d of the window" % t)
                 self._opp_forward(p, j, tr["opp_logp"][t][j] if j < self.opp_slots else w["scratch_f"][2])
                 if j < self.opp_slots:
                     tr["opp_action"][t][j].copy_(net["action"])

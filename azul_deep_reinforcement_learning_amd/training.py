@@ -47,7 +47,8 @@ class BatchedTrainer:
         episode that ended there, the return chain starts at the cut).
         players = 3 / 4 (or extended-rule keys in `rules`): PolicyRollout(players=...) on MultiplayerAzul parts -- the policy is
         BatchedActorCritic(env.obs_size, env.num_actions, hidden), the rollout runs its PyTorch-GEMM path and the learner its PyTorch
-        path (update_from_windows); checkpoints carry the wide records (runner counters included) and the RNG streams as usual."""
+        path (update_from_windows); checkpoints carry the wide records (runner counters included) and the RNG streams as usual.  A module
+        opponent or "self" works there too (PolicyRollout's wide network-opponent path; the opponent's weights travel in the checkpoint)."""
         from .batch import parse_ext_rules
         wide = int(players) != 2 or parse_ext_rules(rules, int(players)) != 0
         dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)

@@ -417,6 +417,19 @@ int azul_batch_net_step_reply(azul_batch_t *b, const int32_t *opp_actions_dev, u
                               uint8_t *done_dev, uint8_t *status_dev, float *obs_opp_dev, uint8_t *mask_opp_dev, uint32_t *owing_dev, void *stream);
 int azul_batch_net_reset_begin(azul_batch_t *b, const uint8_t *active_dev, uint8_t *pending_dev, uint8_t *status_dev, float *obs_opp_dev,
                                uint8_t *mask_opp_dev, uint32_t *owing_dev, void *stream);
+/* The same protocol for batches of three / four players and extended-rule batches (the wide records; azul_batch_net_* refuse them, these
+ * refuse two-player batches): every seat other than the agent's (seat 0) is the opponent.  obs_opp_dev is [N][azul_batch_obs_size],
+ * mask_opp_dev [N][azul_batch_num_actions]; both are written only for the games that still owe an opponent_move(), from the mover's
+ * perspective.  Loop conditions, restarts and statistics are azul_batch_mp_agent_step's, the reward its potential (phi = s[0] - max_{j>0}
+ * s[j], beyond the reference for P > 2); the runner counters (record bytes 228..231) are kept. */
+int azul_batch_mp_net_step_begin(azul_batch_t *b, const int32_t *actions_dev, uint8_t *pending_dev, uint8_t *replies_dev, int32_t *reward_dev,
+                                 uint8_t *done_dev, uint8_t *status_dev, float *obs_opp_dev, uint8_t *mask_opp_dev, uint32_t *owing_dev,
+                                 void *stream);
+int azul_batch_mp_net_step_reply(azul_batch_t *b, const int32_t *opp_actions_dev, uint8_t *pending_dev, uint8_t *replies_dev,
+                                 int32_t *reward_dev, uint8_t *done_dev, uint8_t *status_dev, float *obs_opp_dev, uint8_t *mask_opp_dev,
+                                 uint32_t *owing_dev, void *stream);
+int azul_batch_mp_net_reset_begin(azul_batch_t *b, const uint8_t *active_dev, uint8_t *pending_dev, uint8_t *status_dev, float *obs_opp_dev,
+                                  uint8_t *mask_opp_dev, uint32_t *owing_dev, void *stream);
 /* The A2C update's gradients (Agent.update, agent.py:39-58) for n_samples recorded (observation, mask, action, q-value) samples:
  * forward and backward of  L = mean_i( -logp_i[a_i] * adv_i + 0.5 * adv_i^2 + 0.1 * (-mean_{j legal} logp_i[j]) ),  adv = q - V
  * (advantage not detached, like the reference), on the f32 matrix cores.  `inv_n_total` = 1 / (samples of the whole batch over

@@ -1,9 +1,13 @@
 """Agent steps/s of PolicyRollout(players=3 / 4) (PyTorch-GEMM network + azul_policy_head_n + azul_batch_mp_agent_step, HIP graph per window)
-and the launch time of azul_batch_mp_agent_step alone at 4096 games.  One JSON line per configuration.
+and the launch time of azul_batch_mp_agent_step alone at 4096 games.  One JSON line per configuration and opponent.
 
-Usage: python tools/mp_rollout_bench.py [--games 4096] [--window 32] [--windows 20] [--hidden 180]
+--opponent self: the opponent is a network of the policy's shape (a frozen past self): azul_batch_mp_net_* cuts, one opponent forward and
+one host synchronisation per reply round, no HIP graph.  The line then also reports the reply rounds a step takes (max over the batch).
+
+Usage: python tools/mp_rollout_bench.py [--games 4096] [--window 32] [--windows 20] [--hidden 180] [--opponent random self] [--configs p3_d5 ...]
 """
 import argparse
+import copy
 import json
 import os
 import sys
@@ -24,19 +28,27 @@ CONFIGS = [
 ]
 
 
-def rollout_rate(players, rules, args):
+def rollout_rate(players, rules, args, opponent):
     probe = MultiplayerAzul(2, rules=rules, players=players)
     pol = BatchedActorCritic(probe.obs_size, probe.num_actions, args.hidden)
-    ro = PolicyRollout(pol, n_games=args.games, rules=rules, window=args.window, opponent="random", players=players)
+    opp = copy.deepcopy(pol) if opponent == "self" else "random"
+    ro = PolicyRollout(pol, n_games=args.games, rules=rules, window=args.window, opponent=opp, players=players)
     for _ in range(3):
         ro.run_window()
     ro.synchronize()
+    rounds = []
     t0 = time.perf_counter()
     for _ in range(args.windows):
-        ro.run_window()
+        tr = ro.run_window()
+        if opponent == "self":
+            rounds.append(tr[0]["opp_replies"].max(dim=1).values.float())     # (device tensors: read after the timed region)
     ro.synchronize()
     dt = time.perf_counter() - t0
-    return args.games * args.window * args.windows / dt, ro.use_graph
+    extra = {}
+    if rounds:
+        r = torch.cat(rounds)
+        extra = {"reply_rounds_per_step_mean": round(float(r.mean()), 3), "reply_rounds_per_step_max": int(r.max())}
+    return args.games * args.window * args.windows / dt, ro.use_graph, extra
 
 
 def launch_ms(players, rules, args):
@@ -69,12 +81,18 @@ def main():
     ap.add_argument("--window", type=int, default=32)
     ap.add_argument("--windows", type=int, default=20)
     ap.add_argument("--hidden", type=int, default=180)
+    ap.add_argument("--opponent", nargs="+", choices=("random", "self"), default=["random"])
+    ap.add_argument("--configs", nargs="+", choices=[c[0] for c in CONFIGS], default=[c[0] for c in CONFIGS])
     args = ap.parse_args()
     for name, players, rules in CONFIGS:
-        rate, graph = rollout_rate(players, rules, args)
+        if name not in args.configs:
+            continue
         ms = launch_ms(players, rules, args)
-        print(json.dumps({"config": name, "games": args.games, "window": args.window, "hidden": args.hidden, "graph": graph,
-                          "agent_steps_per_s": round(rate), "mp_agent_step_launch_ms_median": round(ms, 4)}), flush=True)
+        for opponent in args.opponent:
+            rate, graph, extra = rollout_rate(players, rules, args, opponent)
+            print(json.dumps({"config": name, "opponent": opponent, "games": args.games, "window": args.window, "hidden": args.hidden,
+                              "graph": graph, "agent_steps_per_s": round(rate), "mp_agent_step_launch_ms_median": round(ms, 4), **extra}),
+                  flush=True)
 
 
 if __name__ == "__main__":
