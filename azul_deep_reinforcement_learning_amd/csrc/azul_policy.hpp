@@ -120,22 +120,30 @@ __device__ __forceinline__ void policy_head_rows(const float (&x)[NPL], const fl
     const float target = u * S;
     float cum = incl - mine;
     u32 cross = 0;                                       // bit j: target < cum_j (sampling) / x_j == m (argmax)
+    u32 posbits = okbits;                                // bit j: legal AND of positive f32 weight (argmax: a maximum always crosses)
     if (argmax) {                                        // (wave-uniform)
 #pragma unroll
         for (int j = 0; j < NPL; j++) cross |= (x[j] == m ? 1u : 0u) << j;
     } else {
+        posbits = 0;
 #pragma unroll
         for (int j = 0; j < NPL; j++) {
             cum += e[j];
             cross |= (__builtin_bit_cast(u32, target - cum) >> 31) << j;      // the sign of target - cum_j (no NaNs: finite logits)
+            posbits |= (e[j] > 0.f ? 1u : 0u) << j;                           // (illegal actions have e_j = 0)
         }
     }
-    const u32 pickmask = cross & okbits;
+    // Only actions of positive f32 weight can be drawn (np.random.choice on the f32 softmax never returns a probability-0 action): the
+    // row maximum has weight 1, so a row with a legal action has one.  A zero-weight action cannot cross first inside a lane (its cum_j
+    // equals the one before), but at a lane's first position or in the fallback below it could.
+    const u32 pickmask = cross & posbits;
     const int pick = pickmask ? (int)__builtin_ctz(pickmask) : -1;
-    const int lastok = okbits ? 31 - (int)__builtin_clz(okbits) : 0;
-    const u64 hit = __ballot(pickmask != 0u), any = __ballot(okbits != 0u);
+    const int lastok = posbits ? 31 - (int)__builtin_clz(posbits) : 0;
+    const u64 hit = __ballot(pickmask != 0u), any = __ballot(posbits != 0u);
     const u32 hit16 = (u32)(hit >> (16u * grp)) & 0xffffu, any16 = (u32)(any >> (16u * grp)) & 0xffffu;
-    // fp32 round-off can push the target past the last cumulative sum: then the last legal action is taken
+    // fp32 round-off can push the target past the last cumulative sum (u S and the cum_j are the same weights added in different orders):
+    // then the last legal action of positive weight is taken -- the last one of the legal actions would be a draw of probability 0 when
+    // its logit lies ~104 or more below the row maximum
     const u32 lane_sel = hit16 ? (u32)__builtin_ctz(hit16) : (any16 ? 31u - (u32)__builtin_clz(any16) : 0u);
     const int jmine = hit16 ? pick : lastok;
     const int src = (int)((16u * grp + lane_sel) << 2);

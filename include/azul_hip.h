@@ -317,7 +317,10 @@ int azul_batch_observe_all(azul_batch_t *b, int perspective, float *obs_dev, uin
  * (agent.py:64-72), the log-probability of that action and the entropy term -mean(log p over legal actions)
  * (nn_runner.py:32-40).  fp32; randomness = Philox4x32-10(seed, counter [+ *counter_dev], game): keep the step counter in
  * device memory (counter_dev) when the call is replayed from a HIP graph.  `game` is the GLOBAL id game_id_base + row, so a game
- * draws the same numbers however the batch is sharded over GPUs or split into parts.  Rows without a legal action give -1. */
+ * draws the same numbers however the batch is sharded over GPUs or split into parts.  Rows without a legal action give -1.  The draw is
+ * np.random.choice's inverse CDF on the f32 softmax: u = (Philox word 0 >> 8) * 2^-24 with counter words (counter lo, counter hi, game,
+ * 0x415A554C) and key (seed lo, seed hi); only legal actions of positive f32 weight are ever drawn (when round-off puts u * sum past the
+ * last cumulative sum, the last such action). */
 int azul_policy_head(const float *logits_dev, const uint8_t *mask_dev, uint64_t seed, uint64_t counter, const uint64_t *counter_dev,
                      int n_games, uint32_t game_id_base, int32_t *action_dev, float *logp_dev, float *entropy_dev, void *stream);
 /* the same head for rows of num_actions = 180 / 240 / 300 logits and mask bytes (azul_batch_num_actions of any batch): the same Philox

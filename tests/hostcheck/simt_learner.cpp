@@ -1,7 +1,8 @@
 // simt_learner.cpp -- TEST-ONLY: the A2C gradient kernel (csrc/azul_learner.hpp: azul_a2c_grad_kernel -- forward + backward of the
-// reference's loss on the f32 matrix cores, weight-gradient tiles in registers) and the ActorCritic forward + head kernel
-// (csrc/azul_policy.hpp: azul_policy_forward_kernel), UNMODIFIED, as workgroups of emulated wavefronts (simt/simt.hpp) -- a CPU check of
-// their arithmetic against torch autograd and, under ASan / UBSan, of every LDS and global index they form.
+// reference's loss on the f32 matrix cores, weight-gradient tiles in registers), the ActorCritic forward + head kernel
+// (csrc/azul_policy.hpp: azul_policy_forward_kernel) and the heads alone (azul_policy_head_kernel, azul_policy_head_n_kernel), UNMODIFIED,
+// as workgroups of emulated wavefronts (simt/simt.hpp) -- a CPU check of their arithmetic against torch autograd and the host reference of
+// the draws (tests/policy_draw_ref.py) and, under ASan / UBSan, of every LDS and global index they form.
 #define __HIPCC__ 1
 #include "azul_hip.h"
 #include "azul_common.hpp"
@@ -20,6 +21,15 @@ static void fwd_lane(void *arg)
 {
     FwdJob *j = (FwdJob *)arg;
     azul_policy_forward_kernel(j->obs, j->mask, j->W, j->seed, j->counter, nullptr, 0, j->n, j->value, j->action, j->logp, j->entropy, j->logits, j->id_base);
+}
+
+// azul_policy_head_n_kernel<NA, NPL> (the head for 180 / 240 / 300 actions), as azul_policy_head_n launches it
+struct HeadNJob { const float *logits; const uint8_t *mask; u64 seed, counter; u32 n; i32 *action; float *logp, *ent; u32 id_base; };
+template <u32 NA, int NPL>
+static void head_n_lane(void *arg)
+{
+    HeadNJob *j = (HeadNJob *)arg;
+    azul_policy_head_n_kernel<NA, NPL>(j->logits, j->mask, j->seed, j->counter, nullptr, j->n, j->action, j->logp, j->ent, j->id_base);
 }
 
 extern "C" {
@@ -154,6 +164,19 @@ long long sl_head(int n, const float *logits, const uint8_t *mask, unsigned long
     simt::g_grid_dim = {blocks, 1, 1};
     long long ops = 1;
     for (unsigned blk = 0; blk < blocks; blk++) { simt::g_block_idx = {blk, 0, 0}; ops += (long long)simt::run_workgroup(head_lane, &j, 1); }
+    return ops;
+}
+
+long long sl_head_n(int n, int na, const float *logits, const uint8_t *mask, unsigned long long seed, unsigned long long counter, unsigned id_base,
+                    i32 *action, float *logp, float *entropy)
+{
+    void (*lane)(void *) = na == 180 ? head_n_lane<180, 12> : na == 240 ? head_n_lane<240, 15> : na == 300 ? head_n_lane<300, 19> : nullptr;
+    if (!lane || n <= 0) return -1;
+    HeadNJob j = {logits, mask, seed, counter, (u32)n, action, logp, entropy, id_base};
+    const unsigned blocks = ((unsigned)n + 3u) / 4u;
+    simt::g_grid_dim = {blocks, 1, 1};
+    long long ops = 1;
+    for (unsigned blk = 0; blk < blocks; blk++) { simt::g_block_idx = {blk, 0, 0}; ops += (long long)simt::run_workgroup(lane, &j, 1); }
     return ops;
 }
 
