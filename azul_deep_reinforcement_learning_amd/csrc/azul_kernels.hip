@@ -87,6 +87,15 @@ __global__ void __launch_bounds__(64) azul_x_net_kernel(azx::XBatchDev b, azx::X
 #include "azul_rollout2.hpp"
 #include "azul_learner.hpp"
 
+// The persistent policy rollout for wide batches (azul_batch_mp_policy_rollout; x_policy_rollout_body in azul_rollout2.hpp): 16 games per
+// workgroup of eight waves for a whole window, the workgroup's LDS declared here.
+template <u32 P, u32 D, int OPP>
+__global__ void __launch_bounds__(64 * PR2_WAVES) azul_x_policy_rollout_kernel(azx::XBatchDev b, PolicyWeights W, RolloutArgs a, u32 id_base)
+{
+    __shared__ PXShared<P, D> S;
+    x_policy_rollout_body<P, D, OPP>(b, W, a, id_base, S);
+}
+
 // ------------------------------------------------------------------------------------------------
 // host side: C ABI
 // ------------------------------------------------------------------------------------------------
@@ -799,6 +808,42 @@ int azul_batch_policy_rollout_vs(azul_batch_t *b, int n_steps, const azul_net_we
     if (rc == AZUL_SUCCESS && out->returns && n_steps > 32)
         return azul_discounted_returns(out->reward, out->done, out->returns, nullptr, gamma, n_steps, (int)b->d.n, stream);
     return rc;
+}
+
+/* GameRunner / flat self-play of wide batches inside one launch per window (azul_x_policy_rollout_kernel) */
+int azul_batch_mp_policy_rollout(azul_batch_t *b, int n_steps, int opponent_random, const azul_net_weights_t *w, int num_inputs, int hidden_size,
+                                 int num_actions, uint64_t seed, uint64_t counter, uint64_t *counter_dev, const azul_rollout_buffers_t *out, float gamma,
+                                 void *stream)
+{
+    BATCH_GUARD(b, stream);
+    if (!b || n_steps < 0 || !w || !out) return fail(AZUL_ERR_INVALID, "azul_batch_mp_policy_rollout: bad arguments");
+    if (!b->x) return fail(AZUL_ERR_INVALID, "azul_batch_mp_policy_rollout: a two-player batch of 128-byte records: use azul_batch_policy_rollout");
+    if (b->d.move_limit) return fail(AZUL_ERR_INVALID, "azul_batch_mp_policy_rollout: no move limit for wide batches");
+    if (hidden_size != PF_HID) return fail(AZUL_ERR_INVALID, "azul_batch_mp_policy_rollout: only hidden size 180 is compiled in");
+    if (num_inputs != azul_batch_obs_size(b) || num_actions != azul_batch_num_actions(b))
+        return fail(AZUL_ERR_INVALID, "azul_batch_mp_policy_rollout: num_inputs / num_actions must be the batch's azul_batch_obs_size / azul_batch_num_actions");
+    if (!w->w1t || !w->b1 || !w->w2c || !w->b2c || !w->w2a_t || !w->b2a || !out->obs || !out->mask || !out->player || !out->action || !out->reward ||
+        !out->done || !out->value || !out->logp || !out->entropy)
+        return fail(AZUL_ERR_INVALID, "azul_batch_mp_policy_rollout: NULL pointer");
+    if (((uintptr_t)out->obs & 3u) != 0 || ((uintptr_t)out->mask & 3u) != 0)
+        return fail(AZUL_ERR_INVALID, "azul_batch_mp_policy_rollout: obs and mask must be 4-byte aligned");
+    if (n_steps == 0) return AZUL_SUCCESS;
+    PolicyWeights W = {w->w1t, w->b1, w->w2c, w->b2c, w->w2a_t, w->b2a};
+    RolloutArgs a;
+    memset(&a, 0, sizeof(a));
+    a.n_steps = n_steps; a.obs = out->obs; a.mask = out->mask; a.player = out->player; a.action = out->action; a.reward = out->reward;
+    a.done = out->done; a.value = out->value; a.logp = out->logp; a.entropy = out->entropy; a.status = out->status; a.returns = nullptr;
+    a.gamma = gamma; a.seed = (u64)seed; a.counter = (u64)counter; a.counter_dev = (u64 *)counter_dev;
+    const dim3 grid((b->d.n + PF_GAMES - 1) / PF_GAMES), block(64 * PR2_WAVES);
+    const hipStream_t st = (hipStream_t)stream;
+    const azx::XBatchDev xb = xdev(b);
+    const u32 id_base = b->d.id_base;
+    if (opponent_random) AZ_X_DISPATCH(b, hipLaunchKernelGGL((azul_x_policy_rollout_kernel<PP, DD, 1>), grid, block, 0, st, xb, W, a, id_base));
+    else AZ_X_DISPATCH(b, hipLaunchKernelGGL((azul_x_policy_rollout_kernel<PP, DD, 0>), grid, block, 0, st, xb, W, a, id_base));
+    HIP_TRY(hipGetLastError());
+    if (out->returns)                                    // the window's discounted returns: the per-move path's own scan
+        return azul_discounted_returns(out->reward, out->done, out->returns, nullptr, gamma, n_steps, (int)b->d.n, stream);
+    return AZUL_SUCCESS;
 }
 
 int azul_a2c_gradients(const float *obs_dev, const uint8_t *mask_dev, const int32_t *action_dev, const float *qvals_dev, int n_samples,

@@ -18,6 +18,7 @@
 #pragma once
 
 #include "azul_env2.hpp"
+#include "azul_rules_x.hpp"     // the wide-record rules of x_policy_rollout_body below
 
 constexpr u32 PR2_WAVES = 8;
 constexpr u32 PR2_AHEAD = 6;       // k-steps of layer-1 weights in flight (3..6 measured alike, 8 and 12 slower: profiles/round3_policy_rollout_phases.txt)
@@ -561,4 +562,279 @@ __global__ void __launch_bounds__(64 * PR2_WAVES) azul_policy_rollout2_kernel(Ba
 #undef PR2_LOAD1Q
 #undef PR2_LOAD2
 #undef PR2_LOADO
+}
+
+
+// ---- the persistent policy rollout for WIDE batches (3 / 4 players, extended rules; row N4): x_policy_rollout_body ----------------------
+// The same window structure as azul_policy_rollout2_kernel -- eight waves own 16 games for a whole window, wave w plays games 2w and 2w + 1
+// in its 32-lane halves, the same waves run the network on the f32 matrix cores between the env phases -- on azul_rules_x.hpp's P-seat
+// GameRunner.  Per move: env phase -> layer 1 -> layer 2 -> head (+ critic, trajectory stores) -> env phase.
+//   env       OPP 0: azx::policy_step_x (the policy moves for every seat, observation from the mover); OPP 1: azx::agent_step_x (GameRunner with
+//             RandomAgent seats, observation from seat 0).  The game is loaded from / stored to its 256-byte record in LDS around each env
+//             phase exactly as runner_body_x does around each launch (stored only when the step touched it), so nothing of the game is live
+//             across the matrix phases; the MT19937 stream (LDS) and the counters stay open for the window.
+//   matrix    hidden = relu(obs @ w1t + b1) over 23 column tiles of 16 (360 columns), K = obs_size zero-padded in LDS to a multiple of 32;
+//             logits = hidden[:, 180:] @ w2a_t + b2a over ceil(NA / 16) tiles, K = 180.  Wave w owns tiles w, w + 8, w + 16; every tile is one
+//             k-ordered v_mfma_f32_16x16x4_f32 chain, weights read k-major from L2 one chunk of k-steps ahead.
+//   head      policy_head_rows<NPL>, the device code of azul_policy_head_n_kernel, on the LDS logits with the same Philox key: seed,
+//             counter + t, id_base + the game's index.  Waves 0..3, four games each; wave 7 sums the critic, waves 4..6 copy slot t out.
+// What is exact: the env and the head are the per-move path's device code, so for the same logits the trajectories are the same bits; the
+// matrix sums run in a different order than the PyTorch GEMMs of the per-move path, so they agree to f32 rounding (bit for bit when every
+// product and partial sum is exact).
+template <u32 P, u32 D>
+struct PXShape {
+    static constexpr u32 IN = azx::obs_size<P, D>();
+    static constexpr u32 KPAD = (IN + 31u) / 32u * 32u;            // layer 1's K: whole chunks of eight k-steps, zeros past IN
+    static constexpr u32 OBS_STRIDE = KPAD + 4u;                   // 4 (mod 32), like PF_OBS_STRIDE
+    static constexpr u32 NA = azx::Dim<D>::NA;
+    static constexpr u32 NPL = (NA + 15u) / 16u;                   // the head's actions per lane (azul_policy_head_n_kernel<NA, NPL>)
+    static constexpr u32 LOG_STRIDE = NA + (36u - NA % 32u) % 32u; // 4 (mod 32)
+    static constexpr u32 T1 = (PF_H2 + 15) / 16;                   // 23 column tiles of layer 1
+    static constexpr u32 T2 = (NA + 15u) / 16u;                    // 12 / 15 / 19 of layer 2
+    static constexpr u32 NT1 = (T1 + PR2_WAVES - 1u) / PR2_WAVES, NT2 = (T2 + PR2_WAVES - 1u) / PR2_WAVES;
+};
+
+template <u32 P, u32 D>
+struct PXShared {                                                  // the workgroup's LDS (azul_x_policy_rollout_kernel declares it)
+    float obs[PF_GAMES * PXShape<P, D>::OBS_STRIDE];
+    float hid[PF_GAMES * PF_HID_STRIDE];
+    float lg[PF_GAMES * PXShape<P, D>::LOG_STRIDE];
+    float w2c[PF_HID], b1[PF_H2], b2a[PXShape<P, D>::NA];
+    u32 mt[PF_GAMES][624];
+    u32 rec[PF_GAMES][AZUL_RECORD_BYTES_WIDE / 4];
+    double2 tab[azx::Dim<D>::TROWS * T_STRIDE];
+    u32 mask[PF_GAMES][PXShape<P, D>::NA / 4];                     // the legal masks as bytes (NA is a multiple of 4)
+    i32 act[PF_GAMES];
+};
+
+// NT column tiles of one 16-row tile, K = 4 nsteps (nsteps a multiple of CH): acc[i] += A[16 x K] B_i[K x 16].  ap: LDS, row c, k = q;
+// bp[i]: global, k-row 0, this lane's column of tile i; k-rows >= krows read as zeros.  One chunk of CH k-steps is requested ahead.
+template <int NT, int CH>
+AZ_FN void px_chain(const float *ap, const float *const (&bp)[NT], u32 bstride, u32 nsteps, u32 krows, u32 q, pf_f32x4 (&acc)[NT])
+{
+    float bb[CH][NT], av[CH], nb[CH][NT], na[CH];
+    auto load = [&](u32 s0, float (&bd)[CH][NT], float (&ad)[CH]) {
+#pragma unroll
+        for (int s = 0; s < CH; s++) {
+            const u32 kr = 4u * (s0 + (u32)s) + q;
+            const bool in = kr < krows;
+            const size_t off = (size_t)(in ? kr : 0u) * bstride;
+#pragma unroll
+            for (int i = 0; i < NT; i++) { const float v = bp[i][off]; bd[s][i] = in ? v : 0.f; }
+            ad[s] = ap[4u * (s0 + (u32)s)];
+        }
+    };
+    load(0u, bb, av);
+#pragma unroll 1
+    for (u32 s0 = 0; s0 < nsteps; s0 += (u32)CH) {
+        const bool more = s0 + (u32)CH < nsteps;
+        if (more) load(s0 + (u32)CH, nb, na);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int s = 0; s < CH; s++)
+#pragma unroll
+            for (int i = 0; i < NT; i++) acc[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[s], bb[s][i], acc[i], 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+        if (more) {
+#pragma unroll
+            for (int s = 0; s < CH; s++) {
+                av[s] = na[s];
+#pragma unroll
+                for (int i = 0; i < NT; i++) bb[s][i] = nb[s][i];
+            }
+        }
+    }
+}
+
+// One window of T moves for the workgroup's 16 games (blockIdx.x); 512 threads.  OPP: 0 the policy moves for every seat, 1 GameRunner with
+// RandomAgent seats.  The returns are not written here (azul_batch_mp_policy_rollout runs azul_discounted_returns behind the launch).
+template <u32 P, u32 D, int OPP>
+AZ_FN void x_policy_rollout_body(const azx::XBatchDev &b, const PolicyWeights &W, const RolloutArgs &a, u32 id_base, PXShared<P, D> &S)
+{
+    using Sh = PXShape<P, D>;
+    constexpr u32 IN = Sh::IN, NA = Sh::NA, OS = Sh::OBS_STRIDE, LS = Sh::LOG_STRIDE, NPL = Sh::NPL;
+    const u32 tid = threadIdx.x, lane = tid & 63u, l = lane & 31u, half = lane >> 5, c = lane & 15u, q = (lane >> 4) & 3u;
+    const u32 w = (u32)__builtin_amdgcn_readfirstlane((int)(tid >> 6));
+    const u32 n = b.n, g0 = blockIdx.x * PF_GAMES, gl = 2u * w + half, gi = g0 + gl;
+    const bool live = gi < n;
+    const u32 gic = live ? gi : n - 1u;
+    u64 counter = a.counter;
+    if (a.counter_dev) counter += a.counter_dev[0];
+    for (u32 i = tid; i < (u32)PF_HID; i += 64u * PR2_WAVES) S.w2c[i] = W.w2c[i];
+    for (u32 i = tid; i < (u32)PF_H2; i += 64u * PR2_WAVES) S.b1[i] = W.b1[i];
+    for (u32 i = tid; i < NA; i += 64u * PR2_WAVES) S.b2a[i] = W.b2a[i];
+    if (OPP == 1)
+        for (u32 i = tid; i < azx::Dim<D>::TROWS * (u32)T_STRIDE; i += 64u * PR2_WAVES) S.tab[i] = b.tab[i];
+    for (u32 i = tid; i < PF_GAMES * OS; i += 64u * PR2_WAVES) S.obs[i] = 0.f;          // the K padding stays zero for the window
+    for (u32 i = tid; i < PF_GAMES * NA / 4u; i += 64u * PR2_WAVES) S.mask[i / (NA / 4u)][i % (NA / 4u)] = 0u;
+    constexpr u32 RW = AZUL_RECORD_BYTES_WIDE / 4u;
+    for (u32 i = tid; i < PF_GAMES * RW; i += 64u * PR2_WAVES) {
+        const u32 row = i / RW, g = g0 + row;
+        S.rec[row][i % RW] = g < n ? ((const u32 *)(b.state + (size_t)g * AZUL_RECORD_BYTES_WIDE))[i % RW] : 0u;
+    }
+    const float b2c_v = W.b2c[0];
+    __syncthreads();
+
+    // env state of this half's game: the stream (LDS) and the counters stay open for the window.  Everything else of the env -- the game,
+    // the rule constants -- is rebuilt in each env phase, so that the matrix phases do not carry it (the VGPR budget is 256 at 8 waves)
+    const az2::Tab2 tab = {S.tab};
+    uint8_t *rec = (uint8_t *)S.rec[gl];
+    az2::Rng2 r;
+    u32 *gmt = b.mt + (size_t)gic * 624u;
+    az2::rng2_open(r, gmt, S.mt[gl], b.mtpos[gic], l);
+    az2::Counters2 cnt;
+    az2::counters2_open(cnt, b.episodes + gic, b.stuck + gic, b.stat_sum + (size_t)gic * 10, l);
+    u32 st_last = ST_OK;
+
+    // the decision of the state in `g` -> LDS (observation row, mask bytes) and the player byte of trajectory slot `slot` (runner_body_x's queries)
+    auto publish = [&](const azx::GX<P, D> &g, const azx::KX<D> &K, u32 slot) {
+        uint8_t *mrow = (uint8_t *)S.mask[gl];
+        azx::MaskX<D> m;
+        azx::legal_mask_x(g, K, m);
+#pragma unroll
+        for (u32 rr = 0; rr < 6u; rr++) {
+            if (l < (azx::Dim<D>::Q < 32u ? azx::Dim<D>::Q : 32u)) mrow[azx::Dim<D>::Q * rr + l] = (uint8_t)m.bit[rr][0];
+            if (azx::Dim<D>::NW > 1) { if (l + 32u < azx::Dim<D>::Q) mrow[azx::Dim<D>::Q * rr + 32u + l] = (uint8_t)m.bit[rr][azx::Dim<D>::NW - 1]; }
+        }
+        azx::observe_x(g, OPP ? 0u : azx::mex(g), S.obs + gl * OS, l);
+        if (l == 0u) a.player[(size_t)slot * n + gi] = (uint8_t)g.cur;
+    };
+    // trajectory slot `slot` of the workgroup's games <- LDS: [T+1][N][IN] floats and [T+1][N][NA] bytes (dwords: NA is a multiple of 4);
+    // the rows are not 16-byte aligned in general, so every store is a dword.  `idx` in 0..191 over waves 4..6.
+    auto flush = [&](u32 slot, u32 idx) {
+        const size_t cell0 = (size_t)slot * n + g0;
+        float *og = a.obs + cell0 * IN;
+#pragma unroll 1
+        for (u32 e = idx; e < PF_GAMES * IN; e += 192u) {
+            const u32 row = e / IN, k = e - row * IN;
+            if (g0 + row < n) og[e] = S.obs[row * OS + k];
+        }
+        u32 *mg = (u32 *)(a.mask + cell0 * NA);
+#pragma unroll 1
+        for (u32 d = idx; d < PF_GAMES * NA / 4u; d += 192u) {
+            const u32 row = d / (NA / 4u);
+            if (g0 + row < n) mg[d] = S.mask[row][d - row * (NA / 4u)];
+        }
+    };
+    if (live) {
+        azx::KX<D> K;
+        azx::kx_init(K);
+        azx::GX<P, D> g;
+        azx::gx_load(g, rec, l);
+        azx::prime_x(g, K);
+        publish(g, K, 0u);
+    }
+
+    // matrix phases: wave w owns column tiles j = w + 8 i, the lane column 16 j + c (clamped to a real column: dead tiles compute and are dropped)
+#pragma unroll 1
+    for (int t = 0; t < a.n_steps; t++) {
+        const size_t row_t = (size_t)t * n;
+        lds_barrier();                                   // observations and masks of all 16 games are in LDS
+        {
+            const float *bp1[Sh::NT1];
+#pragma unroll
+            for (u32 i = 0; i < Sh::NT1; i++) { const u32 col = 16u * (w + PR2_WAVES * i) + c; bp1[i] = W.w1t + (col < (u32)PF_H2 ? col : 0u); }
+            pf_f32x4 acc[Sh::NT1];
+#pragma unroll
+            for (u32 i = 0; i < Sh::NT1; i++) acc[i] = (pf_f32x4){0.f, 0.f, 0.f, 0.f};
+            px_chain<(int)Sh::NT1, 8>(S.obs + c * OS + q, bp1, (u32)PF_H2, Sh::KPAD / 4u, IN, q, acc);
+#pragma unroll
+            for (u32 i = 0; i < Sh::NT1; i++) {
+                const u32 col = 16u * (w + PR2_WAVES * i) + c;
+                if (col < (u32)PF_H2)
+                    for (int rr = 0; rr < 4; rr++) {             // C layout: column = lane & 15, row = 4 (lane >> 4) + rr
+                        const float h = acc[i][rr] + S.b1[col];
+                        S.hid[(4u * q + rr) * PF_HID_STRIDE + col] = h > 0.f ? h : 0.f;       // F.relu, model.py:24/30
+                    }
+            }
+        }
+        lds_barrier();
+        {
+            const float *bp2[Sh::NT2];
+#pragma unroll
+            for (u32 i = 0; i < Sh::NT2; i++) { const u32 col = 16u * (w + PR2_WAVES * i) + c; bp2[i] = W.w2a_t + (col < NA ? col : 0u); }
+            pf_f32x4 acc[Sh::NT2];
+#pragma unroll
+            for (u32 i = 0; i < Sh::NT2; i++) acc[i] = (pf_f32x4){0.f, 0.f, 0.f, 0.f};
+            px_chain<(int)Sh::NT2, 9>(S.hid + c * PF_HID_STRIDE + PF_HID + q, bp2, NA, (u32)PF_HID / 4u, (u32)PF_HID, q, acc);
+#pragma unroll
+            for (u32 i = 0; i < Sh::NT2; i++) {
+                const u32 col = 16u * (w + PR2_WAVES * i) + c;
+                if (col < NA)
+                    for (int rr = 0; rr < 4; rr++) S.lg[(4u * q + rr) * LS + col] = acc[i][rr] + S.b2a[col];
+            }
+        }
+        lds_barrier();
+        if (w < 4u) {
+            // head: azul_policy_head_n_kernel's lane mapping on the LDS rows, four games per wave
+            const u32 hrow = 4u * w + q, hg = g0 + hrow;
+            const float *row = S.lg + hrow * LS;
+            const uint8_t *mk = (const uint8_t *)S.mask[hrow];
+            float x[NPL];
+            u32 okbits = 0;
+#pragma unroll
+            for (u32 j = 0; j < NPL; j++) {
+                const u32 i = NPL * c + j;
+                const bool in = i < NA;
+                x[j] = in ? row[i] : 0.f;
+                okbits |= ((in && mk[in ? i : 0u] != 0) ? 1u : 0u) << j;
+            }
+            policy_head_rows<(int)NPL>(x, row, okbits, a.seed, counter + (u64)t, hg < n ? hg : n - 1u, lane, hg < n, a.action + row_t, a.logp + row_t,
+                                       a.entropy + row_t, id_base, S.act + 4u * w);
+        } else if (w < 7u) {
+            flush((u32)t, 64u * (w - 4u) + lane);
+        } else {
+            // the critic: lane (row c, quarter q) sums k = q (mod 4), then the quarters are added (azul_policy_forward_kernel's order)
+            float sum = 0.f;
+            const float *hp = S.hid + c * PF_HID_STRIDE;
+#pragma unroll
+            for (int s = 0; s < PF_HID / 4; s++) sum = fmaf(hp[4 * s + q], S.w2c[4 * s + q], sum);
+            sum += __shfl_xor(sum, 16, 64);
+            sum += __shfl_xor(sum, 32, 64);
+            if (q == 0u && g0 + c < n) a.value[row_t + g0 + c] = sum + b2c_v;
+        }
+        lds_barrier();
+        if (live) {
+            // one runner call of azul_x_runner_kernel (XRUN_AGENT_STEP / XRUN_POLICY_STEP) on the record in LDS
+            azx::KX<D> K;
+            azx::kx_init(K);
+            azx::GX<P, D> g;
+            azx::gx_load(g, rec, l);
+            azx::prime_x(g, K);
+            azx::RunX s;
+            azx::runx_load(s, rec);
+            const i32 av = S.act[gl];
+            i32 rew = 0;
+            u32 dn = 0, st;
+            if constexpr (OPP == 1) st = azx::agent_step_x(g, s, av, b.rules, K, r, tab, b.draw_margin, cnt, rew, dn);
+            else st = azx::policy_step_x(g, s, av, b.rules, K, r, b.draw_margin, cnt, rew, dn);
+            if (!(st == ST_ILLEGAL_MOVE || st == ST_BAD_ACTION)) {
+                azx::gx_store(g, rec, l);
+                azx::runx_store(s, rec, l);
+            }
+            if (l == 0u) { a.reward[row_t + gi] = rew; a.done[row_t + gi] = (uint8_t)dn; }
+            st_last = st;
+            publish(g, K, (u32)t + 1u);
+        }
+    }
+    lds_barrier();                                       // the rows of the state after the last move; every record is final
+    if (w >= 4u && w < 7u) flush((u32)a.n_steps, 64u * (w - 4u) + lane);
+    if (live) {
+        az2::rng2_close(r, gmt, b.mtpos + gi, l);
+        az2::counters2_close(cnt, l);
+        if (a.status && l == 0u) a.status[gi] = (uint8_t)st_last;
+    }
+    for (u32 i = tid; i < PF_GAMES * RW; i += 64u * PR2_WAVES) {
+        const u32 row = i / RW, g = g0 + row;
+        if (g < n) ((u32 *)(b.state + (size_t)g * AZUL_RECORD_BYTES_WIDE))[i % RW] = S.rec[row][i % RW];
+    }
+    if (a.counter_dev && tid == 0u) {
+        __threadfence();
+        u64 done_blocks = atomicAdd((unsigned long long *)(a.counter_dev + 1), 1ull);
+        if (done_blocks == (u64)gridDim.x - 1ull) {
+            a.counter_dev[1] = 0ull;
+            a.counter_dev[0] += (u64)a.n_steps;
+            __threadfence();
+        }
+    }
 }

@@ -40,7 +40,7 @@ class PolicyRollout:
     def __init__(self, policy, n_games=4096, parts=1, rules={"first_player": "Random", "tile_pool": "Lid"}, seed_base=0,
                  device=None, window=32, use_graph=True, fused_head=True, sample_seed=0x5EED, opponent=None, fused_mlp=True, persistent=False,
                  action_selection="Distribution", kweights=None, game_id_base=None, ring=1, opponent_selection="Distribution",
-                 opponent_seed=None, opponent_trace=0, move_limit=0, players=2):
+                 opponent_seed=None, opponent_trace=0, move_limit=0, players=2, fused_wide=False):
         """opponent=None: the policy moves for both players (flat self-play, one record per env move).
         opponent="random": the reference's training setup -- the policy is player 1 of GameRunner, the opponent a RandomAgent
         inside the env step (game_runner.py:43-47); one record per AGENT step, observations from the agent's perspective.
@@ -68,7 +68,11 @@ class PolicyRollout:
         when its shape matches the batch (ActorCritic(env.obs_size, env.num_actions), any hidden size: anything else raises ValueError):
         every other seat's opponent_move() goes through MultiplayerAzul.net_* (azul_batch_mp_net_*), answered by the module's actor half as
         PyTorch GEMMs + azul_policy_head_n with the two-player path's Philox keys; no HIP graph, and at most MAX_REPLY_ROUNDS reply rounds
-        per step or opening -- an opponent that keeps answering with moves that are not legal raises RuntimeError."""
+        per step or opening -- an opponent that keeps answering with moves that are not legal raises RuntimeError.
+        `fused_wide=True` (wide batches, opponent=None | "random", ActorCritic(env.obs_size, env.num_actions, hidden 180), fused_head): each
+        window is ONE launch per part (azul_batch_mp_policy_rollout: env, network on the f32 matrix cores and azul_policy_head_n's draw inside
+        one kernel) instead of the per-move GEMMs + head + env launches; the same trajectories (the network's sums in another order: the same
+        bits wherever they are exact), `ring` stays 1.  Anything else with fused_wide=True raises ValueError."""
         assert n_games % parts == 0
         self.players = int(players)
         self.wide = self.players != 2 or parse_ext_rules(rules, self.players) != 0
@@ -82,6 +86,22 @@ class PolicyRollout:
                                  % (self.players, n_obs, n_act, shape[0], shape[1], shape[2]))
         if self.wide and move_limit:
             raise ValueError("no move limit for batches of three / four players or extended rules")
+        self.fused_wide = bool(fused_wide)
+        if self.fused_wide:
+            if not self.wide:
+                raise ValueError("fused_wide=True is the window kernel of batches of three / four players or extended rules; two-player reference "
+                                 "batches have persistent=True")
+            if opponent is not None and not isinstance(opponent, str):
+                raise ValueError("fused_wide=True plays opponent=None or \"random\"; a network opponent runs on the per-cut path (fused_wide=False)")
+            if not fused_head:
+                raise ValueError("fused_wide=True samples with azul_policy_head_n's draw: fused_head=False is the PyTorch sampling path")
+            D = 2 * self.players + 1 if parse_ext_rules(rules, self.players) & L.RULE_DISPLAYS_2P1 else 5
+            n_obs, n_act = 5 * D + 6 + 52 * self.players + 1, (D + 1) * 30
+            shape = (policy.critic_linear1.in_features, policy.actor_linear1.in_features, policy.critic_linear1.out_features,
+                     policy.actor_linear1.out_features, policy.actor_linear2.out_features)
+            if shape != (n_obs, n_obs, 180, 180, n_act):
+                raise ValueError("fused_wide=True is compiled for ActorCritic(%d, %d, hidden 180) on this batch, got inputs %d / %d, hidden %d / %d "
+                                 "and %d actions" % ((n_obs, n_act) + shape))
         self.opp_policy = None
         if opponent is not None and not isinstance(opponent, str):
             self.opp_policy, opponent = opponent, "net"
@@ -171,7 +191,7 @@ class PolicyRollout:
                     self._net_reset(p)                             # GameRunner.reset(): the network opponent opens when it starts
                 env.observe_all(self._persp(), t["obs"][T], t["mask"][T], t["player"][T])     # becomes slot 0 of the first window
         torch.cuda.synchronize(d)
-        self.use_graph = use_graph and not self.persistent and self.opponent != "net"     # one launch per window needs no graph; reply rounds are data-dependent
+        self.use_graph = use_graph and not self.persistent and not self.fused_wide and self.opponent != "net"     # one launch per window needs no graph; reply rounds are data-dependent
         self.graph_error = None
         if self.use_graph:
             try:
@@ -345,6 +365,15 @@ class PolicyRollout:
 
     def _window(self, p, gamma):
         T = self.T
+        if self.fused_wide:                                 # the whole window in one launch (+ the returns scan behind it)
+            env, tr, w, pol = self.envs[p], self.traj[p], self.work[p], self.policy
+            wa = L.NetWeights(*[_p(x) for x in (self.w1t, self.b1, self.w2c, pol.critic_linear2.bias, self.w2a_t, pol.actor_linear2.bias)])
+            out = L.RolloutBuffers(_p(tr["obs"]), _p(tr["mask"]), _p(tr["player"]), _p(tr["action"]), _p(tr["reward"]), _p(tr["done"]),
+                                   _p(tr["value"]), _p(tr["log_prob"]), _p(tr["entropy"]), _p(w["status"]), _p(tr["returns"]), None, None, None, 0)
+            L.check(L.lib.azul_batch_mp_policy_rollout(env._h, T, 1 if self.opponent == "random" else 0, C.byref(wa), self.obs_size, self.H,
+                                                       self.num_actions, self.sample_seed, 0, _p(w["counter"]), C.byref(out), C.c_float(gamma),
+                                                       C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+            return
         if self.persistent and self.ring > 1:
             wi = self.windows_played % self.ring                   # (run_window advances windows_played after all parts)
             self.traj[p] = self._window_views(self.rings[p], wi)

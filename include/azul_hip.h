@@ -401,6 +401,25 @@ typedef struct azul_rollout_buffers {
 int azul_batch_policy_rollout_vs(azul_batch_t *b, int n_steps, const azul_net_weights_t *agent, const azul_net_weights_t *opponent, int num_inputs,
                                  int hidden_size, int num_actions, uint64_t seed, uint64_t opponent_seed, uint64_t counter, uint64_t *counter_dev,
                                  const azul_rollout_buffers_t *out, float gamma, void *stream);
+/* azul_batch_policy_rollout for WIDE batches (three / four players, or any extended rule; two-player reference batches are refused: they
+ * have azul_batch_policy_rollout): a whole window of n_steps moves in ONE launch, 16 games per workgroup of eight waves, the env on the
+ * vector pipe, ActorCritic(obs_size, hidden 180, num_actions) on the f32 matrix cores, the head of azul_policy_head_n.  opponent_random = 0:
+ * the policy moves for every seat (azul_batch_mp_policy_step, perspective = the mover); 1: GameRunner with RandomAgent seats
+ * (azul_batch_mp_agent_step, perspective 0: replies, restarts, AZUL_STUCK guard, statistics and the runner tail, record bytes 228..231).
+ * Per move t: obs / mask / player of the decision to slot t, the network with the weight layouts of azul_policy_forward (w1t
+ * [obs_size][360], b1 [360], w2c [180], b2c [1], w2a_t [180][num_actions], b2a [num_actions]), the draw with Philox key (seed,
+ * counter + *counter_dev + t, game id base + game), the env step; then slot n_steps gets the state after the last move and *counter_dev
+ * advances by n_steps (counter_dev: optional uint64_t[2] as for azul_policy_forward, [1] starts as 0).  Layouts are time-major:
+ * out->obs [T+1][N][obs_size], out->mask [T+1][N][num_actions], out->player [T+1][N], action / reward / done / value / logp / entropy
+ * [T][N]; out->status [N] (optional) is the last move's status; out->returns [T][N] (optional) gets azul_discounted_returns' scan, launched
+ * behind the kernel (the opponent fields of `out` are ignored).  Rows of 198 or 260 floats are not 16-byte aligned: obs and mask need 4-byte
+ * alignment only.  Results: bit-identical to n_steps x (the per-move path's network where its sums are exact + azul_policy_head_n +
+ * azul_batch_mp_agent_step / _policy_step); with general weights value / logits differ from a GEMM only by f32 summation order.
+ * AZUL_ERR_INVALID: a two-player reference batch, a move limit, hidden_size != 180, num_inputs != azul_batch_obs_size or num_actions !=
+ * azul_batch_num_actions of the batch. */
+int azul_batch_mp_policy_rollout(azul_batch_t *b, int n_steps, int opponent_random, const azul_net_weights_t *w, int num_inputs, int hidden_size,
+                                 int num_actions, uint64_t seed, uint64_t counter, uint64_t *counter_dev, const azul_rollout_buffers_t *out, float gamma,
+                                 void *stream);
 /* The same protocol one launch per cut, for opponents evaluated OUTSIDE the library (any network as PyTorch modules, or azul_policy_forward
  * on a second weight set): GameRunner.step / reset are cut at their opponent_move() calls.  pending_dev (uint8 [N], in / out) holds per
  * game 0 = nothing owed (the agent's next decision), 1 = an opponent_move() is owed inside GameRunner.step's loop (game_runner.py:46-47),

@@ -4,7 +4,13 @@ and the launch time of azul_batch_mp_agent_step alone at 4096 games.  One JSON l
 --opponent self: the opponent is a network of the policy's shape (a frozen past self): azul_batch_mp_net_* cuts, one opponent forward and
 one host synchronisation per reply round, no HIP graph.  The line then also reports the reply rounds a step takes (max over the batch).
 
+--fused-wide: the same run also measures PolicyRollout(fused_wide=True) (azul_batch_mp_policy_rollout: one launch per window) against the
+GEMM path with opponent "random": agent steps/s of both, the window kernel's time from HIP events around each window (the returns scan behind
+it included), and the share of the f32 matrix peak (157.3 TFLOP/s) that the FLOPs the shapes imply (2 (obs_size 360 + 180 num_actions + 180)
+per agent step) reach over that kernel time.
+
 Usage: python tools/mp_rollout_bench.py [--games 4096] [--window 32] [--windows 20] [--hidden 180] [--opponent random self] [--configs p3_d5 ...]
+                                        [--fused-wide]
 """
 import argparse
 import copy
@@ -28,8 +34,36 @@ CONFIGS = [
 ]
 
 
+F32_MATRIX_PEAK = 157.3e12
+
+
+def fused_rate(players, rules, args):
+    """(agent steps/s, median window kernel ms, FLOP per agent step) of PolicyRollout(fused_wide=True)."""
+    probe = MultiplayerAzul(2, rules=rules, players=players)
+    torch.manual_seed(0)
+    pol = BatchedActorCritic(probe.obs_size, probe.num_actions, 180)
+    ro = PolicyRollout(pol, n_games=args.games, rules=rules, window=args.window, opponent="random", players=players, fused_wide=True)
+    for _ in range(3):
+        ro.run_window()
+    ro.synchronize()
+    ev = []
+    t0 = time.perf_counter()
+    for _ in range(args.windows):
+        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        s.record(ro.streams[0])
+        ro.run_window()
+        e.record(ro.streams[0])
+        ev.append((s, e))
+    ro.synchronize()
+    dt = time.perf_counter() - t0
+    ms = sorted(s.elapsed_time(e) for s, e in ev)[len(ev) // 2]
+    flop = 2 * (probe.obs_size * 360 + 180 * probe.num_actions + 180)
+    return args.games * args.window * args.windows / dt, ms, flop
+
+
 def rollout_rate(players, rules, args, opponent):
     probe = MultiplayerAzul(2, rules=rules, players=players)
+    torch.manual_seed(0)
     pol = BatchedActorCritic(probe.obs_size, probe.num_actions, args.hidden)
     opp = copy.deepcopy(pol) if opponent == "self" else "random"
     ro = PolicyRollout(pol, n_games=args.games, rules=rules, window=args.window, opponent=opp, players=players)
@@ -83,7 +117,21 @@ def main():
     ap.add_argument("--hidden", type=int, default=180)
     ap.add_argument("--opponent", nargs="+", choices=("random", "self"), default=["random"])
     ap.add_argument("--configs", nargs="+", choices=[c[0] for c in CONFIGS], default=[c[0] for c in CONFIGS])
+    ap.add_argument("--fused-wide", action="store_true")
     args = ap.parse_args()
+    if args.fused_wide:
+        for name, players, rules in CONFIGS:
+            if name not in args.configs:
+                continue
+            gemm, graph, _ = rollout_rate(players, rules, args, "random")
+            fused, ms, flop = fused_rate(players, rules, args)
+            steps = args.games * args.window
+            print(json.dumps({"config": name, "opponent": "random", "games": args.games, "window": args.window, "hidden": 180,
+                              "gemm_agent_steps_per_s": round(gemm), "gemm_graph": graph, "fused_agent_steps_per_s": round(fused),
+                              "speedup": round(fused / gemm, 2), "fused_window_ms_median": round(ms, 4),
+                              "fused_kernel_agent_steps_per_s": round(steps / (ms * 1e-3)), "flop_per_agent_step": flop,
+                              "f32_matrix_peak_share": round(flop * steps / (ms * 1e-3) / F32_MATRIX_PEAK, 4)}), flush=True)
+        return
     for name, players, rules in CONFIGS:
         if name not in args.configs:
             continue
