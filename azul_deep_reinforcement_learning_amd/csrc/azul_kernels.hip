@@ -96,6 +96,17 @@ __global__ void __launch_bounds__(64 * PR2_WAVES) azul_x_policy_rollout_kernel(a
     x_policy_rollout_body<P, D, OPP>(b, W, a, id_base, S);
 }
 
+// ... with a NETWORK opponent (azul_batch_mp_policy_rollout_vs; OPP 2 of x_policy_rollout_body): the reply rounds inside the window, the
+// opponent's biases and the games' reply-loop state in LDS next to PXShared
+template <u32 P, u32 D>
+__global__ void __launch_bounds__(64 * PR2_WAVES) azul_x_policy_rollout_vs_kernel(azx::XBatchDev b, PolicyWeights W, RolloutArgs a, u32 id_base,
+                                                                                   u32 max_replies)
+{
+    __shared__ PXShared<P, D> S;
+    __shared__ PXOpp<D> O;
+    x_policy_rollout_body<P, D, 2>(b, W, a, id_base, S, &O, max_replies);
+}
+
 // ------------------------------------------------------------------------------------------------
 // host side: C ABI
 // ------------------------------------------------------------------------------------------------
@@ -840,6 +851,48 @@ int azul_batch_mp_policy_rollout(azul_batch_t *b, int n_steps, int opponent_rand
     const u32 id_base = b->d.id_base;
     if (opponent_random) AZ_X_DISPATCH(b, hipLaunchKernelGGL((azul_x_policy_rollout_kernel<PP, DD, 1>), grid, block, 0, st, xb, W, a, id_base));
     else AZ_X_DISPATCH(b, hipLaunchKernelGGL((azul_x_policy_rollout_kernel<PP, DD, 0>), grid, block, 0, st, xb, W, a, id_base));
+    HIP_TRY(hipGetLastError());
+    if (out->returns)                                    // the window's discounted returns: the per-move path's own scan
+        return azul_discounted_returns(out->reward, out->done, out->returns, nullptr, gamma, n_steps, (int)b->d.n, stream);
+    return AZUL_SUCCESS;
+}
+
+/* GameRunner with a network opponent for wide batches inside one launch per window (azul_x_policy_rollout_vs_kernel) */
+int azul_batch_mp_policy_rollout_vs(azul_batch_t *b, int n_steps, const azul_net_weights_t *agent, const azul_net_weights_t *opponent, int num_inputs,
+                                    int hidden_size, int num_actions, uint64_t seed, uint64_t opp_seed, uint64_t counter, uint64_t *counter_dev,
+                                    int max_replies, const azul_rollout_buffers_t *out, float gamma, void *stream)
+{
+    BATCH_GUARD(b, stream);
+    if (!b || n_steps < 0 || !agent || !out) return fail(AZUL_ERR_INVALID, "azul_batch_mp_policy_rollout_vs: bad arguments");
+    if (!opponent) return fail(AZUL_ERR_INVALID, "azul_batch_mp_policy_rollout_vs: no opponent (azul_batch_mp_policy_rollout plays without one)");
+    if (!b->x) return fail(AZUL_ERR_INVALID, "azul_batch_mp_policy_rollout_vs: a two-player batch of 128-byte records: use azul_batch_policy_rollout_vs");
+    if (b->d.move_limit) return fail(AZUL_ERR_INVALID, "azul_batch_mp_policy_rollout_vs: no move limit for wide batches");
+    if (hidden_size != PF_HID) return fail(AZUL_ERR_INVALID, "azul_batch_mp_policy_rollout_vs: only hidden size 180 is compiled in (agent and opponent)");
+    if (num_inputs != azul_batch_obs_size(b) || num_actions != azul_batch_num_actions(b))
+        return fail(AZUL_ERR_INVALID, "azul_batch_mp_policy_rollout_vs: num_inputs / num_actions must be the batch's azul_batch_obs_size / azul_batch_num_actions");
+    if (max_replies < 1) return fail(AZUL_ERR_INVALID, "azul_batch_mp_policy_rollout_vs: max_replies must be at least 1");
+    if (!agent->w1t || !agent->b1 || !agent->w2c || !agent->b2c || !agent->w2a_t || !agent->b2a || !opponent->w1t || !opponent->b1 || !opponent->w2a_t ||
+        !opponent->b2a || !out->obs || !out->mask || !out->player || !out->action || !out->reward || !out->done || !out->value || !out->logp || !out->entropy)
+        return fail(AZUL_ERR_INVALID, "azul_batch_mp_policy_rollout_vs: NULL pointer");
+    if (((uintptr_t)out->obs & 3u) != 0 || ((uintptr_t)out->mask & 3u) != 0)
+        return fail(AZUL_ERR_INVALID, "azul_batch_mp_policy_rollout_vs: obs and mask must be 4-byte aligned");
+    if ((out->opp_action || out->opp_logp) && out->opp_slots <= 0)
+        return fail(AZUL_ERR_INVALID, "azul_batch_mp_policy_rollout_vs: opp_slots must be positive with a trace");
+    if (n_steps == 0) return AZUL_SUCCESS;
+    PolicyWeights W = {agent->w1t, agent->b1, agent->w2c, agent->b2c, agent->w2a_t, agent->b2a};
+    RolloutArgs a;
+    memset(&a, 0, sizeof(a));
+    a.n_steps = n_steps; a.obs = out->obs; a.mask = out->mask; a.player = out->player; a.action = out->action; a.reward = out->reward;
+    a.done = out->done; a.value = out->value; a.logp = out->logp; a.entropy = out->entropy; a.status = out->status; a.returns = nullptr;
+    a.gamma = gamma; a.seed = (u64)seed; a.counter = (u64)counter; a.counter_dev = (u64 *)counter_dev;
+    a.Wopp = {opponent->w1t, opponent->b1, opponent->w2c, opponent->b2c, opponent->w2a_t, opponent->b2a};
+    a.opp_seed = (u64)opp_seed;
+    a.opp_action = out->opp_action; a.opp_logp = out->opp_logp; a.opp_replies = out->opp_replies; a.opp_slots = out->opp_slots;
+    const dim3 grid((b->d.n + PF_GAMES - 1) / PF_GAMES), block(64 * PR2_WAVES);
+    const hipStream_t st = (hipStream_t)stream;
+    const azx::XBatchDev xb = xdev(b);
+    const u32 id_base = b->d.id_base;
+    AZ_X_DISPATCH(b, hipLaunchKernelGGL((azul_x_policy_rollout_vs_kernel<PP, DD>), grid, block, 0, st, xb, W, a, id_base, (u32)max_replies));
     HIP_TRY(hipGetLastError());
     if (out->returns)                                    // the window's discounted returns: the per-move path's own scan
         return azul_discounted_returns(out->reward, out->done, out->returns, nullptr, gamma, n_steps, (int)b->d.n, stream);

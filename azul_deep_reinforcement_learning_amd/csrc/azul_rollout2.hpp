@@ -570,7 +570,7 @@ __global__ void __launch_bounds__(64 * PR2_WAVES) azul_policy_rollout2_kernel(Ba
 // in its 32-lane halves, the same waves run the network on the f32 matrix cores between the env phases -- on azul_rules_x.hpp's P-seat
 // GameRunner.  Per move: env phase -> layer 1 -> layer 2 -> head (+ critic, trajectory stores) -> env phase.
 //   env       OPP 0: azx::policy_step_x (the policy moves for every seat, observation from the mover); OPP 1: azx::agent_step_x (GameRunner with
-//             RandomAgent seats, observation from seat 0).  The game is loaded from / stored to its 256-byte record in LDS around each env
+//             RandomAgent seats, observation from seat 0); OPP 2: GameRunner with a NETWORK opponent (azx::net_move_x, see there).  The game is loaded from / stored to its 256-byte record in LDS around each env
 //             phase exactly as runner_body_x does around each launch (stored only when the step touched it), so nothing of the game is live
 //             across the matrix phases; the MT19937 stream (LDS) and the counters stay open for the window.
 //   matrix    hidden = relu(obs @ w1t + b1) over 23 column tiles of 16 (360 columns), K = obs_size zero-padded in LDS to a multiple of 32;
@@ -592,6 +592,8 @@ struct PXShape {
     static constexpr u32 T1 = (PF_H2 + 15) / 16;                   // 23 column tiles of layer 1
     static constexpr u32 T2 = (NA + 15u) / 16u;                    // 12 / 15 / 19 of layer 2
     static constexpr u32 NT1 = (T1 + PR2_WAVES - 1u) / PR2_WAVES, NT2 = (T2 + PR2_WAVES - 1u) / PR2_WAVES;
+    static constexpr u32 TO = (PF_HID + 15) / 16;                  // OPP 2: 12 column tiles of the opponent's layer 1 (its actor half)
+    static constexpr u32 NTO = (TO + PR2_WAVES - 1u) / PR2_WAVES;
 };
 
 template <u32 P, u32 D>
@@ -605,6 +607,16 @@ struct PXShared {                                                  // the workgr
     double2 tab[azx::Dim<D>::TROWS * T_STRIDE];
     u32 mask[PF_GAMES][PXShape<P, D>::NA / 4];                     // the legal masks as bytes (NA is a multiple of 4)
     i32 act[PF_GAMES];
+};
+
+// OPP 2's extra LDS (azul_x_policy_rollout_vs_kernel declares it next to PXShared): the opponent's actor biases, and per game the state of
+// GameRunner.step's reply loop -- its NetStep, whether it owes an opponent_move() in this pass, the opponent head's answer
+template <u32 D>
+struct PXOpp {
+    float b1[PF_HID], b2a[azx::Dim<D>::NA];                        // actor_linear1.bias, actor_linear2.bias of the opponent
+    az2::NetStep ns[PF_GAMES];
+    u32 owe[PF_GAMES];
+    i32 ans[PF_GAMES];
 };
 
 // NT column tiles of one 16-row tile, K = 4 nsteps (nsteps a multiple of CH): acc[i] += A[16 x K] B_i[K x 16].  ap: LDS, row c, k = q;
@@ -647,9 +659,11 @@ AZ_FN void px_chain(const float *ap, const float *const (&bp)[NT], u32 bstride, 
 }
 
 // One window of T moves for the workgroup's 16 games (blockIdx.x); 512 threads.  OPP: 0 the policy moves for every seat, 1 GameRunner with
-// RandomAgent seats.  The returns are not written here (azul_batch_mp_policy_rollout runs azul_discounted_returns behind the launch).
+// RandomAgent seats, 2 GameRunner with a network opponent (a.Wopp; O: PXOpp in LDS, max_replies: reply rounds per step before the loop gives
+// up).  The returns are not written here (azul_batch_mp_policy_rollout / _vs run azul_discounted_returns behind the launch).
 template <u32 P, u32 D, int OPP>
-AZ_FN void x_policy_rollout_body(const azx::XBatchDev &b, const PolicyWeights &W, const RolloutArgs &a, u32 id_base, PXShared<P, D> &S)
+AZ_FN void x_policy_rollout_body(const azx::XBatchDev &b, const PolicyWeights &W, const RolloutArgs &a, u32 id_base, PXShared<P, D> &S,
+                                 PXOpp<D> *O = nullptr, u32 max_replies = 0)
 {
     using Sh = PXShape<P, D>;
     constexpr u32 IN = Sh::IN, NA = Sh::NA, OS = Sh::OBS_STRIDE, LS = Sh::LOG_STRIDE, NPL = Sh::NPL;
@@ -665,6 +679,15 @@ AZ_FN void x_policy_rollout_body(const azx::XBatchDev &b, const PolicyWeights &W
     for (u32 i = tid; i < NA; i += 64u * PR2_WAVES) S.b2a[i] = W.b2a[i];
     if (OPP == 1)
         for (u32 i = tid; i < azx::Dim<D>::TROWS * (u32)T_STRIDE; i += 64u * PR2_WAVES) S.tab[i] = b.tab[i];
+    if constexpr (OPP == 2) {
+        for (u32 i = tid; i < (u32)PF_HID; i += 64u * PR2_WAVES) O->b1[i] = a.Wopp.b1[PF_HID + i];
+        for (u32 i = tid; i < NA; i += 64u * PR2_WAVES) O->b2a[i] = a.Wopp.b2a[i];
+        if (tid < PF_GAMES) {
+            O->ns[tid] = {az2::NET_READY, 0u, 0, 0u, false, (u32)ST_OK};
+            O->owe[tid] = 0u;
+            O->ans[tid] = -1;
+        }
+    }
     for (u32 i = tid; i < PF_GAMES * OS; i += 64u * PR2_WAVES) S.obs[i] = 0.f;          // the K padding stays zero for the window
     for (u32 i = tid; i < PF_GAMES * NA / 4u; i += 64u * PR2_WAVES) S.mask[i / (NA / 4u)][i % (NA / 4u)] = 0u;
     constexpr u32 RW = AZUL_RECORD_BYTES_WIDE / 4u;
@@ -794,7 +817,139 @@ AZ_FN void x_policy_rollout_body(const azx::XBatchDev &b, const PolicyWeights &W
             if (q == 0u && g0 + c < n) a.value[row_t + g0 + c] = sum + b2c_v;
         }
         lds_barrier();
-        if (live) {
+        if constexpr (OPP == 2) {
+            // GameRunner.step against the NETWORK opponent (game_runner.py:43-55, :37-42 answered by a.Wopp), azul_policy_rollout2_kernel<LID, 2>'s
+            // loop on the wide record: pass 0 plays the agent's action, then while any of the workgroup's 16 games owes an opponent_move() (the
+            // other seats' replies, the agent's forced moves, after an episode end the next one's openings) the opponent's forward_actor runs
+            // on the mover-perspective rows of the games that owe (the others sit masked) and pass j + 1 plays answer j.  Round j draws with
+            // Philox key opp_seed + j at counter + t, as PolicyRollout's per-cut path does.  The game, its NetStep and its debt live in LDS
+            // between the passes (O->ns / O->owe), loaded and stored around each env pass: nothing new is live across the matrix phases.
+#pragma unroll 1
+            for (u32 j = 0;; j++) {
+                if (live) {
+                    az2::NetStep ns = O->ns[gl];
+                    if (j == 0u || ns.pending != az2::NET_READY) {
+                        azx::KX<D> K;
+                        azx::kx_init(K);
+                        azx::GX<P, D> g;
+                        azx::gx_load(g, rec, l);
+                        azx::prime_x(g, K);
+                        azx::RunX s;
+                        azx::runx_load(s, rec);
+                        azx::MaskX<D> m;
+                        const u32 st = azx::net_move_x(g, s, S.act[gl], j == 0u, m, b.rules, K, r, b.draw_margin, cnt, ns);
+                        if (!(st == ST_ILLEGAL_MOVE || st == ST_BAD_ACTION)) {
+                            azx::gx_store(g, rec, l);
+                            azx::runx_store(s, rec, l);
+                        }
+                        if (ns.pending != az2::NET_READY) {         // what opponent_move() hands the opponent (game_runner.py:38-39): net_body_x's rows
+                            uint8_t *mrow = (uint8_t *)S.mask[gl];
+#pragma unroll
+                            for (u32 rr = 0; rr < 6u; rr++) {
+                                if (l < (azx::Dim<D>::Q < 32u ? azx::Dim<D>::Q : 32u)) mrow[azx::Dim<D>::Q * rr + l] = (uint8_t)m.bit[rr][0];
+                                if (azx::Dim<D>::NW > 1) { if (l + 32u < azx::Dim<D>::Q) mrow[azx::Dim<D>::Q * rr + 32u + l] = (uint8_t)m.bit[rr][azx::Dim<D>::NW - 1]; }
+                            }
+                            azx::observe_x(g, azx::mex(g), S.obs + gl * OS, l);
+                        }
+                        if (l == 0u) O->ns[gl] = ns;
+                    }
+                    if (l == 0u) O->owe[gl] = ns.pending != az2::NET_READY ? 1u : 0u;
+                }
+                lds_barrier();                                   // every game's debt, observation row and mask are in LDS
+                const bool any = __builtin_amdgcn_ballot_w64(O->owe[lane & 15u] != 0u) != 0ull;     // (the same 16 words in every wave)
+                if (!any || j >= max_replies) break;
+                const u64 okey = a.opp_seed == AZUL_POLICY_ARGMAX ? a.opp_seed : a.opp_seed + (u64)j;
+                {
+                    // layer 1 of forward_actor: columns 180..359 of the opponent's w1t, 12 tiles (wave w: tiles w, w + 8) -> hid[:, 180:]
+                    const float *bpo[Sh::NTO];
+#pragma unroll
+                    for (u32 i = 0; i < Sh::NTO; i++) {
+                        const u32 col = 16u * (w + PR2_WAVES * i) + c;
+                        bpo[i] = a.Wopp.w1t + PF_HID + (col < (u32)PF_HID ? col : 0u);
+                    }
+                    pf_f32x4 acc[Sh::NTO];
+#pragma unroll
+                    for (u32 i = 0; i < Sh::NTO; i++) acc[i] = (pf_f32x4){0.f, 0.f, 0.f, 0.f};
+                    px_chain<(int)Sh::NTO, 8>(S.obs + c * OS + q, bpo, (u32)PF_H2, Sh::KPAD / 4u, IN, q, acc);
+#pragma unroll
+                    for (u32 i = 0; i < Sh::NTO; i++) {
+                        const u32 col = 16u * (w + PR2_WAVES * i) + c;
+                        if (col < (u32)PF_HID)
+                            for (int rr = 0; rr < 4; rr++) {
+                                const float h = acc[i][rr] + O->b1[col];
+                                S.hid[(4u * q + rr) * PF_HID_STRIDE + PF_HID + col] = h > 0.f ? h : 0.f;       // F.relu, model.py:30
+                            }
+                    }
+                }
+                lds_barrier();
+                {
+                    const float *bp2[Sh::NT2];
+#pragma unroll
+                    for (u32 i = 0; i < Sh::NT2; i++) { const u32 col = 16u * (w + PR2_WAVES * i) + c; bp2[i] = a.Wopp.w2a_t + (col < NA ? col : 0u); }
+                    pf_f32x4 acc[Sh::NT2];
+#pragma unroll
+                    for (u32 i = 0; i < Sh::NT2; i++) acc[i] = (pf_f32x4){0.f, 0.f, 0.f, 0.f};
+                    px_chain<(int)Sh::NT2, 9>(S.hid + c * PF_HID_STRIDE + PF_HID + q, bp2, NA, (u32)PF_HID / 4u, (u32)PF_HID, q, acc);
+#pragma unroll
+                    for (u32 i = 0; i < Sh::NT2; i++) {
+                        const u32 col = 16u * (w + PR2_WAVES * i) + c;
+                        if (col < NA)
+                            for (int rr = 0; rr < 4; rr++) S.lg[(4u * q + rr) * LS + col] = acc[i][rr] + O->b2a[col];
+                    }
+                }
+                lds_barrier();
+                if (w < 4u) {
+                    // the opponent's head (agent.py:76-80): azul_policy_head_n's draw, waves 0..3, four games each.  A forward that is not
+                    // finite answers -1, as PolicyRollout's per-cut path does (its logits' sum is tested): the env refuses it, the game keeps
+                    // owing, and the reply cap ends the step
+                    const u32 hrow = 4u * w + q, hg = g0 + hrow;
+                    const float *row = S.lg + hrow * LS;
+                    const uint8_t *mk = (const uint8_t *)S.mask[hrow];
+                    float x[NPL], xs = 0.f;
+                    u32 okbits = 0;
+#pragma unroll
+                    for (u32 jj = 0; jj < NPL; jj++) {
+                        const u32 i = NPL * c + jj;
+                        const bool in = i < NA;
+                        x[jj] = in ? row[i] : 0.f;
+                        xs += x[jj];
+                        okbits |= ((in && mk[in ? i : 0u] != 0) ? 1u : 0u) << jj;
+                    }
+                    const bool finite = __builtin_isfinite(row_sum(xs));
+                    const bool owes = O->owe[hrow] != 0u;
+                    const bool tr = hg < n && owes && a.opp_action && j < (u32)a.opp_slots;
+                    const size_t trow = ((size_t)t * (size_t)(a.opp_slots > 0 ? a.opp_slots : 1) + (j < (u32)a.opp_slots ? j : 0u)) * n;
+                    policy_head_rows<(int)NPL>(x, row, okbits, okey, counter + (u64)t, hg < n ? hg : n - 1u, lane, tr, a.opp_action ? a.opp_action + trow : nullptr,
+                                               a.opp_logp ? a.opp_logp + trow : nullptr, nullptr, id_base, O->ans + 4u * w);
+                    if (c == 0u) {                               // (the lane that wrote the answer)
+                        if (owes) S.act[hrow] = finite ? O->ans[hrow] : -1;
+                        if (tr && !finite) a.opp_action[trow + hg] = -1;
+                    }
+                }
+                lds_barrier();
+            }
+            if (live) {
+                // close the step: a game still owing at the cap gives up as azul_policy_rollout2_kernel<LID, 2> does (pending cleared, AZUL_STUCK
+                // unless the step already has a status, the legal mask of its state); then slot t + 1 from perspective 0, as OPP 1
+                az2::NetStep ns = O->ns[gl];
+                if (ns.pending != az2::NET_READY) {
+                    ns.pending = az2::NET_READY;
+                    if (!ns.st) ns.st = ST_STUCK;
+                    if (l == 0u) O->ns[gl] = ns;
+                }
+                azx::KX<D> K;
+                azx::kx_init(K);
+                azx::GX<P, D> g;
+                azx::gx_load(g, rec, l);
+                azx::prime_x(g, K);
+                if (l == 0u) {
+                    a.reward[row_t + gi] = ns.rew; a.done[row_t + gi] = (uint8_t)ns.dn;
+                    if (a.opp_replies) a.opp_replies[row_t + gi] = (uint8_t)(ns.replies < 255u ? ns.replies : 255u);
+                }
+                st_last = ns.st;
+                publish(g, K, (u32)t + 1u);
+            }
+        } else if (live) {
             // one runner call of azul_x_runner_kernel (XRUN_AGENT_STEP / XRUN_POLICY_STEP) on the record in LDS
             azx::KX<D> K;
             azx::kx_init(K);

@@ -40,7 +40,7 @@ class PolicyRollout:
     def __init__(self, policy, n_games=4096, parts=1, rules={"first_player": "Random", "tile_pool": "Lid"}, seed_base=0,
                  device=None, window=32, use_graph=True, fused_head=True, sample_seed=0x5EED, opponent=None, fused_mlp=True, persistent=False,
                  action_selection="Distribution", kweights=None, game_id_base=None, ring=1, opponent_selection="Distribution",
-                 opponent_seed=None, opponent_trace=0, move_limit=0, players=2, fused_wide=False):
+                 opponent_seed=None, opponent_trace=0, move_limit=0, players=2, fused_wide=False, fused_opponent=False):
         """opponent=None: the policy moves for both players (flat self-play, one record per env move).
         opponent="random": the reference's training setup -- the policy is player 1 of GameRunner, the opponent a RandomAgent
         inside the env step (game_runner.py:43-47); one record per AGENT step, observations from the agent's perspective.
@@ -72,7 +72,13 @@ class PolicyRollout:
         `fused_wide=True` (wide batches, opponent=None | "random", ActorCritic(env.obs_size, env.num_actions, hidden 180), fused_head): each
         window is ONE launch per part (azul_batch_mp_policy_rollout: env, network on the f32 matrix cores and azul_policy_head_n's draw inside
         one kernel) instead of the per-move GEMMs + head + env launches; the same trajectories (the network's sums in another order: the same
-        bits wherever they are exact), `ring` stays 1.  Anything else with fused_wide=True raises ValueError."""
+        bits wherever they are exact), `ring` stays 1.  Anything else with fused_wide=True raises ValueError.
+        `fused_opponent=True` (with fused_wide=True and opponent=<module>, itself ActorCritic(env.obs_size, env.num_actions, hidden 180)): the
+        network opponent's reply rounds run inside the window kernel too (azul_batch_mp_policy_rollout_vs) -- the same keys, counters, answers
+        and trajectories as the per-cut path, opponent_selection, opponent_trace and set_opponent() included.  The opening of the games at
+        construction stays on the per-cut path; openings after episodes that end inside a window are the kernel's.  One difference: a game
+        that still owes an opponent_move() after MAX_REPLY_ROUNDS rounds ends its step with status AZUL_STUCK (unless the step already has a
+        status) instead of raising RuntimeError, as the two-player window kernel does -- raising would cost a host synchronisation per window."""
         assert n_games % parts == 0
         self.players = int(players)
         self.wide = self.players != 2 or parse_ext_rules(rules, self.players) != 0
@@ -91,7 +97,7 @@ class PolicyRollout:
             if not self.wide:
                 raise ValueError("fused_wide=True is the window kernel of batches of three / four players or extended rules; two-player reference "
                                  "batches have persistent=True")
-            if opponent is not None and not isinstance(opponent, str):
+            if opponent is not None and not isinstance(opponent, str) and not fused_opponent:
                 raise ValueError("fused_wide=True plays opponent=None or \"random\"; a network opponent runs on the per-cut path (fused_wide=False)")
             if not fused_head:
                 raise ValueError("fused_wide=True samples with azul_policy_head_n's draw: fused_head=False is the PyTorch sampling path")
@@ -102,6 +108,15 @@ class PolicyRollout:
             if shape != (n_obs, n_obs, 180, 180, n_act):
                 raise ValueError("fused_wide=True is compiled for ActorCritic(%d, %d, hidden 180) on this batch, got inputs %d / %d, hidden %d / %d "
                                  "and %d actions" % ((n_obs, n_act) + shape))
+        self.fused_opponent = bool(fused_opponent)
+        if self.fused_opponent:
+            if not self.fused_wide or opponent is None or isinstance(opponent, str):
+                raise ValueError("fused_opponent=True plays a network opponent inside the window kernel of wide batches: it needs fused_wide=True "
+                                 "and opponent=<module>")
+            if (opponent.critic_linear1.out_features, opponent.actor_linear1.out_features) != (180, 180):
+                raise ValueError("fused_opponent=True is compiled for an opponent of hidden size 180, got %d / %d; other opponents run on the "
+                                 "per-cut path (fused_opponent=False, fused_wide=False)"
+                                 % (opponent.critic_linear1.out_features, opponent.actor_linear1.out_features))
         self.opp_policy = None
         if opponent is not None and not isinstance(opponent, str):
             self.opp_policy, opponent = opponent, "net"
@@ -368,6 +383,16 @@ class PolicyRollout:
         if self.fused_wide:                                 # the whole window in one launch (+ the returns scan behind it)
             env, tr, w, pol = self.envs[p], self.traj[p], self.work[p], self.policy
             wa = L.NetWeights(*[_p(x) for x in (self.w1t, self.b1, self.w2c, pol.critic_linear2.bias, self.w2a_t, pol.actor_linear2.bias)])
+            if self.opponent == "net":                      # fused_opponent: the reply rounds inside the kernel
+                wo = L.NetWeights(*[_p(x) for x in (self.ow1t, self.ob1, self.ow2c, self.ob2c, self.ow2a_t, self.ob2a)])
+                out = L.RolloutBuffers(_p(tr["obs"]), _p(tr["mask"]), _p(tr["player"]), _p(tr["action"]), _p(tr["reward"]), _p(tr["done"]),
+                                       _p(tr["value"]), _p(tr["log_prob"]), _p(tr["entropy"]), _p(w["status"]), _p(tr["returns"]),
+                                       _p(tr["opp_action"]) if self.opp_slots else None, _p(tr["opp_logp"]) if self.opp_slots else None,
+                                       _p(tr["opp_replies"]), self.opp_slots)
+                L.check(L.lib.azul_batch_mp_policy_rollout_vs(env._h, T, C.byref(wa), C.byref(wo), self.obs_size, self.H, self.num_actions,
+                                                              self.sample_seed, self.opponent_seed, 0, _p(w["counter"]), int(self.MAX_REPLY_ROUNDS),
+                                                              C.byref(out), C.c_float(gamma), C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+                return
             out = L.RolloutBuffers(_p(tr["obs"]), _p(tr["mask"]), _p(tr["player"]), _p(tr["action"]), _p(tr["reward"]), _p(tr["done"]),
                                    _p(tr["value"]), _p(tr["log_prob"]), _p(tr["entropy"]), _p(w["status"]), _p(tr["returns"]), None, None, None, 0)
             L.check(L.lib.azul_batch_mp_policy_rollout(env._h, T, 1 if self.opponent == "random" else 0, C.byref(wa), self.obs_size, self.H,

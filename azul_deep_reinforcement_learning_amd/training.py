@@ -37,7 +37,8 @@ AGENT_STAT_KEYS = ("reward", "actor_loss", "critic_loss", "entropy_loss", "ac_lo
 class BatchedTrainer:
     def __init__(self, policy, n_games=4096, window=32, parts=1, learning_rate=3e-4, gamma=0.99, seed_base=0, sample_seed=0x5EED,
                  rules={"first_player": "Random", "tile_pool": "Lid"}, device=None, use_graph=True, persistent=True, results_dir="results",
-                 ring=3, opponent="random", opponent_refresh=0, move_limit=0, players=2, fused_wide=False):
+                 ring=3, opponent="random", opponent_refresh=0, move_limit=0, players=2, fused_wide=False,
+                 fused_opponent=False):
         """ring: trajectory windows kept (persistent rollout with one part): with ring >= 2 every step of every episode is trained
         exactly once (episodes straddle windows; an episode may span ring - 1 window boundaries), like NNRunner.train.
         opponent: "random" (GameRunner's default RandomAgent, the reference's scripts/training.py), a module (GameRunner(opponent=Agent(...)),
@@ -49,7 +50,9 @@ class BatchedTrainer:
         BatchedActorCritic(env.obs_size, env.num_actions, hidden), the rollout runs its per-move PyTorch-GEMM path -- or, with
         fused_wide=True (hidden 180, opponent "random" or None), one window kernel per part (PolicyRollout(fused_wide=True); `persistent` has
         no kernel of its own for wide batches) -- and the learner its PyTorch path (update_from_windows); checkpoints carry the wide records (runner counters included) and the RNG streams as usual.  A module
-        opponent or "self" works there too (PolicyRollout's wide network-opponent path; the opponent's weights travel in the checkpoint)."""
+        opponent or "self" works there too (PolicyRollout's wide network-opponent path; the opponent's weights travel in the checkpoint) --
+        with fused_wide=True and fused_opponent=True (opponent hidden 180) its reply rounds run inside the window kernel
+        (PolicyRollout(fused_opponent=True))."""
         from .batch import parse_ext_rules
         wide = int(players) != 2 or parse_ext_rules(rules, int(players)) != 0
         dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
@@ -64,7 +67,8 @@ class BatchedTrainer:
         self.rollout = PolicyRollout(policy, n_games=n_games, parts=parts, rules=rules, seed_base=seed_base, device=dev, window=window,
                                      use_graph=use_graph, sample_seed=sample_seed, opponent=opponent, persistent=persistent,
                                      kweights=None if wide else self.learner.kweights(dev), ring=ring if (persistent and parts == 1) else 1,
-                                     move_limit=move_limit, players=players, fused_wide=fused_wide)
+                                     move_limit=move_limit, players=players, fused_wide=fused_wide,
+                                     fused_opponent=fused_opponent)
         self.gamma = gamma
         self.results_dir = results_dir
         self.batch = 0

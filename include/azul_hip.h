@@ -420,6 +420,21 @@ int azul_batch_policy_rollout_vs(azul_batch_t *b, int n_steps, const azul_net_we
 int azul_batch_mp_policy_rollout(azul_batch_t *b, int n_steps, int opponent_random, const azul_net_weights_t *w, int num_inputs, int hidden_size,
                                  int num_actions, uint64_t seed, uint64_t counter, uint64_t *counter_dev, const azul_rollout_buffers_t *out, float gamma,
                                  void *stream);
+/* azul_batch_mp_policy_rollout with a NETWORK opponent (GameRunner(opponent=Agent(...)) for P seats; azul_batch_policy_rollout_vs for wide
+ * batches): per agent step the agent's action, then reply rounds inside the kernel while any game of a workgroup owes an opponent_move() --
+ * the other seats' replies, the agent's forced moves, after an episode end the next episode's openings (azul_batch_mp_net_step_begin /
+ * _step_reply, perspective 0 for the trajectory slots).  Round j of a step runs forward_actor of `opponent` (hidden 180: w1t columns
+ * 180..359, b1[180..359], w2a_t, b2a; its critic is not read) on the mover-perspective observation and draws with azul_policy_head_n's
+ * head under Philox key (opp_seed + j, or AZUL_POLICY_ARGMAX; counter + *counter_dev + t, game id base + game); a forward that is not
+ * finite answers -1.  After max_replies rounds a game that still owes gives up: its step ends with status AZUL_STUCK unless the step
+ * already has a status, and the window goes on.  Layouts as azul_batch_mp_policy_rollout; out->opp_action / opp_logp [T][opp_slots][N]
+ * (optional) get each round's answers of the games that owed in it (slots beyond a step's rounds are not written), out->opp_replies [T][N]
+ * (optional) the opponent moves played inside the step.  Results: bit-identical to the per-cut path (azul_policy_head_n on the opponent's
+ * logits + azul_batch_mp_net_*) wherever the network's sums are exact.  AZUL_ERR_INVALID: a two-player reference batch, a move limit,
+ * hidden_size != 180, num_inputs / num_actions not the batch's, a NULL opponent, max_replies < 1. */
+int azul_batch_mp_policy_rollout_vs(azul_batch_t *b, int n_steps, const azul_net_weights_t *agent, const azul_net_weights_t *opponent,
+                                    int num_inputs, int hidden_size, int num_actions, uint64_t seed, uint64_t opp_seed, uint64_t counter,
+                                    uint64_t *counter_dev, int max_replies, const azul_rollout_buffers_t *out, float gamma, void *stream);
 /* The same protocol one launch per cut, for opponents evaluated OUTSIDE the library (any network as PyTorch modules, or azul_policy_forward
  * on a second weight set): GameRunner.step / reset are cut at their opponent_move() calls.  pending_dev (uint8 [N], in / out) holds per
  * game 0 = nothing owed (the agent's next decision), 1 = an opponent_move() is owed inside GameRunner.step's loop (game_runner.py:46-47),

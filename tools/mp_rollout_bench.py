@@ -7,7 +7,9 @@ one host synchronisation per reply round, no HIP graph.  The line then also repo
 --fused-wide: the same run also measures PolicyRollout(fused_wide=True) (azul_batch_mp_policy_rollout: one launch per window) against the
 GEMM path with opponent "random": agent steps/s of both, the window kernel's time from HIP events around each window (the returns scan behind
 it included), and the share of the f32 matrix peak (157.3 TFLOP/s) that the FLOPs the shapes imply (2 (obs_size 360 + 180 num_actions + 180)
-per agent step) reach over that kernel time.
+per agent step) reach over that kernel time.  With --opponent self (and --configs p2_d5x ...) it measures the network opponent instead:
+PolicyRollout(fused_wide=True, fused_opponent=True) (azul_batch_mp_policy_rollout_vs: the reply rounds inside the window kernel) against the
+per-cut path, both with a frozen copy of the policy as the opponent.
 
 Usage: python tools/mp_rollout_bench.py [--games 4096] [--window 32] [--windows 20] [--hidden 180] [--opponent random self] [--configs p3_d5 ...]
                                         [--fused-wide]
@@ -32,33 +34,44 @@ CONFIGS = [
     ("p3_d7", 3, {"first_player": "Random", "tile_pool": "Lid", "displays": "2P+1"}),
     ("p4_d9", 4, {"first_player": "Random", "tile_pool": "Lid", "displays": "2P+1"}),
 ]
+# the extended-rule two-player shape: only on request (--configs p2_d5x)
+EXTRA_CONFIGS = [("p2_d5x", 2, {"first_player": "Random", "tile_pool": "Lid", "bonuses": "end"})]
 
 
 F32_MATRIX_PEAK = 157.3e12
 
 
-def fused_rate(players, rules, args):
-    """(agent steps/s, median window kernel ms, FLOP per agent step) of PolicyRollout(fused_wide=True)."""
+def fused_rate(players, rules, args, opponent="random"):
+    """(agent steps/s, median window kernel ms, FLOP per agent step, reply-round stats) of PolicyRollout(fused_wide=True); opponent "self":
+    fused_opponent=True with a frozen copy of the policy (the FLOP then count the agent's forward only)."""
     probe = MultiplayerAzul(2, rules=rules, players=players)
     torch.manual_seed(0)
     pol = BatchedActorCritic(probe.obs_size, probe.num_actions, 180)
-    ro = PolicyRollout(pol, n_games=args.games, rules=rules, window=args.window, opponent="random", players=players, fused_wide=True)
+    opp = copy.deepcopy(pol) if opponent == "self" else "random"
+    ro = PolicyRollout(pol, n_games=args.games, rules=rules, window=args.window, opponent=opp, players=players, fused_wide=True,
+                       fused_opponent=opponent == "self")
     for _ in range(3):
         ro.run_window()
     ro.synchronize()
-    ev = []
+    ev, rounds = [], []
     t0 = time.perf_counter()
     for _ in range(args.windows):
         s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         s.record(ro.streams[0])
-        ro.run_window()
+        tr = ro.run_window()
         e.record(ro.streams[0])
         ev.append((s, e))
+        if opponent == "self":
+            rounds.append(tr[0]["opp_replies"].max(dim=1).values.float())
     ro.synchronize()
     dt = time.perf_counter() - t0
     ms = sorted(s.elapsed_time(e) for s, e in ev)[len(ev) // 2]
     flop = 2 * (probe.obs_size * 360 + 180 * probe.num_actions + 180)
-    return args.games * args.window * args.windows / dt, ms, flop
+    extra = {}
+    if rounds:
+        r = torch.cat(rounds)
+        extra = {"replies_per_step_max_mean": round(float(r.mean()), 3), "replies_per_step_max": int(r.max())}
+    return args.games * args.window * args.windows / dt, ms, flop, extra
 
 
 def rollout_rate(players, rules, args, opponent):
@@ -116,15 +129,26 @@ def main():
     ap.add_argument("--windows", type=int, default=20)
     ap.add_argument("--hidden", type=int, default=180)
     ap.add_argument("--opponent", nargs="+", choices=("random", "self"), default=["random"])
-    ap.add_argument("--configs", nargs="+", choices=[c[0] for c in CONFIGS], default=[c[0] for c in CONFIGS])
+    ap.add_argument("--configs", nargs="+", choices=[c[0] for c in EXTRA_CONFIGS + CONFIGS], default=[c[0] for c in CONFIGS])
     ap.add_argument("--fused-wide", action="store_true")
     args = ap.parse_args()
+    if args.fused_wide and "self" in args.opponent:
+        for name, players, rules in EXTRA_CONFIGS + CONFIGS:
+            if name not in args.configs:
+                continue
+            cut, _, cut_extra = rollout_rate(players, rules, args, "self")
+            fused, ms, _, extra = fused_rate(players, rules, args, "self")
+            print(json.dumps({"config": name, "opponent": "self", "games": args.games, "window": args.window, "hidden": 180,
+                              "per_cut_agent_steps_per_s": round(cut), "fused_agent_steps_per_s": round(fused), "speedup": round(fused / cut, 2),
+                              "fused_window_ms_median": round(ms, 4), "fused_kernel_agent_steps_per_s": round(args.games * args.window / (ms * 1e-3)),
+                              "per_cut_reply_rounds_per_step_mean": cut_extra.get("reply_rounds_per_step_mean"), **extra}), flush=True)
+        return
     if args.fused_wide:
         for name, players, rules in CONFIGS:
             if name not in args.configs:
                 continue
             gemm, graph, _ = rollout_rate(players, rules, args, "random")
-            fused, ms, flop = fused_rate(players, rules, args)
+            fused, ms, flop, _ = fused_rate(players, rules, args)
             steps = args.games * args.window
             print(json.dumps({"config": name, "opponent": "random", "games": args.games, "window": args.window, "hidden": 180,
                               "gemm_agent_steps_per_s": round(gemm), "gemm_graph": graph, "fused_agent_steps_per_s": round(fused),
