@@ -565,6 +565,48 @@ AZ_FN void count_score2(G2 &g, const K2 &k)
     g.ok1 = ok_board2(g.cp1, g.wall1, k);
 }
 
+// Exactly one game of the wave ends its round on this move and both halves are active (wave-uniform)
+AZ_FN bool lone_round_end(bool eor)
+{
+    const u64 e = __builtin_amdgcn_ballot_w64(eor);
+    return (__builtin_amdgcn_ballot_w64(true) == ~0ull) & (((u32)e == 0u) != ((u32)(e >> 32) == 0u));
+}
+
+// value of the same lane of the OTHER half (pa = the partner's ds_bpermute byte address: (l << 2) | (h4 ^ 128))
+AZ_FN u32 hpartner(u32 v, u32 pa) { return (u32)__builtin_amdgcn_ds_bpermute((int)pa, (int)v); }
+
+// count_score2 when only ONE game of the wave ends its round (lone_round_end): instead of the ending half scoring its two players one
+// after the other while the sibling half waits, the sibling half scores a copy of the ending game's player 1 (its own game is left
+// alone: everything it computes is a temporary) and hands the results back -- one count_player2, ok_board2 and any_row_full per half.
+// The per-player steps are independent of each other except for the lid tally, which is a sum: the results are count_score2's bit for bit.
+// (The transports run unconditionally, outside any divergent region: a gather from an inactive lane would read 0.)
+template <bool LID>
+AZ_FN void count_score2_lone(G2 &g, const K2 &k, bool eor)
+{
+    const u32 pa = (k.l << 2) | (k.h4 ^ 128u);
+    const u32 wall_p = hpartner(g.wall1, pa), cp_p = hpartner(g.cp1, pa), floor_p = hpartner(g.floor1, pa), score_p = hpartner((u32)g.score1, pa),
+              mc_p = hpartner(g.mc1, pa), cl_p = hpartner(g.cl1, pa), fp_p = hpartner((u32)g.fp1, pa);
+    // the ending half: its player 0; the sibling: the ending game's player 1
+    u32 wall = eor ? g.wall0 : wall_p, cp = eor ? g.cp0 : cp_p, fl = eor ? g.floor0 : floor_p;
+    i32 score = eor ? g.score0 : (i32)score_p;
+    u32 mc = eor ? g.mc0 : mc_p, cl = eor ? g.cl0 : cl_p;
+    i32 fp = eor ? g.fp0 : (i32)fp_p;
+    u32 tally = 0;
+    count_player2<LID>(wall, cp, fl, score, mc, cl, fp, tally, k);
+    const u32 ok = ok_board2(cp, wall, k) | (any_row_full(wall) ? 0x80000000u : 0u);      // (the row test rides in bit 31)
+    const u32 wall1 = hpartner(wall, pa), cp1 = hpartner(cp, pa), score1 = hpartner((u32)score, pa), mc1 = hpartner(mc, pa),
+              cl1 = hpartner(cl, pa), fp1 = hpartner((u32)fp, pa), tally1 = hpartner(tally, pa), ok1 = hpartner(ok, pa);
+    if (eor) {
+        g.wall0 = wall; g.cp0 = cp; g.floor0 = fl; g.score0 = score; g.mc0 = mc; g.cl0 = cl; g.fp0 = fp;
+        g.wall1 = wall1; g.cp1 = cp1; g.floor1 = 0; g.score1 = (i32)score1; g.mc1 = mc1; g.cl1 = cl1; g.fp1 = (i32)fp1;
+        if (LID) g.lidp += tally + tally1;
+        g.wc0 = g.wc1 = 0; g.wi0 = g.score0; g.wi1 = g.score1;
+        g.over = (ok | ok1) >> 31;
+        g.ok0 = ok & 0x1ffffffu;
+        g.ok1 = ok1 & 0x1ffffffu;
+    }
+}
+
 // ---- new_round: azul.py:64-89 ------------------------------------------------------------------------------------------------------
 // "Lid" pool (azul.py:79-89): every draw is one random.choices over weights box_c / total -> exactly one random() = two MT words.
 // Deciding a draw.  CPython returns  #{c < 4 : cum_c <= x}  with cum_c the left-to-right fp64 sum of fl(box_j / total) and
@@ -923,10 +965,10 @@ AZ_FN u32 after_move2(G2 &g, u32 first_player, const K2 &k, Rng2 &r, u64 margin,
     // handed in with a complete wall row and the flag clear)
     bool any_done = false;
     if (AZ_UNLIKELY(wave_any(eor | (g.over != 0u)))) {
-        if (eor) {
-            count_score2<LID>(g, k);                         // :307 (also resets the what-if cache)
-            if (g.over) g.eog = 1;                           // :308-309
-        }
+        // :307 (also resets the what-if cache); a round end the wave's other game does not share is scored by both halves
+        if (lone_round_end(eor)) count_score2_lone<LID>(g, k, eor);
+        else if (eor) count_score2<LID>(g, k);
+        if (eor) { if (g.over) g.eog = 1; }                  // :308-309
         AZ_STAMP(SEG_SCORE);
         // MOVE LIMIT (beyond the reference, off unless azul_batch_set_move_limit: k.move_limit == ~0u): a round ended, the game did not, and
         // the episode has played its limit -- under the reference's rules a game can reach a state from which it NEVER ends (every tile of a
