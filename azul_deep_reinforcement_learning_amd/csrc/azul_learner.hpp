@@ -676,3 +676,406 @@ __global__ void __launch_bounds__(256) azul_a2c_apply_kernel(const float *grad, 
         P.a2b[p - (u32)LG_P_B2A] = w;
     }
 }
+
+
+// ==== the WIDE shapes ======================================================================================================
+// The A2C update of agent.py:39-62 for the WIDE network shapes ActorCritic(obs_size, num_actions, hidden 180) of
+// three- and four-player / extended-rule batches (same loss, same sums, same flat layout generalised to `IN` inputs and `A` actions):
+//     dw1t [IN][360] | db1 [360] | dw2c [180] | db2c [1] | 1 pad | dw2a_t [180][A] | db2a [A]  (+ four loss sums for a gradient)
+//
+//   azul_a2c_grad_n_kernel<IN, A>   forward + backward for tiles of 16 samples on the f32 matrix cores (v_mfma_f32_16x16x4_f32).
+//       Partition: the parameter gradient is split over THREE workgroup roles (blockIdx.y) that each recompute the
+//       forward pass of the same sample tiles and keep only their share of the weight gradient in registers:
+//           role 0  dW1t / db1 of the critic's 180 hidden columns          (dz = dv * w2c * relu', no dh GEMM)
+//           role 1  dW1t / db1 of the actor's 180 hidden columns           (dz = dlogits @ W2a * relu')
+//           role 2  dW2a_t / db2a, dw2c / db2c and the loss sums
+//       A role's tiles are spread over the 8 waves (tile w + 8 i): at most 26 (p4_d9, roles 0 / 1) or 29 (p4_d9, role 2) 16x16 tiles,
+//       116 accumulator registers per lane -- the single-workgroup layout of azul_a2c_grad_kernel would need ~310 for p4_d9.
+//       16 samples per pass keep LDS at <= 88 KB (the 32-sample layout of p4_d9 would need ~178 KB).  Weights stream from L2.
+//       p4_d9 (260 inputs, 300 actions) needs 255 VGPRs and spills 68 bytes per lane; the other shapes do not spill.
+//   azul_a2c_reduce_n_kernel        sums the per-part partials in a fixed order (deterministic) -- the three roles of part p write
+//                                   disjoint ranges of partial vector p.
+//   azul_a2c_apply_n_kernel         azul_a2c_apply_kernel's Adam step for these layouts.
+constexpr int LN_WAVES = 8, LN_M = 16, LN_HS = 388;           // samples per pass; LDS row stride of hidden / dz (361 used + tile pads)
+
+struct A2CShapeN {                   // offsets of the flat layout for (in, act); hidden 180
+    u32 in, act, b1, w2c, b2c, w2a, b2a, params;
+};
+__host__ __device__ constexpr A2CShapeN a2c_shape_n(u32 in, u32 act)
+{
+    return {in, act, in * 360u, in * 360u + 360u, in * 360u + 540u, in * 360u + 542u, in * 360u + 542u + 180u * act,
+            in * 360u + 542u + 181u * act};
+}
+
+template <int IN, int A>
+struct LnCfg {
+    static constexpr int FT = (IN + 1 + 15) / 16;              // feature tiles of dW1t (row IN = the ones column: db1)
+    static constexpr int XS = FT * 16 + 4;                     // LDS row stride of the observations
+    static constexpr int CT2 = (A + 15) / 16;                  // action tiles
+    static constexpr int AS = CT2 * 16 + 4;                    // LDS row stride of logits / dlogits
+    static constexpr int KS1 = (IN + 1 + 3) / 4;               // k-steps of layer 1 (inputs + the ones column carrying b1)
+    static constexpr int NT01 = (12 * FT + LN_WAVES - 1) / LN_WAVES, NT2 = (12 * CT2 + LN_WAVES - 1) / LN_WAVES;
+    static constexpr int NT = NT01 > NT2 ? NT01 : NT2;          // accumulator tiles per lane
+    static constexpr A2CShapeN S = a2c_shape_n(IN, A);
+};
+
+__device__ __forceinline__ float ln_sum32(float v)
+{
+    for (int o = 16; o > 0; o >>= 1) v += __shfl_xor(v, o, 32);
+    return v;
+}
+__device__ __forceinline__ float ln_max32(float v)
+{
+    for (int o = 16; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 32));
+    return v;
+}
+
+template <int IN, int A>
+__global__ void __launch_bounds__(64 * LN_WAVES) azul_a2c_grad_n_kernel(PolicyWeights W, LearnerArgs a)
+{
+    using Cf = LnCfg<IN, A>;
+    constexpr int FT = Cf::FT, XS = Cf::XS, CT2 = Cf::CT2, AS = Cf::AS, NT = Cf::NT;
+    __shared__ float xS[LN_M * XS];         // x [16][IN], column IN = 1 (bias row of dW1t), zero pads
+    __shared__ float hS[LN_M * LN_HS];      // relu h [16][360], column 360 = 1 (bias row of dW2a_t), zero pads
+    __shared__ float lgS[LN_M * AS];        // logits, then dL/dlogits
+    __shared__ float dzS[LN_M * LN_HS];     // dL/dz
+    __shared__ float w2cS[PF_HID], gw2cS[PF_HID];
+    __shared__ float valS[LN_M], dvS[LN_M], lossS[5][LN_M];
+    __shared__ u32 idxS[LN_M];
+
+    // lane constants are re-derived at the start of every phase from an opaque copy of threadIdx.x (LN_LANE, as in azul_a2c_grad_kernel):
+    // otherwise the compiler hoists every per-lane weight address out of the pass loop and spills the accumulators
+    u32 tid = threadIdx.x, c = tid & 15u, q = (tid >> 4) & 3u;
+#define LN_LANE() do { u32 t_ = threadIdx.x; asm volatile("" : "+v"(t_)); tid = t_; c = t_ & 15u; q = (t_ >> 4) & 3u; } while (0)
+    const u32 w = (u32)__builtin_amdgcn_readfirstlane((int)(tid >> 6));
+    const u32 role = blockIdx.y;
+    const u32 n = a.n_dev ? (u32)*a.n_dev : a.n, n_tiles = (n + LN_M - 1) / LN_M;
+    const float inv_n = a.inv_n_dev ? *a.inv_n_dev : a.inv_n;
+
+    for (u32 i = tid; i < (u32)(LN_M * XS); i += 64u * LN_WAVES) xS[i] = 0.f;
+    for (u32 i = tid; i < (u32)(LN_M * LN_HS); i += 64u * LN_WAVES) { hS[i] = 0.f; dzS[i] = 0.f; }
+    for (u32 i = tid; i < (u32)(LN_M * AS); i += 64u * LN_WAVES) lgS[i] = 0.f;
+    if (tid < (u32)PF_HID) { w2cS[tid] = W.w2c[tid]; gw2cS[tid] = 0.f; }
+    if (tid < 5u * LN_M) lossS[tid / LN_M][tid % LN_M] = 0.f;
+    __syncthreads();
+    if (tid < (u32)LN_M) { xS[tid * XS + IN] = 1.0f; hS[tid * LN_HS + PF_H2] = 1.0f; }
+
+    pf_f32x4 g[NT];
+#pragma unroll
+    for (int i = 0; i < NT; i++) g[i] = (pf_f32x4){0.f, 0.f, 0.f, 0.f};
+    const float b2c_v = W.b2c[0];
+
+#pragma unroll 1
+    for (u32 tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        LN_LANE();
+        // ---- P0: source rows and observations of the pass (rows past the batch: zero)
+        if (tid < (u32)LN_M) {
+            const u32 s = tile * LN_M + tid;
+            idxS[tid] = s < n ? (a.index ? (u32)a.index[s] : s) : 0xffffffffu;
+        }
+        __syncthreads();
+        for (u32 i = tid; i < (u32)(LN_M * IN); i += 64u * LN_WAVES) {
+            const u32 s = i / (u32)IN, f = i - s * (u32)IN, src = idxS[s];
+            xS[s * XS + f] = src != 0xffffffffu ? a.obs[(size_t)src * IN + f] : 0.f;
+        }
+        __syncthreads();
+        LN_LANE();
+        // ---- P1: hidden = relu([x | 1] @ [w1t ; b1]): 23 column tiles, wave w owns tiles w, w + 8, w + 16
+        {
+            pf_f32x4 acc[3];
+            for (int j = 0; j < 3; j++) acc[j] = (pf_f32x4){0.f, 0.f, 0.f, 0.f};
+            const float *ap = xS + c * XS + q;
+#pragma unroll 4
+            for (int s = 0; s < Cf::KS1; s++) {
+                const u32 k = 4u * (u32)s + q;
+                const float av = ap[4 * s];
+                for (int j = 0; j < 3; j++) {
+                    const u32 col = 16u * (w + 8u * (u32)j) + c;
+                    const float bv = col < (u32)PF_H2 ? (k < (u32)IN ? W.w1t[(size_t)k * PF_H2 + col] : (k == (u32)IN ? W.b1[col] : 0.f)) : 0.f;
+                    if (w + 8u * (u32)j < 23u) acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv, acc[j], 0, 0, 0);
+                }
+            }
+            for (int j = 0; j < 3; j++) {
+                const u32 col = 16u * (w + 8u * (u32)j) + c;
+                if (col < (u32)PF_H2)
+                    for (int rr = 0; rr < 4; rr++) { const float h = acc[j][rr]; hS[(4u * q + rr) * LN_HS + col] = h > 0.f ? h : 0.f; }
+            }
+        }
+        __syncthreads();
+        LN_LANE();
+        // ---- P2: value = h_critic . w2c + b2c (32 lanes per sample); logits = h_actor @ w2a_t + b2a (action tiles w + 8 j)
+        {
+            const u32 s = tid >> 5, l = tid & 31u;
+            float sum = 0.f;
+            for (u32 k = l; k < (u32)PF_HID; k += 32u) sum = fmaf(hS[s * LN_HS + k], w2cS[k], sum);
+            sum = ln_sum32(sum);
+            if (l == 0u) valS[s] = sum + b2c_v;
+            constexpr int J2 = (CT2 + LN_WAVES - 1) / LN_WAVES;
+            pf_f32x4 acc[J2];
+            for (int j = 0; j < J2; j++) acc[j] = (pf_f32x4){0.f, 0.f, 0.f, 0.f};
+            const float *ap = hS + c * LN_HS + PF_HID + q;
+#pragma unroll 4
+            for (int st = 0; st < PF_HID / 4; st++) {
+                const u32 k = 4u * (u32)st + q;
+                const float av = ap[4 * st];
+                for (int j = 0; j < J2; j++) {
+                    const u32 col = 16u * (w + 8u * (u32)j) + c;
+                    const float bv = col < (u32)A ? W.w2a_t[(size_t)k * A + col] : 0.f;
+                    if (w + 8u * (u32)j < (u32)CT2) acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv, acc[j], 0, 0, 0);
+                }
+            }
+            for (int j = 0; j < J2; j++) {
+                const u32 col = 16u * (w + 8u * (u32)j) + c;
+                if (col < (u32)A) {
+                    const float bb = W.b2a[col];
+                    for (int rr = 0; rr < 4; rr++) lgS[(4u * q + rr) * AS + col] = acc[j][rr] + bb;
+                }
+            }
+        }
+        __syncthreads();
+        LN_LANE();
+        // ---- P3: per sample (32 lanes): masked log-softmax, loss terms, dL/dlogits (in place), dL/dv
+        {
+            constexpr int NJ = (A + 31) / 32;
+            const u32 s = tid >> 5, l = tid & 31u, src = idxS[s];
+            const bool valid = src != 0xffffffffu;
+            const u32 sc = valid ? src : 0u;
+            const uint8_t *mp = a.mask + (size_t)sc * A;
+            const float NEG = -3.0e38f;
+            float x[NJ];
+            u32 okbits = 0;
+            float m = NEG;
+            for (int i = 0; i < NJ; i++) {
+                const u32 j = l + 32u * (u32)i;
+                const bool ok = valid && j < (u32)A && mp[j < (u32)A ? j : 0u] != 0;
+                okbits |= (ok ? 1u : 0u) << i;
+                x[i] = ok ? lgS[s * AS + j] : NEG;
+                m = fmaxf(m, x[i]);
+            }
+            m = ln_max32(m);
+            const float cnt = ln_sum32((float)__popc(okbits));
+            float e[NJ], mine = 0.f, zs = 0.f;
+            const i32 act = a.action[sc];
+            float mine_lpa = 0.f;
+            for (int i = 0; i < NJ; i++) {
+                const bool ok = (okbits >> i) & 1u;
+                const float z = ok ? x[i] - m : 0.f;
+                e[i] = ok ? __expf(z) : 0.f;
+                mine += e[i];
+                zs += z;
+                x[i] = z;
+            }
+            const float S = ln_sum32(mine), logS = __logf(S), zsum = ln_sum32(zs);
+            for (int i = 0; i < NJ; i++)
+                if ((i32)(l + 32u * (u32)i) == act && ((okbits >> i) & 1u)) mine_lpa = x[i] - logS;
+            const float logp_a = ln_sum32(mine_lpa);
+            const bool use = valid && cnt > 0.f;                   // rows without a legal action carry no sample
+            const float adv = a.qvals[sc] - valS[s];
+            const float ent_w = 0.1f / (cnt > 0.f ? cnt : 1.f);
+            const float G = -adv - 0.1f;
+            const float invS = 1.0f / S;
+            for (int i = 0; i < NJ; i++) {
+                const u32 j = l + 32u * (u32)i;
+                const bool ok = (okbits >> i) & 1u;
+                const float gj = ((i32)j == act ? -adv : 0.f) - ent_w;
+                const float d = (gj - e[i] * invS * G) * inv_n;
+                if (j < (u32)A) lgS[s * AS + j] = (use && ok) ? d : 0.f;
+            }
+            if (l == 0u) {
+                const float dv = use ? (logp_a - adv) * inv_n : 0.f;
+                dvS[s] = dv;
+                lossS[4][s] += dv;                                 // (slot s belongs to this lane alone: fixed summation order)
+                if (use) {
+                    lossS[0][s] += -logp_a * adv;
+                    lossS[1][s] += adv * adv;
+                    lossS[2][s] += -(zsum / cnt - logS);
+                    lossS[3][s] += 1.f;
+                }
+            }
+        }
+        __syncthreads();
+        LN_LANE();
+        if (role == 2u) {
+            // ---- P4 (role 2): dw2c[k] += sum_s dv[s] h[s][k];  dW2a_t[k][j] += sum_s h_actor1[s][k] dlogits[s][j]  (k = 180: db2a)
+            if (tid < (u32)PF_HID) {
+                float sw = gw2cS[tid];
+                for (int s = 0; s < LN_M; s++) sw = fmaf(dvS[s], hS[s * LN_HS + tid], sw);
+                gw2cS[tid] = sw;
+            }
+            // (one tile at a time, its four sample chunks back to back; the scheduling barrier keeps the compiler from hoisting the
+            // operands of later tiles -- the accumulators own the register file)
+#pragma unroll
+            for (int i = 0; i < NT; i++) {
+                const u32 t = w + 8u * (u32)i;
+                if (t < 12u * (u32)CT2) {
+                    const u32 kt = t % 12u, jt = t / 12u;
+                    const float *ha = hS + q * LN_HS + PF_HID + 16u * kt + c, *la = lgS + q * AS + 16u * jt + c;
+                    float av[LN_M / 4], bv[LN_M / 4];
+                    for (int mch = 0; mch < LN_M / 4; mch++) { av[mch] = ha[4 * mch * LN_HS]; bv[mch] = la[4 * mch * AS]; }
+                    for (int mch = 0; mch < LN_M / 4; mch++) g[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[mch], bv[mch], g[i], 0, 0, 0);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        } else {
+            // ---- P4 (roles 0 / 1): dz of this role's hidden half, then dW1t[f][col] += sum_s [x | 1][s][f] dz[s][col]
+            if (role == 0u) {
+                for (u32 i = tid; i < (u32)(LN_M * PF_HID); i += 64u * LN_WAVES) {
+                    const u32 s = i / (u32)PF_HID, k = i - s * (u32)PF_HID;
+                    dzS[s * LN_HS + k] = hS[s * LN_HS + k] > 0.f ? dvS[s] * w2cS[k] : 0.f;
+                }
+            } else {
+                // dh = dlogits @ W2a (actor_linear2.weight [A][180]): 12 hidden tiles, wave w owns w and w + 8
+                pf_f32x4 acc[2];
+                for (int j = 0; j < 2; j++) acc[j] = (pf_f32x4){0.f, 0.f, 0.f, 0.f};
+                const float *ap = lgS + c * AS + q;
+#pragma unroll 4
+                for (int st = 0; st < A / 4; st++) {
+                    const u32 k = 4u * (u32)st + q;
+                    const float av = ap[4 * st];
+                    for (int j = 0; j < 2; j++) {
+                        const u32 col = 16u * (w + 8u * (u32)j) + c;
+                        const float bv = col < (u32)PF_HID ? a.w2a[(size_t)k * PF_HID + col] : 0.f;
+                        if (w + 8u * (u32)j < 12u) acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv, acc[j], 0, 0, 0);
+                    }
+                }
+                for (int j = 0; j < 2; j++) {
+                    const u32 col = 16u * (w + 8u * (u32)j) + c;
+                    if (col < (u32)PF_HID)
+                        for (int rr = 0; rr < 4; rr++) {
+                            const u32 o = (4u * q + rr) * LN_HS + PF_HID + col;
+                            dzS[o] = hS[o] > 0.f ? acc[j][rr] : 0.f;
+                        }
+                }
+            }
+            __syncthreads();
+            LN_LANE();
+            const u32 ct0 = role == 0u ? 0u : 11u;                 // column tile 11 (columns 176..191) straddles the halves: both roles
+#pragma unroll
+            for (int i = 0; i < NT; i++) {
+                const u32 t = w + 8u * (u32)i;
+                if (t < 12u * (u32)FT) {
+                    const u32 ft = t % (u32)FT, ct = ct0 + t / (u32)FT;
+                    const float *xa = xS + q * XS + 16u * ft + c, *za = dzS + q * LN_HS + 16u * ct + c;
+                    float av[LN_M / 4], bv[LN_M / 4];
+                    for (int mch = 0; mch < LN_M / 4; mch++) { av[mch] = xa[4 * mch * XS]; bv[mch] = za[4 * mch * LN_HS]; }
+                    for (int mch = 0; mch < LN_M / 4; mch++) g[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[mch], bv[mch], g[i], 0, 0, 0);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+        __syncthreads();                                           // the next pass overwrites every LDS array
+    }
+
+    LN_LANE();
+    // ---- this part's share of partial vector blockIdx.x
+    constexpr A2CShapeN S = Cf::S;
+    float *out = a.partial + (size_t)blockIdx.x * (S.params + 4u);
+    if (role == 2u) {
+#pragma unroll
+        for (int i = 0; i < NT; i++) {
+            const u32 t = w + 8u * (u32)i;
+            if (t < 12u * (u32)CT2) {
+                const u32 kt = t % 12u, jt = t / 12u, j = 16u * jt + c;
+                for (int rr = 0; rr < 4; rr++) {
+                    const u32 k = 16u * kt + 4u * q + rr;
+                    if (j < (u32)A && k < (u32)PF_HID) out[S.w2a + k * A + j] = g[i][rr];
+                    else if (j < (u32)A && k == (u32)PF_HID) out[S.b2a + j] = g[i][rr];
+                }
+            }
+        }
+        if (tid < (u32)PF_HID) out[S.w2c + tid] = gw2cS[tid];
+        if (tid < 5u) {
+            float sum = 0.f;
+            for (int i = 0; i < LN_M; i++) sum += lossS[tid][i];
+            if (tid < 4u) out[S.params + tid] = sum;
+            else { out[S.b2c] = sum; out[S.b2c + 1u] = 0.f; }
+        }
+    } else {
+        const u32 lo = role == 0u ? 0u : (u32)PF_HID, hi = lo + (u32)PF_HID, ct0 = role == 0u ? 0u : 11u;
+#pragma unroll
+        for (int i = 0; i < NT; i++) {
+            const u32 t = w + 8u * (u32)i;
+            if (t < 12u * (u32)FT) {
+                const u32 ft = t % (u32)FT, col = 16u * (ct0 + t / (u32)FT) + c;
+                for (int rr = 0; rr < 4; rr++) {
+                    const u32 f = 16u * ft + 4u * q + rr;
+                    if (col >= lo && col < hi) {
+                        if (f < (u32)IN) out[f * PF_H2 + col] = g[i][rr];
+                        else if (f == (u32)IN) out[S.b1 + col] = g[i][rr];
+                    }
+                }
+            }
+        }
+    }
+}
+
+#undef LN_LANE
+
+// sum of the per-part partials in part order (deterministic); `total` floats per partial
+__global__ void __launch_bounds__(256) azul_a2c_reduce_n_kernel(const float *partial, u32 n_parts, u32 total, float *grad)
+{
+    const u32 p = blockIdx.x * 256u + threadIdx.x;
+    if (p >= total) return;
+    float s = 0.f;
+    u32 i = 0;
+    for (; i + 8u <= n_parts; i += 8u) {
+        float v[8];
+#pragma unroll
+        for (int j = 0; j < 8; j++) v[j] = partial[(size_t)(i + j) * total + p];
+#pragma unroll
+        for (int j = 0; j < 8; j++) s += v[j];
+    }
+    for (; i < n_parts; i++) s += partial[(size_t)i * total + p];
+    grad[p] = s;
+}
+
+// azul_a2c_apply_kernel for the layout of shape S (same arithmetic, same gating, same stats row)
+__global__ void __launch_bounds__(256) azul_a2c_apply_n_kernel(A2CShapeN S, const float *grad, float *flat, float *m, float *v, float lr,
+                                                               float beta1, float beta2, float eps, float bias_c1, float bias_c2_sqrt,
+                                                               ModuleParams P, const i32 *step_dev, const float *n_total_dev,
+                                                               float n_total_host, float *stats_out)
+{
+    if (stats_out && blockIdx.x == 0 && threadIdx.x == 0) {
+        const float nn = n_total_dev ? *n_total_dev : n_total_host, inv = 1.0f / (nn > 0.f ? nn : 1.0f);
+        const float la = grad[S.params] * inv, lc = grad[S.params + 1u] * inv, le = grad[S.params + 2u] * inv;
+        stats_out[0] = la; stats_out[1] = lc; stats_out[2] = le; stats_out[3] = 1.0f * la + 0.5f * lc + 0.1f * le; stats_out[4] = nn;
+    }
+    if (n_total_dev && !(*n_total_dev > 0.f)) return;
+    if (step_dev) {
+        __shared__ float bcS[2];
+        if (threadIdx.x == 0) {
+            const double st = (double)step_dev[0];
+            bcS[0] = (float)(1.0 - pow((double)beta1, st));
+            bcS[1] = (float)sqrt(1.0 - pow((double)beta2, st));
+        }
+        __syncthreads();
+        bias_c1 = bcS[0];
+        bias_c2_sqrt = bcS[1];
+    }
+    const u32 p = blockIdx.x * 256u + threadIdx.x;
+    if (p >= S.params || p == S.b2c + 1u) return;
+    const float g = grad[p];
+    const float m1 = m[p] + (g - m[p]) * (1.0f - beta1);
+    const float v1 = v[p] * beta2 + (1.0f - beta2) * g * g;
+    m[p] = m1;
+    v[p] = v1;
+    const float denom = sqrtf(v1) / bias_c2_sqrt + eps;
+    const float w = flat[p] - (lr / bias_c1) * (m1 / denom);
+    flat[p] = w;
+    if (p < S.b1) {
+        const u32 k = p / (u32)PF_H2, col = p - k * (u32)PF_H2;
+        if (col < (u32)PF_HID) P.c1w[col * S.in + k] = w; else P.a1w[(col - PF_HID) * S.in + k] = w;
+    } else if (p < S.w2c) {
+        const u32 col = p - S.b1;
+        if (col < (u32)PF_HID) P.c1b[col] = w; else P.a1b[col - PF_HID] = w;
+    } else if (p < S.b2c) {
+        P.c2w[p - S.w2c] = w;
+    } else if (p == S.b2c) {
+        P.c2b[0] = w;
+    } else if (p < S.b2a) {
+        const u32 i = p - S.w2a, k = i / S.act, j = i - k * S.act;
+        P.a2w[j * PF_HID + k] = w;
+    } else {
+        P.a2b[p - S.b2a] = w;
+    }
+}

@@ -34,15 +34,45 @@ def complete_episode_samples(done):
 
 
 N_PARAMS = 82081            # ActorCritic(136, 180, 180)
+REFERENCE_SHAPE = (136, 180, 180)                                 # (num_inputs, hidden, num_actions)
+# the wide batches' ActorCritic(obs_size, num_actions, hidden 180): three / four players on five displays, three on seven, four on nine
+WIDE_SHAPES = ((188, 180, 180), (240, 180, 180), (198, 180, 240), (260, 180, 300))
+
+
+def flat_layout(num_inputs, hidden, num_actions):
+    """Offsets (start, length) of the flat k-major layout of azul_a2c_gradients / azul_a2c_flat_size:
+    w1t [IN][2H] | b1 [2H] | w2c [H] | b2c [1] | pad | w2a_t [H][A] | b2a [A]; "size" = the float count (parameters + 1 pad)."""
+    h2 = 2 * hidden
+    b1 = num_inputs * h2
+    w2c = b1 + h2
+    b2c = w2c + hidden
+    w2a = b2c + 2
+    b2a = w2a + hidden * num_actions
+    return {"w1t": (0, b1), "b1": (b1, h2), "w2c": (w2c, hidden), "b2c": (b2c, 1), "w2a_t": (w2a, hidden * num_actions),
+            "b2a": (b2a, num_actions), "size": b2a + num_actions}
+
+
+def _policy_shape(pol):
+    if not (hasattr(pol, "critic_linear1") and hasattr(pol, "actor_linear1")):
+        return None
+    return (pol.critic_linear1.in_features, pol.critic_linear1.out_features, pol.actor_linear2.out_features)
 
 
 class A2CLearner:
     def __init__(self, policy, learning_rate=3e-4, gamma=0.99, process_group=None, distributed=None, fused=None, stat_history=4096):
         """fused=True: gradients from the hand-written kernel azul_a2c_gradients (forward + backward on the f32 matrix cores, one
-        launch + a deterministic reduction) instead of PyTorch autograd; needs CUDA tensors and the reference's network shape.
-        Default: fused whenever that is possible."""
+        launch + a deterministic reduction) and Adam from azul_a2c_apply_adam(_n) instead of PyTorch autograd and torch.optim; needs CUDA
+        tensors and a compiled network shape: the reference's ActorCritic(136, 180, 180) or one of the wide batches' WIDE_SHAPES
+        (ActorCritic(obs_size, num_actions, hidden 180) of three / four players on 5 displays, three on 7, four on 9) -- any other shape raises ValueError.
+        Default (fused=None): fused for the reference's shape only."""
         self.policy = policy
         self.fused = fused
+        shape = _policy_shape(policy)
+        if fused is True and shape != REFERENCE_SHAPE and shape not in WIDE_SHAPES:
+            raise ValueError("fused=True is compiled for ActorCritic (num_inputs, hidden, num_actions) in %s, got %s"
+                             % ((REFERENCE_SHAPE,) + WIDE_SHAPES, shape))
+        self.shape = shape
+        self.layout = flat_layout(*shape) if shape is not None else None
         self._ws = None
         self.gamma = gamma
         self.optimizer = self._own_adam = torch.optim.Adam(policy.parameters(), lr=learning_rate)        # agent.py:37
@@ -84,8 +114,8 @@ class A2CLearner:
         return actor_loss, critic_loss, entropy_loss, ac_loss
 
     # ---- hand-written gradient / optimiser path -------------------------------------------------------------------------
-    # One flat k-major vector holds the master copy of the parameters (layout of azul_a2c_gradients' gradient):
-    #     w1t [136][360] | b1 [360] | w2c [180] | b2c [1] | pad | w2a_t [180][180] | b2a [180]
+    # One flat k-major vector holds the master copy of the parameters (layout of azul_a2c_gradients' gradient; flat_layout()):
+    #     w1t [136][360] | b1 [360] | w2c [180] | b2c [1] | pad | w2a_t [180][180] | b2a [180]      (IN inputs / A actions when wide)
     # the policy / rollout kernels read views of it (kweights()), Adam's two moments use the same layout, and
     # azul_a2c_apply_adam writes every step into the flat copy AND into the eight nn.Linear tensors of the module.
     _OFF = {"w1t": (0, 136 * 360), "b1": (48960, 360), "w2c": (49320, 180), "b2c": (49500, 1), "w2a_t": (49502, 180 * 180), "b2a": (81902, 180)}
@@ -95,10 +125,13 @@ class A2CLearner:
         return (obs.is_cuda and hasattr(pol, "critic_linear1") and pol.critic_linear1.in_features == 136 and
                 pol.critic_linear1.out_features == 180 and pol.actor_linear2.out_features == 180 and pol.actor_linear1.out_features == 180)
 
+    def _use_fused(self, obs):
+        """fused=None: the reference's shape only (today's default); fused=True: any compiled shape (checked at construction)."""
+        return self._can_fuse(obs) if self.fused is None else bool(self.fused)
+
     def _ensure_flat(self, dev):
         if self._ws is None or self._ws["flat"].device != dev:
-            from . import _lib as L
-            n = L.A2C_FLAT_SIZE
+            n = self.layout["size"]
             self._ws = {"ws": torch.empty(256, n + 4, device=dev), "grad": torch.empty(n + 4, device=dev), "flat": torch.zeros(n, device=dev),
                         "m": torch.zeros(n, device=dev), "v": torch.zeros(n, device=dev),
                         "step": torch.zeros(1, dtype=torch.int32, device=dev)}        # Adam's step counter lives on the device
@@ -110,22 +143,30 @@ class A2CLearner:
         if self._ws is None:
             return
         pol, f = self.policy, self._ws["flat"]
+        v = self._views(f)
         with torch.no_grad():
-            f[0:48960].view(136, 360).copy_(torch.cat([pol.critic_linear1.weight, pol.actor_linear1.weight], dim=0).t())
-            f[48960:49320].copy_(torch.cat([pol.critic_linear1.bias, pol.actor_linear1.bias]))
-            f[49320:49500].copy_(pol.critic_linear2.weight.reshape(-1))
-            f[49500:49501].copy_(pol.critic_linear2.bias)
-            f[49502:81902].view(180, 180).copy_(pol.actor_linear2.weight.t())
-            f[81902:82082].copy_(pol.actor_linear2.bias)
+            v["w1t"].copy_(torch.cat([pol.critic_linear1.weight, pol.actor_linear1.weight], dim=0).t())
+            v["b1"].copy_(torch.cat([pol.critic_linear1.bias, pol.actor_linear1.bias]))
+            v["w2c"].copy_(pol.critic_linear2.weight.reshape(-1))
+            v["b2c"].copy_(pol.critic_linear2.bias)
+            v["w2a_t"].copy_(pol.actor_linear2.weight.t())
+            v["b2a"].copy_(pol.actor_linear2.bias)
+
+    def _views(self, f):
+        """Views of a flat vector (parameters, gradient or moments) in the kernels' layouts."""
+        IN, H, A = self.shape
+        lay = self.layout
+        v = {k: f[on[0]:on[0] + on[1]] for k, on in lay.items() if k != "size"}
+        v["w1t"] = v["w1t"].view(IN, 2 * H)
+        v["w2a_t"] = v["w2a_t"].view(H, A)
+        return v
 
     def kweights(self, device=None):
         """Views of the flat master copy in the layouts the policy kernels read (None when the fused path is unavailable)."""
         dev = device if device is not None else next(self.policy.parameters()).device
-        if torch.device(dev).type != "cuda" or not self._can_fuse(next(self.policy.parameters())) or self.fused is False:
+        if torch.device(dev).type != "cuda" or self.fused is False or (self.fused is None and not self._can_fuse(next(self.policy.parameters()))):
             return None
-        f = self._ensure_flat(torch.device(dev))["flat"]
-        return {"w1t": f[0:48960].view(136, 360), "b1": f[48960:49320], "w2c": f[49320:49500], "b2c": f[49500:49501],
-                "w2a_t": f[49502:81902].view(180, 180), "b2a": f[81902:82082]}
+        return self._views(self._ensure_flat(torch.device(dev))["flat"])
 
     def optimizer_state(self):
         """What a checkpoint needs: torch's Adam state, plus the fused path's moments and step when it is in use."""
@@ -173,7 +214,7 @@ class A2CLearner:
                 inv_host = 1.0 / float(n_total)
             L.check(L.lib.azul_a2c_gradients(p(obs), p(mask), p(action), p(qvals), int(obs.shape[0]), C.c_float(inv_host),
                                              p(kw["w1t"]), p(kw["b1"]), p(kw["w2c"]), p(kw["b2c"]), p(kw["w2a_t"]), p(kw["b2a"]),
-                                             p(pol.actor_linear2.weight), 136, 180, 180, p(ws["ws"]), 256, p(ws["grad"]), p(index), p(count),
+                                             p(pol.actor_linear2.weight), *self.shape, p(ws["ws"]), 256, p(ws["grad"]), p(index), p(count),
                                              p(inv_dev), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
             g = ws["grad"]
             if self.distributed:
@@ -208,26 +249,28 @@ class A2CLearner:
             grp = self.optimizer.param_groups[0]
             # the step counter and the "any samples at all?" test stay on the device: an update without samples (a window in which
             # no episode ended) leaves parameters, moments and step untouched
-            L.check(L.lib.azul_a2c_apply_adam(p(g), p(ws["flat"]), p(ws["m"]), p(ws["v"]), C.c_float(grp["lr"]), C.c_float(grp["betas"][0]),
-                                              C.c_float(grp["betas"][1]), C.c_float(grp["eps"]), 0,
-                                              p(pol.critic_linear1.weight), p(pol.critic_linear1.bias), p(pol.critic_linear2.weight),
-                                              p(pol.critic_linear2.bias), p(pol.actor_linear1.weight), p(pol.actor_linear1.bias),
-                                              p(pol.actor_linear2.weight), p(pol.actor_linear2.bias), p(ws["step"]), p(n_dev),
-                                              C.c_float(n_host or 0.0), p(row), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+            hp = (C.c_float(grp["lr"]), C.c_float(grp["betas"][0]), C.c_float(grp["betas"][1]), C.c_float(grp["eps"]), 0)
+            mod = (p(pol.critic_linear1.weight), p(pol.critic_linear1.bias), p(pol.critic_linear2.weight), p(pol.critic_linear2.bias),
+                   p(pol.actor_linear1.weight), p(pol.actor_linear1.bias), p(pol.actor_linear2.weight), p(pol.actor_linear2.bias))
+            tail = (p(ws["step"]), p(n_dev), C.c_float(n_host or 0.0), p(row), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+            if self.shape == REFERENCE_SHAPE:
+                L.check(L.lib.azul_a2c_apply_adam(p(g), p(ws["flat"]), p(ws["m"]), p(ws["v"]), *hp, *mod, *tail))
+            else:
+                L.check(L.lib.azul_a2c_apply_adam_n(p(g), p(ws["flat"]), p(ws["m"]), p(ws["v"]), *hp, *self.shape, *mod, *tail))
         else:
             with torch.no_grad():
-                gw1 = g[0:48960].view(136, 360)
-                gb1 = g[48960:49320]
-                pairs = [(pol.critic_linear1.weight, gw1[:, :180].t()), (pol.actor_linear1.weight, gw1[:, 180:].t()),
-                         (pol.critic_linear1.bias, gb1[:180]), (pol.actor_linear1.bias, gb1[180:]),
-                         (pol.critic_linear2.weight, g[49320:49500].view(1, 180)), (pol.critic_linear2.bias, g[49500:49501]),
-                         (pol.actor_linear2.weight, g[49502:81902].view(180, 180).t()), (pol.actor_linear2.bias, g[81902:82082])]
+                gv = self._views(g)
+                gw1, gb1, H = gv["w1t"], gv["b1"], self.shape[1]
+                pairs = [(pol.critic_linear1.weight, gw1[:, :H].t()), (pol.actor_linear1.weight, gw1[:, H:].t()),
+                         (pol.critic_linear1.bias, gb1[:H]), (pol.actor_linear1.bias, gb1[H:]),
+                         (pol.critic_linear2.weight, gv["w2c"].view(1, H)), (pol.critic_linear2.bias, gv["b2c"]),
+                         (pol.actor_linear2.weight, gv["w2a_t"].t()), (pol.actor_linear2.bias, gv["b2a"])]
                 for prm, grad in pairs:
                     if prm.grad is None:
                         prm.grad = torch.empty_like(prm)
                     prm.grad.copy_(grad)
                 # the loss terms the optimiser kernel would have written (this branch is the uncommon one: a few small launches)
-                o = L.A2C_FLAT_SIZE
+                o = self.layout["size"]
                 nn = n_dev.reshape(1).to(torch.float32) if n_dev is not None else torch.full((1,), float(n_host), device=dev)
                 row[0:3] = g[o:o + 3] / nn.clamp(min=1.0)
                 row[3] = ACTOR_COEFF * row[0] + CRITIC_COEFF * row[1] + ENTROPY_COEFF * row[2]
@@ -247,7 +290,7 @@ class A2CLearner:
         n_total = n_local.clone()
         if self.distributed:
             dist.all_reduce(n_total, group=self.group)
-        use_fused = self._can_fuse(obs) if self.fused is None else bool(self.fused)
+        use_fused = self._use_fused(obs)
         if use_fused:
             return self._finish_fused(*self._fused_gradients(obs, mask, action, qvals, n_total=float(n_total)))
         # rows without a legal action (stuck games) carry no sample
@@ -277,10 +320,11 @@ class A2CLearner:
         steps recorded in earlier windows, whose returns run_window has chained backwards through the ring -- and
         azul_a2c_gradients reads them through the index list straight from the ring.  Steps whose episode outlives the ring
         (longer than (ring - 1) * window + 1 agent steps) are dropped and counted in `dropped_steps[1]`.
+        The same holds for a wide rollout (PolicyRollout(fused_wide=True, wide_ring >= 2)) and a fused learner of its shape.
         Otherwise (ring == 1, several parts, PyTorch path): update_from_windows on the newest window."""
         ro = rollout
         tr0 = ro.traj[0]
-        if ro.ring < 2 or ro.parts != 1 or not (self._can_fuse(tr0["obs"]) if self.fused is None else bool(self.fused)):
+        if ro.ring < 2 or ro.parts != 1 or not self._use_fused(tr0["obs"]):
             return self.update_from_windows(ro.traj)
         import ctypes as C
         from . import _lib as L
@@ -342,7 +386,7 @@ class A2CLearner:
         With one part on the GPU the whole update stays on the device: azul_select_complete_samples picks the steps,
         azul_a2c_gradients reads them through the index list -- no compaction copies, no host round trip."""
         tr0 = trajectories[0]
-        if len(trajectories) == 1 and complete_only and (self._can_fuse(tr0["obs"]) if self.fused is None else bool(self.fused)):
+        if len(trajectories) == 1 and complete_only and self._use_fused(tr0["obs"]):
             import ctypes as C
             from . import _lib as L
             T, N = tr0["action"].shape

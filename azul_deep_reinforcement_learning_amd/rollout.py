@@ -40,7 +40,7 @@ class PolicyRollout:
     def __init__(self, policy, n_games=4096, parts=1, rules={"first_player": "Random", "tile_pool": "Lid"}, seed_base=0,
                  device=None, window=32, use_graph=True, fused_head=True, sample_seed=0x5EED, opponent=None, fused_mlp=True, persistent=False,
                  action_selection="Distribution", kweights=None, game_id_base=None, ring=1, opponent_selection="Distribution",
-                 opponent_seed=None, opponent_trace=0, move_limit=0, players=2, fused_wide=False, fused_opponent=False):
+                 opponent_seed=None, opponent_trace=0, move_limit=0, players=2, fused_wide=False, fused_opponent=False, wide_ring=1):
         """opponent=None: the policy moves for both players (flat self-play, one record per env move).
         opponent="random": the reference's training setup -- the policy is player 1 of GameRunner, the opponent a RandomAgent
         inside the env step (game_runner.py:43-47); one record per AGENT step, observations from the agent's perspective.
@@ -72,7 +72,12 @@ class PolicyRollout:
         `fused_wide=True` (wide batches, opponent=None | "random", ActorCritic(env.obs_size, env.num_actions, hidden 180), fused_head): each
         window is ONE launch per part (azul_batch_mp_policy_rollout: env, network on the f32 matrix cores and azul_policy_head_n's draw inside
         one kernel) instead of the per-move GEMMs + head + env launches; the same trajectories (the network's sums in another order: the same
-        bits wherever they are exact), `ring` stays 1.  Anything else with fused_wide=True raises ValueError.
+        bits wherever they are exact).  Anything else with fused_wide=True raises ValueError.
+        `wide_ring` = k >= 2 (fused_wide=True, one part): the ring of the two-player persistent path for wide batches -- each window kernel
+        writes the next window of a ring of k windows (`ring` = k), and azul_discounted_returns_ring chains the returns back through it, so
+        that A2CLearner.update_from_rollout trains every step of every episode once.  The default k = 1 keeps `ring` at 1.
+        `kweights` with fused_wide=True: the k-major weights of a fused A2CLearner of the policy's shape (A2CLearner.kweights(): one copy
+        serves rollout and learner); other wide rollouts ignore it.
         `fused_opponent=True` (with fused_wide=True and opponent=<module>, itself ActorCritic(env.obs_size, env.num_actions, hidden 180)): the
         network opponent's reply rounds run inside the window kernel too (azul_batch_mp_policy_rollout_vs) -- the same keys, counters, answers
         and trajectories as the per-cut path, opponent_selection, opponent_trace and set_opponent() included.  The opening of the games at
@@ -108,6 +113,10 @@ class PolicyRollout:
             if shape != (n_obs, n_obs, 180, 180, n_act):
                 raise ValueError("fused_wide=True is compiled for ActorCritic(%d, %d, hidden 180) on this batch, got inputs %d / %d, hidden %d / %d "
                                  "and %d actions" % ((n_obs, n_act) + shape))
+        if int(wide_ring) < 1:
+            raise ValueError("wide_ring must be >= 1")
+        if int(wide_ring) >= 2 and (not self.fused_wide or parts != 1):
+            raise ValueError("wide_ring >= 2 is the trajectory ring of the wide window kernel: it needs fused_wide=True and parts=1")
         self.fused_opponent = bool(fused_opponent)
         if self.fused_opponent:
             if not self.fused_wide or opponent is None or isinstance(opponent, str):
@@ -131,7 +140,7 @@ class PolicyRollout:
                               policy.critic_linear1.out_features == 180 and policy.actor_linear2.out_features == L.NUM_ACTIONS)
         # persistent=True: the whole window runs in ONE launch per part (azul_batch_policy_rollout); same results
         self.persistent = bool(persistent and self.fused_mlp)
-        self.ring = int(ring) if self.persistent else 1
+        self.ring = int(ring) if self.persistent else (int(wide_ring) if self.fused_wide else 1)
         assert self.ring >= 1
         self.windows_played = 0
         # Agent.get_ac_output's two modes (agent.py:64-72): sample from the masked softmax, or take its first maximum
@@ -146,8 +155,8 @@ class PolicyRollout:
         self.envs, self.streams, self.work, self.traj, self.graphs = [], [], [], [], []
         # kweights: k-major weight tensors owned by someone else (A2CLearner.kweights(): views of its flat master copy, kept current
         # by the optimiser kernel) -- then nothing is copied here and refresh_weights() has nothing to do
-        if self.wide:
-            kweights = None                                # (the 136-shaped flat copy belongs to the two-player kernels)
+        if self.wide and not self.fused_wide:
+            kweights = None                                # (the PyTorch-GEMM path keeps its own copies)
         self._external_kweights = kweights is not None
         if kweights is not None:
             self.H = policy.critic_linear1.out_features
@@ -381,24 +390,41 @@ class PolicyRollout:
     def _window(self, p, gamma):
         T = self.T
         if self.fused_wide:                                 # the whole window in one launch (+ the returns scan behind it)
-            env, tr, w, pol = self.envs[p], self.traj[p], self.work[p], self.policy
-            wa = L.NetWeights(*[_p(x) for x in (self.w1t, self.b1, self.w2c, pol.critic_linear2.bias, self.w2a_t, pol.actor_linear2.bias)])
-            if self.opponent == "net":                      # fused_opponent: the reply rounds inside the kernel
-                wo = L.NetWeights(*[_p(x) for x in (self.ow1t, self.ob1, self.ow2c, self.ob2c, self.ow2a_t, self.ob2a)])
-                out = L.RolloutBuffers(_p(tr["obs"]), _p(tr["mask"]), _p(tr["player"]), _p(tr["action"]), _p(tr["reward"]), _p(tr["done"]),
-                                       _p(tr["value"]), _p(tr["log_prob"]), _p(tr["entropy"]), _p(w["status"]), _p(tr["returns"]),
-                                       _p(tr["opp_action"]) if self.opp_slots else None, _p(tr["opp_logp"]) if self.opp_slots else None,
-                                       _p(tr["opp_replies"]), self.opp_slots)
-                L.check(L.lib.azul_batch_mp_policy_rollout_vs(env._h, T, C.byref(wa), C.byref(wo), self.obs_size, self.H, self.num_actions,
-                                                              self.sample_seed, self.opponent_seed, 0, _p(w["counter"]), int(self.MAX_REPLY_ROUNDS),
-                                                              C.byref(out), C.c_float(gamma), C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
-                return
-            out = L.RolloutBuffers(_p(tr["obs"]), _p(tr["mask"]), _p(tr["player"]), _p(tr["action"]), _p(tr["reward"]), _p(tr["done"]),
-                                   _p(tr["value"]), _p(tr["log_prob"]), _p(tr["entropy"]), _p(w["status"]), _p(tr["returns"]), None, None, None, 0)
-            L.check(L.lib.azul_batch_mp_policy_rollout(env._h, T, 1 if self.opponent == "random" else 0, C.byref(wa), self.obs_size, self.H,
-                                                       self.num_actions, self.sample_seed, 0, _p(w["counter"]), C.byref(out), C.c_float(gamma),
-                                                       C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+            if self.ring > 1:
+                self.traj[p] = self._window_views(self.rings[p], self.windows_played % self.ring)
+            self._window_wide(p, gamma)
+            if self.ring > 1:                               # returns chained back through the ring (as on the persistent path)
+                rg, R = self.rings[p], self.ring * T
+                played = (self.windows_played + 1) * T
+                L.check(L.lib.azul_discounted_returns_ring(_p(rg["reward"]), _p(rg["done"]), _p(rg["returns"]), C.c_float(gamma), R,
+                                                           played % (1 << 40), min(R, played), self.h,
+                                                           C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
             return
+        self._window_two(p, gamma)
+
+    def _window_wide(self, p, gamma):
+        T = self.T
+        env, tr, w, pol = self.envs[p], self.traj[p], self.work[p], self.policy
+        ret = _p(tr["returns"]) if self.ring == 1 else None      # ring: azul_discounted_returns_ring after the launch
+        wa = L.NetWeights(*[_p(x) for x in (self.w1t, self.b1, self.w2c, pol.critic_linear2.bias, self.w2a_t, pol.actor_linear2.bias)])
+        if self.opponent == "net":                      # fused_opponent: the reply rounds inside the kernel
+            wo = L.NetWeights(*[_p(x) for x in (self.ow1t, self.ob1, self.ow2c, self.ob2c, self.ow2a_t, self.ob2a)])
+            out = L.RolloutBuffers(_p(tr["obs"]), _p(tr["mask"]), _p(tr["player"]), _p(tr["action"]), _p(tr["reward"]), _p(tr["done"]),
+                                   _p(tr["value"]), _p(tr["log_prob"]), _p(tr["entropy"]), _p(w["status"]), ret,
+                                   _p(tr["opp_action"]) if self.opp_slots else None, _p(tr["opp_logp"]) if self.opp_slots else None,
+                                   _p(tr["opp_replies"]), self.opp_slots)
+            L.check(L.lib.azul_batch_mp_policy_rollout_vs(env._h, T, C.byref(wa), C.byref(wo), self.obs_size, self.H, self.num_actions,
+                                                          self.sample_seed, self.opponent_seed, 0, _p(w["counter"]), int(self.MAX_REPLY_ROUNDS),
+                                                          C.byref(out), C.c_float(gamma), C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+            return
+        out = L.RolloutBuffers(_p(tr["obs"]), _p(tr["mask"]), _p(tr["player"]), _p(tr["action"]), _p(tr["reward"]), _p(tr["done"]),
+                               _p(tr["value"]), _p(tr["log_prob"]), _p(tr["entropy"]), _p(w["status"]), ret, None, None, None, 0)
+        L.check(L.lib.azul_batch_mp_policy_rollout(env._h, T, 1 if self.opponent == "random" else 0, C.byref(wa), self.obs_size, self.H,
+                                                   self.num_actions, self.sample_seed, 0, _p(w["counter"]), C.byref(out), C.c_float(gamma),
+                                                   C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+
+    def _window_two(self, p, gamma):
+        T = self.T
         if self.persistent and self.ring > 1:
             wi = self.windows_played % self.ring                   # (run_window advances windows_played after all parts)
             self.traj[p] = self._window_views(self.rings[p], wi)

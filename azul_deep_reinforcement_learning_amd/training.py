@@ -38,7 +38,7 @@ class BatchedTrainer:
     def __init__(self, policy, n_games=4096, window=32, parts=1, learning_rate=3e-4, gamma=0.99, seed_base=0, sample_seed=0x5EED,
                  rules={"first_player": "Random", "tile_pool": "Lid"}, device=None, use_graph=True, persistent=True, results_dir="results",
                  ring=3, opponent="random", opponent_refresh=0, move_limit=0, players=2, fused_wide=False,
-                 fused_opponent=False):
+                 fused_opponent=False, fused_learner=False):
         """ring: trajectory windows kept (persistent rollout with one part): with ring >= 2 every step of every episode is trained
         exactly once (episodes straddle windows; an episode may span ring - 1 window boundaries), like NNRunner.train.
         opponent: "random" (GameRunner's default RandomAgent, the reference's scripts/training.py), a module (GameRunner(opponent=Agent(...)),
@@ -52,12 +52,22 @@ class BatchedTrainer:
         no kernel of its own for wide batches) -- and the learner its PyTorch path (update_from_windows); checkpoints carry the wide records (runner counters included) and the RNG streams as usual.  A module
         opponent or "self" works there too (PolicyRollout's wide network-opponent path; the opponent's weights travel in the checkpoint) --
         with fused_wide=True and fused_opponent=True (opponent hidden 180) its reply rounds run inside the window kernel
-        (PolicyRollout(fused_opponent=True))."""
+        (PolicyRollout(fused_opponent=True)).
+        fused_learner=True (wide batches, with fused_wide=True and hidden 180; anything else raises ValueError): the wide batch trains like a
+        two-player one -- PolicyRollout(wide_ring=ring) keeps the last `ring` windows, the learner is A2CLearner(fused=True) (gradients and
+        Adam on the f32 matrix cores, azul_a2c_gradients / azul_a2c_apply_adam_n) reading the ring through azul_select_episode_samples,
+        so every step of every episode is trained once, and rollout and learner share the learner's k-major weight copy.  Checkpoints then
+        carry the ring, the learner's books and the fused moments.  Default False: the wide learner stays on its PyTorch path."""
         from .batch import parse_ext_rules
         wide = int(players) != 2 or parse_ext_rules(rules, int(players)) != 0
+        fused_learner = bool(fused_learner)
+        if fused_learner and wide and not fused_wide:
+            raise ValueError("fused_learner=True trains a wide batch from the ring of its window kernel: it needs fused_wide=True")
         dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         policy = policy.to(dev)
-        self.learner = A2CLearner(policy, learning_rate=learning_rate, gamma=gamma, fused=False if wide else None)
+        wide_fused = wide and fused_learner
+        self.learner = A2CLearner(policy, learning_rate=learning_rate, gamma=gamma,
+                                  fused=(True if wide_fused else False) if wide else (True if fused_learner else None))
         # rollout kernels and learner share ONE k-major copy of the weights (the learner's flat master copy)
         self.opponent_refresh = int(opponent_refresh)
         self._self_opponent = opponent == "self"
@@ -66,9 +76,10 @@ class BatchedTrainer:
             opponent = copy.deepcopy(policy)
         self.rollout = PolicyRollout(policy, n_games=n_games, parts=parts, rules=rules, seed_base=seed_base, device=dev, window=window,
                                      use_graph=use_graph, sample_seed=sample_seed, opponent=opponent, persistent=persistent,
-                                     kweights=None if wide else self.learner.kweights(dev), ring=ring if (persistent and parts == 1) else 1,
+                                     kweights=None if (wide and not wide_fused) else self.learner.kweights(dev),
+                                     ring=ring if (persistent and parts == 1) else 1,
                                      move_limit=move_limit, players=players, fused_wide=fused_wide,
-                                     fused_opponent=fused_opponent)
+                                     fused_opponent=fused_opponent, wide_ring=ring if (wide_fused and parts == 1) else 1)
         self.gamma = gamma
         self.results_dir = results_dir
         self.batch = 0

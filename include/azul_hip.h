@@ -475,7 +475,14 @@ int azul_batch_mp_net_reset_begin(azul_batch_t *b, const uint8_t *active_dev, ui
  * AZUL_A2C_FLAT_SIZE + 4 floats: dw1t [136][360] | db1 [360] | dw2c [180] | db2c [1] | 1 pad | dw2a_t [180][180] | db2a [180] | sums
  * over the samples used of the actor / critic / entropy terms and their count.  workspace_dev: workspace_parts x that many floats (one partial per workgroup; 256 parts use
  * every CU).  Rows without a legal action carry no sample.  Optional device-side inputs: index_dev [n] (sample s is row index_dev[s]
- * of the arrays), n_samples_dev (the count; n_samples is then only an upper bound), inv_n_total_dev.  Only (136, 180, 180) is compiled in. */
+ * of the arrays), n_samples_dev (the count; n_samples is then only an upper bound), inv_n_total_dev.
+ * Compiled shapes (num_inputs, hidden_size, num_actions): the reference's (136, 180, 180), and the wide batches' ActorCritic(obs_size,
+ * num_actions, hidden 180) of azul_batch_obs_size / azul_batch_num_actions: (188, 180, 180) three players on five displays, (240, 180, 180)
+ * four players, (198, 180, 240) three players on seven displays, (260, 180, 300) four players on nine displays.  For the wide shapes the
+ * layout is azul_a2c_flat_size's (dw1t [num_inputs][360] | db1 [360] | dw2c [180] | db2c [1] | 1 pad | dw2a_t [180][num_actions] |
+ * db2a [num_actions]) + the four sums, workspace_dev holds workspace_parts x (azul_a2c_flat_size + 4) floats, and only 4-byte alignment is
+ * required (observation rows of 198 and 260 floats are 4-byte aligned only).  Same loss, sums and rules as the reference shape; the
+ * result is bit-reproducible (fixed reduction order).  Any other shape: AZUL_ERR_INVALID. */
 int azul_a2c_gradients(const float *obs_dev, const uint8_t *mask_dev, const int32_t *action_dev, const float *qvals_dev, int n_samples,
                        float inv_n_total, const float *w1t_dev, const float *b1_dev, const float *w2c_dev, const float *b2c_dev,
                        const float *w2a_t_dev, const float *b2a_dev, const float *w2a_dev, int num_inputs, int hidden_size, int num_actions,
@@ -495,6 +502,18 @@ int azul_a2c_apply_adam(const float *grad_dev, float *flat_dev, float *exp_avg_d
                         float eps, int step, float *critic1_w, float *critic1_b, float *critic2_w, float *critic2_b, float *actor1_w,
                         float *actor1_b, float *actor2_w, float *actor2_b, int32_t *step_dev, const float *n_total_dev, float n_total_host,
                         float *stats_out_dev, void *stream);
+/* Float count of the flat k-major layout of ActorCritic(num_inputs, num_actions, hidden_size) -- the parameters + 1 pad float:
+ * dw1t [num_inputs][2 hidden] | db1 [2 hidden] | dw2c [hidden] | db2c [1] | 1 pad | dw2a_t [hidden][num_actions] | db2a [num_actions]
+ * (the pad keeps dw2a_t 8-byte aligned) -- for the shapes azul_a2c_gradients compiles (AZUL_A2C_FLAT_SIZE for (136, 180, 180));
+ * AZUL_ERR_INVALID for any other shape.  Gradient buffers are this + 4 floats (the loss sums). */
+int azul_a2c_flat_size(int num_inputs, int hidden_size, int num_actions);
+/* azul_a2c_apply_adam for any shape azul_a2c_flat_size accepts: the same Adam arithmetic (torch.optim.Adam, agent.py:37), step_dev /
+ * n_total_dev gating, stats_out_dev row and write-back into the eight nn.Linear tensors (actor2_w is [num_actions][hidden], critic1_w /
+ * actor1_w [hidden][num_inputs]) on the flat layout of (num_inputs, hidden_size, num_actions).  AZUL_ERR_INVALID for other shapes. */
+int azul_a2c_apply_adam_n(const float *grad_dev, float *flat_dev, float *exp_avg_dev, float *exp_avg_sq_dev, float lr, float beta1, float beta2,
+                          float eps, int step, int num_inputs, int hidden_size, int num_actions, float *critic1_w, float *critic1_b,
+                          float *critic2_w, float *critic2_b, float *actor1_w, float *actor1_b, float *actor2_w, float *actor2_b,
+                          int32_t *step_dev, const float *n_total_dev, float n_total_host, float *stats_out_dev, void *stream);
 /* Which steps of a window feed the update (NNRunner.train uses whole episodes, nn_runner.py:59-76): the steps whose episode ends
  * inside the window and that carry an action (>= 0).  done / action are time-major [n_steps][n_games]; index_dev receives the flat
  * indices t * n_games + g (game by game, steps ascending), count_dev[0] their number.  Feeds azul_a2c_gradients' index_dev /

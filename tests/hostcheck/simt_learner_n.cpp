@@ -1,0 +1,82 @@
+// simt_learner_n.cpp -- TEST-ONLY: the wide-shape A2C kernels of csrc/azul_learner.hpp (azul_a2c_grad_n_kernel<IN, A>: three workgroup roles
+// per part, gradient tiles in registers; azul_a2c_apply_n_kernel: Adam on the shape's flat layout), UNMODIFIED, as workgroups of emulated
+// wavefronts (simt/simt.hpp) -- a CPU check of their arithmetic against torch and, under ASan / UBSan, of every LDS and global index.
+#define __HIPCC__ 1
+#include "azul_hip.h"
+#include "azul_common.hpp"
+#include "azul_tables.hpp"
+using namespace az;
+#include "azul_selfplay_kernels.hpp"
+#include "azul_policy.hpp"
+#include "azul_rollout2.hpp"
+#include "azul_learner.hpp"
+
+struct GradNJob { PolicyWeights W; LearnerArgs a; };
+template <int IN, int A>
+static void grad_n_lane(void *arg) { GradNJob *j = (GradNJob *)arg; azul_a2c_grad_n_kernel<IN, A>(j->W, j->a); }
+
+struct AdamNJob { A2CShapeN S; const float *grad; float *flat, *m, *v; float lr, b1, b2, eps, bc1, bc2s; ModuleParams P; const i32 *step; const float *nt; float *stats; };
+static void adam_n_lane(void *arg)
+{
+    AdamNJob *j = (AdamNJob *)arg;
+    azul_a2c_apply_n_kernel(j->S, j->grad, j->flat, j->m, j->v, j->lr, j->b1, j->b2, j->eps, j->bc1, j->bc2s, j->P, j->step, j->nt, 0.f, j->stats);
+}
+
+extern "C" {
+
+unsigned long long sln_buffer_oob() { return simt::g_buffer_oob; }
+int sln_flat_size(int in, int act) { return (int)a2c_shape_n((u32)in, (u32)act).params; }
+
+// azul_a2c_grad_n_kernel<in, act> on n samples with grid (parts, 3), then azul_a2c_reduce_n_kernel's sum in part order -> grad [flat + 4]
+long long sln_gradients(int in, int act, int n, int parts, const float *obs, const uint8_t *mask, const i32 *action, const float *qvals,
+                        const i32 *index, float inv_n, const float *w1t, const float *b1, const float *w2c, const float *b2c, const float *w2a_t,
+                        const float *b2a, const float *w2a, float *partial, float *grad)
+{
+    GradNJob j;
+    memset(&j, 0, sizeof(j));
+    j.W = {w1t, b1, w2c, b2c, w2a_t, b2a};
+    j.a.obs = obs; j.a.mask = mask; j.a.action = action; j.a.qvals = qvals; j.a.n = (u32)n; j.a.inv_n = inv_n; j.a.w2a = w2a;
+    j.a.partial = partial; j.a.index = index;
+    void (*fn)(void *) = nullptr;
+    if (in == 188 && act == 180) fn = grad_n_lane<188, 180>;
+    else if (in == 240 && act == 180) fn = grad_n_lane<240, 180>;
+    else if (in == 198 && act == 240) fn = grad_n_lane<198, 240>;
+    else if (in == 260 && act == 300) fn = grad_n_lane<260, 300>;
+    else return -1;
+    const u32 total = a2c_shape_n((u32)in, (u32)act).params + 4u;
+    simt::g_grid_dim = {(unsigned)parts, 3, 1};
+    long long ops = 0;
+    for (int role = 0; role < 3; role++)
+        for (int blk = 0; blk < parts; blk++) {
+            simt::g_block_idx = {(unsigned)blk, (unsigned)role, 0};
+            ops += (long long)simt::run_workgroup(fn, &j, (int)LN_WAVES, 512u << 10);
+        }
+    for (u32 p = 0; p < total; p++) {
+        float s = 0.f;
+        for (int i = 0; i < parts; i++) s += partial[(size_t)i * total + p];
+        grad[p] = s;
+    }
+    return ops;
+}
+
+// azul_a2c_apply_n_kernel (one Adam step, host-side bias corrections of step `step`)
+long long sln_adam(int in, int act, const float *grad, float *flat, float *m, float *v, float lr, float beta1, float beta2, float eps, int step,
+                   float *c1w, float *c1b, float *c2w, float *c2b, float *a1w, float *a1b, float *a2w, float *a2b)
+{
+    AdamNJob j;
+    j.S = a2c_shape_n((u32)in, (u32)act);
+    j.grad = grad; j.flat = flat; j.m = m; j.v = v; j.lr = lr; j.b1 = beta1; j.b2 = beta2; j.eps = eps;
+    j.bc1 = (float)(1.0 - pow((double)beta1, (double)step)); j.bc2s = (float)sqrt(1.0 - pow((double)beta2, (double)step));
+    j.P = {c1w, c1b, c2w, c2b, a1w, a1b, a2w, a2b};
+    j.step = nullptr; j.nt = nullptr; j.stats = nullptr;
+    const unsigned blocks = (j.S.params + 255u) / 256u;
+    simt::g_grid_dim = {blocks, 1, 1};
+    long long ops = 0;
+    for (unsigned blk = 0; blk < blocks; blk++) {
+        simt::g_block_idx = {blk, 0, 0};
+        ops += (long long)simt::run_workgroup(adam_n_lane, &j, 4);
+    }
+    return ops;
+}
+
+}
