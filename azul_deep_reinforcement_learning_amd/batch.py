@@ -69,6 +69,13 @@ def parse_ext_rules(rules, players=2):
     return flags
 
 
+def batch_shape(players, rules):
+    """(obs_size, num_actions) of a batch of `players` seats under `rules`, before there is a batch to ask: what azul_batch_obs_size /
+    azul_batch_num_actions answer (D factory displays: 5 D + 6 + 52 P + 1 observations, (D + 1) * 30 actions)."""
+    D = 2 * players + 1 if parse_ext_rules(rules, players) & L.RULE_DISPLAYS_2P1 else 5
+    return 5 * D + 6 + 52 * players + 1, (D + 1) * 30
+
+
 def ext_rules_dict(flags):
     """AZUL_RULE_* flags -> the rules-dict keys parse_ext_rules reads."""
     d = {}

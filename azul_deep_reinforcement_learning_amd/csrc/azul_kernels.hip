@@ -752,15 +752,92 @@ static int launch_rollout(azul_batch_t *b, const PolicyWeights &W, const Rollout
     return AZUL_SUCCESS;
 }
 
+struct NetShape { int inputs, hidden, actions; };
+struct DrawKeys { uint64_t seed, opp_seed, counter; uint64_t *counter_dev; };
+
+static int fail_in(const char *who, const char *what)
+{
+    g_err = std::string(who) + ": " + what;              // every message begins with the public entry that was called
+    return AZUL_ERR_INVALID;
+}
+
+// The one host path of a window launch: every azul_batch_[mp_]policy_rollout* entry packs its arguments and calls this.  `wide` = an _mp_
+// entry (the azul_x_* kernels), otherwise the two-player kernel; opp = 0 the policy moves for every seat, 1 RandomAgent seats, 2 the
+// `opponent` net.  Where the two families differ the condition says so: those differences are behaviour (include/azul_hip.h).
+static int rollout_window(azul_batch_t *b, const char *who, bool wide, int n_steps, int opp, const azul_net_weights_t *agent,
+                          const azul_net_weights_t *opponent, NetShape shape, DrawKeys keys, const azul_rollout_buffers_t *out, float gamma,
+                          int max_replies, void *stream)
+{
+    const bool net = opp == 2;
+    if (!b || n_steps < 0 || !agent || !out) return fail_in(who, "bad arguments");
+    if (net && !opponent) return fail_in(who, "no opponent (the entry without _vs plays without one)");
+    if (wide != b->x)
+        return fail_in(who, wide ? (net ? "a two-player batch of 128-byte records: use azul_batch_policy_rollout_vs"
+                                        : "a two-player batch of 128-byte records: use azul_batch_policy_rollout")
+                                 : "the policy entries are compiled for the reference's two-player game (ActorCritic(136, 180): 180 actions, 136 "
+                                   "observations; game_runner.py:50) -- not for 3 / 4 players or extended rules");
+    if (wide) {                                              // the wide kernels: no move limit, the batch's own sizes, a bound on the reply rounds
+        if (b->d.move_limit) return fail_in(who, "no move limit for wide batches");
+        if (shape.hidden != PF_HID) return fail_in(who, "only hidden size 180 is compiled in (agent and opponent)");
+        if (shape.inputs != azul_batch_obs_size(b) || shape.actions != azul_batch_num_actions(b))
+            return fail_in(who, "num_inputs / num_actions must be the batch's azul_batch_obs_size / azul_batch_num_actions");
+        if (net && max_replies < 1) return fail_in(who, "max_replies must be at least 1");
+    } else if (shape.inputs != PF_IN || shape.hidden != PF_HID || shape.actions != PF_ACT)
+        return fail_in(who, "only ActorCritic(136, 180, hidden 180) is compiled in");
+    if (!agent->w1t || !agent->b1 || !agent->w2c || !agent->b2c || !agent->w2a_t || !agent->b2a || !out->obs || !out->mask || !out->player ||
+        !out->action || !out->reward || !out->done || !out->value || !out->logp || !out->entropy ||
+        (net && (!opponent->w1t || !opponent->b1 || !opponent->w2a_t || !opponent->b2a)))      // only forward_actor's half of the opponent is read
+        return fail_in(who, "NULL pointer");
+    if (wide) {                                              // rows of 198 or 260 floats are not 16-byte aligned
+        if (((uintptr_t)out->obs & 3u) != 0 || ((uintptr_t)out->mask & 3u) != 0) return fail_in(who, "obs and mask must be 4-byte aligned");
+    } else {
+        if (net ? (((uintptr_t)agent->w1t & 15u) != 0 || ((uintptr_t)opponent->w1t & 15u) != 0 || ((uintptr_t)agent->w2a_t & 7u) != 0 ||
+                   ((uintptr_t)opponent->w2a_t & 7u) != 0)
+                : ((uintptr_t)agent->w1t & 7u) != 0)        // the flat entries ask for less than _vs: kept as each documents it
+            return fail_in(who, net ? "w1t must be 16-byte aligned, w2a_t 8-byte aligned" : "w1t_dev must be 8-byte aligned");
+        if (((uintptr_t)out->obs & 15u) != 0 || ((uintptr_t)out->mask & 3u) != 0)
+            return fail_in(who, "obs must be 16-byte aligned, mask 4-byte aligned");
+    }
+    if (net && (out->opp_action || out->opp_logp) && out->opp_slots <= 0) return fail_in(who, "opp_slots must be positive with a trace");
+    if (wide && n_steps == 0) return AZUL_SUCCESS;           // (the two-player kernel is launched with an empty window too: it writes slot 0)
+    const PolicyWeights W = {agent->w1t, agent->b1, agent->w2c, agent->b2c, agent->w2a_t, agent->b2a};
+    // returns: the two-player kernel writes a window of up to 32 steps itself (it keeps the rewards in 32 lanes); the wide kernels never do
+    RolloutArgs a = {n_steps, out->obs, out->mask, out->player, out->action, out->reward, out->done, out->value, out->logp, out->entropy, out->status,
+                     wide ? nullptr : out->returns, gamma, (u64)keys.seed, (u64)keys.counter, (u64 *)keys.counter_dev};
+    if (net) {                                               // (without a network opponent the opponent fields of `out` are ignored)
+        a.Wopp = {opponent->w1t, opponent->b1, opponent->w2c, opponent->b2c, opponent->w2a_t, opponent->b2a};
+        a.opp_seed = (u64)keys.opp_seed;
+        a.opp_action = out->opp_action; a.opp_logp = out->opp_logp; a.opp_replies = out->opp_replies; a.opp_slots = out->opp_slots;
+    }
+    if (!wide) {
+        const int rc = launch_rollout(b, W, a, opp, stream);
+        if (rc != AZUL_SUCCESS) return rc;
+    } else {
+        const dim3 grid((b->d.n + PF_GAMES - 1) / PF_GAMES), block(64 * PR2_WAVES);
+        const hipStream_t st = (hipStream_t)stream;
+        const azx::XBatchDev xb = xdev(b);
+        const u32 id_base = b->d.id_base;
+        if (net) AZ_X_DISPATCH(b, hipLaunchKernelGGL((azul_x_policy_rollout_vs_kernel<PP, DD>), grid, block, 0, st, xb, W, a, id_base, (u32)max_replies));
+        else if (opp) AZ_X_DISPATCH(b, hipLaunchKernelGGL((azul_x_policy_rollout_kernel<PP, DD, 1>), grid, block, 0, st, xb, W, a, id_base));
+        else AZ_X_DISPATCH(b, hipLaunchKernelGGL((azul_x_policy_rollout_kernel<PP, DD, 0>), grid, block, 0, st, xb, W, a, id_base));
+        HIP_TRY(hipGetLastError());
+    }
+    if (out->returns && (wide || n_steps > 32))              // the window's discounted returns behind the kernel: the per-move path's own scan
+        return azul_discounted_returns(out->reward, out->done, out->returns, nullptr, gamma, n_steps, (int)b->d.n, stream);
+    return AZUL_SUCCESS;
+}
+
 int azul_batch_policy_rollout(azul_batch_t *b, int n_steps, int opponent_random, const float *w1t_dev, const float *b1_dev,
                               const float *w2c_dev, const float *b2c_dev, const float *w2a_t_dev, const float *b2a_dev, int num_inputs,
                               int hidden_size, int num_actions, uint64_t seed, uint64_t counter, uint64_t *counter_dev, float *obs_dev,
                               uint8_t *mask_dev, uint8_t *player_dev, int32_t *action_dev, int32_t *reward_dev, uint8_t *done_dev,
                               float *value_dev, float *logp_dev, float *entropy_dev, uint8_t *status_dev, void *stream)
 {
-    return azul_batch_policy_rollout_returns(b, n_steps, opponent_random, w1t_dev, b1_dev, w2c_dev, b2c_dev, w2a_t_dev, b2a_dev, num_inputs, hidden_size,
-                                             num_actions, seed, counter, counter_dev, obs_dev, mask_dev, player_dev, action_dev, reward_dev, done_dev,
-                                             value_dev, logp_dev, entropy_dev, status_dev, nullptr, 0.f, stream);
+    BATCH_GUARD(b, stream);
+    const azul_net_weights_t w = {w1t_dev, b1_dev, w2c_dev, b2c_dev, w2a_t_dev, b2a_dev};
+    const azul_rollout_buffers_t out = {obs_dev, mask_dev, player_dev, action_dev, reward_dev, done_dev, value_dev, logp_dev, entropy_dev, status_dev};
+    return rollout_window(b, "azul_batch_policy_rollout", false, n_steps, opponent_random ? 1 : 0, &w, nullptr, {num_inputs, hidden_size, num_actions},
+                          {seed, 0, counter, counter_dev}, &out, 0.f, 0, stream);
 }
 
 int azul_batch_policy_rollout_returns(azul_batch_t *b, int n_steps, int opponent_random, const float *w1t_dev, const float *b1_dev,
@@ -771,24 +848,11 @@ int azul_batch_policy_rollout_returns(azul_batch_t *b, int n_steps, int opponent
                                       void *stream)
 {
     BATCH_GUARD(b, stream);
-    if (!b || n_steps < 0) return fail(AZUL_ERR_INVALID, "azul_batch_policy_rollout: bad arguments");
-    if (b->x) return fail(AZUL_ERR_INVALID, "azul_batch_policy_rollout: the policy entries are compiled for the reference's two-player game "
-                                            "(ActorCritic(136, 180): 180 actions, 136 observations; game_runner.py:50) -- not for 3 / 4 players or extended rules");
-    if (num_inputs != PF_IN || hidden_size != PF_HID || num_actions != PF_ACT)
-        return fail(AZUL_ERR_INVALID, "azul_batch_policy_rollout: only ActorCritic(136, 180, hidden 180) is compiled in");
-    if (!w1t_dev || !b1_dev || !w2c_dev || !b2c_dev || !w2a_t_dev || !b2a_dev || !obs_dev || !mask_dev || !player_dev || !action_dev ||
-        !reward_dev || !done_dev || !value_dev || !logp_dev || !entropy_dev)
-        return fail(AZUL_ERR_INVALID, "azul_batch_policy_rollout: NULL pointer");
-    if (((uintptr_t)w1t_dev & 7u) != 0) return fail(AZUL_ERR_INVALID, "azul_batch_policy_rollout: w1t_dev must be 8-byte aligned");
-    if (((uintptr_t)obs_dev & 15u) != 0 || ((uintptr_t)mask_dev & 3u) != 0)
-        return fail(AZUL_ERR_INVALID, "azul_batch_policy_rollout: obs_dev must be 16-byte aligned, mask_dev 4-byte aligned");
-    PolicyWeights W = {w1t_dev, b1_dev, w2c_dev, b2c_dev, w2a_t_dev, b2a_dev};
-    RolloutArgs a = {n_steps, obs_dev, mask_dev, player_dev, action_dev, reward_dev, done_dev, value_dev, logp_dev, entropy_dev, status_dev,
-                     returns_dev, gamma, (u64)seed, (u64)counter, (u64 *)counter_dev};
-    int rc = launch_rollout(b, W, a, opponent_random ? 1 : 0, stream);
-    if (rc == AZUL_SUCCESS && returns_dev && n_steps > 32)       // the kernel keeps a window's rewards in 32 lanes: longer windows get the separate scan
-        return azul_discounted_returns(reward_dev, done_dev, returns_dev, nullptr, gamma, n_steps, (int)b->d.n, stream);
-    return rc;
+    const azul_net_weights_t w = {w1t_dev, b1_dev, w2c_dev, b2c_dev, w2a_t_dev, b2a_dev};
+    const azul_rollout_buffers_t out = {obs_dev, mask_dev, player_dev, action_dev, reward_dev, done_dev, value_dev, logp_dev, entropy_dev, status_dev,
+                                        returns_dev};
+    return rollout_window(b, "azul_batch_policy_rollout_returns", false, n_steps, opponent_random ? 1 : 0, &w, nullptr,
+                          {num_inputs, hidden_size, num_actions}, {seed, 0, counter, counter_dev}, &out, gamma, 0, stream);
 }
 
 /* GameRunner(opponent=Agent(...)) inside the persistent rollout (game_runner.py:27-30, 37-47, 84-85; scripts/run_batch.py:6-10) */
@@ -797,28 +861,8 @@ int azul_batch_policy_rollout_vs(azul_batch_t *b, int n_steps, const azul_net_we
                                  const azul_rollout_buffers_t *out, float gamma, void *stream)
 {
     BATCH_GUARD(b, stream);
-    if (!b || n_steps < 0 || !agent || !opponent || !out) return fail(AZUL_ERR_INVALID, "azul_batch_policy_rollout_vs: bad arguments");
-    if (b->x) return fail(AZUL_ERR_INVALID, "azul_batch_policy_rollout_vs: the policy entries are compiled for the reference's two-player game");
-    if (num_inputs != PF_IN || hidden_size != PF_HID || num_actions != PF_ACT)
-        return fail(AZUL_ERR_INVALID, "azul_batch_policy_rollout_vs: only ActorCritic(136, 180, hidden 180) is compiled in");
-    if (!agent->w1t || !agent->b1 || !agent->w2c || !agent->b2c || !agent->w2a_t || !agent->b2a || !opponent->w1t || !opponent->b1 || !opponent->w2a_t ||
-        !opponent->b2a || !out->obs || !out->mask || !out->player || !out->action || !out->reward || !out->done || !out->value || !out->logp || !out->entropy)
-        return fail(AZUL_ERR_INVALID, "azul_batch_policy_rollout_vs: NULL pointer");
-    if (((uintptr_t)agent->w1t & 15u) != 0 || ((uintptr_t)opponent->w1t & 15u) != 0 || ((uintptr_t)agent->w2a_t & 7u) != 0 || ((uintptr_t)opponent->w2a_t & 7u) != 0)
-        return fail(AZUL_ERR_INVALID, "azul_batch_policy_rollout_vs: w1t must be 16-byte aligned, w2a_t 8-byte aligned");
-    if (((uintptr_t)out->obs & 15u) != 0 || ((uintptr_t)out->mask & 3u) != 0)
-        return fail(AZUL_ERR_INVALID, "azul_batch_policy_rollout_vs: obs must be 16-byte aligned, mask 4-byte aligned");
-    if ((out->opp_action || out->opp_logp) && out->opp_slots <= 0) return fail(AZUL_ERR_INVALID, "azul_batch_policy_rollout_vs: opp_slots must be positive with a trace");
-    PolicyWeights W = {agent->w1t, agent->b1, agent->w2c, agent->b2c, agent->w2a_t, agent->b2a};
-    RolloutArgs a = {n_steps, out->obs, out->mask, out->player, out->action, out->reward, out->done, out->value, out->logp, out->entropy, out->status,
-                     out->returns, gamma, (u64)seed, (u64)counter, (u64 *)counter_dev};
-    a.Wopp = {opponent->w1t, opponent->b1, opponent->w2c, opponent->b2c, opponent->w2a_t, opponent->b2a};
-    a.opp_seed = (u64)opponent_seed;
-    a.opp_action = out->opp_action; a.opp_logp = out->opp_logp; a.opp_replies = out->opp_replies; a.opp_slots = out->opp_slots;
-    int rc = launch_rollout(b, W, a, 2, stream);
-    if (rc == AZUL_SUCCESS && out->returns && n_steps > 32)
-        return azul_discounted_returns(out->reward, out->done, out->returns, nullptr, gamma, n_steps, (int)b->d.n, stream);
-    return rc;
+    return rollout_window(b, "azul_batch_policy_rollout_vs", false, n_steps, 2, agent, opponent, {num_inputs, hidden_size, num_actions},
+                          {seed, opponent_seed, counter, counter_dev}, out, gamma, 0, stream);
 }
 
 /* GameRunner / flat self-play of wide batches inside one launch per window (azul_x_policy_rollout_kernel) */
@@ -827,34 +871,8 @@ int azul_batch_mp_policy_rollout(azul_batch_t *b, int n_steps, int opponent_rand
                                  void *stream)
 {
     BATCH_GUARD(b, stream);
-    if (!b || n_steps < 0 || !w || !out) return fail(AZUL_ERR_INVALID, "azul_batch_mp_policy_rollout: bad arguments");
-    if (!b->x) return fail(AZUL_ERR_INVALID, "azul_batch_mp_policy_rollout: a two-player batch of 128-byte records: use azul_batch_policy_rollout");
-    if (b->d.move_limit) return fail(AZUL_ERR_INVALID, "azul_batch_mp_policy_rollout: no move limit for wide batches");
-    if (hidden_size != PF_HID) return fail(AZUL_ERR_INVALID, "azul_batch_mp_policy_rollout: only hidden size 180 is compiled in");
-    if (num_inputs != azul_batch_obs_size(b) || num_actions != azul_batch_num_actions(b))
-        return fail(AZUL_ERR_INVALID, "azul_batch_mp_policy_rollout: num_inputs / num_actions must be the batch's azul_batch_obs_size / azul_batch_num_actions");
-    if (!w->w1t || !w->b1 || !w->w2c || !w->b2c || !w->w2a_t || !w->b2a || !out->obs || !out->mask || !out->player || !out->action || !out->reward ||
-        !out->done || !out->value || !out->logp || !out->entropy)
-        return fail(AZUL_ERR_INVALID, "azul_batch_mp_policy_rollout: NULL pointer");
-    if (((uintptr_t)out->obs & 3u) != 0 || ((uintptr_t)out->mask & 3u) != 0)
-        return fail(AZUL_ERR_INVALID, "azul_batch_mp_policy_rollout: obs and mask must be 4-byte aligned");
-    if (n_steps == 0) return AZUL_SUCCESS;
-    PolicyWeights W = {w->w1t, w->b1, w->w2c, w->b2c, w->w2a_t, w->b2a};
-    RolloutArgs a;
-    memset(&a, 0, sizeof(a));
-    a.n_steps = n_steps; a.obs = out->obs; a.mask = out->mask; a.player = out->player; a.action = out->action; a.reward = out->reward;
-    a.done = out->done; a.value = out->value; a.logp = out->logp; a.entropy = out->entropy; a.status = out->status; a.returns = nullptr;
-    a.gamma = gamma; a.seed = (u64)seed; a.counter = (u64)counter; a.counter_dev = (u64 *)counter_dev;
-    const dim3 grid((b->d.n + PF_GAMES - 1) / PF_GAMES), block(64 * PR2_WAVES);
-    const hipStream_t st = (hipStream_t)stream;
-    const azx::XBatchDev xb = xdev(b);
-    const u32 id_base = b->d.id_base;
-    if (opponent_random) AZ_X_DISPATCH(b, hipLaunchKernelGGL((azul_x_policy_rollout_kernel<PP, DD, 1>), grid, block, 0, st, xb, W, a, id_base));
-    else AZ_X_DISPATCH(b, hipLaunchKernelGGL((azul_x_policy_rollout_kernel<PP, DD, 0>), grid, block, 0, st, xb, W, a, id_base));
-    HIP_TRY(hipGetLastError());
-    if (out->returns)                                    // the window's discounted returns: the per-move path's own scan
-        return azul_discounted_returns(out->reward, out->done, out->returns, nullptr, gamma, n_steps, (int)b->d.n, stream);
-    return AZUL_SUCCESS;
+    return rollout_window(b, "azul_batch_mp_policy_rollout", true, n_steps, opponent_random ? 1 : 0, w, nullptr, {num_inputs, hidden_size, num_actions},
+                          {seed, 0, counter, counter_dev}, out, gamma, 0, stream);
 }
 
 /* GameRunner with a network opponent for wide batches inside one launch per window (azul_x_policy_rollout_vs_kernel) */
@@ -863,40 +881,8 @@ int azul_batch_mp_policy_rollout_vs(azul_batch_t *b, int n_steps, const azul_net
                                     int max_replies, const azul_rollout_buffers_t *out, float gamma, void *stream)
 {
     BATCH_GUARD(b, stream);
-    if (!b || n_steps < 0 || !agent || !out) return fail(AZUL_ERR_INVALID, "azul_batch_mp_policy_rollout_vs: bad arguments");
-    if (!opponent) return fail(AZUL_ERR_INVALID, "azul_batch_mp_policy_rollout_vs: no opponent (azul_batch_mp_policy_rollout plays without one)");
-    if (!b->x) return fail(AZUL_ERR_INVALID, "azul_batch_mp_policy_rollout_vs: a two-player batch of 128-byte records: use azul_batch_policy_rollout_vs");
-    if (b->d.move_limit) return fail(AZUL_ERR_INVALID, "azul_batch_mp_policy_rollout_vs: no move limit for wide batches");
-    if (hidden_size != PF_HID) return fail(AZUL_ERR_INVALID, "azul_batch_mp_policy_rollout_vs: only hidden size 180 is compiled in (agent and opponent)");
-    if (num_inputs != azul_batch_obs_size(b) || num_actions != azul_batch_num_actions(b))
-        return fail(AZUL_ERR_INVALID, "azul_batch_mp_policy_rollout_vs: num_inputs / num_actions must be the batch's azul_batch_obs_size / azul_batch_num_actions");
-    if (max_replies < 1) return fail(AZUL_ERR_INVALID, "azul_batch_mp_policy_rollout_vs: max_replies must be at least 1");
-    if (!agent->w1t || !agent->b1 || !agent->w2c || !agent->b2c || !agent->w2a_t || !agent->b2a || !opponent->w1t || !opponent->b1 || !opponent->w2a_t ||
-        !opponent->b2a || !out->obs || !out->mask || !out->player || !out->action || !out->reward || !out->done || !out->value || !out->logp || !out->entropy)
-        return fail(AZUL_ERR_INVALID, "azul_batch_mp_policy_rollout_vs: NULL pointer");
-    if (((uintptr_t)out->obs & 3u) != 0 || ((uintptr_t)out->mask & 3u) != 0)
-        return fail(AZUL_ERR_INVALID, "azul_batch_mp_policy_rollout_vs: obs and mask must be 4-byte aligned");
-    if ((out->opp_action || out->opp_logp) && out->opp_slots <= 0)
-        return fail(AZUL_ERR_INVALID, "azul_batch_mp_policy_rollout_vs: opp_slots must be positive with a trace");
-    if (n_steps == 0) return AZUL_SUCCESS;
-    PolicyWeights W = {agent->w1t, agent->b1, agent->w2c, agent->b2c, agent->w2a_t, agent->b2a};
-    RolloutArgs a;
-    memset(&a, 0, sizeof(a));
-    a.n_steps = n_steps; a.obs = out->obs; a.mask = out->mask; a.player = out->player; a.action = out->action; a.reward = out->reward;
-    a.done = out->done; a.value = out->value; a.logp = out->logp; a.entropy = out->entropy; a.status = out->status; a.returns = nullptr;
-    a.gamma = gamma; a.seed = (u64)seed; a.counter = (u64)counter; a.counter_dev = (u64 *)counter_dev;
-    a.Wopp = {opponent->w1t, opponent->b1, opponent->w2c, opponent->b2c, opponent->w2a_t, opponent->b2a};
-    a.opp_seed = (u64)opp_seed;
-    a.opp_action = out->opp_action; a.opp_logp = out->opp_logp; a.opp_replies = out->opp_replies; a.opp_slots = out->opp_slots;
-    const dim3 grid((b->d.n + PF_GAMES - 1) / PF_GAMES), block(64 * PR2_WAVES);
-    const hipStream_t st = (hipStream_t)stream;
-    const azx::XBatchDev xb = xdev(b);
-    const u32 id_base = b->d.id_base;
-    AZ_X_DISPATCH(b, hipLaunchKernelGGL((azul_x_policy_rollout_vs_kernel<PP, DD>), grid, block, 0, st, xb, W, a, id_base, (u32)max_replies));
-    HIP_TRY(hipGetLastError());
-    if (out->returns)                                    // the window's discounted returns: the per-move path's own scan
-        return azul_discounted_returns(out->reward, out->done, out->returns, nullptr, gamma, n_steps, (int)b->d.n, stream);
-    return AZUL_SUCCESS;
+    return rollout_window(b, "azul_batch_mp_policy_rollout_vs", true, n_steps, 2, agent, opponent, {num_inputs, hidden_size, num_actions},
+                          {seed, opp_seed, counter, counter_dev}, out, gamma, max_replies, stream);
 }
 
 /* the wide shapes of azul_learner.hpp: (obs_size, num_actions) of p3_d5, p4_d5, p3_d7, p4_d9; hidden 180 */
@@ -912,15 +898,13 @@ int azul_a2c_flat_size(int num_inputs, int hidden_size, int num_actions)
 #define AZ_LN_DISPATCH(IN_, A_, launch) \
     if (num_inputs == IN_ && num_actions == A_) { constexpr int LN_IN = IN_, LN_A = A_; launch; }
 
+// (azul_a2c_gradients, its only caller, has checked the arguments)
 static int a2c_gradients_n(const float *obs_dev, const uint8_t *mask_dev, const int32_t *action_dev, const float *qvals_dev, int n_samples,
                            float inv_n_total, const float *w1t_dev, const float *b1_dev, const float *w2c_dev, const float *b2c_dev,
                            const float *w2a_t_dev, const float *b2a_dev, const float *w2a_dev, int num_inputs, int num_actions,
                            float *workspace_dev, int workspace_parts, float *grad_dev, const int32_t *index_dev, const int32_t *n_samples_dev,
                            const float *inv_n_total_dev, void *stream)
 {
-    if (!w1t_dev || !b1_dev || !w2c_dev || !b2c_dev || !w2a_t_dev || !b2a_dev || !w2a_dev || !workspace_dev || !grad_dev || n_samples < 0 ||
-        workspace_parts <= 0 || (n_samples > 0 && (!obs_dev || !mask_dev || !action_dev || !qvals_dev)))
-        return fail(AZUL_ERR_INVALID, "azul_a2c_gradients: bad arguments");
     STREAM_GUARD(stream);
     const hipStream_t st = (hipStream_t)stream;
     const u32 total = a2c_shape_n((u32)num_inputs, (u32)num_actions).params + 4u;
@@ -946,17 +930,17 @@ int azul_a2c_gradients(const float *obs_dev, const uint8_t *mask_dev, const int3
                        float *workspace_dev, int workspace_parts, float *grad_dev, const int32_t *index_dev, const int32_t *n_samples_dev,
                        const float *inv_n_total_dev, void *stream)
 {
-    if (num_inputs != PF_IN || hidden_size != PF_HID || num_actions != PF_ACT) {
-        if (azul_a2c_flat_size(num_inputs, hidden_size, num_actions) < 0)
-            return fail(AZUL_ERR_INVALID, "azul_a2c_gradients: compiled shapes are ActorCritic(136, 180), (188, 180), (240, 180), (198, 240) "
-                                          "and (260, 300), hidden 180");
-        return a2c_gradients_n(obs_dev, mask_dev, action_dev, qvals_dev, n_samples, inv_n_total, w1t_dev, b1_dev, w2c_dev, b2c_dev, w2a_t_dev,
-                               b2a_dev, w2a_dev, num_inputs, num_actions, workspace_dev, workspace_parts, grad_dev, index_dev, n_samples_dev,
-                               inv_n_total_dev, stream);
-    }
+    const bool reference = num_inputs == PF_IN && hidden_size == PF_HID && num_actions == PF_ACT;
+    if (!reference && azul_a2c_flat_size(num_inputs, hidden_size, num_actions) < 0)
+        return fail(AZUL_ERR_INVALID, "azul_a2c_gradients: compiled shapes are ActorCritic(136, 180), (188, 180), (240, 180), (198, 240) "
+                                      "and (260, 300), hidden 180");
     if (!w1t_dev || !b1_dev || !w2c_dev || !b2c_dev || !w2a_t_dev || !b2a_dev || !w2a_dev || !workspace_dev || !grad_dev || n_samples < 0 ||
         workspace_parts <= 0 || (n_samples > 0 && (!obs_dev || !mask_dev || !action_dev || !qvals_dev)))
         return fail(AZUL_ERR_INVALID, "azul_a2c_gradients: bad arguments");
+    if (!reference)                                          // a wide shape: the kernels of azul_learner.hpp's second half
+        return a2c_gradients_n(obs_dev, mask_dev, action_dev, qvals_dev, n_samples, inv_n_total, w1t_dev, b1_dev, w2c_dev, b2c_dev, w2a_t_dev,
+                               b2a_dev, w2a_dev, num_inputs, num_actions, workspace_dev, workspace_parts, grad_dev, index_dev, n_samples_dev,
+                               inv_n_total_dev, stream);
     if (((uintptr_t)w2a_t_dev & 7u) != 0 || ((uintptr_t)w2a_dev & 7u) != 0 || ((uintptr_t)mask_dev & 3u) != 0)
         return fail(AZUL_ERR_INVALID, "azul_a2c_gradients: weights must be 8-byte aligned, mask_dev 4-byte aligned");
     STREAM_GUARD(stream);

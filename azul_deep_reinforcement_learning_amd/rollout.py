@@ -20,16 +20,22 @@ observation, legal mask, action, reward, done, value, log-prob of the action and
 `-mean(log p over legal actions)` (nn_runner.py:36-40), plus the player who moved and the discounted returns.
 """
 import ctypes as C
+import operator
 
 import torch
 
 from . import _lib as L
-from .batch import BatchedAzul, parse_ext_rules
+from .batch import BatchedAzul, batch_shape, parse_ext_rules
 from .multiplayer import MultiplayerAzul
 
 
 def _p(t):
     return C.c_void_p(t.data_ptr())
+
+
+# azul_batch_policy_rollout_returns takes what the two launch structs hold one by one: all weights, and the buffers obs .. returns
+_WEIGHT_FIELDS = operator.attrgetter(*[k for k, _ in L.NetWeights._fields_])
+_FLAT_BUFFER_FIELDS = operator.attrgetter(*[k for k, _ in L.RolloutBuffers._fields_[:11]])
 
 
 class PolicyRollout:
@@ -84,12 +90,41 @@ class PolicyRollout:
         construction stays on the per-cut path; openings after episodes that end inside a window are the kernel's.  One difference: a game
         that still owes an opponent_move() after MAX_REPLY_ROUNDS rounds ends its step with status AZUL_STUCK (unless the step already has a
         status) instead of raising RuntimeError, as the two-player window kernel does -- raising would cost a host synchronisation per window."""
+        self._check_modes(policy, n_games, parts, rules, window, use_graph, fused_head, opponent, fused_mlp, persistent, action_selection, ring,
+                          opponent_selection, opponent_trace, move_limit, players, fused_wide, fused_opponent, wide_ring)
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        self.policy = policy.to(self.device).eval()
+        self.windows_played = 0
+        self.sample_seed = L.POLICY_ARGMAX if action_selection == "Max" else int(sample_seed)
+        self.game_id_base = int(seed_base if game_id_base is None else game_id_base) & 0xFFFFFFFF
+        self.opponent_seed = L.POLICY_ARGMAX if opponent_selection == "Max" else \
+            (int(opponent_seed) if opponent_seed is not None else (int(sample_seed) ^ 0x4F50504F4E454E54)) & 0xFFFFFFFFFFFFFFFF
+        self._stage_weights(kweights)
+        self.envs, self.streams, self.work, self.traj, self.graphs, self.rings = [], [], [], [], [], []
+        for p in range(parts):
+            self._alloc_part(p, rules, seed_base, move_limit)
+        torch.cuda.synchronize(self.device)
+        self.graph_error = None
+        if self.use_graph:
+            try:
+                self._capture()
+            except Exception as e:          # capture is a launch-overhead optimisation only
+                self.graph_error = repr(e)
+                self.graphs = []
+                self.use_graph = False
+                torch.cuda.synchronize(self.device)
+
+    def _check_modes(self, policy, n_games, parts, rules, window, use_graph, fused_head, opponent, fused_mlp, persistent, action_selection, ring,
+                     opponent_selection, opponent_trace, move_limit, players, fused_wide, fused_opponent, wide_ring):
+        """Every refusal of the constructor, and the flags the modes resolve to -- from the arguments and the modules' shapes alone: no
+        device and no library call, so nothing is allocated before a refusal."""
         assert n_games % parts == 0
+        self.n, self.parts, self.h, self.T = n_games, parts, n_games // parts, window
         self.players = int(players)
         self.wide = self.players != 2 or parse_ext_rules(rules, self.players) != 0
-        if self.wide and opponent is not None and not isinstance(opponent, str):
-            D = 2 * self.players + 1 if parse_ext_rules(rules, self.players) & L.RULE_DISPLAYS_2P1 else 5
-            n_obs, n_act = 5 * D + 6 + 52 * self.players + 1, (D + 1) * 30       # azul_batch_obs_size / azul_batch_num_actions
+        net = opponent is not None and not isinstance(opponent, str)
+        n_obs, n_act = batch_shape(self.players, rules)          # azul_batch_obs_size / azul_batch_num_actions
+        if self.wide and net:
             shape = (opponent.critic_linear1.in_features, opponent.actor_linear1.in_features, opponent.actor_linear2.out_features)
             if shape != (n_obs, n_obs, n_act):
                 raise ValueError("a network opponent for batches of %d players / extended rules must take the batch's observation and give its "
@@ -102,12 +137,10 @@ class PolicyRollout:
             if not self.wide:
                 raise ValueError("fused_wide=True is the window kernel of batches of three / four players or extended rules; two-player reference "
                                  "batches have persistent=True")
-            if opponent is not None and not isinstance(opponent, str) and not fused_opponent:
+            if net and not fused_opponent:
                 raise ValueError("fused_wide=True plays opponent=None or \"random\"; a network opponent runs on the per-cut path (fused_wide=False)")
             if not fused_head:
                 raise ValueError("fused_wide=True samples with azul_policy_head_n's draw: fused_head=False is the PyTorch sampling path")
-            D = 2 * self.players + 1 if parse_ext_rules(rules, self.players) & L.RULE_DISPLAYS_2P1 else 5
-            n_obs, n_act = 5 * D + 6 + 52 * self.players + 1, (D + 1) * 30
             shape = (policy.critic_linear1.in_features, policy.actor_linear1.in_features, policy.critic_linear1.out_features,
                      policy.actor_linear1.out_features, policy.actor_linear2.out_features)
             if shape != (n_obs, n_obs, 180, 180, n_act):
@@ -119,7 +152,7 @@ class PolicyRollout:
             raise ValueError("wide_ring >= 2 is the trajectory ring of the wide window kernel: it needs fused_wide=True and parts=1")
         self.fused_opponent = bool(fused_opponent)
         if self.fused_opponent:
-            if not self.fused_wide or opponent is None or isinstance(opponent, str):
+            if not self.fused_wide or not net:
                 raise ValueError("fused_opponent=True plays a network opponent inside the window kernel of wide batches: it needs fused_wide=True "
                                  "and opponent=<module>")
             if (opponent.critic_linear1.out_features, opponent.actor_linear1.out_features) != (180, 180):
@@ -127,13 +160,10 @@ class PolicyRollout:
                                  "per-cut path (fused_opponent=False, fused_wide=False)"
                                  % (opponent.critic_linear1.out_features, opponent.actor_linear1.out_features))
         self.opp_policy = None
-        if opponent is not None and not isinstance(opponent, str):
+        if net:
             self.opp_policy, opponent = opponent, "net"
         assert opponent in (None, "random", "net")
         self.opponent = opponent
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        self.policy = policy.to(self.device).eval()
-        self.n, self.parts, self.h, self.T = n_games, parts, n_games // parts, window
         self.fused_head = fused_head
         # the one-launch forward (azul_policy_forward) is compiled for the reference's ActorCritic(136, 180, hidden 180)
         self.fused_mlp = bool(fused_mlp and fused_head and not self.wide and policy.critic_linear1.in_features == L.OBS_SIZE and
@@ -142,89 +172,76 @@ class PolicyRollout:
         self.persistent = bool(persistent and self.fused_mlp)
         self.ring = int(ring) if self.persistent else (int(wide_ring) if self.fused_wide else 1)
         assert self.ring >= 1
-        self.windows_played = 0
         # Agent.get_ac_output's two modes (agent.py:64-72): sample from the masked softmax, or take its first maximum
         assert action_selection in ("Distribution", "Max") and (fused_head or action_selection == "Distribution")
         self.action_selection = action_selection
-        self.sample_seed = L.POLICY_ARGMAX if action_selection == "Max" else int(sample_seed)
-        self.game_id_base = int(seed_base if game_id_base is None else game_id_base) & 0xFFFFFFFF
         assert opponent_selection in ("Distribution", "Max")
-        self.opponent_seed = L.POLICY_ARGMAX if opponent_selection == "Max" else \
-            (int(opponent_seed) if opponent_seed is not None else (int(sample_seed) ^ 0x4F50504F4E454E54)) & 0xFFFFFFFFFFFFFFFF
         self.opp_slots = int(opponent_trace) if self.opponent == "net" else 0
-        self.envs, self.streams, self.work, self.traj, self.graphs = [], [], [], [], []
-        # kweights: k-major weight tensors owned by someone else (A2CLearner.kweights(): views of its flat master copy, kept current
-        # by the optimiser kernel) -- then nothing is copied here and refresh_weights() has nothing to do
+        assert self.opponent != "net" or self.fused_mlp or self.wide, \
+            "the network opponent runs on the library's forward (ActorCritic(136, 180, hidden 180))"
+        # one launch per window needs no graph; reply rounds are data-dependent (a capture that fails clears the flag again)
+        self.use_graph = bool(use_graph and not self.persistent and not self.fused_wide and self.opponent != "net")
+
+    def _stage_weights(self, kweights):
+        """The k-major weight copies the kernels and GEMMs read.  kweights: tensors owned by someone else (A2CLearner.kweights(): views of
+        its flat master copy, kept current by the optimiser kernel) -- then nothing is copied here and refresh_weights() has nothing to do."""
         if self.wide and not self.fused_wide:
             kweights = None                                # (the PyTorch-GEMM path keeps its own copies)
         self._external_kweights = kweights is not None
+        self.H = self.policy.critic_linear1.out_features
         if kweights is not None:
-            self.H = policy.critic_linear1.out_features
             self.w1t, self.b1, self.w2c, self.w2a_t = kweights["w1t"], kweights["b1"], kweights["w2c"], kweights["w2a_t"]
             self.w2c_t = self.w2c.view(-1, 1)
         self.refresh_weights()
         if self.opponent == "net":
-            assert self.fused_mlp or self.wide, "the network opponent runs on the library's forward (ActorCritic(136, 180, hidden 180))"
             self.opp_policy = self.opp_policy.to(self.device).eval()
             self.set_opponent(self.opp_policy)
-        d, h, T = self.device, self.h, window
-        for p in range(parts):
-            env = MultiplayerAzul(h, rules=rules, device=d, players=self.players) if self.wide else BatchedAzul(h, rules=rules, device=d)
-            env.seed(seed_base + p * h)                            # seeds follow the global game id
-            env.set_id_base(self.game_id_base + p * h)             # ... and so does the sampler's Philox key
-            if move_limit:
-                env.set_move_limit(move_limit)
-            env.runner_init()                                      # GameRunner()
-            if opponent == "random":
-                env.reset()                                        # GameRunner.reset(): the opponent opens when it starts
-            elif opponent == "net":
-                pass                                               # ... with the network opponent: below, once the work buffers exist
-            else:
-                env.runner_init()                                  # reset() without pre-moves (flat self-play)
-            self.envs.append(env)
-            self.streams.append(torch.cuda.Stream(device=d))
-            R = self.ring * T
-            self.obs_size, self.num_actions = env.obs_size, env.num_actions
-            rg = {"obs": torch.zeros(R + 1, h, env.obs_size, device=d), "mask": torch.zeros(R + 1, h, env.num_actions, dtype=torch.uint8, device=d),
-                  "player": torch.zeros(R + 1, h, dtype=torch.uint8, device=d),
-                  "action": torch.zeros(R, h, dtype=torch.int32, device=d), "reward": torch.zeros(R, h, dtype=torch.int32, device=d),
-                  "done": torch.zeros(R, h, dtype=torch.uint8, device=d),
-                  "value": torch.zeros(R, h, 1, device=d), "log_prob": torch.zeros(R, h, device=d), "entropy": torch.zeros(R, h, device=d),
-                  "returns": torch.zeros(R, h, device=d), "carry": torch.zeros(h, device=d)}
+
+    def _alloc_part(self, p, rules, seed_base, move_limit):
+        """Part p: its games (opened as GameRunner opens them), its stream, its trajectory ring and work buffers."""
+        d, h, T = self.device, self.h, self.T
+        env = MultiplayerAzul(h, rules=rules, device=d, players=self.players) if self.wide else BatchedAzul(h, rules=rules, device=d)
+        env.seed(seed_base + p * h)                            # seeds follow the global game id
+        env.set_id_base(self.game_id_base + p * h)             # ... and so does the sampler's Philox key
+        if move_limit:
+            env.set_move_limit(move_limit)
+        env.runner_init()                                      # GameRunner()
+        if self.opponent == "random":
+            env.reset()                                        # GameRunner.reset(): the opponent opens when it starts
+        elif self.opponent is None:
+            env.runner_init()                                  # reset() without pre-moves (flat self-play)
+        self.envs.append(env)                                  # (the network opponent opens below, once the work buffers exist)
+        self.streams.append(torch.cuda.Stream(device=d))
+        R = self.ring * T
+        self.obs_size, self.num_actions = env.obs_size, env.num_actions
+        rg = {"obs": torch.zeros(R + 1, h, env.obs_size, device=d), "mask": torch.zeros(R + 1, h, env.num_actions, dtype=torch.uint8, device=d),
+              "player": torch.zeros(R + 1, h, dtype=torch.uint8, device=d),
+              "action": torch.zeros(R, h, dtype=torch.int32, device=d), "reward": torch.zeros(R, h, dtype=torch.int32, device=d),
+              "done": torch.zeros(R, h, dtype=torch.uint8, device=d),
+              "value": torch.zeros(R, h, 1, device=d), "log_prob": torch.zeros(R, h, device=d), "entropy": torch.zeros(R, h, device=d),
+              "returns": torch.zeros(R, h, device=d), "carry": torch.zeros(h, device=d)}
+        if self.opponent == "net":
+            rg["opp_replies"] = torch.zeros(R, h, dtype=torch.uint8, device=d)
+            if self.opp_slots:
+                rg["opp_action"] = torch.full((R, self.opp_slots, h), -1, dtype=torch.int32, device=d)
+                rg["opp_logp"] = torch.zeros(R, self.opp_slots, h, device=d)
+        self.rings.append(rg)
+        t = self._window_views(rg, self.ring - 1)             # the "previous" window: its slot T seeds the first window
+        w = {"hidden": torch.zeros(h, 2 * self.H, device=d), "logits": torch.zeros(h, env.num_actions, device=d),
+             "status": torch.zeros(h, dtype=torch.uint8, device=d),
+             "counter": torch.tensor([0, 0], dtype=torch.int64, device=d)}     # [0] Philox step counter, [1] launch ticket
+        if self.opponent == "net":
+            w["net"] = env.net_state()
+            w["scratch_f"] = torch.zeros(3, h, device=d)       # the opponent forward's value / entropy (not recorded) and untraced log-prob
+            if self.wide:                                      # the opponent's actor half as PyTorch GEMMs (its own hidden size)
+                w["opp_hidden"] = torch.zeros(h, self.ob1.numel() // 2, device=d)
+                w["opp_logits"] = torch.zeros(h, env.num_actions, device=d)
+        self.traj.append(t)
+        self.work.append(w)
+        with torch.cuda.stream(self.streams[p]):
             if self.opponent == "net":
-                rg["opp_replies"] = torch.zeros(R, h, dtype=torch.uint8, device=d)
-                if self.opp_slots:
-                    rg["opp_action"] = torch.full((R, self.opp_slots, h), -1, dtype=torch.int32, device=d)
-                    rg["opp_logp"] = torch.zeros(R, self.opp_slots, h, device=d)
-            self.rings = getattr(self, "rings", [])
-            self.rings.append(rg)
-            t = self._window_views(rg, self.ring - 1)             # the "previous" window: its slot T seeds the first window
-            w = {"hidden": torch.zeros(h, 2 * self.H, device=d), "logits": torch.zeros(h, env.num_actions, device=d),
-                 "status": torch.zeros(h, dtype=torch.uint8, device=d),
-                 "counter": torch.tensor([0, 0], dtype=torch.int64, device=d)}     # [0] Philox step counter, [1] launch ticket
-            if self.opponent == "net":
-                w["net"] = env.net_state()
-                w["scratch_f"] = torch.zeros(3, h, device=d)       # the opponent forward's value / entropy (not recorded) and untraced log-prob
-                if self.wide:                                      # the opponent's actor half as PyTorch GEMMs (its own hidden size)
-                    w["opp_hidden"] = torch.zeros(h, self.ob1.numel() // 2, device=d)
-                    w["opp_logits"] = torch.zeros(h, env.num_actions, device=d)
-            self.traj.append(t)
-            self.work.append(w)
-            with torch.cuda.stream(self.streams[p]):
-                if self.opponent == "net":
-                    self._net_reset(p)                             # GameRunner.reset(): the network opponent opens when it starts
-                env.observe_all(self._persp(), t["obs"][T], t["mask"][T], t["player"][T])     # becomes slot 0 of the first window
-        torch.cuda.synchronize(d)
-        self.use_graph = use_graph and not self.persistent and not self.fused_wide and self.opponent != "net"     # one launch per window needs no graph; reply rounds are data-dependent
-        self.graph_error = None
-        if self.use_graph:
-            try:
-                self._capture()
-            except Exception as e:          # capture is a launch-overhead optimisation only
-                self.graph_error = repr(e)
-                self.graphs = []
-                self.use_graph = False
-                torch.cuda.synchronize(d)
+                self._net_reset(p)                             # GameRunner.reset(): the network opponent opens when it starts
+            env.observe_all(self._persp(), t["obs"][T], t["mask"][T], t["player"][T])     # becomes slot 0 of the first window
 
     def _window_views(self, rg, w):
         """Views of window `w` of a ring: T + 1 slots of obs / mask / player (slot T = the state after the window), T of the rest."""
@@ -238,20 +255,27 @@ class PolicyRollout:
     def _persp(self):
         return 0 if self.opponent in ("random", "net") else L.PERSP_CURRENT     # NNRunner observes with perspective 0 (game_runner.py:56)
 
-    def set_opponent(self, policy_or_state_dict):
-        """Install the network opponent's weights (k-major copies, updated IN PLACE): a module with the reference's four layers or its
-        state_dict -- e.g. `ro.set_opponent(policy)` every so many updates trains against a frozen past self."""
-        sd = policy_or_state_dict.state_dict() if hasattr(policy_or_state_dict, "state_dict") else policy_or_state_dict
+    def _stage(self, get, prefix, names):
+        """The k-major copies `names` of the reference's four layers (`get`: parameter name -> tensor) as attributes prefix + name,
+        updated IN PLACE once they exist: captured HIP graphs and whoever shares kweights() keep reading the same addresses."""
         with torch.no_grad():
-            g = lambda k: sd[k].detach().to(self.device, torch.float32)
-            fresh = {"ow1t": torch.cat([g("critic_linear1.weight"), g("actor_linear1.weight")], dim=0).t(),
-                     "ob1": torch.cat([g("critic_linear1.bias"), g("actor_linear1.bias")]), "ow2c": g("critic_linear2.weight").reshape(-1),
-                     "ob2c": g("critic_linear2.bias").reshape(-1), "ow2a_t": g("actor_linear2.weight").t(), "ob2a": g("actor_linear2.bias")}
-            for name, v in fresh.items():
+            g = lambda k: get(k).detach().to(self.device, torch.float32)
+            build = {"w1t": lambda: torch.cat([g("critic_linear1.weight"), g("actor_linear1.weight")], dim=0).t(),
+                     "b1": lambda: torch.cat([g("critic_linear1.bias"), g("actor_linear1.bias")]),
+                     "w2c": lambda: g("critic_linear2.weight").reshape(-1), "w2c_t": lambda: g("critic_linear2.weight").t(),
+                     "b2c": lambda: g("critic_linear2.bias").reshape(-1),
+                     "w2a_t": lambda: g("actor_linear2.weight").t(), "b2a": lambda: g("actor_linear2.bias")}
+            for name, v in [(prefix + k, build[k]()) for k in names]:
                 if hasattr(self, name):
                     getattr(self, name).copy_(v)
                 else:
                     setattr(self, name, v.contiguous().clone())
+
+    def set_opponent(self, policy_or_state_dict):
+        """Install the network opponent's weights (k-major copies, updated IN PLACE): a module with the reference's four layers or its
+        state_dict -- e.g. `ro.set_opponent(policy)` every so many updates trains against a frozen past self."""
+        sd = policy_or_state_dict.state_dict() if hasattr(policy_or_state_dict, "state_dict") else policy_or_state_dict
+        self._stage(sd.__getitem__, "o", ("w1t", "b1", "w2c", "b2c", "w2a_t", "b2a"))
 
     def _opp_forward(self, p, j, logp_out):
         """The opponent's get_a_output (agent.py:73-81) for the games of part p that owe an opponent_move(): forward_actor of its net on
@@ -304,24 +328,37 @@ class PolicyRollout:
     def refresh_weights(self):
         """(Re)build the fused first-layer weights from the policy's parameters -- call after every optimiser step.  The
         staging tensors are updated IN PLACE: a captured HIP graph keeps reading the same addresses."""
-        pol = self.policy
-        if self._external_kweights:
-            return
-        with torch.no_grad():
-            self.H = pol.critic_linear1.out_features
-            fresh = {"w1t": torch.cat([pol.critic_linear1.weight, pol.actor_linear1.weight], dim=0).t(),
-                     "b1": torch.cat([pol.critic_linear1.bias, pol.actor_linear1.bias]),
-                     "w2c_t": pol.critic_linear2.weight.t(), "w2a_t": pol.actor_linear2.weight.t(),
-                     "w2c": pol.critic_linear2.weight.reshape(-1)}
-            for name, v in fresh.items():
-                if hasattr(self, name):
-                    getattr(self, name).copy_(v)
-                else:
-                    setattr(self, name, v.contiguous().clone())
+        if not self._external_kweights:
+            self._stage(self.policy.get_parameter, "", ("w1t", "b1", "w2c_t", "w2a_t", "w2c"))      # (the biases of layer 2 are read in place)
 
     def kweights(self):
         """The k-major weight copies (refresh_weights keeps them current): the learner's gradient kernel reads the same layouts."""
         return {"w1t": self.w1t, "b1": self.b1, "w2c": self.w2c, "w2a_t": self.w2a_t}
+
+    def _net_weights(self, opponent=False):
+        """azul_net_weights_t of the agent (the second layer's biases straight from the module) or of the network opponent."""
+        pol = self.policy
+        w = (self.ow1t, self.ob1, self.ow2c, self.ob2c, self.ow2a_t, self.ob2a) if opponent else \
+            (self.w1t, self.b1, self.w2c, pol.critic_linear2.bias, self.w2a_t, pol.actor_linear2.bias)
+        return L.NetWeights(*[x.data_ptr() for x in w])
+
+    def _buffers(self, tr, w, returns):
+        """azul_rollout_buffers_t of a window's views; the opponent fields only with a network opponent (the trace only when asked for)."""
+        net, trace = self.opponent == "net", self.opp_slots > 0
+        ptr = lambda k: tr[k].data_ptr()
+        return L.RolloutBuffers(ptr("obs"), ptr("mask"), ptr("player"), ptr("action"), ptr("reward"), ptr("done"), ptr("value"), ptr("log_prob"),
+                                ptr("entropy"), w["status"].data_ptr(), returns, ptr("opp_action") if trace else None,
+                                ptr("opp_logp") if trace else None, ptr("opp_replies") if net else None, self.opp_slots)
+
+    def _head(self, p, t):
+        """Masked softmax, draw, log-prob and entropy of move t from work["logits"]: azul_policy_head for the reference's 180 actions,
+        azul_policy_head_n for a wide batch's; the step counter moves on behind it."""
+        tr, w = self.traj[p], self.work[p]
+        head = (_p(w["logits"]), _p(tr["mask"][t]), self.sample_seed, 0, _p(w["counter"]), self.h)
+        tail = (self.game_id_base + p * self.h, _p(tr["action"][t]), _p(tr["log_prob"][t]), _p(tr["entropy"][t]),
+                C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
+        L.check(L.lib.azul_policy_head_n(*head, self.num_actions, *tail) if self.wide else L.lib.azul_policy_head(*head, *tail))
+        w["counter"][:1].add_(1)
 
     # one move of one part, enqueued on the current stream
     def _move(self, p, t):
@@ -342,16 +379,8 @@ class PolicyRollout:
             w["hidden"].relu_()
             torch.addmm(pol.critic_linear2.bias, w["hidden"][:, :H], self.w2c_t, out=tr["value"][t])          # agent.py:66
             torch.addmm(pol.actor_linear2.bias, w["hidden"][:, H:], self.w2a_t, out=w["logits"])               # agent.py:67
-            if self.fused_head and self.wide:
-                L.check(L.lib.azul_policy_head_n(_p(w["logits"]), _p(mask), self.sample_seed, 0, _p(w["counter"]), self.h, self.num_actions,
-                                                 self.game_id_base + p * self.h, _p(tr["action"][t]), _p(tr["log_prob"][t]), _p(tr["entropy"][t]),
-                                                 C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
-                w["counter"][:1].add_(1)
-            elif self.fused_head:
-                L.check(L.lib.azul_policy_head(_p(w["logits"]), _p(mask), self.sample_seed, 0, _p(w["counter"]), self.h, self.game_id_base + p * self.h,
-                                               _p(tr["action"][t]), _p(tr["log_prob"][t]), _p(tr["entropy"][t]),
-                                               C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
-                w["counter"][:1].add_(1)
+            if self.fused_head:
+                self._head(p, t)
             else:
                 legal = mask.bool()
                 logits = w["logits"].masked_fill(~legal, float("-inf"))
@@ -388,75 +417,45 @@ class PolicyRollout:
             env.policy_step(tr["action"][t], tr["reward"][t], tr["done"][t], w["status"], tr["obs"][t + 1], tr["mask"][t + 1], tr["player"][t + 1])
 
     def _window(self, p, gamma):
-        T = self.T
-        if self.fused_wide:                                 # the whole window in one launch (+ the returns scan behind it)
-            if self.ring > 1:
-                self.traj[p] = self._window_views(self.rings[p], self.windows_played % self.ring)
-            self._window_wide(p, gamma)
-            if self.ring > 1:                               # returns chained back through the ring (as on the persistent path)
-                rg, R = self.rings[p], self.ring * T
-                played = (self.windows_played + 1) * T
-                L.check(L.lib.azul_discounted_returns_ring(_p(rg["reward"]), _p(rg["done"]), _p(rg["returns"]), C.c_float(gamma), R,
-                                                           played % (1 << 40), min(R, played), self.h,
-                                                           C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
-            return
-        self._window_two(p, gamma)
+        if self.persistent or self.fused_wide:
+            self._window_kernel(p, gamma)
+        else:
+            self._window_moves(p, gamma)
 
-    def _window_wide(self, p, gamma):
-        T = self.T
-        env, tr, w, pol = self.envs[p], self.traj[p], self.work[p], self.policy
-        ret = _p(tr["returns"]) if self.ring == 1 else None      # ring: azul_discounted_returns_ring after the launch
-        wa = L.NetWeights(*[_p(x) for x in (self.w1t, self.b1, self.w2c, pol.critic_linear2.bias, self.w2a_t, pol.actor_linear2.bias)])
-        if self.opponent == "net":                      # fused_opponent: the reply rounds inside the kernel
-            wo = L.NetWeights(*[_p(x) for x in (self.ow1t, self.ob1, self.ow2c, self.ob2c, self.ow2a_t, self.ob2a)])
-            out = L.RolloutBuffers(_p(tr["obs"]), _p(tr["mask"]), _p(tr["player"]), _p(tr["action"]), _p(tr["reward"]), _p(tr["done"]),
-                                   _p(tr["value"]), _p(tr["log_prob"]), _p(tr["entropy"]), _p(w["status"]), ret,
-                                   _p(tr["opp_action"]) if self.opp_slots else None, _p(tr["opp_logp"]) if self.opp_slots else None,
-                                   _p(tr["opp_replies"]), self.opp_slots)
-            L.check(L.lib.azul_batch_mp_policy_rollout_vs(env._h, T, C.byref(wa), C.byref(wo), self.obs_size, self.H, self.num_actions,
-                                                          self.sample_seed, self.opponent_seed, 0, _p(w["counter"]), int(self.MAX_REPLY_ROUNDS),
-                                                          C.byref(out), C.c_float(gamma), C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
-            return
-        out = L.RolloutBuffers(_p(tr["obs"]), _p(tr["mask"]), _p(tr["player"]), _p(tr["action"]), _p(tr["reward"]), _p(tr["done"]),
-                               _p(tr["value"]), _p(tr["log_prob"]), _p(tr["entropy"]), _p(w["status"]), ret, None, None, None, 0)
-        L.check(L.lib.azul_batch_mp_policy_rollout(env._h, T, 1 if self.opponent == "random" else 0, C.byref(wa), self.obs_size, self.H,
-                                                   self.num_actions, self.sample_seed, 0, _p(w["counter"]), C.byref(out), C.c_float(gamma),
-                                                   C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
-
-    def _window_two(self, p, gamma):
-        T = self.T
-        if self.persistent and self.ring > 1:
-            wi = self.windows_played % self.ring                   # (run_window advances windows_played after all parts)
-            self.traj[p] = self._window_views(self.rings[p], wi)
+    def _window_kernel(self, p, gamma):
+        """The whole window of part p in one launch (+ the returns scan behind it): the two-player kernel (persistent) or the wide one
+        (fused_wide), with the opponent inside.  The only place a window kernel is launched from."""
+        T, env, w = self.T, self.envs[p], self.work[p]
+        if self.ring > 1:
+            self.traj[p] = self._window_views(self.rings[p], self.windows_played % self.ring)     # (run_window advances windows_played after all parts)
         tr = self.traj[p]
-        if self.persistent:
-            env, w, pol = self.envs[p], self.work[p], self.policy
-            st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-            if self.opponent == "net":
-                wa = L.NetWeights(*[_p(x) for x in (self.w1t, self.b1, self.w2c, pol.critic_linear2.bias, self.w2a_t, pol.actor_linear2.bias)])
-                wo = L.NetWeights(*[_p(x) for x in (self.ow1t, self.ob1, self.ow2c, self.ob2c, self.ow2a_t, self.ob2a)])
-                out = L.RolloutBuffers(_p(tr["obs"]), _p(tr["mask"]), _p(tr["player"]), _p(tr["action"]), _p(tr["reward"]), _p(tr["done"]),
-                                       _p(tr["value"]), _p(tr["log_prob"]), _p(tr["entropy"]), _p(w["status"]),
-                                       _p(tr["returns"]) if self.ring == 1 else None, _p(tr["opp_action"]) if self.opp_slots else None,
-                                       _p(tr["opp_logp"]) if self.opp_slots else None, _p(tr["opp_replies"]), self.opp_slots)
-                L.check(L.lib.azul_batch_policy_rollout_vs(env._h, T, C.byref(wa), C.byref(wo), L.OBS_SIZE, self.H, L.NUM_ACTIONS, self.sample_seed,
-                                                           self.opponent_seed, 0, _p(w["counter"]), C.byref(out), C.c_float(gamma), st))
+        st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        wa = self._net_weights()
+        out = self._buffers(tr, w, tr["returns"].data_ptr() if self.ring == 1 else None)          # ring: the chain below writes the returns
+        shape, ctr, rnd = (self.obs_size, self.H, self.num_actions), _p(w["counter"]), 1 if self.opponent == "random" else 0
+        if self.opponent == "net":                          # the reply rounds inside the kernel
+            wo = self._net_weights(opponent=True)
+            if self.wide:
+                L.check(L.lib.azul_batch_mp_policy_rollout_vs(env._h, T, C.byref(wa), C.byref(wo), *shape, self.sample_seed, self.opponent_seed, 0, ctr,
+                                                              int(self.MAX_REPLY_ROUNDS), C.byref(out), C.c_float(gamma), st))
             else:
-              L.check(L.lib.azul_batch_policy_rollout_returns(
-                env._h, T, 1 if self.opponent == "random" else 0, _p(self.w1t), _p(self.b1), _p(self.w2c), _p(pol.critic_linear2.bias),
-                _p(self.w2a_t), _p(pol.actor_linear2.bias), L.OBS_SIZE, self.H, L.NUM_ACTIONS, self.sample_seed, 0, _p(w["counter"]),
-                _p(tr["obs"]), _p(tr["mask"]), _p(tr["player"]), _p(tr["action"]), _p(tr["reward"]), _p(tr["done"]), _p(tr["value"]),
-                _p(tr["log_prob"]), _p(tr["entropy"]), _p(w["status"]), _p(tr["returns"]) if self.ring == 1 else None, C.c_float(gamma), st))
-            if self.ring == 1:
-                return
+                L.check(L.lib.azul_batch_policy_rollout_vs(env._h, T, C.byref(wa), C.byref(wo), *shape, self.sample_seed, self.opponent_seed, 0, ctr,
+                                                           C.byref(out), C.c_float(gamma), st))
+        elif self.wide:
+            L.check(L.lib.azul_batch_mp_policy_rollout(env._h, T, rnd, C.byref(wa), *shape, self.sample_seed, 0, ctr, C.byref(out), C.c_float(gamma), st))
+        else:                                               # this entry takes the same pointers one by one
+            L.check(L.lib.azul_batch_policy_rollout_returns(env._h, T, rnd, *_WEIGHT_FIELDS(wa), *shape, self.sample_seed, 0, ctr,
+                                                            *_FLAT_BUFFER_FIELDS(out), C.c_float(gamma), st))
+        if self.ring > 1:
             # returns of the new window and, chained backwards through the ring, of the older windows: the value flowing out of a
             # window's first step flows into the window before it (nn_runner.py:70-76 across window boundaries) -- one launch
-            rg = self.rings[p]
-            R = self.ring * T
-            played = (self.windows_played + 1) * T
+            rg, R, played = self.rings[p], self.ring * T, (self.windows_played + 1) * T
             L.check(L.lib.azul_discounted_returns_ring(_p(rg["reward"]), _p(rg["done"]), _p(rg["returns"]), C.c_float(gamma), R,
                                                        played % (1 << 40), min(R, played), self.h, st))
-            return
+
+    def _window_moves(self, p, gamma):
+        """The window of part p move by move (what a HIP graph captures): slot T of the last window becomes slot 0, T moves, the returns scan."""
+        T, tr = self.T, self.traj[p]
         tr["obs"][0].copy_(tr["obs"][T])
         tr["mask"][0].copy_(tr["mask"][T])
         tr["player"][0].copy_(tr["player"][T])

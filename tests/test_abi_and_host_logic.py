@@ -112,6 +112,27 @@ def test_argument_validation_needs_no_gpu():
                                          one, None, None) == L.ERR_INVALID
     with pytest.raises(L.AzulHipError):
         L.check(lib.azul_batch_selfplay(None, 4, None, None, None, None, None, None, None, None))
+    # the five window entries: what their one launcher refuses before it looks at the batch
+    f32 = ctypes.c_float
+    wts, bufs = L.NetWeights(*[one] * 6), L.RolloutBuffers(*[one] * 14, 0)
+    wr, br = ctypes.byref(wts), ctypes.byref(bufs)
+    flat =lambda b, n: (b, n, 0) + (one,) * 6 + (136, 180, 180, 1, 0, None) + (one,) * 9 + (None,)
+    window = {
+        "azul_batch_policy_rollout": lambda b, n, a, o: lib.azul_batch_policy_rollout(*flat(b, n), None),
+        "azul_batch_policy_rollout_returns": lambda b, n, a, o: lib.azul_batch_policy_rollout_returns(*flat(b, n), one, f32(0.9), None),
+        "azul_batch_policy_rollout_vs": lambda b, n, a, o: lib.azul_batch_policy_rollout_vs(b, n, a, wr, 136, 180, 180, 1, 2, 0, None, o, f32(0.9), None),
+        "azul_batch_mp_policy_rollout": lambda b, n, a, o: lib.azul_batch_mp_policy_rollout(b, n, 0, a, 188, 180, 180, 1, 0, None, o, f32(0.9), None),
+        "azul_batch_mp_policy_rollout_vs": lambda b, n, a, o: lib.azul_batch_mp_policy_rollout_vs(b, n, a, wr, 188, 180, 180, 1, 2, 0, None, 8, o, f32(0.9),
+                                                                                               None)}
+    for name, call in window.items():
+        said = name[:-len("_returns")] if name.endswith("_returns") else name       # the stem the two flat entries share is enough for both
+        # without a batch nothing else is looked at: NULL weights, NULL out and a negative n_steps beside it are not dereferenced
+        for n, a, o in ((4, wr, br), (-1, wr, br), (4, None, br), (4, wr, None), (-1, None, None)):
+            assert call(None, n, a, o) == L.ERR_INVALID
+            assert lib.azul_last_error_string().decode().startswith(said)
+    assert lib.azul_batch_policy_rollout_vs(None, 4, wr, None, 136, 180, 180, 1, 2, 0, None, br, f32(0.9), None) == L.ERR_INVALID      # no opponent
+    assert lib.azul_batch_mp_policy_rollout_vs(None, 4, wr, None, 188, 180, 180, 1, 2, 0, None, 8, br, f32(0.9), None) == L.ERR_INVALID
+    assert lib.azul_last_error_string().decode().startswith("azul_batch_mp_policy_rollout_vs")
 
 
 def test_product_sources_carry_no_experiment_switches_and_no_kernel_selection_by_environment():
