@@ -29,6 +29,34 @@ typedef int64_t  i64;
 
 namespace wv {
 AZ_FN u32 lane() { return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
+
+// Where the hardware put this wave: HW_REG_HW_ID (register 4: wave slot [3:0], SIMD [5:4], CU [11:8], SH [12], SE [15:13]) and
+// HW_REG_XCC_ID (register 20: XCD [3:0]), whole registers through s_getreg_b32 (simm16 = id | offset << 6 | (size - 1) << 11).
+// g++ has no such builtin, and the lockstep emulation (tests/hostcheck/simt) runs one wave at a time -- slot 0 of nowhere: there the read is
+// a constant 0, chosen by `if constexpr` (the call sits in a template with a type-dependent argument, so g++ never looks the name up).
+// LOCKSTEP_EMULATION is told from the clock builtin's type: gfx950's s_memtime returns unsigned long, the emulation's stand-in is the literal
+// 0ull.  azul_kernels.hip asserts that the product is compiled with it false: the device build cannot fall back to the constant.
+template <class A, class B> struct same_type { static constexpr bool value = false; };
+template <class A> struct same_type<A, A> { static constexpr bool value = true; };
+constexpr bool LOCKSTEP_EMULATION = same_type<decltype(__builtin_amdgcn_s_memtime()), unsigned long long>::value;
+template <int SIMM16> struct HwReg { static constexpr int value = SIMM16; };
+template <class R> AZ_FN u32 getreg(R)
+{
+    if constexpr (LOCKSTEP_EMULATION) return 0u;
+    else return __builtin_amdgcn_s_getreg(R::value);
+}
+AZ_FN u32 hw_id() { return getreg(HwReg<(4 | (31 << 11))>()); }
+AZ_FN u32 hw_xcc_id() { return getreg(HwReg<(20 | (31 << 11))>()); }
+// THE TWO WAVES OF A SIMD TAKE TURNS AT PRIORITY 1.  The self-play kernels run one-wave workgroups, two resident per SIMD for the whole
+// launch (the registers allow no third), and at equal priority the SIMD's issue arbitration favours the older wave on every conflict:
+// measured per wave (tools/wave_timeline.py, profiles/wave_timeline_before.txt) the older one left its 512-move loop after 0.67 of the
+// younger one's time, which then ran on alone at a single wave's issue rate -- and the launch ends with the last wave.  A static
+// priority for either slot only swaps the roles (no gain); what wins is alternation: the kernels' counted loop is a nest, and at the head
+// of every block of PRIO_BLOCK moves a wave sets priority 1 or 0, starting from bit 0 of its hardware wave slot (the two waves of a SIMD
+// sit in slots 0 and 1) and flipping each block.  Nothing is added inside a move.  Grids that backfill are not slowed by it
+// (profiles/launch_tail_ab.txt).  s_setprio takes an immediate and ignores EXEC: `hi` must be wave-uniform (a scalar branch).
+constexpr int PRIO_BLOCK = 128;    // 64: -4.4 %, 96: -6.9 %, 128: -8.1 %, 192: -9.0 %, 256: -7.7 % launch time at 4096 games x 512 moves
+AZ_FN void set_prio(bool hi) { if (hi) __builtin_amdgcn_s_setprio(1); else __builtin_amdgcn_s_setprio(0); }
 } // namespace wv
 
 namespace az {
@@ -46,14 +74,27 @@ enum { T_ROWS = 31, T_BINADES = 8, T_STRIDE = 9 /* pairs per row: eight binades 
 // contains no stamp; never quote the diagnostic build's run time, only its SHARES (tools/segment_profile.py).
 enum { SEG_MASK = 0, SEG_SAMPLE, SEG_MOVE, SEG_AFTERMOVE, SEG_TAIL, SEG_NEWROUND, SEG_SCORE, SEG_RESET, SEG_LOOP, SEG_COUNT };
 constexpr int AZ_PROF_SLOTS = 48;   // u64 slots of BatchDev::prof: the self-play kernel's SEG_COUNT segments, the rollout kernel's phases (0..8) and matrix sub-phases (16..31)
+// The same build also writes ONE RECORD PER WAVE of a self-play launch (tools/wave_timeline.py): AZ_WAVE_REC_WORDS u64 at wave_prof[8 x
+// logical wave], lane 0, plain vector stores --
+//   [0..3] s_memtime at kernel entry, at loop start, at loop end, after rng2_close      [4] blockIdx.x | HW_REG_HW_ID << 32
+//   [5] HW_REG_XCC_ID | logical wave << 32      [6] round ends | rounds dealt << 32      [7] episode resets | regenerations << 32
+// (the four counts are GAME-moves of the wave's two games that took the rare block)
+enum { WCNT_ROUND_END = 0, WCNT_DEAL, WCNT_RESET, WCNT_COUNT };
+constexpr int AZ_WAVE_REC_WORDS = 8;
 #if defined(AZ_PROFILE_SEGMENTS)
-struct SegProf { u64 last; u64 acc[SEG_COUNT]; };
+struct SegProf { u64 last; u64 acc[SEG_COUNT]; u32 cnt[WCNT_COUNT]; };
+// `cond` is uniform over each 32-lane half: the ballot's population / 32 is the number of the wave's games it holds for
+#define AZ_COUNT(which, cond) do { if (prof_) prof_->cnt[which] += (u32)__popcll(__builtin_amdgcn_ballot_w64(cond)) >> 5; } while (0)
+struct WaveStamps { u64 entry, loop_start, loop_end; };
+#define AZ_WAVE_STAMP(field) (wstamps.field = __builtin_amdgcn_s_memtime())
 // (null-safe: callers outside the self-play kernels pass no SegProf -- an unguarded store would be undefined behaviour, which the
 // compiler is free to "optimise" into dropping the code behind the stamp: such a build ran the policy rollout 26 % faster, and wrong)
 #define AZ_STAMP(seg) do { if (prof_) { u64 now_ = __builtin_amdgcn_s_memtime(); prof_->acc[seg] += now_ - prof_->last; prof_->last = now_; } } while (0)
 #else
 struct SegProf { int unused; };
 #define AZ_STAMP(seg) do { } while (0)
+#define AZ_COUNT(which, cond) do { } while (0)
+#define AZ_WAVE_STAMP(field) do { } while (0)
 #endif
 
 struct Rules {

@@ -179,6 +179,8 @@ struct DeviceGuard {
 // first statement of an entry without a batch
 #define STREAM_GUARD(stream) DeviceGuard guard_; if (guard_.enter(-1, (void *)(stream), __func__)) return guard_.rc
 
+static_assert(!wv::LOCKSTEP_EMULATION, "the product reads the wave slot from HW_REG_HW_ID (azul_common.hpp)");
+
 extern "C" {
 
 const char *azul_last_error_string(void) { return g_err.c_str(); }
@@ -189,7 +191,11 @@ const char *azul_version(void)
 
 static void batch_free(azul_batch *b)
 {
-    void *bufs[] = {b->d.state, b->d.mt, b->d.mtpos, b->d.episodes, b->d.stuck, b->d.stat_sum, b->d.prof, b->Tx};
+    void *bufs[] = {b->d.state, b->d.mt, b->d.mtpos, b->d.episodes, b->d.stuck, b->d.stat_sum, b->d.prof, b->Tx,
+#if defined(AZ_PROFILE_SEGMENTS)
+                    b->d.wave_prof,
+#endif
+    };
     for (void *p : bufs) if (p) (void)hipFree(p);
     if (b->ev0) (void)hipEventDestroy(b->ev0);
     if (b->ev1) (void)hipEventDestroy(b->ev1);
@@ -215,6 +221,10 @@ static int batch_alloc(azul_batch *b, int n_games, int first_player, int tile_po
     HIP_TRY(hipMalloc((void **)&b->d.stat_sum, N * 10 * sizeof(double)));
     HIP_TRY(hipMalloc((void **)&b->d.prof, AZ_PROF_SLOTS * sizeof(u64)));
     HIP_TRY(hipMemset(b->d.prof, 0, AZ_PROF_SLOTS * sizeof(u64)));
+#if defined(AZ_PROFILE_SEGMENTS)
+    HIP_TRY(hipMalloc((void **)&b->d.wave_prof, (N + 1) / 2 * AZ_WAVE_REC_WORDS * sizeof(u64)));
+    HIP_TRY(hipMemset(b->d.wave_prof, 0, (N + 1) / 2 * AZ_WAVE_REC_WORDS * sizeof(u64)));
+#endif
     {   // the sampler's table: built with CPython's very additions and checked entry by entry on this host (azul_tables.hpp)
         const int rows = 5 * (b->displays + 1) + 1;
         std::vector<double> hX((size_t)rows * T_STRIDE * 2);
@@ -1459,6 +1469,19 @@ int azul_batch_segment_profile(azul_batch_t *b, uint64_t *cycles_host, int n, in
     if (reset) HIP_TRY(hipMemset(b->d.prof, 0, AZ_PROF_SLOTS * sizeof(u64)));
     return AZUL_SUCCESS;
 }
+
+#if defined(AZ_PROFILE_SEGMENTS)
+// DIAGNOSTIC BUILD ONLY (tools/wave_timeline.py; not part of the C ABI): the per-wave records of the last two-player self-play launch,
+// AZ_WAVE_REC_WORDS u64 per wave (azul_common.hpp)
+int azul_batch_wave_timeline(azul_batch_t *b, uint64_t *records_host, int n_waves)
+{
+    BATCH_GUARD(b, nullptr);
+    if (!b || b->x || !records_host || n_waves < 1 || (u32)n_waves > (b->d.n + 1u) / 2u) return fail(AZUL_ERR_INVALID, "azul_batch_wave_timeline: bad arguments");
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(records_host, b->d.wave_prof, (size_t)n_waves * AZ_WAVE_REC_WORDS * sizeof(u64), hipMemcpyDeviceToHost));
+    return AZUL_SUCCESS;
+}
+#endif
 
 int azul_selfplay_kernel_resources(azul_batch_t *b, int padded_rows, int mask_bits, int *vgprs, int *lds_bytes, int *scratch_bytes,
                                    int *resident_waves_per_cu)

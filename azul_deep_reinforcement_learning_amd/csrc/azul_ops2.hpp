@@ -24,6 +24,9 @@ struct BatchDev {
     u64 *prof;           // [SEG_COUNT] segment cycle sums (only written by the -DAZ_PROFILE_SEGMENTS diagnostic build)
     u32 id_base;         // global id of game 0 (azul_batch_set_id_base): keys the policy sampler's Philox stream
     u32 move_limit;      // 0 = none (the reference's behaviour), else an episode is cut at the first end of a round with move_counter >= this (azul_batch_set_move_limit)
+#if defined(AZ_PROFILE_SEGMENTS)
+    u64 *wave_prof;      // [ceil(N / 2)][AZ_WAVE_REC_WORDS] one record per wave of the last self-play launch (diagnostic build only, azul_common.hpp)
+#endif
 };
 
 enum {

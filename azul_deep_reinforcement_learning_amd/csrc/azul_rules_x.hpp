@@ -1066,26 +1066,33 @@ AZ_FN void selfplay_body_x(const XBatchDev &b, const XTraj &t, u32 wave_id, u32 
 #else
     SegProf *pp = nullptr;
 #endif
+    u32 turn = wv::hw_id() & 1u;     // blocks of wv::PRIO_BLOCK moves: the two waves of a SIMD take turns at priority 1 (azul_common.hpp)
 #pragma unroll 1
-    for (int s = 0; s < t.n_steps; s++) {
-        if (!dead) selfplay_step_x<P, D, OUT, PAD, BITS>(g, b.rules, K, r, tab, b.draw_margin, cnt, o, dead, pp);
-        else {
-            // the game was stopped by a rule error (bag and lid empty without the short-deal rule; the reference raises, azul.py:86-87): no
-            // move is played in this slot -- it is marked like a stuck slot (action -1, done 2) and counted with them, so that whoever
-            // counts env moves as slots minus `stuck` stays right and the trajectory carries no stale data
-            cnt.stuck_add += 1u;
-            {
-                MaskX<D> none;                           // ... an empty mask row, like a stuck slot's (nothing is legal)
+    for (int s0 = 0; s0 < t.n_steps; s0 += wv::PRIO_BLOCK) {
+        wv::set_prio(turn != 0u);
+        turn ^= 1u;
+        const int s1 = s0 + wv::PRIO_BLOCK < t.n_steps ? s0 + wv::PRIO_BLOCK : t.n_steps;
+#pragma unroll 1
+        for (int s = s0; s < s1; s++) {
+            if (!dead) selfplay_step_x<P, D, OUT, PAD, BITS>(g, b.rules, K, r, tab, b.draw_margin, cnt, o, dead, pp);
+            else {
+                // the game was stopped by a rule error (bag and lid empty without the short-deal rule; the reference raises, azul.py:86-87): no
+                // move is played in this slot -- it is marked like a stuck slot (action -1, done 2) and counted with them, so that whoever
+                // counts env moves as slots minus `stuck` stays right and the trajectory carries no stale data
+                cnt.stuck_add += 1u;
+                {
+                    MaskX<D> none;                           // ... an empty mask row, like a stuck slot's (nothing is legal)
 #pragma unroll
-                for (u32 rr = 0; rr < 6u; rr++)
+                    for (u32 rr = 0; rr < 6u; rr++)
 #pragma unroll
-                    for (u32 ww = 0; ww < Dim<D>::NW; ww++) { none.m[rr][ww] = 0u; none.bit[rr][ww] = 0u; }
-                if (OUT == 1 || (OUT == 2 && o.mask)) store_mask_x<D, (PAD && OUT == 1)>(o, none, l);
-                if ((OUT == 1 && BITS) || (OUT == 2 && o.maskbits)) store_maskbits_x<D>(o, none, l);
+                        for (u32 ww = 0; ww < Dim<D>::NW; ww++) { none.m[rr][ww] = 0u; none.bit[rr][ww] = 0u; }
+                    if (OUT == 1 || (OUT == 2 && o.mask)) store_mask_x<D, (PAD && OUT == 1)>(o, none, l);
+                    if ((OUT == 1 && BITS) || (OUT == 2 && o.maskbits)) store_maskbits_x<D>(o, none, l);
+                }
+                outputs_x<P, D, OUT>(g, o, -1, 2u, l);
             }
-            outputs_x<P, D, OUT>(g, o, -1, 2u, l);
+            o.e += b.n;
         }
-        o.e += b.n;
     }
 #if defined(AZ_PROFILE_SEGMENTS)
     if (lane == 0u) for (int q = 0; q < SEG_COUNT; q++) atomicAdd((unsigned long long *)(b.prof + q), (unsigned long long)prof.acc[q]);

@@ -217,6 +217,9 @@ struct Rng2 {
     u32 dirty;       // a regeneration happened: LDS differs from global memory
     u32 wbase, wend; // the window `win` serves words wbase .. wend-1 (wend == 0: none loaded)
     u32 win;         // lane l: TEMPERED word wbase + l
+#if defined(AZ_PROFILE_SEGMENTS)
+    u32 regens;      // diagnostic build: regenerations since rng2_open (the per-wave record, azul_common.hpp)
+#endif
 };
 
 // the batch's move limit (BatchDev::move_limit: 0 = none) into / out of the game's LDS region; written once per kernel by lane 0 of the half
@@ -237,6 +240,9 @@ AZ_FN void lds_sync() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); _
 AZ_FN void rng2_open(Rng2 &r, const u32 *gmt, u32 *lds, u32 pos, u32 l)
 {
     r.lds = lds; r.tlds = nullptr; r.pos = pos; r.dirty = 0; r.wbase = 0; r.wend = 0; r.win = 0;
+#if defined(AZ_PROFILE_SEGMENTS)
+    r.regens = 0;
+#endif
     u32 w[20];
 #pragma unroll
     for (u32 q = 0; q < 20u; q++) { u32 i = l + 32u * q; w[q] = i < 624u ? gmt[i] : 0u; }     // all loads in flight, then the LDS writes
@@ -283,6 +289,9 @@ AZ_FN void rng2_twist(Rng2 &r, u32 l)
         lds_sync();
     }
     r.dirty = 1;
+#if defined(AZ_PROFILE_SEGMENTS)
+    r.regens += 1u;
+#endif
     r.pos = 0;
     r.wend = 0;
 }
@@ -336,6 +345,23 @@ AZ_FN void rng2_close(Rng2 &r, u32 *gmt, u32 *pos_out, u32 l)
     }
     if (l == 0u) *pos_out = r.pos;
 }
+
+#if defined(AZ_PROFILE_SEGMENTS)
+// DIAGNOSTIC: the wave's record of a self-play launch (layout: azul_common.hpp), written by lane 0 after the stream is closed
+AZ_FN void wave_record(u64 *wave_prof, const WaveStamps &t, u32 wave_id, bool two_games, const SegProf &p, u32 regens, u32 lane)
+{
+    const u64 t_close = __builtin_amdgcn_s_memtime();
+    const u32 rg = (u32)__builtin_amdgcn_readlane((int)regens, 0) + (two_games ? (u32)__builtin_amdgcn_readlane((int)regens, 32) : 0u);
+    if (lane == 0u) {
+        u64 *w = wave_prof + (size_t)wave_id * AZ_WAVE_REC_WORDS;
+        w[0] = t.entry; w[1] = t.loop_start; w[2] = t.loop_end; w[3] = t_close;
+        w[4] = (u64)blockIdx.x | ((u64)wv::hw_id() << 32);
+        w[5] = (u64)wv::hw_xcc_id() | ((u64)wave_id << 32);
+        w[6] = (u64)p.cnt[WCNT_ROUND_END] | ((u64)p.cnt[WCNT_DEAL] << 32);
+        w[7] = (u64)p.cnt[WCNT_RESET] | ((u64)rg << 32);
+    }
+}
+#endif
 
 // ---- legal-move mask: six 32-bit words per game ---------------------------------------------------------------------------
 struct Mask2 {
@@ -969,12 +995,14 @@ AZ_FN u32 after_move2(G2 &g, u32 first_player, const K2 &k, Rng2 &r, u64 margin,
         if (lone_round_end(eor)) count_score2_lone<LID>(g, k, eor);
         else if (eor) count_score2<LID>(g, k);
         if (eor) { if (g.over) g.eog = 1; }                  // :308-309
+        AZ_COUNT(WCNT_ROUND_END, eor);
         AZ_STAMP(SEG_SCORE);
         // MOVE LIMIT (beyond the reference, off unless azul_batch_set_move_limit: k.move_limit == ~0u): a round ended, the game did not, and
         // the episode has played its limit -- under the reference's rules a game can reach a state from which it NEVER ends (every tile of a
         // colour locked in lines that cannot be completed: no wall row can fill, azul.py:184-191 stays false): it is cut here, no round dealt
         // (the cut rides on `over` -- 0 / 1 from the walls, 3 here; the episode reset below clears it)
         if (LIM) { if (eor & !g.over) { if (g.moves >= rng2_move_limit(r)) g.over = 3u; } }
+        AZ_COUNT(WCNT_DEAL, eor & !g.over);
         if (eor & !g.over) st = new_round2<LID>(g, r, margin, k);      // :311
         AZ_STAMP(SEG_NEWROUND);
         any_done = wave_any((g.over != 0u) & (st == ST_OK));
@@ -988,6 +1016,7 @@ AZ_FN u32 after_move2(G2 &g, u32 first_player, const K2 &k, Rng2 &r, u64 margin,
     AZ_STAMP(SEG_TAIL);
     u32 ret = st != ST_OK ? (0x100u | st) : dn;
     if (AZ_UNLIKELY(any_done)) {
+        AZ_COUNT(WCNT_RESET, (dn != 0u) & (st == ST_OK));
         if ((dn != 0u) & (st == ST_OK)) {
             if (!LIM || dn == 1u) {
                 const double f0 = (double)(g.fps & 0xffffu), f1 = (double)(g.fps >> 16);

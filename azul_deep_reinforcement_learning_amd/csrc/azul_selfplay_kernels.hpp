@@ -160,6 +160,10 @@ __global__ void __launch_bounds__(64) azul_selfplay2_kernel(BatchDev b, TrajArgs
     __shared__ u32 mt_lds[2][az2::MT_LDS_WORDS];          // (+ the move limit: az2::rng2_set_move_limit)
     __shared__ u32 mtt_lds[2][624];                        // the same words tempered (az2::Rng2::tlds)
     __shared__ double2 tabfs_lds[T_PAIRS];                 // {Fr[J][b], S[J]} + the floor-only pairs: both table values of a decision in one 16-byte read
+#if defined(AZ_PROFILE_SEGMENTS)
+    WaveStamps wstamps;
+#endif
+    AZ_WAVE_STAMP(entry);
     const u32 lane = wv::lane(), l = lane & 31u, half = lane >> 5;
     for (u32 i = lane; i < (u32)T_PAIRS; i += 64u) tabfs_lds[i] = b.tab[i];
     az2::lds_sync();
@@ -190,7 +194,8 @@ __global__ void __launch_bounds__(64) azul_selfplay2_kernel(BatchDev b, TrajArgs
 #if defined(AZ_PROFILE_SEGMENTS)
     SegProf prof;
     for (int q = 0; q < SEG_COUNT; q++) prof.acc[q] = 0;
-    prof.last = __builtin_amdgcn_s_memtime();
+    for (int q = 0; q < WCNT_COUNT; q++) prof.cnt[q] = 0;
+    prof.last = AZ_WAVE_STAMP(loop_start);
     SegProf *pp = &prof;
 #else
     SegProf *pp = nullptr;
@@ -203,28 +208,46 @@ __global__ void __launch_bounds__(64) azul_selfplay2_kernel(BatchDev b, TrajArgs
     // The host therefore launches the LIM instantiation (limit 0 = none) for every batch it has written records into (azul_kernels.hip:
     // azul_batch::handed_in), so the default one only ever sees states that play produced.
     bool dead = false;               // (set inside the rare blocks only: the common path carries no test for it)
+    // The loop is a nest: blocks of wv::PRIO_BLOCK moves, and at the head of each the wave takes or yields priority (azul_common.hpp).
+    u32 turn = wv::hw_id() & 1u;
     if (LIM) {
         u32 skipped = 0;
 #pragma unroll 1
-        for (int s = 0; s < t.n_steps; s++) {
-            if (!dead) az2::selfplay_step2<LID, OUT, PAD, BITS, true>(g, b.rules.first_player, k, r, tab, margin, cnt, o, pp, dead);
-            else skipped += 1u;
-            o.e += b.n;
+        for (int s0 = 0; s0 < t.n_steps; s0 += wv::PRIO_BLOCK) {
+            wv::set_prio(turn != 0u);
+            turn ^= 1u;
+            const int s1 = s0 + wv::PRIO_BLOCK < t.n_steps ? s0 + wv::PRIO_BLOCK : t.n_steps;
+#pragma unroll 1
+            for (int s = s0; s < s1; s++) {
+                if (!dead) az2::selfplay_step2<LID, OUT, PAD, BITS, true>(g, b.rules.first_player, k, r, tab, margin, cnt, o, pp, dead);
+                else skipped += 1u;
+                o.e += b.n;
+            }
         }
         if (AZ_UNLIKELY(az2::wave_any(dead))) {
             if (dead) az2::dead_slots2<OUT, PAD, BITS>(g, o, cnt, b.n, o.e, skipped, l);
         }
     } else {
 #pragma unroll 1
-        for (int s = 0; s < t.n_steps; s++) {
-            if (!dead) az2::selfplay_step2<LID, OUT, PAD, BITS, false>(g, b.rules.first_player, k, r, tab, margin, cnt, o, pp, dead);
-            o.e += b.n;
+        for (int s0 = 0; s0 < t.n_steps; s0 += wv::PRIO_BLOCK) {
+            wv::set_prio(turn != 0u);
+            turn ^= 1u;
+            const int s1 = s0 + wv::PRIO_BLOCK < t.n_steps ? s0 + wv::PRIO_BLOCK : t.n_steps;
+#pragma unroll 1
+            for (int s = s0; s < s1; s++) {
+                if (!dead) az2::selfplay_step2<LID, OUT, PAD, BITS, false>(g, b.rules.first_player, k, r, tab, margin, cnt, o, pp, dead);
+                o.e += b.n;
+            }
         }
     }
+    AZ_WAVE_STAMP(loop_end);
 #if defined(AZ_PROFILE_SEGMENTS)
     if (lane == 0u) for (int q = 0; q < SEG_COUNT; q++) atomicAdd((unsigned long long *)(b.prof + q), (unsigned long long)prof.acc[q]);
 #endif
     az2::g2_store(g, rec, l);
     az2::rng2_close(r, gmt, b.mtpos + gi, l);
     az2::counters2_close(cnt, l);
+#if defined(AZ_PROFILE_SEGMENTS)
+    az2::wave_record(b.wave_prof, wstamps, wave_id, wave_id * 2u + 1u < b.n, prof, r.regens, lane);
+#endif
 }
