@@ -575,6 +575,10 @@ int azul_pack_c1(const float *obs_dev, const uint8_t *mask_dev, const uint8_t *p
  * are 256-byte wide records (bytes of absent players and the reserved tail are not written), mask rows are dense.  A game of such a
  * batch that a rule error stops (bag and lid empty without AZUL_RULE_SHORT_DEAL, where the reference raises: azul.py:86-87) plays no
  * further move in this launch: its remaining slots carry action -1 / done 2 and are counted in `stuck` like the slots of a stuck game.
+ * The slot of the stopping move itself carries the mask before the move, the chosen action and done 0; the record (and every later rec_dev
+ * row) and the stream stay as the failing step left them -- the move played, the round scored, the new round dealt as far as the tiles went.
+ * The stop is not remembered across launches: the NEXT launch plays the record on like any state handed in (whatever is legal in the partly
+ * dealt round; a restart through the stuck path when nothing is) -- exactly what the oracle's stream does from its own post-failure state.
  * The same holds for a TWO-player batch ("Lid" pool, box and lid both empty when a round has to be dealt) once the host has written
  * records into it (azul_batch_set_state, azul_game_call's record_in) or it has a move limit: play from azul_batch_init / _reset cannot
  * reach such a state, so a batch that was never handed a record runs the instantiation without that bookkeeping (the benchmarked one).

@@ -19,6 +19,7 @@ import pytest
 import torch
 
 from oracle import oracle as oz
+from tests import wide_stream_cases as W
 
 pytestmark = pytest.mark.gpu
 
@@ -88,21 +89,23 @@ def test_beyond_the_reference_parity_unpinned_selfplay_equals_the_oracle(players
                 try:
                     o = s.advance(T)
                 except RuntimeError:
-                    # bag and lid ran dry without the short-deal rule: the oracle stops (OZ_BOX_EMPTY, where the reference raises); the device
-                    # game stays as it was.  Compare the moves before it.
+                    # bag and lid ran dry without the short-deal rule: the oracle stops (OZ_BOX_EMPTY, where the reference raises).  The exact
+                    # pin of tests/wide_stream_cases.py: the slots before the stop, the stopping slot, the marked slots after it (action -1,
+                    # done 2, empty mask row, `stuck`), final record, all 624 words + index, counters -- launch by launch.
                     assert not ext & oz.EXT_SHORT_DEAL, tag
                     box_empty += 1
-                    s2 = oz.StreamX(seed0 + g, P, first_player=first, tile_pool=pool, ext=ext)
-                    ok = 0
-                    while True:
-                        try:
-                            o1 = s2.advance(1)
-                        except RuntimeError:
-                            break
-                        if variant != "none":
-                            assert np.array_equal(mask_all[ok, g], o1["mask"][0]) and act_all[ok, g] == o1["action"][0], tag + (ok,)
-                        ok += 1
-                    assert ok < T
+                    got = {"final": recs, "mt": mts, "pos": poss, "episodes": cnt["episodes"], "stuck": cnt["stuck"], "stat_sums": cnt["stat_sums"]}
+                    if variant != "none":
+                        got.update(mask=mask_all, action=act_all, done=done_all, reward=rew_all)
+                    if variant == "records":
+                        got["rec"] = tr["records"].cpu().numpy()
+                    if variant == "full":
+                        got.update(packed=tr["packed"].cpu().numpy(), maskbits=tr["maskbits"].cpu().numpy())
+                    s2 = W.new_stream(seed0 + g, (P, ext, first, pool))
+                    for k in ((T // 2, T - T // 2) if variant == "none" else (T,)):
+                        e = W.play_oracle(s2, k)
+                    assert variant == "none" or e.ok < T, tag
+                    W.compare(e, got, g, tag)
                     continue
                 if variant != "none":
                     assert np.array_equal(mask_all[:, g], o["mask"]), tag
@@ -132,6 +135,9 @@ def test_beyond_the_reference_parity_unpinned_selfplay_equals_the_oracle(players
         assert box_empty == 0
         if P == 4 and ext & oz.EXT_DISPLAYS_2P1:
             assert short_deals > 0
+    if P == 4 and ext == oz.EXT_DISPLAYS_2P1:
+        # the oracle alone says so (tests/test_wide_stream_cases.py): seeds 5108, 5109, 5114 and 5130 stop under "Lid" / first player Random
+        assert box_empty >= 4 * 3
 
 
 @pytest.mark.parametrize("players", [2, 3, 4])

@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 from oracle import oracle as oz
+from tests import wide_stream_cases as W
 
 HERE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "hostcheck")
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -43,87 +44,70 @@ def split_ext(pool, ext):
     return xpool, int(bool(ext & oz.EXT_END_BONUS)), int(bool(ext & oz.EXT_SHORT_DEAL))
 
 
+class Emulated:
+    """A batch under the emulation: the arrays a device batch keeps (records, MT19937 states + indices, counters) live here across launches."""
+
+    def __init__(self, L, cfg, streams, margin=0):
+        self.L, self.cfg, self.margin, self.n = L, cfg, margin, len(streams)
+        P, ext, first, pool = cfg
+        self.D = W.displays(P, ext)
+        self.NA = W.num_actions(P, ext)
+        n = self.n
+        self.state = np.stack([W.record_bytes(s) for s in streams]).copy()
+        self.mt = np.stack([s.rng_state()[0] for s in streams]).astype(np.uint32).copy()
+        self.pos = np.array([s.rng_state()[1] for s in streams], dtype=np.uint32)
+        self.ep, self.stuck, self.ss = np.zeros(n, np.uint64), np.zeros(n, np.uint32), np.zeros((n, 10))
+
+    def launch(self, T, variant):
+        """-> what the launch wrote, in the layout tests/wide_stream_cases.compare reads; every buffer is prefilled with junk except the
+        record snapshots (a wide record's absent players and reserved tail are not written)."""
+        P, ext, first, pool = self.cfg
+        n, NA, D = self.n, self.NA, self.D
+        pitch = W.PAD_PITCH[D] if variant in (0, 1) else NA
+        NL = (NA + 63) // 64
+        out = {}
+        if variant != 4:
+            out = {"mask": np.full((T, n, pitch), 0xEE, np.uint8), "action": np.full((T, n), -7, np.int32), "reward": np.full((T, n), -7, np.int32),
+                   "done": np.full((T, n), 9, np.uint8)}
+            if variant == 0:
+                out["maskbits"] = np.full((T, n, NL), 0x5A5A5A5A5A5A5A5A, np.uint64)
+            if variant != 3:
+                out["packed"] = np.full((T, n), 0x77777777, np.uint32)
+            else:
+                out["rec"] = np.zeros((T, n, 256), np.uint8)
+                out["maskbits"] = np.full((T, n, NL), 0x5A5A5A5A5A5A5A5A, np.uint64)
+        xpool, eb, sd = split_ext(pool, ext)
+        ops = self.L.shx_selfplay(n, P, D, ptr(self.state), ptr(self.mt), ptr(self.pos), ptr(self.ep), ptr(self.stuck), ptr(self.ss), first, xpool, eb,
+                                  sd, self.margin, T, variant, ptr(out.get("mask")), pitch, ptr(out.get("maskbits")), ptr(out.get("action")),
+                                  ptr(out.get("reward")), ptr(out.get("done")), ptr(out.get("packed")), ptr(out.get("rec")))
+        assert ops > 0
+        out.update(final=self.state, mt=self.mt, pos=self.pos, episodes=self.ep, stuck=self.stuck, stat_sums=self.ss)
+        return out
+
+
 def run_streams(L, P, first, pool, ext, n, T, variant, seed0, margin=0, prepare=None):
-    D = 2 * P + 1 if ext & oz.EXT_DISPLAYS_2P1 else 5
-    NA = (D + 1) * 30
-    streams = [oz.StreamX(seed0 + g, P, first_player=first, tile_pool=pool, ext=ext) for g in range(n)]
+    cfg = (P, ext, first, pool)
+    streams = [W.new_stream(seed0 + g, cfg) for g in range(n)]
     if prepare:
         prepare(streams)
-    state = np.stack([np.frombuffer(s.record().tobytes(), np.uint8) for s in streams]).copy()
-    mt = np.stack([s.rng_state()[0] for s in streams]).astype(np.uint32).copy()
-    pos = np.array([s.rng_state()[1] for s in streams], dtype=np.uint32)
-    ep, stuck, ss = np.zeros(n, np.uint64), np.zeros(n, np.uint32), np.zeros((n, 10))
-    pitch = {5: 192, 7: 256, 9: 320}[D] if variant in (0, 1) else NA
-    NL = (NA + 63) // 64
-    out = {}
-    if variant != 4:
-        out = {"mask": np.full((T, n, pitch), 0xEE, np.uint8), "action": np.full((T, n), -7, np.int32), "reward": np.full((T, n), -7, np.int32),
-               "done": np.full((T, n), 9, np.uint8)}
-        if variant == 0:
-            out["maskbits"] = np.zeros((T, n, NL), np.uint64)
-        if variant != 3:
-            out["packed"] = np.zeros((T, n), np.uint32)
-        else:
-            out["rec"] = np.zeros((T, n, 256), np.uint8)
-            out["maskbits"] = np.zeros((T, n, NL), np.uint64)
-    xpool, eb, sd = split_ext(pool, ext)
-    ops = L.shx_selfplay(n, P, D, ptr(state), ptr(mt), ptr(pos), ptr(ep), ptr(stuck), ptr(ss), first, xpool, eb, sd, margin, T, variant,
-                         ptr(out.get("mask")), pitch, ptr(out.get("maskbits")), ptr(out.get("action")), ptr(out.get("reward")),
-                         ptr(out.get("done")), ptr(out.get("packed")), ptr(out.get("rec")))
-    assert ops > 0
-    return streams, state, mt, pos, ep, stuck, ss, out, NA
+    emu = Emulated(L, cfg, streams, margin)
+    out = emu.launch(T, variant)
+    return streams, emu.state, emu.mt, emu.pos, emu.ep, emu.stuck, emu.ss, out, emu.NA
 
 
 def check_streams(L, P, first, pool, ext, n, T, variant, seed0, margin=0, prepare=None):
+    """Every game against the shared expectation (tests/wide_stream_cases.py) -- a game that stops on OZ_BOX_EMPTY included, exactly: the
+    slots before the stop, the stopping slot, the marked slots after it, final record, stream, counters."""
     streams, state, mt, pos, ep, stuck, ss, out, NA = run_streams(L, P, first, pool, ext, n, T, variant, seed0, margin, prepare)
-    finished = 0
+    stopped = 0
     for g, s in enumerate(streams):
-        tag = (P, first, pool, ext, variant, g)
-        try:
-            o = s.advance(T)
-        except RuntimeError:
-            # bag and lid ran dry without the short-deal rule: the oracle stops at that move (OZ_BOX_EMPTY); the device game stays as it
-            # was after its last complete move.  Compare the moves before it.
-            assert not ext & oz.EXT_SHORT_DEAL, tag
-            s2 = oz.StreamX(seed0 + g, P, first_player=first, tile_pool=pool, ext=ext)
-            ok = 0
-            while True:
-                try:
-                    o1 = s2.advance(1)
-                except RuntimeError:
-                    break
-                if variant != 4:
-                    assert np.array_equal(out["mask"][ok, g, :NA], o1["mask"][0]) and out["action"][ok, g] == o1["action"][0], tag + (ok,)
-                ok += 1
-            assert ok < T
-            if variant != 4:
-                # the slots after the stop: no move played -- marked like stuck slots (action -1, done 2) and counted with them
-                assert (out["action"][ok + 1:, g] == -1).all() and (out["done"][ok + 1:, g] == 2).all(), tag
-                assert not out["mask"][ok + 1:, g, :NA].any(), tag      # ... with an empty mask row (no stale bytes in the trajectory)
-            assert int(stuck[g]) >= T - ok - 1, tag
-            continue
-        if variant != 4:
-            assert np.array_equal(out["mask"][:, g, :NA], o["mask"]), tag
-            assert np.array_equal(out["action"][:, g], o["action"]), tag
-            assert np.array_equal(out["done"][:, g], o["done"]), tag
-            assert not out["reward"][:, g].any(), tag                 # GameRunner's shaped reward is two-player (game_runner.py:50)
-        if "maskbits" in out:
-            nb = (NA + 7) // 8
-            bits = out["maskbits"][:, g].view(np.uint8).reshape(T, -1)[:, :nb]
-            assert np.array_equal(bits, np.packbits(o["mask"].astype(bool), axis=1, bitorder="little")), tag
-        if "packed" in out:
-            p = out["packed"][:, g]
-            a = np.where((p & 0xFF) == 0xFF, (p >> 16).astype(np.int32), (p & 0xFF).astype(np.int32))
-            a[a == 0xFFFF] = -1
-            assert np.array_equal(a, o["action"]) and np.array_equal((p >> 8) & 0xFF, o["done"]), tag
-        if "rec" in out:
-            assert out["rec"][:, g].tobytes() == o["rec_after"].tobytes(), tag
-        assert state[g].tobytes() == s.record().tobytes(), tag
-        assert np.array_equal(mt[g], s.rng_state()[0]) and int(pos[g]) == s.rng_state()[1], tag
-        assert int(ep[g]) == int(s.episodes.value) and int(stuck[g]) == int(s.stuck.value), tag
-        assert np.allclose(ss[g], s.stats_sum, rtol=0, atol=1e-9), tag
-        finished += int(ep[g])
-    return finished
+        e = W.play_oracle(s, T)
+        if e.ok < T:
+            assert not ext & oz.EXT_SHORT_DEAL, (P, first, pool, ext, variant, g)
+            stopped += 1
+        W.compare(e, out, g, (P, first, pool, ext, variant))
+    check_streams.stopped = stopped
+    return int(ep.sum())
 
 
 @pytest.mark.parametrize("players", [3, 4])
@@ -222,3 +206,50 @@ def test_factory_draw_across_a_regeneration_and_through_the_fp64_path(players, e
     check_streams(L, players, oz.FIRST_RANDOM, oz.POOL_LID, ext, n=16, T=40, variant=3, seed0=300, prepare=near_the_end_of_the_state)
     check_streams(L, players, oz.FIRST_RANDOM, oz.POOL_LID, ext, n=4, T=60, variant=3, seed0=310, margin=0x7fffffff)
     check_streams(L, players, oz.FIRST_RANDOM, oz.POOL_LID, ext, n=8, T=30, variant=3, seed0=320, margin=0x7fffffff, prepare=near_the_end_of_the_state)
+
+
+# ---- the edges of the wide self-play kernels, stated once in tests/wide_stream_cases.py (the GPU runs the same cases on whole batches:
+# tests/test_gpu_wide_selfplay_edges.py) ---------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("which", sorted(W.STOP_CONFIGS))
+def test_a_stopped_game_is_pinned_exactly_and_a_second_launch_plays_it_on(which):
+    """OZ_BOX_EMPTY: slots before the stop, the stopping slot, the marked slots, final record = the oracle's after its failing call, all 624
+    words + index, `stuck` = the oracle's + exactly T - ok - 1; a stopped game beside a live sibling in either half and beside another stopped
+    game.  `dead` is a local of one launch: the next launch plays the record on like any handed-in state -- the oracle continued from its own
+    post-failure state."""
+    L = load()
+    cfg, seeds, slots = W.stop_seeds(which)
+    oks = {g: W.moves_until_stop(W.new_stream(int(seeds[g]), cfg), W.STOP_T) for g in slots}
+    first = sorted(slots, key=lambda g: oks[g])[:3]              # the three earliest stops (the emulation runs a fiber per lane)
+    T = max(oks[g] for g in first) + 12
+    pick = [first[0], 1, 2, first[1], first[2], first[1]]        # X. | .X | XX : half 0 / half 1 beside a live sibling, a stopped pair
+    pick[1], pick[2] = [g for g in range(len(seeds)) if g not in slots][:2]
+    for variant in (3, 1, 0):
+        streams = [W.new_stream(int(seeds[g]), cfg) for g in pick]
+        emu = Emulated(L, cfg, streams)
+        out = emu.launch(T, variant)
+        es = [W.play_oracle(s, T) for s in streams]
+        stopped = [g for g, e in enumerate(es) if e.ok < T]
+        assert stopped == [0, 3, 4, 5] and W.sibling_placements(stopped, 6) == {"half0", "half1", "pair"}
+        for g, e in enumerate(es):
+            W.compare(e, out, g, (which, variant))
+        W.must_differ(W.shifted_stop(es[0], 1), out, 0)
+        W.must_differ(W.shifted_stop(es[0], -1), out, 0)
+        if variant == 3:
+            out2 = emu.launch(40, variant)
+            for g, s in enumerate(streams):
+                W.compare(W.play_oracle(s, 40), out2, g, (which, variant, "second launch"))
+
+
+@pytest.mark.parametrize("cfg", [W.CONFIGS[0], W.CONFIGS[3]], ids=W.config_id)
+def test_handed_in_games_finished_and_stuck_slots_continue_like_the_oracle(cfg):
+    L = load()
+    keep = [0, 1, 2, 3, W.HAND_IN_ENDED[0], W.HAND_IN_ENDED[1], W.HAND_IN_STUCK[0] - 1, W.HAND_IN_STUCK[0], W.HAND_IN_STUCK[1], W.HAND_IN_STUCK[1] + 1]
+    allg = W.hand_in_streams(cfg, 6200)
+    streams = [allg[g] for g in keep]                    # ended flag in half 0 and half 1, stuck in half 1 and half 0
+    emu = Emulated(L, cfg, streams)
+    out = emu.launch(60, 3)
+    for g, s in enumerate(streams):
+        e = W.play_oracle(s, 60)
+        if keep[g] in W.HAND_IN_ENDED + W.HAND_IN_STUCK:
+            assert e.action[0] == -1 and e.done[0] == 2 and e.stuck >= 1
+        W.compare(e, out, g, (W.config_id(cfg), keep[g]))
