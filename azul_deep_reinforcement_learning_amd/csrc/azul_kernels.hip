@@ -1025,6 +1025,8 @@ int azul_select_episode_samples(const uint8_t *done_ring_dev, const int32_t *act
     if (!done_ring_dev || !action_ring_dev || !pending_dev || !index_dev || !count_dev || !scratch_dev || window_steps <= 0 || ring_windows <= 0 ||
         n_games <= 0 || steps_played < window_steps || steps_played % window_steps != 0 || steps_played > 0x7fff0000ll)
         return fail(AZUL_ERR_INVALID, "azul_select_episode_samples: bad arguments");
+    if ((int64_t)window_steps * (int64_t)ring_windows * (int64_t)n_games > (int64_t)INT32_MAX)      // the indices slot * n_games + game are int32
+        return fail(AZUL_ERR_INVALID, "azul_select_episode_samples: window_steps * ring_windows * n_games exceeds INT32_MAX");
     STREAM_GUARD(stream);
     const u32 N = (u32)n_games, blocks = (N + 3u) / 4u;      // one wave per game, four games per workgroup
     const int R = window_steps * ring_windows;
@@ -1041,6 +1043,8 @@ int azul_select_complete_samples(const uint8_t *done_dev, const int32_t *action_
 {
     if (!done_dev || !action_dev || !index_dev || !count_dev || n_steps < 0 || n_games <= 0)
         return fail(AZUL_ERR_INVALID, "azul_select_complete_samples: bad arguments");
+    if ((int64_t)n_steps * (int64_t)n_games > (int64_t)INT32_MAX)                                   // the indices t * n_games + game are int32
+        return fail(AZUL_ERR_INVALID, "azul_select_complete_samples: n_steps * n_games exceeds INT32_MAX");
     STREAM_GUARD(stream);
     hipLaunchKernelGGL(azul_select_complete_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, done_dev, action_dev, n_steps, (u32)n_games,
                        index_dev, count_dev);

@@ -517,7 +517,7 @@ int azul_a2c_apply_adam_n(const float *grad_dev, float *flat_dev, float *exp_avg
 /* Which steps of a window feed the update (NNRunner.train uses whole episodes, nn_runner.py:59-76): the steps whose episode ends
  * inside the window and that carry an action (>= 0).  done / action are time-major [n_steps][n_games]; index_dev receives the flat
  * indices t * n_games + g (game by game, steps ascending), count_dev[0] their number.  Feeds azul_a2c_gradients' index_dev /
- * n_samples_dev without a host round trip. */
+ * n_samples_dev without a host round trip.  The indices are int32: n_steps * n_games above INT32_MAX is AZUL_ERR_INVALID. */
 int azul_select_complete_samples(const uint8_t *done_dev, const int32_t *action_dev, int n_steps, int n_games, int32_t *index_dev,
                                  int32_t *count_dev, void *stream);
 /* The same selection over a RING of `ring_windows` windows of `window_steps` agent steps each, so that EVERY step of EVERY episode is
@@ -529,7 +529,10 @@ int azul_select_complete_samples(const uint8_t *done_dev, const int32_t *action_
  * through the ring with the carry, so those steps' returns are exact).  index_dev receives flat indices slot * n_games + game (game by
  * game, steps ascending), count_dev[0] their number, count_dev[1] ACCUMULATES the steps that had left the ring before their episode
  * ended (zero it once); countf_dev (optional, float[2]) receives the count and 1 / max(count, 1) as floats (what azul_a2c_gradients'
- * inv_n_total_dev and azul_a2c_apply_adam's n_total_dev read); scratch_dev: int32 [3 n_games + ceil(n_games / 4)]. */
+ * inv_n_total_dev and azul_a2c_apply_adam's n_total_dev read); scratch_dev: int32 [3 n_games + ceil(n_games / 4)].
+ * Limits (AZUL_ERR_INVALID before any launch): the indices are int32, so window_steps * ring_windows * n_games must not exceed INT32_MAX;
+ * the step clock is int32 too: steps_played must not exceed 0x7fff0000 (a caller whose clock grows rebases steps_played and pending_dev
+ * by whole rings, which moves no slot). */
 int azul_select_episode_samples(const uint8_t *done_ring_dev, const int32_t *action_ring_dev, int window_steps, int ring_windows, int n_games,
                                 int64_t steps_played, int32_t *pending_dev, int32_t *index_dev, int32_t *count_dev, float *countf_dev,
                                 int32_t *scratch_dev, void *stream);

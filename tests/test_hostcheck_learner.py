@@ -9,7 +9,10 @@ import os
 import subprocess
 
 import numpy as np
+import pytest
 import torch
+
+from tests import training_ring_cases as M
 
 HERE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "hostcheck")
 
@@ -317,3 +320,97 @@ def test_the_remaining_small_kernels_under_emulation():
     for i in range(parts):
         s = s + partial[i]
     assert np.array_equal(grad, s)
+
+
+# ---- the case table of tests/training_ring_cases.py through the same kernels: what tests/test_gpu_training_ring.py asks of the GPU -------
+_ids = lambda cases: [c.id for c in cases]
+GUARD = 64
+
+
+def _ring_lib():
+    L = load()
+    for name in ("sl_select_complete", "sl_select_ring", "sl_returns", "sl_returns_ring"):
+        getattr(L, name).restype = C.c_longlong
+    L.sl_select_complete.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    L.sl_select_ring.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 5
+    L.sl_returns.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_int]
+    L.sl_returns_ring.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_longlong, C.c_int, C.c_int]
+    return L
+
+
+def _guarded(n):
+    return np.full(n + GUARD, M.SENTINEL, np.int32)
+
+
+@pytest.mark.parametrize("case", M.COMPLETE_CASES, ids=_ids(M.COMPLETE_CASES))
+def test_select_complete_kernel_under_emulation_on_the_case_table(case):
+    """azul_select_complete_kernel at its edges: more than one chunk of 1024 games (the base carried between chunks), the last end at
+    step 63 (the action mask's last bit) and 64 (the re-read path), T = 0, a lone game.  Every case runs here (each well under a second)."""
+    L = _ring_lib()
+    done, action = case.build()
+    N, T = case.N, case.T
+    want, n = M.select_complete(done, action)
+    index, count = _guarded(T * N), _guarded(1)
+    done, action = np.ascontiguousarray(done), np.ascontiguousarray(action)
+    if T == 0:                                                   # (no rows: the kernel must not read a single element)
+        done, action = np.zeros(1, np.uint8), np.zeros(1, np.int32)
+    assert L.sl_select_complete(ptr(done), ptr(action), T, N, ptr(index), ptr(count)) > 0
+    M.compare_index(case.id, index, count[0], want, N)
+    M.compare_guard(case.id, index[n:], "index behind the selection")
+    M.compare_guard(case.id, count[1:], "count guard")
+
+
+def _run_ring_case(L, case):
+    case.build()
+    N, T, D, R = case.N, case.T, case.D, case.R
+    pend = case.first_pending().astype(np.int32)
+    count, countf = np.zeros(2, np.int32), np.zeros(2, np.float32)
+    n_scratch = 3 * N + (N + 3) // 4
+    for w, (want, want_pend, want_dropped) in enumerate(case.expected()):
+        dr, ar = case.ring_after(w)
+        index, scratch = _guarded(R * N), _guarded(n_scratch)
+        assert L.sl_select_ring(ptr(dr), ptr(ar), T, D, N, case.steps_played(w), ptr(pend), ptr(index), ptr(count), ptr(countf), ptr(scratch)) > 0
+        cid = "%s window %d" % (case.id, w)
+        M.compare_index(cid, index, count[0], want, N)
+        assert int(count[1]) == want_dropped, "%s: dropped %d, model %d" % (cid, int(count[1]), want_dropped)
+        M.compare_countf(cid, countf, len(want))
+        M.compare_pending(cid, pend, want_pend)
+        M.compare_guard(cid, index[len(want):], "index behind the selection")
+        M.compare_guard(cid, scratch[n_scratch:], "scratch guard")
+
+
+@pytest.mark.parametrize("case", M.RING_CASES + M.SHIFT_CASES, ids=_ids(M.RING_CASES + M.SHIFT_CASES))
+def test_select_ring_kernels_under_emulation_on_the_case_table(case):
+    """azul_select_ring_count_kernel / _write_kernel on the sequences of the case table: windows of more than 64 steps, episodes of
+    exactly 64 and of more steps inside the ring, more than 256 workgroups (the strided base sum), partial last workgroups, a lone game
+    on one slot, and the step clock at the top of its range.  Every case runs all its windows here, none is left to the GPU alone; the
+    slowest, measured: ring-N1023-T8-D3 11.4 s, ring-N1029-T8-D3 11.5 s, ring-N1029-T8-D3-shifted 11.3 s (11 windows each)."""
+    _run_ring_case(_ring_lib(), case)
+
+
+@pytest.mark.parametrize("case", M.WINDOW_CASES, ids=_ids(M.WINDOW_CASES))
+def test_returns_kernel_under_emulation_on_the_case_table(case):
+    L = _ring_lib()
+    reward, done, carry = case.build()
+    want, want_carry = M.returns_window(reward, done, case.gamma, carry)
+    T, N = case.T, case.N
+    out = M.nan_pattern((T + 1, N))
+    guard_row = out[T].copy()
+    c = None if carry is None else np.concatenate([carry, M.nan_pattern(GUARD)])
+    assert L.sl_returns(ptr(np.ascontiguousarray(reward)), ptr(np.ascontiguousarray(done)), ptr(out), ptr(c), np.float32(case.gamma), T, N) > 0
+    M.compare_returns(case.id, out[:T], want)
+    M.compare_returns(case.id, out[T], guard_row, "the row behind the returns")
+    if carry is not None:
+        M.compare_returns(case.id, c[:N], want_carry, "carry")
+        M.compare_returns(case.id, c[N:], M.nan_pattern(GUARD), "the words behind the carry")
+
+
+@pytest.mark.parametrize("case", M.RETRING_CASES, ids=_ids(M.RETRING_CASES))
+def test_returns_ring_kernel_under_emulation_on_the_case_table(case):
+    L = _ring_lib()
+    reward, done, ret_in = case.build()
+    want = M.returns_ring(reward, done, ret_in, case.gamma, case.ring, case.played, case.span)
+    out = np.concatenate([ret_in, M.nan_pattern((1, case.N), salt=3)])
+    assert L.sl_returns_ring(ptr(reward), ptr(done), ptr(out), np.float32(case.gamma), case.ring, case.played, case.span, case.N) > 0
+    M.compare_returns(case.id, out[:case.ring], want)
+    M.compare_returns(case.id, out[case.ring:], M.nan_pattern((1, case.N), salt=3), "the row behind the ring")
