@@ -38,15 +38,16 @@ unsigned long long sl_buffer_oob() { return simt::g_buffer_oob; }
 void sl_layout(int *out) { out[0] = LG_P_W1; out[1] = LG_P_B1; out[2] = LG_P_W2C; out[3] = LG_P_B2C; out[4] = LG_P_W2A; out[5] = LG_P_B2A; out[6] = LG_P_LOSS; out[7] = LG_P_TOTAL; }
 
 // the gradient kernel on n samples with `parts` workgroups, then azul_a2c_reduce_kernel's sum in workgroup order -> grad [LG_P_TOTAL]
-long long sl_gradients(int n, int parts, const float *obs, const uint8_t *mask, const i32 *action, const float *qvals, const i32 *index, float inv_n,
-                       const float *w1t, const float *b1, const float *w2c, const float *b2c, const float *w2a_t, const float *b2a,
-                       const float *w2a, float *partial /* [parts][LG_P_TOTAL] */, float *grad)
+// (n_dev / inv_n_dev: the sample count and 1 / count "in device memory", overriding n and inv_n as on the device-count path)
+long long sl_gradients_dev(int n, int parts, const float *obs, const uint8_t *mask, const i32 *action, const float *qvals, const i32 *index, float inv_n,
+                           const i32 *n_dev, const float *inv_n_dev, const float *w1t, const float *b1, const float *w2c, const float *b2c,
+                           const float *w2a_t, const float *b2a, const float *w2a, float *partial /* [parts][LG_P_TOTAL] */, float *grad)
 {
     GradJob j;
     memset(&j, 0, sizeof(j));
     j.W = {w1t, b1, w2c, b2c, w2a_t, b2a};
     j.a.obs = obs; j.a.mask = mask; j.a.action = action; j.a.qvals = qvals; j.a.n = (u32)n; j.a.inv_n = inv_n; j.a.w2a = w2a;
-    j.a.partial = partial; j.a.index = index;
+    j.a.partial = partial; j.a.index = index; j.a.n_dev = n_dev; j.a.inv_n_dev = inv_n_dev;
     simt::g_grid_dim = {(unsigned)parts, 1, 1};
     long long ops = 0;
     for (int blk = 0; blk < parts; blk++) {
@@ -59,6 +60,13 @@ long long sl_gradients(int n, int parts, const float *obs, const uint8_t *mask, 
         grad[p] = s;
     }
     return ops;
+}
+
+long long sl_gradients(int n, int parts, const float *obs, const uint8_t *mask, const i32 *action, const float *qvals, const i32 *index, float inv_n,
+                       const float *w1t, const float *b1, const float *w2c, const float *b2c, const float *w2a_t, const float *b2a,
+                       const float *w2a, float *partial, float *grad)
+{
+    return sl_gradients_dev(n, parts, obs, mask, action, qvals, index, inv_n, nullptr, nullptr, w1t, b1, w2c, b2c, w2a_t, b2a, w2a, partial, grad);
 }
 
 long long sl_forward(int n, const float *obs, const uint8_t *mask, const float *w1t, const float *b1, const float *w2c, const float *b2c,

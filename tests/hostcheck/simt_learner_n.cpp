@@ -28,15 +28,16 @@ unsigned long long sln_buffer_oob() { return simt::g_buffer_oob; }
 int sln_flat_size(int in, int act) { return (int)a2c_shape_n((u32)in, (u32)act).params; }
 
 // azul_a2c_grad_n_kernel<in, act> on n samples with grid (parts, 3), then azul_a2c_reduce_n_kernel's sum in part order -> grad [flat + 4]
-long long sln_gradients(int in, int act, int n, int parts, const float *obs, const uint8_t *mask, const i32 *action, const float *qvals,
-                        const i32 *index, float inv_n, const float *w1t, const float *b1, const float *w2c, const float *b2c, const float *w2a_t,
-                        const float *b2a, const float *w2a, float *partial, float *grad)
+// (n_dev / inv_n_dev: the sample count and 1 / count "in device memory", overriding n and inv_n as on the device-count path)
+long long sln_gradients_dev(int in, int act, int n, int parts, const float *obs, const uint8_t *mask, const i32 *action, const float *qvals,
+                            const i32 *index, float inv_n, const i32 *n_dev, const float *inv_n_dev, const float *w1t, const float *b1,
+                            const float *w2c, const float *b2c, const float *w2a_t, const float *b2a, const float *w2a, float *partial, float *grad)
 {
     GradNJob j;
     memset(&j, 0, sizeof(j));
     j.W = {w1t, b1, w2c, b2c, w2a_t, b2a};
     j.a.obs = obs; j.a.mask = mask; j.a.action = action; j.a.qvals = qvals; j.a.n = (u32)n; j.a.inv_n = inv_n; j.a.w2a = w2a;
-    j.a.partial = partial; j.a.index = index;
+    j.a.partial = partial; j.a.index = index; j.a.n_dev = n_dev; j.a.inv_n_dev = inv_n_dev;
     void (*fn)(void *) = nullptr;
     if (in == 188 && act == 180) fn = grad_n_lane<188, 180>;
     else if (in == 240 && act == 180) fn = grad_n_lane<240, 180>;
@@ -57,6 +58,14 @@ long long sln_gradients(int in, int act, int n, int parts, const float *obs, con
         grad[p] = s;
     }
     return ops;
+}
+
+long long sln_gradients(int in, int act, int n, int parts, const float *obs, const uint8_t *mask, const i32 *action, const float *qvals,
+                        const i32 *index, float inv_n, const float *w1t, const float *b1, const float *w2c, const float *b2c, const float *w2a_t,
+                        const float *b2a, const float *w2a, float *partial, float *grad)
+{
+    return sln_gradients_dev(in, act, n, parts, obs, mask, action, qvals, index, inv_n, nullptr, nullptr, w1t, b1, w2c, b2c, w2a_t, b2a, w2a,
+                             partial, grad);
 }
 
 // azul_a2c_apply_n_kernel (one Adam step, host-side bias corrections of step `step`)

@@ -414,3 +414,59 @@ def test_returns_ring_kernel_under_emulation_on_the_case_table(case):
     assert L.sl_returns_ring(ptr(reward), ptr(done), ptr(out), np.float32(case.gamma), case.ring, case.played, case.span, case.N) > 0
     M.compare_returns(case.id, out[:case.ring], want)
     M.compare_returns(case.id, out[case.ring:], M.nan_pattern((1, case.N), salt=3), "the row behind the ring")
+
+
+# ---- a subset of the case table of tests/a2c_grad_ref.py through the per-element comparison of tests/test_gpu_a2c_grad_edges.py -----
+def _edge_lib():
+    L = load()
+    L.sl_gradients_dev.restype = C.c_longlong
+    L.sl_gradients_dev.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 5 + [C.c_float] + [C.c_void_p] * 11
+    return L
+
+
+def _run_edge_case(L, c, mask=None):
+    lay = (C.c_int * 8)()
+    L.sl_layout(lay)
+    TOTAL = lay[7]
+    w = c["w"]
+    w2a = np.ascontiguousarray(w["w2a_t"].T)
+    tiles = (c["n"] + 31) // 32
+    parts = min(c["parts"], tiles)                                      # (the host entry launches min(tiles, workspace_parts) workgroups)
+    partial, grad = np.zeros((parts, TOTAL), np.float32), np.full(TOTAL, np.nan, np.float32)
+    mask = c["mask"] if mask is None else mask
+    n_dev = inv_dev = None
+    inv_host = c["inv_n"] if c["inv_n"] is not None else 1.0 / max(c["n"], 1)
+    if c["index"] is not None:
+        assert int(c["index"].min()) >= 0 and int(c["index"].max()) < c["obs"].shape[0]
+        n_dev, inv_dev, inv_host = np.array([c["count"]], np.int32), np.array([1.0 / max(c["count"], 1)], np.float32), 1.0
+    oob0 = L.sl_buffer_oob()
+    L.sl_gradients_dev(c["n"], parts, ptr(c["obs"]), ptr(mask), ptr(c["action"]), ptr(c["q"]), ptr(c["index"]), inv_host, ptr(n_dev), ptr(inv_dev),
+                       ptr(w["w1t"]), ptr(w["b1"]), ptr(w["w2c"]), ptr(w["b2c"]), ptr(w["w2a_t"]), ptr(w["b2a"]), ptr(w2a), ptr(partial), ptr(grad))
+    assert L.sl_buffer_oob() == oob0
+    return grad
+
+
+def _check_edge(R, shape, tag, got, c, ref):
+    flat, sums, N, _ = ref
+    size = R.flat_size(*shape)
+    K = R.k_case(R.yardstick(shape, c))
+    worst, zeros_ok = R.normalised_error(got[:size], flat, N)
+    assert np.isfinite(got).all() and zeros_ok, tag
+    assert worst <= K, (tag, worst, K)
+    assert got[R.offsets(*shape)["pad"][0]] == 0.0 and got[size + 3] == sums[3], tag
+
+
+def test_gradient_kernel_under_emulation_on_the_edge_case_table():
+    """The reference shape at the position sweep's rows 0, M - 1, M and 2M, n = M + 1 on one and two parts, one legal action, only the
+    last action legal, and a device count that ends inside a tile (entries past it point at a NaN row): every element within
+    K_case 2^-24 N of the float64 reference.  Measured: 14 s."""
+    from tests import a2c_grad_ref as R
+    L = _edge_lib()
+    shape = R.SHAPES["ref"]
+    for name in R.EMULATION_CASES:
+        c = R.build("ref", name)
+        _check_edge(R, shape, name, _run_edge_case(L, c), c, R.reference(shape, c["w"], *R.call_args(c)))
+    c = R.build("ref", "sweep")
+    for k in R.emulation_sweep_rows(*shape):
+        one = dict(c, obs=c["obs"][k:k + 1], mask=c["mask"][k:k + 1], action=c["action"][k:k + 1], q=c["q"][k:k + 1], inv_n=1.0 / c["n"])
+        _check_edge(R, shape, "sweep row %d" % k, _run_edge_case(L, c, R.sweep_mask(c, k)), one, R.reference(shape, c["w"], *R.call_args(one)))

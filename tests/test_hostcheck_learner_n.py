@@ -29,6 +29,8 @@ def load():
     L = C.CDLL(LIB)
     L.sln_gradients.restype = C.c_longlong
     L.sln_gradients.argtypes = [C.c_int] * 4 + [C.c_void_p] * 5 + [C.c_float] + [C.c_void_p] * 9
+    L.sln_gradients_dev.restype = C.c_longlong
+    L.sln_gradients_dev.argtypes = [C.c_int] * 4 + [C.c_void_p] * 5 + [C.c_float] + [C.c_void_p] * 11
     L.sln_adam.restype = C.c_longlong
     L.sln_adam.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 4 + [C.c_float] * 4 + [C.c_int] + [C.c_void_p] * 8
     L.sln_flat_size.restype = C.c_int
@@ -103,6 +105,51 @@ def test_wide_gradients_p3_d5_under_emulation_match_autograd():
 
 def test_wide_gradients_p4_d9_under_emulation_match_autograd():
     _check_gradients(260, 300, 70, 2, 12)            # 5 tiles: passes of 3 and 2, last tile of 6 samples
+
+
+def _run_edge_case(L, IN, A, c, mask=None):
+    size = L.sln_flat_size(IN, A)
+    w = c["w"]
+    w2a = np.ascontiguousarray(w["w2a_t"].T)
+    parts = min(c["parts"], (c["n"] + 15) // 16)                        # (the host entry launches min(tiles, workspace_parts) parts)
+    partial, grad = np.zeros((parts, size + 4), np.float32), np.full(size + 4, np.nan, np.float32)
+    mask = c["mask"] if mask is None else mask
+    n_dev = inv_dev = None
+    inv_host = c["inv_n"] if c["inv_n"] is not None else 1.0 / max(c["n"], 1)
+    if c["index"] is not None:
+        assert int(c["index"].min()) >= 0 and int(c["index"].max()) < c["obs"].shape[0]
+        n_dev, inv_dev, inv_host = np.array([c["count"]], np.int32), np.array([1.0 / max(c["count"], 1)], np.float32), 1.0
+    L.sln_gradients_dev(IN, A, c["n"], parts, ptr(c["obs"]), ptr(mask), ptr(c["action"]), ptr(c["q"]), ptr(c["index"]), C.c_float(inv_host),
+                        ptr(n_dev), ptr(inv_dev), ptr(w["w1t"]), ptr(w["b1"]), ptr(w["w2c"]), ptr(w["b2c"]), ptr(w["w2a_t"]), ptr(w["b2a"]),
+                        ptr(w2a), ptr(partial), ptr(grad))
+    assert L.sln_buffer_oob() == 0
+    return grad
+
+
+def test_wide_gradients_p4_d9_under_emulation_on_the_edge_case_table():
+    """p4_d9 on a subset of the case table of tests/a2c_grad_ref.py, through the per-element comparison of
+    tests/test_gpu_a2c_grad_edges.py: the position sweep's rows 0, M - 1, M and 2M, n = M + 1 on one and two parts, one legal action,
+    only the last action legal, and a device count that ends inside a tile.  Measured: 19 s."""
+    from tests import a2c_grad_ref as R
+    L = load()
+    shape = IN, A = R.SHAPES["p4_d9"]
+    size = R.flat_size(IN, A)
+
+    def check(tag, got, c, ref):
+        flat, sums, N, _ = ref
+        K = R.k_case(R.yardstick(shape, c))
+        worst, zeros_ok = R.normalised_error(got[:size], flat, N)
+        assert np.isfinite(got).all() and zeros_ok, tag
+        assert worst <= K, (tag, worst, K)
+        assert got[R.offsets(IN, A)["pad"][0]] == 0.0 and got[size + 3] == sums[3], tag
+
+    for name in R.EMULATION_CASES:
+        c = R.build("p4_d9", name)
+        check(name, _run_edge_case(L, IN, A, c), c, R.reference(shape, c["w"], *R.call_args(c)))
+    c = R.build("p4_d9", "sweep")
+    for k in R.emulation_sweep_rows(IN, A):
+        one = dict(c, obs=c["obs"][k:k + 1], mask=c["mask"][k:k + 1], action=c["action"][k:k + 1], q=c["q"][k:k + 1], inv_n=1.0 / c["n"])
+        check("sweep row %d" % k, _run_edge_case(L, IN, A, c, R.sweep_mask(c, k)), one, R.reference(shape, c["w"], *R.call_args(one)))
 
 
 def test_wide_adam_under_emulation_matches_torch_adam():
