@@ -908,32 +908,6 @@ int azul_a2c_flat_size(int num_inputs, int hidden_size, int num_actions)
 #define AZ_LN_DISPATCH(IN_, A_, launch) \
     if (num_inputs == IN_ && num_actions == A_) { constexpr int LN_IN = IN_, LN_A = A_; launch; }
 
-// (azul_a2c_gradients, its only caller, has checked the arguments)
-static int a2c_gradients_n(const float *obs_dev, const uint8_t *mask_dev, const int32_t *action_dev, const float *qvals_dev, int n_samples,
-                           float inv_n_total, const float *w1t_dev, const float *b1_dev, const float *w2c_dev, const float *b2c_dev,
-                           const float *w2a_t_dev, const float *b2a_dev, const float *w2a_dev, int num_inputs, int num_actions,
-                           float *workspace_dev, int workspace_parts, float *grad_dev, const int32_t *index_dev, const int32_t *n_samples_dev,
-                           const float *inv_n_total_dev, void *stream)
-{
-    STREAM_GUARD(stream);
-    const hipStream_t st = (hipStream_t)stream;
-    const u32 total = a2c_shape_n((u32)num_inputs, (u32)num_actions).params + 4u;
-    const u32 tiles = ((u32)n_samples + LN_M - 1) / LN_M;
-    const u32 parts = tiles < (u32)workspace_parts ? tiles : (u32)workspace_parts;
-    if (parts == 0) { HIP_TRY(hipMemsetAsync(grad_dev, 0, sizeof(float) * total, st)); return AZUL_SUCCESS; }
-    PolicyWeights W = {w1t_dev, b1_dev, w2c_dev, b2c_dev, w2a_t_dev, b2a_dev};
-    LearnerArgs a = {obs_dev, mask_dev, action_dev, qvals_dev, (u32)n_samples, inv_n_total, w2a_dev, workspace_dev, index_dev, n_samples_dev,
-                     inv_n_total_dev};
-    const dim3 grid(parts, 3), block(64 * LN_WAVES);      // three workgroup roles per part (azul_learner.hpp)
-    AZ_LN_DISPATCH(188, 180, hipLaunchKernelGGL((azul_a2c_grad_n_kernel<LN_IN, LN_A>), grid, block, 0, st, W, a))
-    AZ_LN_DISPATCH(240, 180, hipLaunchKernelGGL((azul_a2c_grad_n_kernel<LN_IN, LN_A>), grid, block, 0, st, W, a))
-    AZ_LN_DISPATCH(198, 240, hipLaunchKernelGGL((azul_a2c_grad_n_kernel<LN_IN, LN_A>), grid, block, 0, st, W, a))
-    AZ_LN_DISPATCH(260, 300, hipLaunchKernelGGL((azul_a2c_grad_n_kernel<LN_IN, LN_A>), grid, block, 0, st, W, a))
-    hipLaunchKernelGGL(azul_a2c_reduce_n_kernel, dim3((total + 255) / 256), dim3(256), 0, st, (const float *)workspace_dev, parts, total, grad_dev);
-    HIP_TRY(hipGetLastError());
-    return AZUL_SUCCESS;
-}
-
 int azul_a2c_gradients(const float *obs_dev, const uint8_t *mask_dev, const int32_t *action_dev, const float *qvals_dev, int n_samples,
                        float inv_n_total, const float *w1t_dev, const float *b1_dev, const float *w2c_dev, const float *b2c_dev,
                        const float *w2a_t_dev, const float *b2a_dev, const float *w2a_dev, int num_inputs, int hidden_size, int num_actions,
@@ -941,28 +915,33 @@ int azul_a2c_gradients(const float *obs_dev, const uint8_t *mask_dev, const int3
                        const float *inv_n_total_dev, void *stream)
 {
     const bool reference = num_inputs == PF_IN && hidden_size == PF_HID && num_actions == PF_ACT;
-    if (!reference && azul_a2c_flat_size(num_inputs, hidden_size, num_actions) < 0)
+    if (azul_a2c_flat_size(num_inputs, hidden_size, num_actions) < 0)
         return fail(AZUL_ERR_INVALID, "azul_a2c_gradients: compiled shapes are ActorCritic(136, 180), (188, 180), (240, 180), (198, 240) "
                                       "and (260, 300), hidden 180");
     if (!w1t_dev || !b1_dev || !w2c_dev || !b2c_dev || !w2a_t_dev || !b2a_dev || !w2a_dev || !workspace_dev || !grad_dev || n_samples < 0 ||
         workspace_parts <= 0 || (n_samples > 0 && (!obs_dev || !mask_dev || !action_dev || !qvals_dev)))
         return fail(AZUL_ERR_INVALID, "azul_a2c_gradients: bad arguments");
-    if (!reference)                                          // a wide shape: the kernels of azul_learner.hpp's second half
-        return a2c_gradients_n(obs_dev, mask_dev, action_dev, qvals_dev, n_samples, inv_n_total, w1t_dev, b1_dev, w2c_dev, b2c_dev, w2a_t_dev,
-                               b2a_dev, w2a_dev, num_inputs, num_actions, workspace_dev, workspace_parts, grad_dev, index_dev, n_samples_dev,
-                               inv_n_total_dev, stream);
-    if (((uintptr_t)w2a_t_dev & 7u) != 0 || ((uintptr_t)w2a_dev & 7u) != 0 || ((uintptr_t)mask_dev & 3u) != 0)
+    if (reference && (((uintptr_t)w2a_t_dev & 7u) != 0 || ((uintptr_t)w2a_dev & 7u) != 0 || ((uintptr_t)mask_dev & 3u) != 0))
         return fail(AZUL_ERR_INVALID, "azul_a2c_gradients: weights must be 8-byte aligned, mask_dev 4-byte aligned");
     STREAM_GUARD(stream);
     const hipStream_t st = (hipStream_t)stream;
-    const u32 tiles = ((u32)n_samples + LG_M - 1) / LG_M;
+    const u32 total = a2c_shape_n((u32)num_inputs, (u32)num_actions).params + 4u;
+    const u32 per_pass = reference ? LG_M : LN_M;            // samples per pass of the shape's gradient kernel (azul_learner.hpp)
+    const u32 tiles = ((u32)n_samples + per_pass - 1) / per_pass;
     const u32 parts = tiles < (u32)workspace_parts ? tiles : (u32)workspace_parts;
-    if (parts == 0) { HIP_TRY(hipMemsetAsync(grad_dev, 0, sizeof(float) * LG_P_TOTAL, st)); return AZUL_SUCCESS; }
+    if (parts == 0) { HIP_TRY(hipMemsetAsync(grad_dev, 0, sizeof(float) * total, st)); return AZUL_SUCCESS; }
     PolicyWeights W = {w1t_dev, b1_dev, w2c_dev, b2c_dev, w2a_t_dev, b2a_dev};
     LearnerArgs a = {obs_dev, mask_dev, action_dev, qvals_dev, (u32)n_samples, inv_n_total, w2a_dev, workspace_dev, index_dev, n_samples_dev,
                      inv_n_total_dev};
-    hipLaunchKernelGGL(azul_a2c_grad_kernel, dim3(parts), dim3(64 * LG_WAVES), 0, st, W, a);
-    hipLaunchKernelGGL(azul_a2c_reduce_kernel, dim3((LG_P_TOTAL + 255) / 256), dim3(256), 0, st, workspace_dev, parts, grad_dev);
+    if (reference) hipLaunchKernelGGL(azul_a2c_grad_kernel, dim3(parts), dim3(64 * LG_WAVES), 0, st, W, a);
+    const dim3 grid(parts, 3), block(64 * LN_WAVES);      // the wide shapes: three workgroup roles per part (azul_learner.hpp)
+    AZ_LN_DISPATCH(188, 180, hipLaunchKernelGGL((azul_a2c_grad_n_kernel<LN_IN, LN_A>), grid, block, 0, st, W, a))
+    AZ_LN_DISPATCH(240, 180, hipLaunchKernelGGL((azul_a2c_grad_n_kernel<LN_IN, LN_A>), grid, block, 0, st, W, a))
+    AZ_LN_DISPATCH(198, 240, hipLaunchKernelGGL((azul_a2c_grad_n_kernel<LN_IN, LN_A>), grid, block, 0, st, W, a))
+    AZ_LN_DISPATCH(260, 300, hipLaunchKernelGGL((azul_a2c_grad_n_kernel<LN_IN, LN_A>), grid, block, 0, st, W, a))
+    const dim3 rgrid((total + 255) / 256), rblock(256);
+    if (reference) hipLaunchKernelGGL(azul_a2c_reduce_kernel, rgrid, rblock, 0, st, (const float *)workspace_dev, parts, grad_dev);
+    else hipLaunchKernelGGL(azul_a2c_reduce_n_kernel, rgrid, rblock, 0, st, (const float *)workspace_dev, parts, total, grad_dev);
     HIP_TRY(hipGetLastError());
     return AZUL_SUCCESS;
 }
@@ -976,23 +955,41 @@ extern "C" int azul_debug_lg_profile(uint64_t *host, int n, int reset)
 }
 #endif
 
+// the one Adam step behind azul_a2c_apply_adam and azul_a2c_apply_adam_n (`who`: the entry that was called)
+static int a2c_apply_adam(const char *who, const float *grad_dev, float *flat_dev, float *exp_avg_dev, float *exp_avg_sq_dev, float lr, float beta1,
+                          float beta2, float eps, int step, int num_inputs, int hidden_size, int num_actions, const ModuleParams &P,
+                          int32_t *step_dev, const float *n_total_dev, float n_total_host, float *stats_out_dev, void *stream)
+{
+    if (azul_a2c_flat_size(num_inputs, hidden_size, num_actions) < 0) return fail_in(who, "shape not compiled in (see azul_a2c_flat_size)");
+    if (!grad_dev || !flat_dev || !exp_avg_dev || !exp_avg_sq_dev || (!step_dev && step < 1) || !P.c1w || !P.c1b || !P.c2w || !P.c2b || !P.a1w ||
+        !P.a1b || !P.a2w || !P.a2b)
+        return fail_in(who, "bad arguments");
+    STREAM_GUARD(stream);
+    const double st = step_dev ? 1.0 : (double)step;
+    const double bc1 = 1.0 - pow((double)beta1, st), bc2 = 1.0 - pow((double)beta2, st);
+    const hipStream_t hs = (hipStream_t)stream;
+    const A2CShapeN S = a2c_shape_n((u32)num_inputs, (u32)num_actions);
+    const dim3 grid((S.params + 255) / 256), block(256);
+    const float c1 = (float)bc1, c2s = (float)sqrt(bc2);
+    if (step_dev) hipLaunchKernelGGL(azul_a2c_step_kernel, dim3(1), dim3(64), 0, hs, step_dev, n_total_dev);
+    if (num_inputs == PF_IN && num_actions == PF_ACT)        // the reference shape: its layout is a compile-time constant of the kernel
+        hipLaunchKernelGGL(azul_a2c_apply_kernel, grid, block, 0, hs, grad_dev, flat_dev, exp_avg_dev, exp_avg_sq_dev, lr, beta1, beta2, eps, c1, c2s, P,
+                           (const i32 *)step_dev, n_total_dev, n_total_host, stats_out_dev);
+    else
+        hipLaunchKernelGGL(azul_a2c_apply_n_kernel, grid, block, 0, hs, S, grad_dev, flat_dev, exp_avg_dev, exp_avg_sq_dev, lr, beta1, beta2, eps, c1, c2s,
+                           P, (const i32 *)step_dev, n_total_dev, n_total_host, stats_out_dev);
+    HIP_TRY(hipGetLastError());
+    return AZUL_SUCCESS;
+}
+
 int azul_a2c_apply_adam(const float *grad_dev, float *flat_dev, float *exp_avg_dev, float *exp_avg_sq_dev, float lr, float beta1, float beta2,
                         float eps, int step, float *critic1_w, float *critic1_b, float *critic2_w, float *critic2_b, float *actor1_w,
                         float *actor1_b, float *actor2_w, float *actor2_b, int32_t *step_dev, const float *n_total_dev, float n_total_host,
                         float *stats_out_dev, void *stream)
 {
-    if (!grad_dev || !flat_dev || !exp_avg_dev || !exp_avg_sq_dev || (!step_dev && step < 1) || !critic1_w || !critic1_b || !critic2_w ||
-        !critic2_b || !actor1_w || !actor1_b || !actor2_w || !actor2_b)
-        return fail(AZUL_ERR_INVALID, "azul_a2c_apply_adam: bad arguments");
-    STREAM_GUARD(stream);
-    const double st = step_dev ? 1.0 : (double)step;
-    const double bc1 = 1.0 - pow((double)beta1, st), bc2 = 1.0 - pow((double)beta2, st);
-    ModuleParams P = {critic1_w, critic1_b, critic2_w, critic2_b, actor1_w, actor1_b, actor2_w, actor2_b};
-    if (step_dev) hipLaunchKernelGGL(azul_a2c_step_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, step_dev, n_total_dev);
-    hipLaunchKernelGGL(azul_a2c_apply_kernel, dim3((LG_P_PARAMS + 255) / 256), dim3(256), 0, (hipStream_t)stream, grad_dev, flat_dev, exp_avg_dev,
-                       exp_avg_sq_dev, lr, beta1, beta2, eps, (float)bc1, (float)sqrt(bc2), P, (const i32 *)step_dev, n_total_dev, n_total_host, stats_out_dev);
-    HIP_TRY(hipGetLastError());
-    return AZUL_SUCCESS;
+    return a2c_apply_adam("azul_a2c_apply_adam", grad_dev, flat_dev, exp_avg_dev, exp_avg_sq_dev, lr, beta1, beta2, eps, step, PF_IN, PF_HID, PF_ACT,
+                          {critic1_w, critic1_b, critic2_w, critic2_b, actor1_w, actor1_b, actor2_w, actor2_b}, step_dev, n_total_dev, n_total_host,
+                          stats_out_dev, stream);
 }
 
 int azul_a2c_apply_adam_n(const float *grad_dev, float *flat_dev, float *exp_avg_dev, float *exp_avg_sq_dev, float lr, float beta1, float beta2,
@@ -1000,22 +997,9 @@ int azul_a2c_apply_adam_n(const float *grad_dev, float *flat_dev, float *exp_avg
                           float *critic2_w, float *critic2_b, float *actor1_w, float *actor1_b, float *actor2_w, float *actor2_b,
                           int32_t *step_dev, const float *n_total_dev, float n_total_host, float *stats_out_dev, void *stream)
 {
-    if (azul_a2c_flat_size(num_inputs, hidden_size, num_actions) < 0)
-        return fail(AZUL_ERR_INVALID, "azul_a2c_apply_adam_n: shape not compiled in (see azul_a2c_flat_size)");
-    if (!grad_dev || !flat_dev || !exp_avg_dev || !exp_avg_sq_dev || (!step_dev && step < 1) || !critic1_w || !critic1_b || !critic2_w ||
-        !critic2_b || !actor1_w || !actor1_b || !actor2_w || !actor2_b)
-        return fail(AZUL_ERR_INVALID, "azul_a2c_apply_adam_n: bad arguments");
-    STREAM_GUARD(stream);
-    const double st = step_dev ? 1.0 : (double)step;
-    const double bc1 = 1.0 - pow((double)beta1, st), bc2 = 1.0 - pow((double)beta2, st);
-    const A2CShapeN S = a2c_shape_n((u32)num_inputs, (u32)num_actions);
-    ModuleParams P = {critic1_w, critic1_b, critic2_w, critic2_b, actor1_w, actor1_b, actor2_w, actor2_b};
-    if (step_dev) hipLaunchKernelGGL(azul_a2c_step_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, step_dev, n_total_dev);
-    hipLaunchKernelGGL(azul_a2c_apply_n_kernel, dim3((S.params + 255) / 256), dim3(256), 0, (hipStream_t)stream, S, grad_dev, flat_dev, exp_avg_dev,
-                       exp_avg_sq_dev, lr, beta1, beta2, eps, (float)bc1, (float)sqrt(bc2), P, (const i32 *)step_dev, n_total_dev, n_total_host,
-                       stats_out_dev);
-    HIP_TRY(hipGetLastError());
-    return AZUL_SUCCESS;
+    return a2c_apply_adam("azul_a2c_apply_adam_n", grad_dev, flat_dev, exp_avg_dev, exp_avg_sq_dev, lr, beta1, beta2, eps, step, num_inputs,
+                          hidden_size, num_actions, {critic1_w, critic1_b, critic2_w, critic2_b, actor1_w, actor1_b, actor2_w, actor2_b}, step_dev,
+                          n_total_dev, n_total_host, stats_out_dev, stream);
 }
 
 int azul_select_episode_samples(const uint8_t *done_ring_dev, const int32_t *action_ring_dev, int window_steps, int ring_windows, int n_games,

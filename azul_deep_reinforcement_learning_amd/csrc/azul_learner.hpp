@@ -5,7 +5,11 @@
 //                            matrix cores (v_mfma_f32_16x16x4_f32).  A workgroup of 8 waves walks over its share of the sample tiles
 //                            and keeps its partial weight gradients IN REGISTERS for the whole launch (dW1: 207 16x16 tiles, dW2: 144
 //                            tiles -> 176 accumulator registers per lane), then writes one partial gradient vector per workgroup.
+//   azul_a2c_grad_n_kernel   the same for the four wide shapes (second half of this file).
 //   azul_a2c_reduce_kernel   sums the per-workgroup partials in a fixed order (deterministic) into one flat gradient + loss terms.
+//   azul_a2c_apply_kernel    Adam on the flat master copy + the eight nn.Linear tensors (azul_a2c_step_kernel: its device step counter).
+//   The reduce and the Adam step are one body each (a2c_reduce, a2c_apply) for all five shapes, their layout from a2c_shape_n; the
+//   reference shape enters with its layout a compile-time constant, the wide shapes (_n entries) pass theirs as an argument.
 //
 // Loss per sample i (agent.py:45-57; n = number of samples of the whole batch, all ranks):
 //     adv = q - v                                      (NOT detached in the actor term, like the reference)
@@ -16,11 +20,23 @@
 // Gradient vector layout (k-major like the forward weights): dw1t [136][360] | db1 [360] | dw2c [180] | db2c [1]
 // | (1 pad) | dw2a_t [180][180] | db2a [180]  = 82082 floats, followed by the four loss sums (actor, critic, entropy, count of
 // samples used).  The same layout holds the k-major master copy of the parameters and Adam's moments (azul_a2c_apply_kernel).
+// The wide shapes use it with their own `IN` inputs and `A` actions: a2c_shape_n below is its one definition.
 #pragma once
 
-constexpr int LG_P_W1 = 0, LG_P_B1 = LG_P_W1 + PF_IN * PF_H2, LG_P_W2C = LG_P_B1 + PF_H2, LG_P_B2C = LG_P_W2C + PF_HID,
-              LG_P_W2A = LG_P_B2C + 2 /* one pad float: the matrix starts 8-byte aligned */, LG_P_B2A = LG_P_W2A + PF_HID * PF_ACT,
-              LG_P_PARAMS = LG_P_B2A + PF_ACT, LG_P_LOSS = LG_P_PARAMS, LG_P_TOTAL = LG_P_PARAMS + 4;
+// The one definition of the flat layout, for every shape (in, act) with hidden 180 (azul_a2c_flat_size lists the compiled ones)
+struct A2CShapeN {                   // offsets of the flat layout for (in, act); hidden 180
+    u32 in, act, b1, w2c, b2c, w2a, b2a, params;
+};
+__host__ __device__ constexpr A2CShapeN a2c_shape_n(u32 in, u32 act)
+{
+    return {in, act, in * 360u, in * 360u + 360u, in * 360u + 540u, in * 360u + 542u /* one pad float: the matrix starts 8-byte aligned */,
+            in * 360u + 542u + 180u * act, in * 360u + 542u + 181u * act};
+}
+
+// ... and its (136, 180) case under the names azul_a2c_grad_kernel uses
+constexpr A2CShapeN LG_SHAPE = a2c_shape_n(PF_IN, PF_ACT);
+constexpr int LG_P_W1 = 0, LG_P_B1 = (int)LG_SHAPE.b1, LG_P_W2C = (int)LG_SHAPE.w2c, LG_P_B2C = (int)LG_SHAPE.b2c, LG_P_W2A = (int)LG_SHAPE.w2a,
+              LG_P_B2A = (int)LG_SHAPE.b2a, LG_P_PARAMS = (int)LG_SHAPE.params, LG_P_LOSS = LG_P_PARAMS, LG_P_TOTAL = LG_P_PARAMS + 4;
 static_assert(LG_P_PARAMS == 82082 && LG_P_W2A % 2 == 0, "ActorCritic(136, 180, 180): 82081 parameters + 1 pad");
 
 constexpr u32 LG_WAVES = 8, LG_AHEAD = 6 /* k-steps of weights in flight; 4..6 measured alike, 8 and 12 slower */;
@@ -448,22 +464,33 @@ __global__ void __launch_bounds__(64 * LG_WAVES) azul_a2c_grad_kernel(PolicyWeig
 #undef voff2
 #undef LG_LANE
 
-// sum of the per-workgroup partials in workgroup order (deterministic); optionally scaled loss sums stay raw (caller divides)
-__global__ void __launch_bounds__(256) azul_a2c_reduce_kernel(const float *partial, u32 n_parts, float *grad /* [LG_P_TOTAL] */)
+// sum of the per-part partials of `total` floats each, in part order (deterministic); the loss sums stay raw (the caller divides).  A part
+// is one workgroup of azul_a2c_grad_kernel or the three roles of azul_a2c_grad_n_kernel, which write disjoint ranges of its vector.
+// One body, two entries: the reference shape's passes its compile-time stride (as a kernel argument the stride costs that launch 3.7 %
+// and the layout costs its Adam step 3 %: LABNOTES.md), the wide shapes' takes it as an argument.
+__device__ __forceinline__ void a2c_reduce(const float *partial, u32 n_parts, const u32 total, float *grad /* [total] */)
 {
     const u32 p = blockIdx.x * 256u + threadIdx.x;
-    if (p >= (u32)LG_P_TOTAL) return;
+    if (p >= total) return;
     float s = 0.f;
     u32 i = 0;
-    for (; i + 8u <= n_parts; i += 8u) {                 // eight loads in flight, added in workgroup order (the order is what is fixed)
+    for (; i + 8u <= n_parts; i += 8u) {                 // eight loads in flight, added in part order (the order is what is fixed)
         float v[8];
 #pragma unroll
-        for (int j = 0; j < 8; j++) v[j] = partial[(size_t)(i + j) * LG_P_TOTAL + p];
+        for (int j = 0; j < 8; j++) v[j] = partial[(size_t)(i + j) * total + p];
 #pragma unroll
         for (int j = 0; j < 8; j++) s += v[j];
     }
-    for (; i < n_parts; i++) s += partial[(size_t)i * LG_P_TOTAL + p];
+    for (; i < n_parts; i++) s += partial[(size_t)i * total + p];
     grad[p] = s;
+}
+__global__ void __launch_bounds__(256) azul_a2c_reduce_kernel(const float *partial, u32 n_parts, float *grad /* [LG_P_TOTAL] */)
+{
+    a2c_reduce(partial, n_parts, (u32)LG_P_TOTAL, grad);
+}
+__global__ void __launch_bounds__(256) azul_a2c_reduce_n_kernel(const float *partial, u32 n_parts, u32 total, float *grad)
+{
+    a2c_reduce(partial, n_parts, total, grad);
 }
 
 
@@ -627,14 +654,15 @@ __global__ void azul_a2c_step_kernel(i32 *step_dev, const float *n_total_dev)
     if (threadIdx.x == 0 && blockIdx.x == 0 && (!n_total_dev || *n_total_dev > 0.f)) step_dev[0] += 1;
 }
 
-__global__ void __launch_bounds__(256) azul_a2c_apply_kernel(const float *grad, float *flat, float *m, float *v, float lr, float beta1,
-                                                             float beta2, float eps, float bias_c1, float bias_c2_sqrt, ModuleParams P,
-                                                             const i32 *step_dev, const float *n_total_dev, float n_total_host, float *stats_out)
+// One body for the layout S of the module's shape, two entries below (see a2c_reduce).
+__device__ __forceinline__ void a2c_apply(const A2CShapeN S, const float *grad, float *flat, float *m, float *v, float lr, float beta1, float beta2,
+                                          float eps, float bias_c1, float bias_c2_sqrt, ModuleParams P, const i32 *step_dev,
+                                          const float *n_total_dev, float n_total_host, float *stats_out)
 {
     if (stats_out && blockIdx.x == 0 && threadIdx.x == 0) {
         // the update's loss terms as the reference logs them (agent.py:51-58): means over the batch, ac_loss = 1 a + 0.5 c + 0.1 e
         const float nn = n_total_dev ? *n_total_dev : n_total_host, inv = 1.0f / (nn > 0.f ? nn : 1.0f);
-        const float la = grad[LG_P_LOSS] * inv, lc = grad[LG_P_LOSS + 1] * inv, le = grad[LG_P_LOSS + 2] * inv;
+        const float la = grad[S.params] * inv, lc = grad[S.params + 1u] * inv, le = grad[S.params + 2u] * inv;
         stats_out[0] = la; stats_out[1] = lc; stats_out[2] = le; stats_out[3] = 1.0f * la + 0.5f * lc + 0.1f * le; stats_out[4] = nn;
     }
     if (n_total_dev && !(*n_total_dev > 0.f)) return;    // a window without a finished episode: no samples, no step
@@ -650,7 +678,7 @@ __global__ void __launch_bounds__(256) azul_a2c_apply_kernel(const float *grad, 
         bias_c2_sqrt = bcS[1];
     }
     const u32 p = blockIdx.x * 256u + threadIdx.x;
-    if (p >= (u32)LG_P_PARAMS || p == (u32)LG_P_B2C + 1u) return;
+    if (p >= S.params || p == S.b2c + 1u) return;
     const float g = grad[p];
     const float m1 = m[p] + (g - m[p]) * (1.0f - beta1);               // exp_avg.lerp_(grad, 1 - beta1)
     const float v1 = v[p] * beta2 + (1.0f - beta2) * g * g;            // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value = 1 - beta2)
@@ -659,22 +687,35 @@ __global__ void __launch_bounds__(256) azul_a2c_apply_kernel(const float *grad, 
     const float denom = sqrtf(v1) / bias_c2_sqrt + eps;
     const float w = flat[p] - (lr / bias_c1) * (m1 / denom);           // param.addcdiv_(exp_avg, denom, value = -step_size)
     flat[p] = w;
-    if (p < (u32)LG_P_B1) {
+    if (p < S.b1) {
         const u32 k = p / (u32)PF_H2, col = p - k * (u32)PF_H2;
-        if (col < (u32)PF_HID) P.c1w[col * PF_IN + k] = w; else P.a1w[(col - PF_HID) * PF_IN + k] = w;
-    } else if (p < (u32)LG_P_W2C) {
-        const u32 col = p - (u32)LG_P_B1;
+        if (col < (u32)PF_HID) P.c1w[col * S.in + k] = w; else P.a1w[(col - PF_HID) * S.in + k] = w;
+    } else if (p < S.w2c) {
+        const u32 col = p - S.b1;
         if (col < (u32)PF_HID) P.c1b[col] = w; else P.a1b[col - PF_HID] = w;
-    } else if (p < (u32)LG_P_B2C) {
-        P.c2w[p - (u32)LG_P_W2C] = w;
-    } else if (p == (u32)LG_P_B2C) {
+    } else if (p < S.b2c) {
+        P.c2w[p - S.w2c] = w;
+    } else if (p == S.b2c) {
         P.c2b[0] = w;
-    } else if (p < (u32)LG_P_B2A) {
-        const u32 i = p - (u32)LG_P_W2A, k = i / (u32)PF_ACT, j = i - k * (u32)PF_ACT;
+    } else if (p < S.b2a) {
+        const u32 i = p - S.w2a, k = i / S.act, j = i - k * S.act;
         P.a2w[j * PF_HID + k] = w;
     } else {
-        P.a2b[p - (u32)LG_P_B2A] = w;
+        P.a2b[p - S.b2a] = w;
     }
+}
+__global__ void __launch_bounds__(256) azul_a2c_apply_kernel(const float *grad, float *flat, float *m, float *v, float lr, float beta1,
+                                                             float beta2, float eps, float bias_c1, float bias_c2_sqrt, ModuleParams P,
+                                                             const i32 *step_dev, const float *n_total_dev, float n_total_host, float *stats_out)
+{
+    a2c_apply(LG_SHAPE, grad, flat, m, v, lr, beta1, beta2, eps, bias_c1, bias_c2_sqrt, P, step_dev, n_total_dev, n_total_host, stats_out);
+}
+__global__ void __launch_bounds__(256) azul_a2c_apply_n_kernel(A2CShapeN S, const float *grad, float *flat, float *m, float *v, float lr,
+                                                               float beta1, float beta2, float eps, float bias_c1, float bias_c2_sqrt,
+                                                               ModuleParams P, const i32 *step_dev, const float *n_total_dev,
+                                                               float n_total_host, float *stats_out)
+{
+    a2c_apply(S, grad, flat, m, v, lr, beta1, beta2, eps, bias_c1, bias_c2_sqrt, P, step_dev, n_total_dev, n_total_host, stats_out);
 }
 
 
@@ -693,19 +734,9 @@ __global__ void __launch_bounds__(256) azul_a2c_apply_kernel(const float *grad, 
 //       116 accumulator registers per lane -- the single-workgroup layout of azul_a2c_grad_kernel would need ~310 for p4_d9.
 //       16 samples per pass keep LDS at <= 88 KB (the 32-sample layout of p4_d9 would need ~178 KB).  Weights stream from L2.
 //       p4_d9 (260 inputs, 300 actions) needs 255 VGPRs and spills 68 bytes per lane; the other shapes do not spill.
-//   azul_a2c_reduce_n_kernel        sums the per-part partials in a fixed order (deterministic) -- the three roles of part p write
-//                                   disjoint ranges of partial vector p.
-//   azul_a2c_apply_n_kernel         azul_a2c_apply_kernel's Adam step for these layouts.
+//   The three roles of part p write disjoint ranges of partial vector p; azul_a2c_reduce_n_kernel and azul_a2c_apply_n_kernel above are
+//   the reference shape's reduce and Adam bodies, handed the shape's layout.
 constexpr int LN_WAVES = 8, LN_M = 16, LN_HS = 388;           // samples per pass; LDS row stride of hidden / dz (361 used + tile pads)
-
-struct A2CShapeN {                   // offsets of the flat layout for (in, act); hidden 180
-    u32 in, act, b1, w2c, b2c, w2a, b2a, params;
-};
-__host__ __device__ constexpr A2CShapeN a2c_shape_n(u32 in, u32 act)
-{
-    return {in, act, in * 360u, in * 360u + 360u, in * 360u + 540u, in * 360u + 542u, in * 360u + 542u + 180u * act,
-            in * 360u + 542u + 181u * act};
-}
 
 template <int IN, int A>
 struct LnCfg {
@@ -1010,72 +1041,3 @@ __global__ void __launch_bounds__(64 * LN_WAVES) azul_a2c_grad_n_kernel(PolicyWe
 }
 
 #undef LN_LANE
-
-// sum of the per-part partials in part order (deterministic); `total` floats per partial
-__global__ void __launch_bounds__(256) azul_a2c_reduce_n_kernel(const float *partial, u32 n_parts, u32 total, float *grad)
-{
-    const u32 p = blockIdx.x * 256u + threadIdx.x;
-    if (p >= total) return;
-    float s = 0.f;
-    u32 i = 0;
-    for (; i + 8u <= n_parts; i += 8u) {
-        float v[8];
-#pragma unroll
-        for (int j = 0; j < 8; j++) v[j] = partial[(size_t)(i + j) * total + p];
-#pragma unroll
-        for (int j = 0; j < 8; j++) s += v[j];
-    }
-    for (; i < n_parts; i++) s += partial[(size_t)i * total + p];
-    grad[p] = s;
-}
-
-// azul_a2c_apply_kernel for the layout of shape S (same arithmetic, same gating, same stats row)
-__global__ void __launch_bounds__(256) azul_a2c_apply_n_kernel(A2CShapeN S, const float *grad, float *flat, float *m, float *v, float lr,
-                                                               float beta1, float beta2, float eps, float bias_c1, float bias_c2_sqrt,
-                                                               ModuleParams P, const i32 *step_dev, const float *n_total_dev,
-                                                               float n_total_host, float *stats_out)
-{
-    if (stats_out && blockIdx.x == 0 && threadIdx.x == 0) {
-        const float nn = n_total_dev ? *n_total_dev : n_total_host, inv = 1.0f / (nn > 0.f ? nn : 1.0f);
-        const float la = grad[S.params] * inv, lc = grad[S.params + 1u] * inv, le = grad[S.params + 2u] * inv;
-        stats_out[0] = la; stats_out[1] = lc; stats_out[2] = le; stats_out[3] = 1.0f * la + 0.5f * lc + 0.1f * le; stats_out[4] = nn;
-    }
-    if (n_total_dev && !(*n_total_dev > 0.f)) return;
-    if (step_dev) {
-        __shared__ float bcS[2];
-        if (threadIdx.x == 0) {
-            const double st = (double)step_dev[0];
-            bcS[0] = (float)(1.0 - pow((double)beta1, st));
-            bcS[1] = (float)sqrt(1.0 - pow((double)beta2, st));
-        }
-        __syncthreads();
-        bias_c1 = bcS[0];
-        bias_c2_sqrt = bcS[1];
-    }
-    const u32 p = blockIdx.x * 256u + threadIdx.x;
-    if (p >= S.params || p == S.b2c + 1u) return;
-    const float g = grad[p];
-    const float m1 = m[p] + (g - m[p]) * (1.0f - beta1);
-    const float v1 = v[p] * beta2 + (1.0f - beta2) * g * g;
-    m[p] = m1;
-    v[p] = v1;
-    const float denom = sqrtf(v1) / bias_c2_sqrt + eps;
-    const float w = flat[p] - (lr / bias_c1) * (m1 / denom);
-    flat[p] = w;
-    if (p < S.b1) {
-        const u32 k = p / (u32)PF_H2, col = p - k * (u32)PF_H2;
-        if (col < (u32)PF_HID) P.c1w[col * S.in + k] = w; else P.a1w[(col - PF_HID) * S.in + k] = w;
-    } else if (p < S.w2c) {
-        const u32 col = p - S.b1;
-        if (col < (u32)PF_HID) P.c1b[col] = w; else P.a1b[col - PF_HID] = w;
-    } else if (p < S.b2c) {
-        P.c2w[p - S.w2c] = w;
-    } else if (p == S.b2c) {
-        P.c2b[0] = w;
-    } else if (p < S.b2a) {
-        const u32 i = p - S.w2a, k = i / S.act, j = i - k * S.act;
-        P.a2w[j * PF_HID + k] = w;
-    } else {
-        P.a2b[p - S.b2a] = w;
-    }
-}

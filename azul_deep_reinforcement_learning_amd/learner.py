@@ -33,7 +33,6 @@ def complete_episode_samples(done):
     return torch.flip(torch.cummax(torch.flip(d, dims=[0]).to(torch.uint8), dim=0).values, dims=[0]).bool()
 
 
-N_PARAMS = 82081            # ActorCritic(136, 180, 180)
 REFERENCE_SHAPE = (136, 180, 180)                                 # (num_inputs, hidden, num_actions)
 # the wide batches' ActorCritic(obs_size, num_actions, hidden 180): three / four players on five displays, three on seven, four on nine
 WIDE_SHAPES = ((188, 180, 180), (240, 180, 180), (198, 180, 240), (260, 180, 300))
@@ -61,7 +60,7 @@ def _policy_shape(pol):
 class A2CLearner:
     def __init__(self, policy, learning_rate=3e-4, gamma=0.99, process_group=None, distributed=None, fused=None, stat_history=4096):
         """fused=True: gradients from the hand-written kernel azul_a2c_gradients (forward + backward on the f32 matrix cores, one
-        launch + a deterministic reduction) and Adam from azul_a2c_apply_adam(_n) instead of PyTorch autograd and torch.optim; needs CUDA
+        launch + a deterministic reduction) and Adam from azul_a2c_apply_adam_n instead of PyTorch autograd and torch.optim; needs CUDA
         tensors and a compiled network shape: the reference's ActorCritic(136, 180, 180) or one of the wide batches' WIDE_SHAPES
         (ActorCritic(obs_size, num_actions, hidden 180) of three / four players on 5 displays, three on 7, four on 9) -- any other shape raises ValueError.
         Default (fused=None): fused for the reference's shape only."""
@@ -76,7 +75,7 @@ class A2CLearner:
         self._ws = None
         self.gamma = gamma
         self.optimizer = self._own_adam = torch.optim.Adam(policy.parameters(), lr=learning_rate)        # agent.py:37
-        self.fused_apply = True           # the fused path steps with azul_a2c_apply_adam while `optimizer` is the learner's own Adam
+        self.fused_apply = True           # the fused path steps with azul_a2c_apply_adam_n while `optimizer` is the learner's own Adam
         self.group = process_group
         self.distributed = (dist.is_available() and dist.is_initialized()) if distributed is None else distributed
         # the last updates' loss terms (device scalars; bounded: the reference keeps one float per logged batch, agent.py:19-24)
@@ -117,13 +116,11 @@ class A2CLearner:
     # One flat k-major vector holds the master copy of the parameters (layout of azul_a2c_gradients' gradient; flat_layout()):
     #     w1t [136][360] | b1 [360] | w2c [180] | b2c [1] | pad | w2a_t [180][180] | b2a [180]      (IN inputs / A actions when wide)
     # the policy / rollout kernels read views of it (kweights()), Adam's two moments use the same layout, and
-    # azul_a2c_apply_adam writes every step into the flat copy AND into the eight nn.Linear tensors of the module.
-    _OFF = {"w1t": (0, 136 * 360), "b1": (48960, 360), "w2c": (49320, 180), "b2c": (49500, 1), "w2a_t": (49502, 180 * 180), "b2a": (81902, 180)}
+    # azul_a2c_apply_adam_n writes every step into the flat copy AND into the eight nn.Linear tensors of the module.
 
     def _can_fuse(self, obs):
         pol = self.policy
-        return (obs.is_cuda and hasattr(pol, "critic_linear1") and pol.critic_linear1.in_features == 136 and
-                pol.critic_linear1.out_features == 180 and pol.actor_linear2.out_features == 180 and pol.actor_linear1.out_features == 180)
+        return obs.is_cuda and _policy_shape(pol) == REFERENCE_SHAPE and pol.actor_linear1.out_features == REFERENCE_SHAPE[1]
 
     def _use_fused(self, obs):
         """fused=None: the reference's shape only (today's default); fused=True: any compiled shape (checked at construction)."""
@@ -235,7 +232,7 @@ class A2CLearner:
         return ws["stats"][self.updates % ws["stats"].shape[0]]
 
     def _finish_fused(self, n_dev, n_host):
-        """Optimiser step: azul_a2c_apply_adam on the flat copy + module (the learner's own Adam), or -- when the caller installed
+        """Optimiser step: azul_a2c_apply_adam_n on the flat copy + module (the learner's own Adam), or -- when the caller installed
         another optimiser -- the flat gradient scattered into the parameters' .grad and that optimiser's step.  The update's loss
         terms (agent.py:51-58) are written by the same kernel into a row of a device-resident ring: no small launches follow."""
         import ctypes as C
@@ -253,10 +250,7 @@ class A2CLearner:
             mod = (p(pol.critic_linear1.weight), p(pol.critic_linear1.bias), p(pol.critic_linear2.weight), p(pol.critic_linear2.bias),
                    p(pol.actor_linear1.weight), p(pol.actor_linear1.bias), p(pol.actor_linear2.weight), p(pol.actor_linear2.bias))
             tail = (p(ws["step"]), p(n_dev), C.c_float(n_host or 0.0), p(row), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-            if self.shape == REFERENCE_SHAPE:
-                L.check(L.lib.azul_a2c_apply_adam(p(g), p(ws["flat"]), p(ws["m"]), p(ws["v"]), *hp, *mod, *tail))
-            else:
-                L.check(L.lib.azul_a2c_apply_adam_n(p(g), p(ws["flat"]), p(ws["m"]), p(ws["v"]), *hp, *self.shape, *mod, *tail))
+            L.check(L.lib.azul_a2c_apply_adam_n(p(g), p(ws["flat"]), p(ws["m"]), p(ws["v"]), *hp, *self.shape, *mod, *tail))
         else:
             with torch.no_grad():
                 gv = self._views(g)

@@ -489,7 +489,8 @@ int azul_a2c_gradients(const float *obs_dev, const uint8_t *mask_dev, const int3
                        float *workspace_dev, int workspace_parts, float *grad_dev, const int32_t *index_dev, const int32_t *n_samples_dev,
                        const float *inv_n_total_dev, void *stream);
 #define AZUL_A2C_FLAT_SIZE 82082      /* 82081 parameters of ActorCritic(136, 180, 180) in the k-major layout above + 1 pad float */
-/* torch.optim.Adam's step (defaults: betas 0.9 / 0.999, eps 1e-8, no weight decay; same arithmetic) on the flat k-major master copy of
+/* azul_a2c_apply_adam_n (below) for ActorCritic(136, 180, 180): the same call with the shape filled in.
+ * torch.optim.Adam's step (defaults: betas 0.9 / 0.999, eps 1e-8, no weight decay; same arithmetic) on the flat k-major master copy of
  * the parameters (layout of azul_a2c_gradients' gradient; w1t / b1 / w2c / b2c / w2a_t / b2a of the policy entries are views of it),
  * with the two moment vectors in the same layout; `step` counts from 1.  The updated values are also written into the eight PyTorch
  * parameter tensors (nn.Linear layouts), so module, kernels and optimiser state stay in sync without re-layout launches.
@@ -507,7 +508,7 @@ int azul_a2c_apply_adam(const float *grad_dev, float *flat_dev, float *exp_avg_d
  * (the pad keeps dw2a_t 8-byte aligned) -- for the shapes azul_a2c_gradients compiles (AZUL_A2C_FLAT_SIZE for (136, 180, 180));
  * AZUL_ERR_INVALID for any other shape.  Gradient buffers are this + 4 floats (the loss sums). */
 int azul_a2c_flat_size(int num_inputs, int hidden_size, int num_actions);
-/* azul_a2c_apply_adam for any shape azul_a2c_flat_size accepts: the same Adam arithmetic (torch.optim.Adam, agent.py:37), step_dev /
+/* azul_a2c_apply_adam's step for any shape azul_a2c_flat_size accepts: the same Adam arithmetic (torch.optim.Adam, agent.py:37), step_dev /
  * n_total_dev gating, stats_out_dev row and write-back into the eight nn.Linear tensors (actor2_w is [num_actions][hidden], critic1_w /
  * actor1_w [hidden][num_inputs]) on the flat layout of (num_inputs, hidden_size, num_actions).  AZUL_ERR_INVALID for other shapes. */
 int azul_a2c_apply_adam_n(const float *grad_dev, float *flat_dev, float *exp_avg_dev, float *exp_avg_sq_dev, float lr, float beta1, float beta2,

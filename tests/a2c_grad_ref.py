@@ -374,6 +374,11 @@ for _name, (_m, _a) in (("1", (0, 1)), ("M-1", (1, -1)), ("M", (1, 0)), ("M+1", 
                         ("4M+3", (4, 3))):
     for _p in (1, 2, 3, 256):
         CASES.append(Case("n=%s-parts%d" % (_name, _p), b_size(_m, _a, _p), "size"))
+# azul_a2c_reduce_kernel adds eight parts per round and the rest one by one: 7, 8, 9 and 17 parts actually launched (the host entry
+# launches min(tiles, workspace_parts); the other size cases launch at most 5)
+REDUCE_EDGE_PARTS = collections.OrderedDict([("6M+9", 7), ("7M+9", 8), ("8M+9", 9), ("16M+9", 17)])
+for _name in REDUCE_EDGE_PARTS:
+    CASES.append(Case("n=%s-parts17" % _name, b_size(int(_name.split("M")[0]), 9, 17), "size"))
 CASES.append(Case("n=389-parts3", b_long, "long"))           # run on the wide shapes whose action count ends inside a 16-column tile
 CASES += [Case(nm, _edge(fn, 50 + i), "edge") for i, (nm, fn) in enumerate([
     ("one-legal-first", _one_legal("first")), ("one-legal-last", _one_legal("last")), ("one-legal-random", _one_legal("random")),

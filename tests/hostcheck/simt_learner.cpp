@@ -12,6 +12,7 @@ using namespace az;
 #include "azul_policy.hpp"
 #include "azul_rollout2.hpp"
 #include "azul_learner.hpp"
+#include "simt_a2c_launch.hpp"
 
 struct GradJob { PolicyWeights W; LearnerArgs a; };
 static void grad_lane(void *arg) { GradJob *j = (GradJob *)arg; azul_a2c_grad_kernel(j->W, j->a); }
@@ -54,12 +55,7 @@ long long sl_gradients_dev(int n, int parts, const float *obs, const uint8_t *ma
         simt::g_block_idx = {(unsigned)blk, 0, 0};
         ops += (long long)simt::run_workgroup(grad_lane, &j, (int)LG_WAVES, 512u << 10);
     }
-    for (int p = 0; p < LG_P_TOTAL; p++) {                 // (azul_a2c_reduce_kernel: the partials added in workgroup order)
-        float s = 0.f;
-        for (int i = 0; i < parts; i++) s += partial[(size_t)i * LG_P_TOTAL + p];
-        grad[p] = s;
-    }
-    return ops;
+    return ops + run_reduce(LG_SHAPE, partial, parts, grad);
 }
 
 long long sl_gradients(int n, int parts, const float *obs, const uint8_t *mask, const i32 *action, const float *qvals, const i32 *index, float inv_n,
@@ -131,29 +127,11 @@ long long sl_returns_ring(const i32 *reward, const uint8_t *done, float *out, fl
 
 
 // azul_a2c_apply_adam's launches: the step counter, then Adam on the flat k-major master copy + the eight nn.Linear tensors
-struct AdamJob { const float *grad; float *flat, *m, *v; float lr, b1, b2, eps; ModuleParams mp; i32 *step; const float *n_total; float *stats; int phase; };
-static void adam_lane(void *arg)
-{
-    AdamJob *j = (AdamJob *)arg;
-    if (j->phase == 0) azul_a2c_step_kernel(j->step, j->n_total);
-    else azul_a2c_apply_kernel(j->grad, j->flat, j->m, j->v, j->lr, j->b1, j->b2, j->eps, 1.f, 1.f, j->mp, j->step, j->n_total, 0.f, j->stats);
-}
 long long sl_adam(const float *grad, float *flat, float *m, float *v, float lr, float beta1, float beta2, float eps, float *c1w, float *c1b,
                   float *c2w, float *c2b, float *a1w, float *a1b, float *a2w, float *a2b, i32 *step, const float *n_total, float *stats5)
 {
-    AdamJob j = {grad, flat, m, v, lr, beta1, beta2, eps, {c1w, c1b, c2w, c2b, a1w, a1b, a2w, a2b}, step, n_total, stats5, 0};
-    long long ops = 1;
-    simt::g_grid_dim = {1, 1, 1};
-    simt::g_block_idx = {0, 0, 0};
-    ops += (long long)simt::run_workgroup(adam_lane, &j, 1);
-    j.phase = 1;
-    const unsigned blocks = ((unsigned)LG_P_PARAMS + 255u) / 256u;
-    simt::g_grid_dim = {blocks, 1, 1};
-    for (unsigned blk = 0; blk < blocks; blk++) {
-        simt::g_block_idx = {blk, 0, 0};
-        ops += (long long)simt::run_workgroup(adam_lane, &j, 4, 128u << 10);
-    }
-    return ops;
+    AdamJob j = {LG_SHAPE, grad, flat, m, v, lr, beta1, beta2, eps, 1.f, 1.f, {c1w, c1b, c2w, c2b, a1w, a1b, a2w, a2b}, step, n_total, stats5, 0};
+    return run_adam(j);
 }
 
 
@@ -224,16 +202,6 @@ long long sl_seed(int n, u32 *mt, u32 *mtpos, unsigned long long seed_base, cons
     return ops;
 }
 
-struct RedJob { const float *partial; u32 parts; float *grad; };
-static void red_lane(void *arg) { RedJob *j = (RedJob *)arg; azul_a2c_reduce_kernel(j->partial, j->parts, j->grad); }
-long long sl_reduce(const float *partial, int parts, float *grad)
-{
-    RedJob j = {partial, (u32)parts, grad};
-    const unsigned blocks = ((unsigned)LG_P_TOTAL + 255u) / 256u;
-    simt::g_grid_dim = {blocks, 1, 1};
-    long long ops = 1;
-    for (unsigned blk = 0; blk < blocks; blk++) { simt::g_block_idx = {blk, 0, 0}; ops += (long long)simt::run_workgroup(red_lane, &j, 4, 128u << 10); }
-    return ops;
-}
+long long sl_reduce(const float *partial, int parts, float *grad) { return run_reduce(LG_SHAPE, partial, parts, grad); }
 
 }

@@ -1,5 +1,5 @@
 // simt_learner_n.cpp -- TEST-ONLY: the wide-shape A2C kernels of csrc/azul_learner.hpp (azul_a2c_grad_n_kernel<IN, A>: three workgroup roles
-// per part, gradient tiles in registers; azul_a2c_apply_n_kernel: Adam on the shape's flat layout), UNMODIFIED, as workgroups of emulated
+// per part, gradient tiles in registers; azul_a2c_reduce_n_kernel and azul_a2c_apply_n_kernel on the shape's flat layout), UNMODIFIED, as workgroups of emulated
 // wavefronts (simt/simt.hpp) -- a CPU check of their arithmetic against torch and, under ASan / UBSan, of every LDS and global index.
 #define __HIPCC__ 1
 #include "azul_hip.h"
@@ -10,17 +10,11 @@ using namespace az;
 #include "azul_policy.hpp"
 #include "azul_rollout2.hpp"
 #include "azul_learner.hpp"
+#include "simt_a2c_launch.hpp"
 
 struct GradNJob { PolicyWeights W; LearnerArgs a; };
 template <int IN, int A>
 static void grad_n_lane(void *arg) { GradNJob *j = (GradNJob *)arg; azul_a2c_grad_n_kernel<IN, A>(j->W, j->a); }
-
-struct AdamNJob { A2CShapeN S; const float *grad; float *flat, *m, *v; float lr, b1, b2, eps, bc1, bc2s; ModuleParams P; const i32 *step; const float *nt; float *stats; };
-static void adam_n_lane(void *arg)
-{
-    AdamNJob *j = (AdamNJob *)arg;
-    azul_a2c_apply_n_kernel(j->S, j->grad, j->flat, j->m, j->v, j->lr, j->b1, j->b2, j->eps, j->bc1, j->bc2s, j->P, j->step, j->nt, 0.f, j->stats);
-}
 
 extern "C" {
 
@@ -44,7 +38,6 @@ long long sln_gradients_dev(int in, int act, int n, int parts, const float *obs,
     else if (in == 198 && act == 240) fn = grad_n_lane<198, 240>;
     else if (in == 260 && act == 300) fn = grad_n_lane<260, 300>;
     else return -1;
-    const u32 total = a2c_shape_n((u32)in, (u32)act).params + 4u;
     simt::g_grid_dim = {(unsigned)parts, 3, 1};
     long long ops = 0;
     for (int role = 0; role < 3; role++)
@@ -52,12 +45,7 @@ long long sln_gradients_dev(int in, int act, int n, int parts, const float *obs,
             simt::g_block_idx = {(unsigned)blk, (unsigned)role, 0};
             ops += (long long)simt::run_workgroup(fn, &j, (int)LN_WAVES, 512u << 10);
         }
-    for (u32 p = 0; p < total; p++) {
-        float s = 0.f;
-        for (int i = 0; i < parts; i++) s += partial[(size_t)i * total + p];
-        grad[p] = s;
-    }
-    return ops;
+    return ops + run_reduce(a2c_shape_n((u32)in, (u32)act), partial, parts, grad);
 }
 
 long long sln_gradients(int in, int act, int n, int parts, const float *obs, const uint8_t *mask, const i32 *action, const float *qvals,
@@ -72,20 +60,9 @@ long long sln_gradients(int in, int act, int n, int parts, const float *obs, con
 long long sln_adam(int in, int act, const float *grad, float *flat, float *m, float *v, float lr, float beta1, float beta2, float eps, int step,
                    float *c1w, float *c1b, float *c2w, float *c2b, float *a1w, float *a1b, float *a2w, float *a2b)
 {
-    AdamNJob j;
-    j.S = a2c_shape_n((u32)in, (u32)act);
-    j.grad = grad; j.flat = flat; j.m = m; j.v = v; j.lr = lr; j.b1 = beta1; j.b2 = beta2; j.eps = eps;
-    j.bc1 = (float)(1.0 - pow((double)beta1, (double)step)); j.bc2s = (float)sqrt(1.0 - pow((double)beta2, (double)step));
-    j.P = {c1w, c1b, c2w, c2b, a1w, a1b, a2w, a2b};
-    j.step = nullptr; j.nt = nullptr; j.stats = nullptr;
-    const unsigned blocks = (j.S.params + 255u) / 256u;
-    simt::g_grid_dim = {blocks, 1, 1};
-    long long ops = 0;
-    for (unsigned blk = 0; blk < blocks; blk++) {
-        simt::g_block_idx = {blk, 0, 0};
-        ops += (long long)simt::run_workgroup(adam_n_lane, &j, 4);
-    }
-    return ops;
+    AdamJob j = {a2c_shape_n((u32)in, (u32)act), grad, flat, m, v, lr, beta1, beta2, eps, (float)(1.0 - pow((double)beta1, (double)step)),
+                 (float)sqrt(1.0 - pow((double)beta2, (double)step)), {c1w, c1b, c2w, c2b, a1w, a1b, a2w, a2b}, nullptr, nullptr, nullptr, 0};
+    return run_adam(j);
 }
 
 }

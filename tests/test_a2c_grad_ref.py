@@ -94,13 +94,17 @@ def test_case_preconditions_and_f32_yardstick(shape_name, case_name):
     for k in ("obs", "mask", "action", "q", "index"):                    # deterministic builders
         assert (c[k] is None and c2[k] is None) or np.array_equal(c[k], c2[k], equal_nan=True)
     meta, rows = c["meta"], c["obs"].shape[0]
-    want_n = {"1": 1, "M-1": M - 1, "M": M, "M+1": M + 1, "2M-1": 2 * M - 1, "2M": 2 * M, "2M+1": 2 * M + 1, "4M+3": 4 * M + 3, "389": 389, "0": 0}
+    want_n = {"1": 1, "M-1": M - 1, "M": M, "M+1": M + 1, "2M-1": 2 * M - 1, "2M": 2 * M, "2M+1": 2 * M + 1, "4M+3": 4 * M + 3, "389": 389, "0": 0,
+              "6M+9": 6 * M + 9, "7M+9": 7 * M + 9, "8M+9": 8 * M + 9, "16M+9": 16 * M + 9}
     group = R.BY_NAME[case_name].group
     if group == "sweep":
         assert c["n"] == rows == 2 * M + 1 and c["parts"] == 2
     elif group in ("size", "long"):
         assert c["n"] == rows == want_n[case_name[2:].rsplit("-parts", 1)[0]]
         assert c["parts"] == int(case_name.split("parts")[1])
+        live = R.REDUCE_EDGE_PARTS.get(case_name[2:].rsplit("-parts", 1)[0])
+        if live is not None:                                             # the parts the host entry launches: min(tiles, workspace_parts)
+            assert min(c["parts"], -(-c["n"] // M)) == live
     elif group == "edge":
         assert c["n"] == rows == M + 1
     else:

@@ -1,5 +1,5 @@
 """The wide-shape A2C kernels on CPU: azul_a2c_grad_n_kernel<IN, A> (csrc/azul_learner.hpp: three workgroup roles per part, gradient
-tiles in registers) and azul_a2c_apply_n_kernel, compiled UNMODIFIED by g++ and run as workgroups of emulated wavefronts
+tiles in registers), azul_a2c_reduce_n_kernel and azul_a2c_apply_n_kernel on their layouts, compiled UNMODIFIED by g++ and run as workgroups of emulated wavefronts
 (tests/hostcheck/simt) -- gradients and loss sums against float64 autograd of the reference's loss (agent.py:39-62) for p3_d5 and
 p4_d9 with several passes per part, a ragged last tile and rows without a legal action; Adam against torch.optim.Adam."""
 import ctypes as C
@@ -19,7 +19,7 @@ SIMT_FLAGS = ["-O0", "-g", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off"
 def load():
     src = os.path.join(HERE, "simt_learner_n.cpp")
     csrc = os.path.join(ROOT, "azul_deep_reinforcement_learning_amd", "csrc")
-    deps = [src, os.path.join(csrc, "azul_learner.hpp"), os.path.join(csrc, "azul_policy.hpp"), os.path.join(HERE, "simt", "simt.hpp"),
+    deps = [src, os.path.join(HERE, "simt_a2c_launch.hpp"), os.path.join(csrc, "azul_learner.hpp"), os.path.join(csrc, "azul_policy.hpp"), os.path.join(HERE, "simt", "simt.hpp"),
             os.path.join(HERE, "simt", "hip", "hip_runtime.h"), os.path.join(ROOT, "include", "azul_hip.h")]
     if not os.path.exists(LIB) or os.path.getmtime(LIB) < max(os.path.getmtime(d) for d in deps):
         tmp = LIB + ".%d.tmp" % os.getpid()

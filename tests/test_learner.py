@@ -318,7 +318,7 @@ def test_window_without_a_finished_episode_is_a_no_op(golden_dir):
 
 @pytest.mark.gpu
 def test_fused_adam_matches_torch_adam(golden_dir):
-    """azul_a2c_apply_adam (flat master copy + module written by one kernel) vs torch.optim.Adam fed the same kernel gradients: the
+    """azul_a2c_apply_adam_n (flat master copy + module written by one kernel) vs torch.optim.Adam fed the same kernel gradients: the
     parameters after five updates, the flat copy's consistency with the module, and a save / load of the optimiser state."""
     from azul_deep_reinforcement_learning_amd.learner import A2CLearner
     g = _golden(golden_dir)
@@ -351,6 +351,49 @@ def test_fused_adam_matches_torch_adam(golden_dir):
     w1t = torch.cat([nets[0].critic_linear1.weight, nets[0].actor_linear1.weight], dim=0).t()
     assert torch.equal(kw["w1t"], w1t) and torch.equal(kw["w2a_t"], nets[0].actor_linear2.weight.t())
     assert torch.equal(kw["b1"], torch.cat([nets[0].critic_linear1.bias, nets[0].actor_linear1.bias])) and torch.equal(kw["b2c"], nets[0].critic_linear2.bias)
+
+
+@pytest.mark.gpu
+def test_apply_adam_is_apply_adam_n_for_the_reference_shape():
+    """azul_a2c_apply_adam against azul_a2c_apply_adam_n(..., 136, 180, 180, ...) on copies of the same state, bit for bit (flat copy,
+    both moments, the step, the stats row, the eight module tensors) after each of three steps: the device step counter with samples,
+    the same with n_total_dev = 0 (nothing but the stats row may change), and step_dev = NULL with a host step."""
+    import ctypes as C
+    from azul_deep_reinforcement_learning_amd import _lib as L
+    from azul_deep_reinforcement_learning_amd.learner import REFERENCE_SHAPE, flat_layout
+    size = flat_layout(*REFERENCE_SHAPE)["size"]
+    gen = torch.Generator().manual_seed(3)
+    rnd = lambda *shape: torch.randn(*shape, generator=gen)
+    mods0 = [rnd(180, 136), rnd(180), rnd(1, 180), rnd(1), rnd(180, 136), rnd(180), rnd(180, 180), rnd(180)]
+    state0 = {"flat": rnd(size) * 0.05, "m": rnd(size) * 1e-3, "v": rnd(size).abs() * 1e-5, "step": torch.tensor([4], dtype=torch.int32),
+              "stats": torch.full((5,), float("nan"))}
+    sides = [({k: v.clone().cuda() for k, v in state0.items()}, [m.clone().cuda() for m in mods0]) for _ in range(2)]
+    p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+    stream = lambda: C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    for use_dev, n_total, host_step in ((True, 37.0, 0), (True, 0.0, 0), (False, None, 6)):
+        grad = (rnd(size + 4) * 1e-2).cuda()
+        nt = None if n_total is None else torch.tensor([n_total], device="cuda")
+        before = [[t.clone() for t in list(st.values()) + mods] for st, mods in sides]
+        for side, (st, mods) in enumerate(sides):
+            head = (p(grad), p(st["flat"]), p(st["m"]), p(st["v"]), C.c_float(3e-4), C.c_float(0.9), C.c_float(0.999), C.c_float(1e-8), host_step)
+            tail = [p(m) for m in mods] + [p(st["step"]) if use_dev else None, p(nt), C.c_float(11.0), p(st["stats"]), stream()]
+            if side == 0:
+                L.check(L.lib.azul_a2c_apply_adam(*head, *tail))
+            else:
+                L.check(L.lib.azul_a2c_apply_adam_n(*head, *REFERENCE_SHAPE, *tail))
+        torch.cuda.synchronize()
+        (sa, ma), (sb, mb) = sides
+        for k in sa:
+            assert torch.equal(sa[k], sb[k]), (k, n_total)
+        for i, (x, y) in enumerate(zip(ma, mb)):
+            assert torch.equal(x, y), (i, n_total)
+        assert torch.isfinite(sa["stats"]).all() and float(sa["stats"][4]) == (11.0 if n_total is None else n_total)
+        moved = [not torch.equal(b, a) for b, a in zip(before[0], list(sa.values()) + ma)]
+        if n_total == 0.0:                                   # an empty window: only the stats row is written
+            assert moved == [False, False, False, False, True] + [False] * 8
+        else:                                                # everything moves; the device counter only when it is in use
+            assert moved == [True, True, True, use_dev, True] + [True] * 8
+    assert int(sides[0][0]["step"][0]) == 5
 
 
 # ---------------------------------------------------------------- ring of windows: every step trained exactly once
