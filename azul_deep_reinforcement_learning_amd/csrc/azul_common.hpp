@@ -8,6 +8,9 @@
 //                                        side of the policy rollout -- two games per 64-lane wavefront, state in VGPRs
 //   azul_rules_x.hpp                     P = 2..4 players, D = 5 or 2 P + 1 displays, the extended rule switches (row N4), built from the
 //                                        same wave primitives (half ballots, LDS-crossbar gathers, wall pricing, parallel factory draw)
+// The __global__ functions are in headers too (azul_selfplay_kernels.hpp; azul_x_kernels.hpp for the rule kernels of the wide record;
+// azul_policy.hpp, azul_rollout2.hpp, azul_learner.hpp), so that the emulation below compiles the kernels themselves; azul_kernels.hip
+// holds the host side.
 // This is gfx950 device code only: there is no CPU execution path in the product (tests/hostcheck/simt emulates the 64 lanes in lockstep to
 // run these headers, unmodified, in the build container).
 // Reference lines: azulnet/azul.py:184-191 (is_end_of_game), :200-210 (count_floor), :294-295 (score clamp); CPython 3.10 _randommodule.c

@@ -11,7 +11,7 @@
 //   azul_seed_kernel            one THREAD per game: CPython init_by_array is a strictly sequential 1247-step recurrence
 //   azul_op_kernel              every single-call rule / runner entry point of the ABI for two-player batches (azul_ops2.hpp)
 //   azul_x_op_kernel            the rule entries for batches of 3- / 4-player games and for extended-rule batches (row N4;
-//                               azul_rules_x.hpp: 256-byte wide records)
+//                               azul_x_kernels.hpp on azul_rules_x.hpp: 256-byte wide records)
 //   azul_selfplay2_kernel       state register-resident across n_steps env moves (the hot path); azul_x_selfplay_kernel: row N4's
 //   azul_returns_kernel         discounted returns over a trajectory window
 //   azul_pack_c1_kernel         the C1 wire record of the opt-in trajectory all-gather (184 bytes per agent step); azul_clock_probe_kernel (diagnostic)
@@ -38,74 +38,11 @@ using namespace az;
 // ------------------------------------------------------------------------------------------------
 #include "azul_selfplay_kernels.hpp"
 
-#include "azul_rules_x.hpp"
-
-// Rule entries for batches of three / four players and for extended-rule batches (row N4): one launch = one rule call per game, two games
-// per wavefront (azx::op_body_x).  grid = ceil(count / 2) one-wave workgroups.
-template <u32 P, u32 D>
-__global__ void __launch_bounds__(64) azul_x_op_kernel(azx::XBatchDev b, azx::XOp a)
-{
-    __shared__ u32 mt_lds[2][624];
-    __shared__ double2 tab_lds[azx::Dim<D>::TROWS * T_STRIDE];
-    azx::op_body_x<P, D>(b, a, blockIdx.x, mt_lds, tab_lds);
-}
-
-// Their flat random-agent self-play, persistent like azul_selfplay2_kernel (two games per wavefront, state in VGPRs, MT19937 streams and
-// their tempered copies in LDS, XCD-aware game placement).
-template <u32 P, u32 D, int OUT, bool PAD, bool BITS>
-__global__ void __launch_bounds__(64) azul_x_selfplay_kernel(azx::XBatchDev b, azx::XTraj t)
-{
-    __shared__ u32 mt_lds[2][624];
-    __shared__ u32 mtt_lds[2][624];
-    __shared__ double2 tab_lds[azx::Dim<D>::TROWS * T_STRIDE];
-    const u32 nb = gridDim.x, xcd = blockIdx.x & 7u, q8 = nb >> 3, rem = nb & 7u;
-    const u32 wave_id = xcd * q8 + (xcd < rem ? xcd : rem) + (blockIdx.x >> 3);      // every XCD plays a contiguous range of games
-    azx::selfplay_body_x<P, D, OUT, PAD, BITS>(b, t, wave_id, mt_lds, mtt_lds, tab_lds);
-}
-
-// GameRunner for P seats on the wide record (azul_batch_mp_* entries; azx::runner_body_x in azul_rules_x.hpp): one runner call per game, two games per wavefront
-// (azx::runner_body_x), the game in VGPRs from the agent's move through the replies, the reset and the observation.
-template <u32 P, u32 D>
-__global__ void __launch_bounds__(64) azul_x_runner_kernel(azx::XBatchDev b, azx::XRun a)
-{
-    __shared__ u32 mt_lds[2][624];
-    __shared__ double2 tab_lds[azx::Dim<D>::TROWS * T_STRIDE];
-    azx::runner_body_x<P, D>(b, a, blockIdx.x, mt_lds, tab_lds);
-}
-
-// The same GameRunner with an EXTERNAL opponent (azul_batch_mp_net_* entries; azx::net_body_x): one cut of the protocol per launch -- the
-// agent's move, one opponent_move() of every game that owes one, or the fresh game -- and what the opponent is handed.  A kernel of its own:
-// azul_x_runner_kernel's register budget stays as it is.
-template <u32 P, u32 D>
-__global__ void __launch_bounds__(64) azul_x_net_kernel(azx::XBatchDev b, azx::XNet a)
-{
-    __shared__ u32 mt_lds[2][624];
-    azx::net_body_x<P, D>(b, a, blockIdx.x, mt_lds);
-}
+#include "azul_x_kernels.hpp"
 
 #include "azul_policy.hpp"
 #include "azul_rollout2.hpp"
 #include "azul_learner.hpp"
-
-// The persistent policy rollout for wide batches (azul_batch_mp_policy_rollout; x_policy_rollout_body in azul_rollout2.hpp): 16 games per
-// workgroup of eight waves for a whole window, the workgroup's LDS declared here.
-template <u32 P, u32 D, int OPP>
-__global__ void __launch_bounds__(64 * PR2_WAVES) azul_x_policy_rollout_kernel(azx::XBatchDev b, PolicyWeights W, RolloutArgs a, u32 id_base)
-{
-    __shared__ PXShared<P, D> S;
-    x_policy_rollout_body<P, D, OPP>(b, W, a, id_base, S);
-}
-
-// ... with a NETWORK opponent (azul_batch_mp_policy_rollout_vs; OPP 2 of x_policy_rollout_body): the reply rounds inside the window, the
-// opponent's biases and the games' reply-loop state in LDS next to PXShared
-template <u32 P, u32 D>
-__global__ void __launch_bounds__(64 * PR2_WAVES) azul_x_policy_rollout_vs_kernel(azx::XBatchDev b, PolicyWeights W, RolloutArgs a, u32 id_base,
-                                                                                   u32 max_replies)
-{
-    __shared__ PXShared<P, D> S;
-    __shared__ PXOpp<D> O;
-    x_policy_rollout_body<P, D, 2>(b, W, a, id_base, S, &O, max_replies);
-}
 
 // ------------------------------------------------------------------------------------------------
 // host side: C ABI

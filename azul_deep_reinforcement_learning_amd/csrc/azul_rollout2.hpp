@@ -1,7 +1,8 @@
 // azul_rollout2.hpp -- the persistent policy rollout (row N1 / N2: the batched NNRunner.run_episode loop, nn_runner.py:17-47) with the
 // ENV SIDE ON THE VECTOR PIPE: a workgroup of 8 waves owns 16 games for a whole window, wave w plays games 2w and 2w + 1 in its two
 // 32-lane halves with azul_selfplay2.hpp's rules (state in VGPRs, half-uniform), and the same 8 waves run the network on the f32
-// matrix cores between the env phases.  Included by azul_kernels.hip after azul_policy.hpp.
+// matrix cores between the env phases.  Included by azul_kernels.hip after azul_policy.hpp; the __global__ functions of the wide window
+// kernels are at the end of this file.
 //
 // Why on the vector pipe: rounds 1-2 ran sixteen one-game waves per workgroup whose rule code sat on the CU's ONE scalar ALU, and every
 // move waited for the slowest of the sixteen games (env step 6.2 k + waiting 7.2 k of 33.2 k cycles per move; LABNOTES.md).  Here a move's
@@ -597,7 +598,7 @@ struct PXShape {
 };
 
 template <u32 P, u32 D>
-struct PXShared {                                                  // the workgroup's LDS (azul_x_policy_rollout_kernel declares it)
+struct PXShared {                                                  // the workgroup's LDS (azul_x_policy_rollout_kernel below declares it)
     float obs[PF_GAMES * PXShape<P, D>::OBS_STRIDE];
     float hid[PF_GAMES * PF_HID_STRIDE];
     float lg[PF_GAMES * PXShape<P, D>::LOG_STRIDE];
@@ -963,10 +964,7 @@ AZ_FN void x_policy_rollout_body(const azx::XBatchDev &b, const PolicyWeights &W
             u32 dn = 0, st;
             if constexpr (OPP == 1) st = azx::agent_step_x(g, s, av, b.rules, K, r, tab, b.draw_margin, cnt, rew, dn);
             else st = azx::policy_step_x(g, s, av, b.rules, K, r, b.draw_margin, cnt, rew, dn);
-            if (!(st == ST_ILLEGAL_MOVE || st == ST_BAD_ACTION)) {
-                azx::gx_store(g, rec, l);
-                azx::runx_store(s, rec, l);
-            }
+            if (!(st == ST_ILLEGAL_MOVE || st == ST_BAD_ACTION)) azx::store_runner_x(g, s, rec, l);
             if (l == 0u) { a.reward[row_t + gi] = rew; a.done[row_t + gi] = (uint8_t)dn; }
             st_last = st;
             publish(g, K, (u32)t + 1u);
@@ -992,4 +990,24 @@ AZ_FN void x_policy_rollout_body(const azx::XBatchDev &b, const PolicyWeights &W
             __threadfence();
         }
     }
+}
+
+// The persistent policy rollout for wide batches (azul_batch_mp_policy_rollout; x_policy_rollout_body above): 16 games per
+// workgroup of eight waves for a whole window, the workgroup's LDS declared here.
+template <u32 P, u32 D, int OPP>
+__global__ void __launch_bounds__(64 * PR2_WAVES) azul_x_policy_rollout_kernel(azx::XBatchDev b, PolicyWeights W, RolloutArgs a, u32 id_base)
+{
+    __shared__ PXShared<P, D> S;
+    x_policy_rollout_body<P, D, OPP>(b, W, a, id_base, S);
+}
+
+// ... with a NETWORK opponent (azul_batch_mp_policy_rollout_vs; OPP 2 of x_policy_rollout_body): the reply rounds inside the window, the
+// opponent's biases and the games' reply-loop state in LDS next to PXShared
+template <u32 P, u32 D>
+__global__ void __launch_bounds__(64 * PR2_WAVES) azul_x_policy_rollout_vs_kernel(azx::XBatchDev b, PolicyWeights W, RolloutArgs a, u32 id_base,
+                                                                                   u32 max_replies)
+{
+    __shared__ PXShared<P, D> S;
+    __shared__ PXOpp<D> O;
+    x_policy_rollout_body<P, D, 2>(b, W, a, id_base, S, &O, max_replies);
 }

@@ -1,6 +1,6 @@
 // azul_rules_x.hpp -- the Azul rules for P = 2, 3, 4 players on D = 5 or 2 P + 1 factory displays, TWO GAMES PER 64-LANE WAVEFRONT
 // (lanes 0..31 / 32..63, the mapping of azul_selfplay2.hpp), with the rule switches of row N4 of SURVEY.md 8f.  Included by
-// azul_kernels.hip after azul_selfplay2.hpp, whose building blocks it uses (half ballots, LDS-crossbar gathers, DPP reductions, the
+// azul_x_kernels.hpp and azul_rollout2.hpp on top of azul_selfplay2.hpp, whose building blocks it uses (half ballots, LDS-crossbar gathers, DPP reductions, the
 // MT19937 stream with its tempered copy, the wall pricing, the parallel factory draw).
 //
 // What is what:
@@ -553,6 +553,15 @@ AZ_FN bool mask_test_x(const MaskX<D> &m, u32 a, u32 l)
     return ((w >> (q & 31u)) & 1u) != 0u;
 }
 
+// action a = source + S colour + Q row (< NA) -> its three parts
+struct ActX { u32 row, c, s; };
+template <u32 D>
+AZ_FN ActX decode_action_x(u32 a)
+{
+    const u32 row = a / Dim<D>::Q, q = a - row * Dim<D>::Q, c = q / Dim<D>::S;
+    return {row, c, q - c * Dim<D>::S};
+}
+
 // ---- step: azul.py:296-313 ---------------------------------------------------------------------------------------------------------------
 template <u32 P, u32 D>
 AZ_FN u32 checked_step_x(GX<P, D> &g, const RulesX &rules, const KX<D> &K, Rng2 &r, u64 margin, i32 a)
@@ -562,8 +571,8 @@ AZ_FN u32 checked_step_x(GX<P, D> &g, const RulesX &rules, const KX<D> &K, Rng2 
     MaskX<D> m;
     legal_mask_x(g, K, m);
     if (!mask_test_x<D>(m, (u32)a, K.k.l)) return ST_ILLEGAL_MOVE;   // :301-302, state untouched
-    const u32 row = (u32)a / Dim<D>::Q, q = (u32)a - row * Dim<D>::Q, c = q / Dim<D>::S, s = q - c * Dim<D>::S;
-    do_move_x(g, s, c, row, rules.pool != (u32)XPOOL_RANDOM, K);     // :304
+    const ActX mv = decode_action_x<D>((u32)a);
+    do_move_x(g, mv.s, mv.c, mv.row, rules.pool != (u32)XPOOL_RANDOM, K);     // :304
     sources_x(g);
     return after_move_x(g, rules, r, margin, K);
 }
@@ -860,8 +869,8 @@ AZ_FN i32 random_agent_x(const MaskX<D> &m, Rng2 &r, const Tab2 &T, const K2 &k)
     return a;
 }
 
-// ---- kernel bodies (azul_kernels.hip wraps them in __global__ functions that own the LDS; tests/hostcheck/simt_rules_x.cpp runs the
-// very same bodies on the lockstep 64-lane emulation) -------------------------------------------------------------------------------------
+// ---- kernel bodies (azul_x_kernels.hpp wraps them in __global__ functions that own the LDS; tests/hostcheck/simt_rules_x.cpp launches
+// those kernels on the lockstep 64-lane emulation) ----------------------------------------------------------------------------------------
 struct XBatchDev {
     uint8_t *state;      // [N][256]
     u32 *mt;             // [N][624]
@@ -915,6 +924,40 @@ AZ_FN void stage_tab_x(const double2 *tab, double2 *tab_lds, u32 lane)
     lds_sync();
 }
 
+// ---- the steps the bodies share (and x_policy_rollout_body of azul_rollout2.hpp).  Thin on purpose: nothing here keeps state of its own ----
+// a legal mask as NA bytes, row r's action q at row[Q r + q]: lane l writes bit l and (D > 5) bit 32 + l of each of the six rows
+template <u32 D>
+AZ_FN void store_mask_bytes_x(const MaskX<D> &m, uint8_t *row, u32 l)
+{
+    row += l;
+#pragma unroll
+    for (u32 rr = 0; rr < 6u; rr++) {
+        if (l < (Dim<D>::Q < 32u ? Dim<D>::Q : 32u)) row[Dim<D>::Q * rr] = (uint8_t)m.bit[rr][0];
+        if (Dim<D>::NW > 1) { if (l < Dim<D>::Q - 32u) row[Dim<D>::Q * rr + 32u] = (uint8_t)m.bit[rr][Dim<D>::NW - 1]; }
+    }
+}
+
+// the lane constants, and the game of a 256-byte record with its derived fields
+template <u32 P, u32 D>
+AZ_FN void open_game_x(GX<P, D> &g, KX<D> &K, const uint8_t *rec, u32 l)
+{
+    kx_init(K);
+    gx_load(g, rec, l);
+    prime_x(g, K);
+}
+
+// game gi's MT19937 stream (into `lds`) and counters, from / back to the batch's arrays
+AZ_FN void open_stream_x(Rng2 &r, Counters2 &cnt, const XBatchDev &b, u32 gi, u32 *lds, u32 l)
+{
+    rng2_open(r, b.mt + (size_t)gi * 624u, lds, b.mtpos[gi], l);
+    counters2_open(cnt, b.episodes + gi, b.stuck + gi, b.stat_sum + (size_t)gi * 10, l);
+}
+AZ_FN void close_stream_x(Rng2 &r, const Counters2 &cnt, const XBatchDev &b, u32 gi, u32 l)
+{
+    rng2_close(r, b.mt + (size_t)gi * 624u, b.mtpos + gi, l);
+    counters2_close(cnt, l);
+}
+
 // one rule call per game (two games per wave): Azul.__init__ / new_round / move / next_player / count_score / step, the RandomAgent sampler
 // on the game's own or a caller's mask, and the queries (mask, observation, flags, statistics, player to move) on the state after the call
 template <u32 P, u32 D>
@@ -952,8 +995,8 @@ AZ_FN void op_body_x(const XBatchDev &b, const XOp &a, u32 pair /* games 2 pair,
         case XOP_MOVE: {
             const i32 av = a.actions[oi];
             if (av < 0 || av >= (i32)Dim<D>::NA) { st = ST_BAD_ACTION; dirty_state = false; break; }
-            const u32 row = (u32)av / Dim<D>::Q, q = (u32)av - row * Dim<D>::Q, c = q / Dim<D>::S, s = q - c * Dim<D>::S;
-            do_move_x(g, s, c, row, tracked, K);
+            const ActX mv = decode_action_x<D>((u32)av);
+            do_move_x(g, mv.s, mv.c, mv.row, tracked, K);
             sources_x(g);
         } break;
         case XOP_NEXT_PLAYER:
@@ -1016,12 +1059,7 @@ AZ_FN void op_body_x(const XBatchDev &b, const XOp &a, u32 pair /* games 2 pair,
     if (a.mask) {
         MaskX<D> m;
         legal_mask_x(g, K, m);
-        uint8_t *row = a.mask + (size_t)oi * Dim<D>::NA + l;
-#pragma unroll
-        for (u32 rr = 0; rr < 6u; rr++) {
-            if (l < (Dim<D>::Q < 32u ? Dim<D>::Q : 32u)) row[Dim<D>::Q * rr] = (uint8_t)m.bit[rr][0];
-            if (Dim<D>::NW > 1) { if (l < Dim<D>::Q - 32u) row[Dim<D>::Q * rr + 32u] = (uint8_t)m.bit[rr][Dim<D>::NW - 1]; }
-        }
+        store_mask_bytes_x<D>(m, a.mask + (size_t)oi * Dim<D>::NA, l);
     }
     if (a.obs) observe_x(g, (u32)a.persp < P ? (u32)a.persp : mex(g), a.obs + (size_t)oi * obs_size<P, D>(), l);
     if (a.flags) {
@@ -1044,11 +1082,9 @@ AZ_FN void selfplay_body_x(const XBatchDev &b, const XTraj &t, u32 wave_id, u32 
     if (gi >= b.n) return;                               // odd batch: the last wave plays one game
     uint8_t *rec = b.state + (size_t)gi * AZUL_RECORD_BYTES_WIDE;
     KX<D> K;
-    kx_init(K);
     const Tab2 tab = {tab_lds};
     GX<P, D> g;
-    gx_load(g, rec, l);
-    prime_x(g, K);
+    open_game_x(g, K, rec, l);
     Rng2 r;
     u32 *gmt = b.mt + (size_t)gi * 624u;
     rng2_open(r, gmt, mt_lds[half], b.mtpos[gi], l);
@@ -1103,8 +1139,8 @@ AZ_FN void selfplay_body_x(const XBatchDev &b, const XTraj &t, u32 wave_id, u32 
 }
 
 // ---- GameRunner for P = 2, 3, 4 players on D = 5 or 2 P + 1 displays, TWO GAMES PER 64-LANE WAVEFRONT, on top of the rules above
-// (state in VGPRs, one game per 32-lane half).  runner_body_x is the body of azul_x_runner_kernel; tests/hostcheck/simt_runner_x.cpp runs it,
-// unmodified, under the lockstep 64-lane emulation against a model composed from the oracle's primitives (tests/mp_runner_model.py).
+// (state in VGPRs, one game per 32-lane half).  runner_body_x is the body of azul_x_runner_kernel; tests/hostcheck/simt_runner_x.cpp runs that
+// kernel, unmodified, under the lockstep 64-lane emulation against a model composed from the oracle's primitives (tests/mp_runner_model.py).
 //
 // What it is: GameRunner.__init__ / step / reset of the reference (azulnet/game_runner.py:23-36, 43-55, 76-85) statement for statement on an
 // Azul(players = P), the agent in seat 0 ("player 1"), every other seat replying with its own RandomAgent draw (:87-97) from the game's
@@ -1147,6 +1183,20 @@ AZ_FN void runx_load(RunX &s, const uint8_t *rec)
 AZ_FN void runx_store(const RunX &s, uint8_t *rec, u32 l)
 {
     if (l == 0u) *(u32 *)(rec + 228) = ((u32)s.phi & 0xffffu) | ((s.moves & 0xffffu) << 16);
+}
+
+// open_game_x + the runner's tail; and both written back
+template <u32 P, u32 D>
+AZ_FN void open_runner_x(GX<P, D> &g, RunX &s, KX<D> &K, const uint8_t *rec, u32 l)
+{
+    open_game_x(g, K, rec, l);
+    runx_load(s, rec);
+}
+template <u32 P, u32 D>
+AZ_FN void store_runner_x(const GX<P, D> &g, const RunX &s, uint8_t *rec, u32 l)
+{
+    gx_store(g, rec, l);
+    runx_store(s, rec, l);
 }
 
 template <u32 D>
@@ -1195,8 +1245,8 @@ AZ_FN u32 opponent_loop_x(GX<P, D> &g, RunX &s, const RulesX &rules, const KX<D>
         if (L == 0u) return ST_STUCK;                                  // RandomAgent: random.choices on all-zero weights raises
         if (g.eog) return ST_GAME_ENDED;                               // azul.py:298-299
         const i32 a = random_agent_x<D>(m, r, T, K.k);                 // :97
-        const u32 row = (u32)a / Dim<D>::Q, q = (u32)a - row * Dim<D>::Q, c = q / Dim<D>::S, src = q - c * Dim<D>::S;
-        do_move_x(g, src, c, row, tracked, K);                         // Azul.step on a legal action (azul.py:304-313)
+        const ActX mv = decode_action_x<D>((u32)a);
+        do_move_x(g, mv.s, mv.c, mv.row, tracked, K);                  // Azul.step on a legal action (azul.py:304-313)
         sources_x(g);
         const u32 st = after_move_x(g, rules, r, margin, K);
         if (st) return st;
@@ -1304,20 +1354,15 @@ AZ_FN void runner_body_x(const XBatchDev &b, const XRun &a, u32 pair, u32 (*mt_l
     const bool act = a.active ? (a.active[gi] != 0) : true;
     uint8_t *rec = b.state + (size_t)gi * AZUL_RECORD_BYTES_WIDE;
     KX<D> K;
-    kx_init(K);
     const Tab2 tab = {tab_lds};
     GX<P, D> g;
-    gx_load(g, rec, l);
-    prime_x(g, K);
     RunX s;
-    runx_load(s, rec);
+    open_runner_x(g, s, K, rec, l);
     const bool steps = a.op == XRUN_STEP || a.op == XRUN_AGENT_STEP || a.op == XRUN_POLICY_STEP;
     if (act && a.op != XRUN_PREVIEW) {
         Rng2 r;
-        u32 *gmt = b.mt + (size_t)gi * 624u;
-        rng2_open(r, gmt, mt_lds[half], b.mtpos[gi], l);
         Counters2 cnt;
-        counters2_open(cnt, b.episodes + gi, b.stuck + gi, b.stat_sum + (size_t)gi * 10, l);
+        open_stream_x(r, cnt, b, gi, mt_lds[half], l);
         u32 st = ST_OK;
         i32 rew = 0;
         u32 dn = 0;
@@ -1344,12 +1389,8 @@ AZ_FN void runner_body_x(const XBatchDev &b, const XRun &a, u32 pair, u32 (*mt_l
         }
         // an illegal / out-of-range action (and, for the plain step, a finished game) leaves the game untouched
         const bool dirty = !(st == ST_ILLEGAL_MOVE || st == ST_BAD_ACTION || (a.op == XRUN_STEP && st == ST_GAME_ENDED));
-        if (dirty) {
-            gx_store(g, rec, l);
-            runx_store(s, rec, l);
-        }
-        rng2_close(r, gmt, b.mtpos + gi, l);
-        counters2_close(cnt, l);
+        if (dirty) store_runner_x(g, s, rec, l);
+        close_stream_x(r, cnt, b, gi, l);
         if (l == 0u) {
             if (steps && a.reward) a.reward[gi] = rew;
             if (steps && a.done) a.done[gi] = (uint8_t)dn;
@@ -1364,12 +1405,7 @@ AZ_FN void runner_body_x(const XBatchDev &b, const XRun &a, u32 pair, u32 (*mt_l
     if (a.mask) {
         MaskX<D> m;
         legal_mask_x(g, K, m);
-        uint8_t *row = a.mask + (size_t)gi * Dim<D>::NA + l;
-#pragma unroll
-        for (u32 rr = 0; rr < 6u; rr++) {
-            if (l < (Dim<D>::Q < 32u ? Dim<D>::Q : 32u)) row[Dim<D>::Q * rr] = (uint8_t)m.bit[rr][0];
-            if (Dim<D>::NW > 1) { if (l < Dim<D>::Q - 32u) row[Dim<D>::Q * rr + 32u] = (uint8_t)m.bit[rr][Dim<D>::NW - 1]; }
-        }
+        store_mask_bytes_x<D>(m, a.mask + (size_t)gi * Dim<D>::NA, l);
     }
     if (a.obs) observe_x(g, (u32)a.persp < P ? (u32)a.persp : mex(g), a.obs + (size_t)gi * obs_size<P, D>(), l);
     if (a.player && l == 0u) a.player[gi] = (uint8_t)g.cur;
@@ -1491,20 +1527,15 @@ AZ_FN void net_body_x(const XBatchDev &b, const XNet &a, u32 pair, u32 (*mt_lds)
     const u32 pend = a.op == XNET_REPLY ? (u32)a.pending[gi] : (u32)NET_READY;
     uint8_t *rec = b.state + (size_t)gi * AZUL_RECORD_BYTES_WIDE;
     KX<D> K;
-    kx_init(K);
     GX<P, D> g;
-    gx_load(g, rec, l);
-    prime_x(g, K);
     RunX s;
-    runx_load(s, rec);
+    open_runner_x(g, s, K, rec, l);
     MaskX<D> m;
     bool owes = false;
     if (act && (reset || agent || pend != NET_READY)) {                // (a reply round leaves the games that owe nothing alone)
         Rng2 r;
-        u32 *gmt = b.mt + (size_t)gi * 624u;
-        rng2_open(r, gmt, mt_lds[half], b.mtpos[gi], l);
         Counters2 cnt;
-        counters2_open(cnt, b.episodes + gi, b.stuck + gi, b.stat_sum + (size_t)gi * 10, l);
+        open_stream_x(r, cnt, b, gi, mt_lds[half], l);
         NetStep ns;
         u32 st = ST_OK;
         if (reset) {
@@ -1515,12 +1546,8 @@ AZ_FN void net_body_x(const XBatchDev &b, const XNet &a, u32 pair, u32 (*mt_lds)
             ns.st = a.status ? a.status[gi] : 0u;                              // the step's status is its FIRST status that was not OK
             st = net_move_x(g, s, a.actions[gi], agent, m, b.rules, K, r, b.draw_margin, cnt, ns);
         }
-        if (!(st == ST_ILLEGAL_MOVE || st == ST_BAD_ACTION)) {
-            gx_store(g, rec, l);
-            runx_store(s, rec, l);
-        }
-        rng2_close(r, gmt, b.mtpos + gi, l);
-        counters2_close(cnt, l);
+        if (!(st == ST_ILLEGAL_MOVE || st == ST_BAD_ACTION)) store_runner_x(g, s, rec, l);
+        close_stream_x(r, cnt, b, gi, l);
         if (l == 0u) {
             a.pending[gi] = (uint8_t)ns.pending;
             if (a.replies) a.replies[gi] = (uint8_t)(ns.replies < 255u ? ns.replies : 255u);
@@ -1532,14 +1559,7 @@ AZ_FN void net_body_x(const XBatchDev &b, const XNet &a, u32 pair, u32 (*mt_lds)
     }
     // what the opponent is handed: the state and legal mask (left in `m` by net_settle_x) from the mover's perspective (game_runner.py:38-39)
     if (owes) {
-        if (a.mask) {
-            uint8_t *row = a.mask + (size_t)gi * Dim<D>::NA + l;
-#pragma unroll
-            for (u32 rr = 0; rr < 6u; rr++) {
-                if (l < (Dim<D>::Q < 32u ? Dim<D>::Q : 32u)) row[Dim<D>::Q * rr] = (uint8_t)m.bit[rr][0];
-                if (Dim<D>::NW > 1) { if (l < Dim<D>::Q - 32u) row[Dim<D>::Q * rr + 32u] = (uint8_t)m.bit[rr][Dim<D>::NW - 1]; }
-            }
-        }
+        if (a.mask) store_mask_bytes_x<D>(m, a.mask + (size_t)gi * Dim<D>::NA, l);
         if (a.obs) observe_x(g, mex(g), a.obs + (size_t)gi * obs_size<P, D>(), l);
     }
     const u64 who = __builtin_amdgcn_ballot_w64(owes && l == 0u);      // one atomic per wave

@@ -9,13 +9,18 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _lib = None
 
 
+def build(name, here=_HERE):
+    """The ONE way to build a shim: `make <name>` in tests/hostcheck (or a copy of it), whose Makefile has one rule and one dependency
+    list for all of them.  Returns the library's path."""
+    subprocess.check_call(["make", "-s", "-C", here, name], stdout=subprocess.DEVNULL)
+    return os.path.join(here, name)
+
+
 def lib():
     """The two-player rule kernel (azul_op_kernel on csrc/azul_ops2.hpp) under the lockstep wave emulation: simt_ops2.cpp."""
     global _lib
     if _lib is None:
-        name = os.environ.get("AZUL_SIMT_OPS_LIB", "libsimt_ops2.so")      # tests/hostcheck/run_sanitizers.sh: libsimt_ops2_asan.so
-        subprocess.check_call(["make", "-s", "-C", _HERE, name], stdout=subprocess.DEVNULL)
-        L = C.CDLL(os.path.join(_HERE, name))
+        L = C.CDLL(build(os.environ.get("AZUL_SIMT_OPS_LIB", "libsimt_ops2.so")))      # tests/hostcheck/run_sanitizers.sh: libsimt_ops2_asan.so
         L.sh2_op.restype = C.c_int
         L.sh2_op.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_ulonglong, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_uint] + [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 13
         L.sh2_op_batch.restype = C.c_int
@@ -40,9 +45,7 @@ EXT_DISPLAYS_2P1, EXT_END_BONUS, EXT_SHORT_DEAL, EXT_FINITE_BAG = 1, 2, 4, 8
 def xlib():
     global _xlib
     if _xlib is None:
-        name = os.environ.get("AZUL_SIMT_X_LIB", "libsimt_rules_x.so")
-        subprocess.check_call(["make", "-s", "-C", _HERE, name], stdout=subprocess.DEVNULL)
-        L = C.CDLL(os.path.join(_HERE, name))
+        L = C.CDLL(build(os.environ.get("AZUL_SIMT_X_LIB", "libsimt_rules_x.so")))
         L.shx_op.restype = C.c_int
         L.shx_op.argtypes = [C.c_void_p] + [C.c_int] * 6 + [C.c_ulonglong, C.c_int, C.c_int] + [C.c_void_p] * 5 + [C.c_int] + [C.c_void_p] * 6 + [C.c_uint]
         _xlib = L
@@ -51,7 +54,7 @@ def xlib():
 
 def x_op(rec, players, first, pool, ext, op, action, mt, pos, mask_in=None, want_mask=False, want_flags=False, want_stats=False, want_obs=None,
          margin=0, want_next=False, pos_set=None):
-    """One rule call of the emulated azul_x_op_kernel body on one 256-byte record.  `pool` / `ext`: the ABI's tile_pool and AZUL_RULE_*
+    """One rule call of the emulated azul_x_op_kernel on one 256-byte record.  `pool` / `ext`: the ABI's tile_pool and AZUL_RULE_*
     flags.  Returns a dict: status, mask, flags, stats, obs, action, player, rng_dirty."""
     D = 2 * players + 1 if ext & EXT_DISPLAYS_2P1 else 5
     NA, NOBS = (D + 1) * 30, 5 * D + 6 + 52 * players + 1
@@ -178,7 +181,7 @@ class EmuBackend:
 
 
 class EmuBackendX(EmuBackend):
-    """Three / four players and extended rules (csrc/azul_rules_x.hpp: the body of azul_x_op_kernel under the lockstep wave emulation)
+    """Three / four players and extended rules (csrc/azul_x_kernels.hpp: azul_x_op_kernel under the lockstep wave emulation)
     behind the same interface: 256-byte wide records, Azul's own methods, the sampler, get_state."""
 
     def __init__(self, first_player, tile_pool, players, ext=0):

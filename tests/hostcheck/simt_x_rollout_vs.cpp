@@ -1,8 +1,6 @@
-// simt_x_rollout_vs.cpp -- TEST-ONLY: the window kernel of wide batches with a NETWORK opponent (x_policy_rollout_body<P, D, 2> of
-// csrc/azul_rollout2.hpp, the body of azul_x_policy_rollout_vs_kernel: the agent's pass, then reply rounds on the opponent's weights while
-// any game of the workgroup owes an opponent_move()), UNMODIFIED, as a workgroup of eight emulated wavefronts (simt/simt.hpp:
-// run_workgroup).  The workgroup's LDS is declared here as azul_kernels.hip's wrapper declares it.  Built by
-// tests/test_hostcheck_x_rollout_vs.py with the flags of tests/hostcheck/Makefile.
+// simt_x_rollout_vs.cpp -- TEST-ONLY: the window kernel of wide batches with a NETWORK opponent (azul_x_policy_rollout_vs_kernel of
+// csrc/azul_rollout2.hpp: the agent's pass, then reply rounds on the opponent's weights while any game of the workgroup owes an
+// opponent_move()), UNMODIFIED, as a workgroup of eight emulated wavefronts (simt/simt.hpp: run_workgroup) on the kernel's own LDS.
 #define __HIPCC__ 1
 #include "azul_hip.h"
 #include "azul_common.hpp"
@@ -11,25 +9,15 @@ using namespace az;
 #include "azul_ops2.hpp"
 #include "azul_policy.hpp"
 #include "azul_rollout2.hpp"
+#include "simt_x_common.hpp"
 
 struct XJobVs { azx::XBatchDev b; PolicyWeights W; RolloutArgs a; u32 id_base, max_replies; };
 
 template <u32 P, u32 D>
 static void lane_run(void *arg)
 {
-    __shared__ PXShared<P, D> S;
-    __shared__ PXOpp<D> O;
     XJobVs *j = (XJobVs *)arg;
-    x_policy_rollout_body<P, D, 2>(j->b, j->W, j->a, j->id_base, S, &O, j->max_replies);
-}
-
-typedef void (*lane_fn)(void *);
-static lane_fn pick_fn(int players, int displays)
-{
-#define AZ_CASE(PP, DD) if (players == PP && displays == DD) return lane_run<PP, DD>
-    AZ_CASE(2, 5); AZ_CASE(3, 5); AZ_CASE(3, 7); AZ_CASE(4, 5); AZ_CASE(4, 9);
-#undef AZ_CASE
-    return nullptr;
+    azul_x_policy_rollout_vs_kernel<P, D>(j->b, j->W, j->a, j->id_base, j->max_replies);
 }
 
 extern "C" {
@@ -45,12 +33,11 @@ long long sxv_rollout(int n_games, int players, int displays, uint8_t *state, u3
                       float *entropy, uint8_t *status, i32 *opp_action, float *opp_logp, uint8_t *opp_replies, int opp_slots,
                       unsigned long long seed, unsigned long long opp_seed, unsigned long long counter, int max_replies)
 {
-    lane_fn fn = pick_fn(players, displays);
+    lane_fn fn = SIMT_X_PICK(lane_run, players, displays);
     if (!fn || n_games <= 0 || max_replies < 1) return -1;
     XJobVs j;
     memset(&j, 0, sizeof(j));
-    j.b = {state, mt, mtpos, episodes, stuck, stat_sum, (u32)n_games, AZ_DRAW_MARGIN,
-           {(u32)first_player, (u32)pool, (u32)end_bonus, (u32)short_deal}, nullptr, nullptr};
+    j.b = x_batch(n_games, state, mt, mtpos, episodes, stuck, stat_sum, first_player, pool, end_bonus, short_deal, nullptr);
     j.W = {w[0], w[1], w[2], w[3], w[4], w[5]};
     j.a.n_steps = n_steps; j.a.obs = obs; j.a.mask = mask; j.a.player = player; j.a.action = action; j.a.reward = reward; j.a.done = done;
     j.a.value = value; j.a.logp = logp; j.a.entropy = entropy; j.a.status = status; j.a.seed = seed; j.a.counter = counter;
@@ -58,14 +45,7 @@ long long sxv_rollout(int n_games, int players, int displays, uint8_t *state, u3
     j.a.opp_seed = opp_seed; j.a.opp_action = opp_action; j.a.opp_logp = opp_logp; j.a.opp_replies = opp_replies; j.a.opp_slots = opp_slots;
     j.id_base = id_base;
     j.max_replies = (u32)max_replies;
-    const unsigned blocks = ((unsigned)n_games + PF_GAMES - 1u) / PF_GAMES;
-    simt::g_grid_dim = {blocks, 1, 1};
-    long long ops = 0;
-    for (unsigned blk = 0; blk < blocks; blk++) {
-        simt::g_block_idx = {blk, 0, 0};
-        ops += (long long)simt::run_workgroup(fn, &j, (int)PR2_WAVES);
-    }
-    return ops;
+    return x_launch(fn, &j, ((unsigned)n_games + PF_GAMES - 1u) / PF_GAMES, PR2_WAVES);
 }
 
 }

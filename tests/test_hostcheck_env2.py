@@ -7,22 +7,20 @@ refusal paths (illegal action, out-of-range action, stuck slot).  The same runs 
 Reference: azulnet/game_runner.py:43-97, azulnet/azul.py:296-313, azulnet/nn_runner.py:17-47."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from oracle import oracle as oz
+from tests.hostcheck import hostcheck
 
-HERE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "hostcheck")
 RULES = {"lid_randomfirst": (0, 1), "random_first1": (1, 0), "lid_first2": (2, 1)}      # (first_player code, tile_pool code)
 ST_ILLEGAL, ST_STUCK, ST_BAD_ACTION = 1, 3, 4          # csrc/azul_common.hpp
 
 
 def load(name=None):
     name = name or os.environ.get("AZUL_SIMT_ENV_LIB", "libsimt_env2.so")           # run_sanitizers.sh: the _ubsan / _asan builds
-    subprocess.check_call(["make", "-s", "-C", HERE, name], stdout=subprocess.DEVNULL)
-    L = C.CDLL(os.path.join(HERE, name))
+    L = C.CDLL(hostcheck.build(name))
     L.sh2_rollout_env.restype = C.c_longlong
     L.sh2_rollout_env.argtypes = [C.c_int] + [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_ulonglong, C.c_int, C.c_int] + [C.c_void_p] * 8
     return L

@@ -6,21 +6,19 @@ MFMA, buffer loads, s_barrier) against PyTorch on the CPU: values / logits / log
 global index these kernels form is checked too."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 from tests import training_ring_cases as M
+from tests.hostcheck import hostcheck
 
-HERE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "hostcheck")
 
 
 def load(name=None):
     name = name or os.environ.get("AZUL_SIMT_LEARNER_LIB", "libsimt_learner.so")
-    subprocess.check_call(["make", "-s", "-C", HERE, name], stdout=subprocess.DEVNULL)
-    L = C.CDLL(os.path.join(HERE, name))
+    L = C.CDLL(hostcheck.build(name))
     L.sl_gradients.restype = C.c_longlong
     L.sl_gradients.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 5 + [C.c_float] + [C.c_void_p] * 9
     L.sl_forward.restype = C.c_longlong

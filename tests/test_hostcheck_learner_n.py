@@ -3,30 +3,15 @@ tiles in registers), azul_a2c_reduce_n_kernel and azul_a2c_apply_n_kernel on the
 (tests/hostcheck/simt) -- gradients and loss sums against float64 autograd of the reference's loss (agent.py:39-62) for p3_d5 and
 p4_d9 with several passes per part, a ragged last tile and rows without a legal action; Adam against torch.optim.Adam."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import torch
 
-HERE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "hostcheck")
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(HERE, "libsimt_learner_n.so")
-SIMT_FLAGS = ["-O0", "-g", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fno-omit-frame-pointer", "-fno-optimize-sibling-calls",
-              "-Wall", "-Wno-unused-function", "-Wno-unknown-pragmas", "-Wno-attributes", "-Wno-unused-variable", "-Wno-unused-but-set-variable"]
+from tests.hostcheck import hostcheck
 
 
 def load():
-    src = os.path.join(HERE, "simt_learner_n.cpp")
-    csrc = os.path.join(ROOT, "azul_deep_reinforcement_learning_amd", "csrc")
-    deps = [src, os.path.join(HERE, "simt_a2c_launch.hpp"), os.path.join(csrc, "azul_learner.hpp"), os.path.join(csrc, "azul_policy.hpp"), os.path.join(HERE, "simt", "simt.hpp"),
-            os.path.join(HERE, "simt", "hip", "hip_runtime.h"), os.path.join(ROOT, "include", "azul_hip.h")]
-    if not os.path.exists(LIB) or os.path.getmtime(LIB) < max(os.path.getmtime(d) for d in deps):
-        tmp = LIB + ".%d.tmp" % os.getpid()
-        subprocess.check_call([os.environ.get("CXX", "g++")] + SIMT_FLAGS + ["-I", os.path.join(HERE, "simt"), "-I", csrc, "-I",
-                                                                       os.path.join(ROOT, "include"), "-o", tmp, src])
-        os.replace(tmp, LIB)
-    L = C.CDLL(LIB)
+    L = C.CDLL(hostcheck.build("libsimt_learner_n.so"))
     L.sln_gradients.restype = C.c_longlong
     L.sln_gradients.argtypes = [C.c_int] * 4 + [C.c_void_p] * 5 + [C.c_float] + [C.c_void_p] * 9
     L.sln_gradients_dev.restype = C.c_longlong

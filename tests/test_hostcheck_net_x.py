@@ -13,34 +13,22 @@ index, and the episode / stuck / statistics counters.
 import ctypes as C
 import os
 import random
-import subprocess
 
 import numpy as np
 import pytest
 
 from oracle import oracle as oz
 from tests.mp_net_model import READY, MPNetRunner
-from tests.test_hostcheck_runner_x import SIMT_FLAGS, _craft, ptr
+from tests.test_hostcheck_runner_x import _craft, ptr
 from tests.test_mp_runner_model import parse_key
+from tests.hostcheck import hostcheck
 
-HERE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "hostcheck")
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(HERE, "libsimt_net_x.so")
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "runner_players_net.npz")
 XNET = {"begin": 0, "reply": 1, "reset": 2}
 
 
 def load():
-    src = os.path.join(HERE, "simt_net_x.cpp")
-    csrc = os.path.join(ROOT, "azul_deep_reinforcement_learning_amd", "csrc")
-    deps = [src, os.path.join(csrc, "azul_rules_x.hpp"), os.path.join(csrc, "azul_env2.hpp"), os.path.join(csrc, "azul_selfplay2.hpp"),
-            os.path.join(csrc, "azul_common.hpp"), os.path.join(HERE, "simt", "simt.hpp"), os.path.join(ROOT, "include", "azul_hip.h")]
-    if not os.path.exists(LIB) or os.path.getmtime(LIB) < max(os.path.getmtime(d) for d in deps):
-        tmp = LIB + ".%d.tmp" % os.getpid()
-        subprocess.check_call([os.environ.get("CXX", "g++")] + SIMT_FLAGS + ["-I", os.path.join(HERE, "simt"), "-I", csrc, "-I",
-                                                                       os.path.join(ROOT, "include"), "-o", tmp, src])
-        os.replace(tmp, LIB)
-    L = C.CDLL(LIB)
+    L = C.CDLL(hostcheck.build("libsimt_net_x.so"))
     L.shx_net.restype = C.c_longlong
     L.shx_net.argtypes = [C.c_int] * 3 + [C.c_void_p] * 6 + [C.c_int] * 5 + [C.c_void_p] * 10
     return L

@@ -11,21 +11,19 @@ run_workgroup, s_barrier, MFMA and buffer-load emulation).  Checked per move and
 Under ASan / UBSan (tests/hostcheck/run_sanitizers.sh) every LDS and global index the kernel forms is checked as well."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from oracle import oracle as oz
 from tests.test_hostcheck_env2 import RULES, oracle_play, ptr, start_batch
+from tests.hostcheck import hostcheck
 
-HERE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "hostcheck")
 
 
 def load(name=None):
     name = name or os.environ.get("AZUL_SIMT_ROLLOUT_LIB", "libsimt_rollout2.so")
-    subprocess.check_call(["make", "-s", "-C", HERE, name], stdout=subprocess.DEVNULL)
-    L = C.CDLL(os.path.join(HERE, name))
+    L = C.CDLL(hostcheck.build(name))
     L.sr2_rollout.restype = C.c_longlong
     L.sr2_rollout.argtypes = ([C.c_int] + [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_int, C.c_uint] + [C.c_void_p] * 6 + [C.c_int] + [C.c_void_p] * 11
                               + [C.c_float, C.c_ulonglong, C.c_ulonglong])

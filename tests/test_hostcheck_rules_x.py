@@ -9,23 +9,21 @@ counters, statistics sums.
     oracle's OZ_EXT_* restatement of the rulebook (cross-checked by tests/ext_rules_model.py) is the comparison."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from oracle import oracle as oz
 from tests import wide_stream_cases as W
+from tests.hostcheck import hostcheck
 
-HERE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "hostcheck")
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 XOP = {"query": 0, "init": 1, "new_round": 2, "move": 3, "next_player": 4, "count_score": 5, "step": 6, "random_action": 7, "sample_mask": 8}
 
 
 def load(name=None):
     name = name or os.environ.get("AZUL_SIMT_X_LIB", "libsimt_rules_x.so")        # run_sanitizers.sh: the _ubsan / _asan builds
-    subprocess.check_call(["make", "-s", "-C", HERE, name], stdout=subprocess.DEVNULL)
-    L = C.CDLL(os.path.join(HERE, name))
+    L = C.CDLL(hostcheck.build(name))
     L.shx_selfplay.restype = C.c_longlong
     L.shx_selfplay.argtypes = ([C.c_int] * 3 + [C.c_void_p] * 6 + [C.c_int] * 4 + [C.c_ulonglong, C.c_int, C.c_int, C.c_void_p, C.c_int]
                                + [C.c_void_p] * 6)
@@ -206,6 +204,17 @@ def test_factory_draw_across_a_regeneration_and_through_the_fp64_path(players, e
     check_streams(L, players, oz.FIRST_RANDOM, oz.POOL_LID, ext, n=16, T=40, variant=3, seed0=300, prepare=near_the_end_of_the_state)
     check_streams(L, players, oz.FIRST_RANDOM, oz.POOL_LID, ext, n=4, T=60, variant=3, seed0=310, margin=0x7fffffff)
     check_streams(L, players, oz.FIRST_RANDOM, oz.POOL_LID, ext, n=8, T=30, variant=3, seed0=320, margin=0x7fffffff, prepare=near_the_end_of_the_state)
+
+
+@pytest.mark.parametrize("players,ext,n", [(3, 0, n) for n in (1, 2, 15, 16, 17, 19)] + [(4, oz.EXT_DISPLAYS_2P1, 17)],
+                         ids=lambda v: str(v))
+def test_the_kernels_own_grid_plays_every_game_once(players, ext, n):
+    """azul_x_selfplay_kernel's XCD placement (blockIdx.x -> the wave's pair of games) under the emulation, launched with the true grid of
+    ceil(n / 2) blocks: 1, 1, 8, 8, 9 and 10 blocks -- a grid below eight, exactly eight, and the remainders 1 and 2 of the split over the
+    eight XCDs.  Every game's slots, record, stream and counters equal the oracle's stream of its GLOBAL id (seed0 + g), which holds only if
+    the placement is a permutation that plays each game once.  (4, 9) beside (3, 5): the 51-row and the 31-row sampling table, each in the
+    LDS the kernel itself declares for its shape."""
+    check_streams(load(), players, oz.FIRST_RANDOM, oz.POOL_LID, ext, n=n, T=30, variant=3, seed0=500)
 
 
 # ---- the edges of the wide self-play kernels, stated once in tests/wide_stream_cases.py (the GPU runs the same cases on whole batches:

@@ -11,6 +11,7 @@ index, and the episode / stuck / statistics counters.
 import ctypes as C
 import os
 import random
+import shutil
 import subprocess
 
 import numpy as np
@@ -18,28 +19,14 @@ import pytest
 
 from oracle import oracle as oz
 from tests.mp_runner_model import MPRunner
+from tests.hostcheck import hostcheck
 
-HERE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "hostcheck")
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(HERE, "libsimt_runner_x.so")
-# tests/hostcheck/Makefile's SIMT_FLAGS, restated (-O0: the emulation's reconvergence rule relies on code addresses following source order)
-SIMT_FLAGS = ["-O0", "-g", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fno-omit-frame-pointer", "-fno-optimize-sibling-calls", "-Wall",
-              "-Wno-unused-function", "-Wno-unknown-pragmas", "-Wno-attributes", "-Wno-unused-variable", "-Wno-unused-but-set-variable"]
 XRUN = {"init": 0, "reset": 1, "step": 2, "agent_step": 3, "policy_step": 4, "preview": 5}
 PERSP_MOVER = 7
 
 
 def load():
-    src = os.path.join(HERE, "simt_runner_x.cpp")
-    csrc = os.path.join(ROOT, "azul_deep_reinforcement_learning_amd", "csrc")
-    deps = [src, os.path.join(csrc, "azul_rules_x.hpp"), os.path.join(csrc, "azul_selfplay2.hpp"), os.path.join(csrc, "azul_common.hpp"),
-            os.path.join(HERE, "simt", "simt.hpp"), os.path.join(ROOT, "include", "azul_hip.h")]
-    if not os.path.exists(LIB) or os.path.getmtime(LIB) < max(os.path.getmtime(d) for d in deps):
-        tmp = LIB + ".%d.tmp" % os.getpid()
-        subprocess.check_call([os.environ.get("CXX", "g++")] + SIMT_FLAGS + ["-I", os.path.join(HERE, "simt"), "-I", csrc, "-I",
-                                                                            os.path.join(ROOT, "include"), "-o", tmp, src])
-        os.replace(tmp, LIB)
-    L = C.CDLL(LIB)
+    L = C.CDLL(hostcheck.build("libsimt_runner_x.so"))
     L.shx_runner.restype = C.c_longlong
     L.shx_runner.argtypes = [C.c_int] * 3 + [C.c_void_p] * 6 + [C.c_int] * 5 + [C.c_void_p] * 6 + [C.c_int] + [C.c_void_p] * 3
     return L
@@ -190,3 +177,19 @@ def test_nobody_can_move_gives_done_2(P):
     assert emu.models[0].mask().sum() == 0
     out = emu.run("policy_step", [-1, -1], persp=PERSP_MOVER)
     assert list(out["done"]) == [2, 2] and emu.stuck.sum() == 2
+
+
+def test_a_header_edit_puts_the_shim_out_of_date(tmp_path):
+    """tests/hostcheck/Makefile keeps ONE dependency list for every shim (all of csrc/, include/azul_hip.h, simt/, the shared shim
+    headers).  This file once kept a list of its own that left out csrc/azul_tables.hpp, so an edit there was tested against a stale
+    library.  On a COPY of the tree (nothing of the repository's own is rebuilt): build, touch the header, ask `make -q`."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    for d in ("tests/hostcheck", "azul_deep_reinforcement_learning_amd/csrc", "include"):
+        shutil.copytree(os.path.join(root, d), str(tmp_path / d), ignore=shutil.ignore_patterns("*.so", "*.tmp", "__pycache__"))
+    here, name = str(tmp_path / "tests" / "hostcheck"), "libsimt_runner_x.so"
+    lib = hostcheck.build(name, here)
+    assert os.path.dirname(lib) == here and os.path.exists(lib)
+    assert subprocess.call(["make", "-q", "-C", here, name]) == 0          # up to date
+    stamp = os.path.getmtime(lib) + 2
+    os.utime(str(tmp_path / "azul_deep_reinforcement_learning_amd" / "csrc" / "azul_tables.hpp"), (stamp, stamp))
+    assert subprocess.call(["make", "-q", "-C", here, name]) == 1          # out of date

@@ -7,21 +7,19 @@ definitions, and the same runs under UBSan / ASan (tests/hostcheck/Makefile; the
 Reference: azulnet/game_runner.py:43-55, 76-97; azulnet/azul.py:64-313."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from oracle import oracle as oz
+from tests.hostcheck import hostcheck
 
-HERE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "hostcheck")
 RULES = {"lid_randomfirst": (0, 1), "random_first1": (1, 0), "lid_first2": (2, 1)}      # (first_player code, tile_pool code)
 
 
 def load(name=None):
     name = name or os.environ.get("AZUL_SIMT_LIB", "libsimt_selfplay2.so")        # run_sanitizers.sh: the _ubsan / _asan builds
-    subprocess.check_call(["make", "-s", "-C", HERE, name], stdout=subprocess.DEVNULL)
-    L = C.CDLL(os.path.join(HERE, name))
+    L = C.CDLL(hostcheck.build(name))
     L.sh2_selfplay.restype = C.c_longlong
     L.sh2_selfplay.argtypes = [C.c_int] + [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_ulonglong, C.c_int, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 6
     return L

@@ -12,9 +12,7 @@ workgroup).  Every move of every game is checked against references that share n
 The games start part-way through their episodes (random legal moves on the models first), so that episodes end and restart inside the
 window; the batch of 37 games leaves the last workgroup ragged."""
 import ctypes as C
-import os
 import random
-import subprocess
 
 import numpy as np
 import pytest
@@ -22,27 +20,13 @@ import pytest
 from oracle import oracle as oz
 from tests import policy_draw_ref as pdr
 from tests.mp_runner_model import MPRunner
+from tests.hostcheck import hostcheck
 
-HERE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "hostcheck")
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(HERE, "libsimt_x_rollout.so")
-# tests/hostcheck/Makefile's SIMT_FLAGS, restated (-O0: the emulation's reconvergence rule relies on code addresses following source order)
-SIMT_FLAGS = ["-O0", "-g", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fno-omit-frame-pointer", "-fno-optimize-sibling-calls", "-Wall",
-              "-Wno-unused-function", "-Wno-unknown-pragmas", "-Wno-attributes", "-Wno-unused-variable", "-Wno-unused-but-set-variable"]
 GUARD = 7                      # guard cells past the end of every output array
 
 
 def load():
-    src = os.path.join(HERE, "simt_x_rollout.cpp")
-    csrc = os.path.join(ROOT, "azul_deep_reinforcement_learning_amd", "csrc")
-    deps = [src, os.path.join(HERE, "simt", "simt.hpp"), os.path.join(HERE, "simt", "hip", "hip_runtime.h"), os.path.join(ROOT, "include", "azul_hip.h")]
-    deps += [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".hpp")]
-    if not os.path.exists(LIB) or os.path.getmtime(LIB) < max(os.path.getmtime(d) for d in deps):
-        tmp = LIB + ".%d.tmp" % os.getpid()
-        subprocess.check_call([os.environ.get("CXX", "g++")] + SIMT_FLAGS + ["-I", os.path.join(HERE, "simt"), "-I", csrc, "-I",
-                                                                            os.path.join(ROOT, "include"), "-o", tmp, src])
-        os.replace(tmp, LIB)
-    L = C.CDLL(LIB)
+    L = C.CDLL(hostcheck.build("libsimt_x_rollout.so"))
     L.sxr_rollout.restype = C.c_longlong
     L.sxr_rollout.argtypes = ([C.c_int] * 4 + [C.c_void_p] * 6 + [C.c_int] * 4 + [C.c_uint, C.c_void_p, C.c_int] + [C.c_void_p] * 10
                               + [C.c_ulonglong, C.c_ulonglong])

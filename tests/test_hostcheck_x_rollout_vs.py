@@ -14,9 +14,7 @@ game is checked against references that share no code with the kernel:
 The games start part-way through their episodes, so that episodes end, and the next episodes' openings are played, inside reply rounds; the
 batch of 37 games leaves the last workgroup ragged."""
 import ctypes as C
-import os
 import random
-import subprocess
 
 import numpy as np
 import pytest
@@ -24,25 +22,14 @@ import pytest
 from oracle import oracle as oz
 from tests import policy_draw_ref as pdr
 from tests.mp_net_model import READY, MPNetRunner
-from tests.test_hostcheck_x_rollout import GUARD, SIMT_FLAGS, buf, ptr, weights
+from tests.test_hostcheck_x_rollout import GUARD, buf, ptr, weights
+from tests.hostcheck import hostcheck
 
-HERE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "hostcheck")
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(HERE, "libsimt_x_rollout_vs.so")
 SLOTS = 64                     # trace slots per step: more than any step's reply rounds with legal answers
 
 
 def load():
-    src = os.path.join(HERE, "simt_x_rollout_vs.cpp")
-    csrc = os.path.join(ROOT, "azul_deep_reinforcement_learning_amd", "csrc")
-    deps = [src, os.path.join(HERE, "simt", "simt.hpp"), os.path.join(HERE, "simt", "hip", "hip_runtime.h"), os.path.join(ROOT, "include", "azul_hip.h")]
-    deps += [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".hpp")]
-    if not os.path.exists(LIB) or os.path.getmtime(LIB) < max(os.path.getmtime(d) for d in deps):
-        tmp = LIB + ".%d.tmp" % os.getpid()
-        subprocess.check_call([os.environ.get("CXX", "g++")] + SIMT_FLAGS + ["-I", os.path.join(HERE, "simt"), "-I", csrc, "-I",
-                                                                            os.path.join(ROOT, "include"), "-o", tmp, src])
-        os.replace(tmp, LIB)
-    L = C.CDLL(LIB)
+    L = C.CDLL(hostcheck.build("libsimt_x_rollout_vs.so"))
     L.sxv_rollout.restype = C.c_longlong
     L.sxv_rollout.argtypes = ([C.c_int] * 3 + [C.c_void_p] * 6 + [C.c_int] * 4 + [C.c_uint, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 13
                               + [C.c_int, C.c_ulonglong, C.c_ulonglong, C.c_ulonglong, C.c_int])

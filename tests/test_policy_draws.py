@@ -14,14 +14,13 @@ the (NPL + 4) u sum |z| of zsum.  On the existing tests' regime (randn x 3 logit
 atol 2e-5, rtol 1e-5 (asserted below)."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from tests import policy_draw_ref as R
+from tests.hostcheck import hostcheck
 
-HERE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "hostcheck")
 
 # (seed, counter, id_base): nonzero high key words (the opponent key sample_seed ^ 0x4F50504F4E454E54), counters across the 2^32 carry and
 # the net-opponent paths' 2^64 - 1, a nonzero id_base
@@ -33,8 +32,7 @@ EXTREME_IDS = {0: [174611, 2193503], 1: [2703464, 12026210], 2: [18417450], 3: [
 
 
 def _lib():
-    subprocess.check_call(["make", "-s", "-C", HERE, "libsimt_learner.so"], stdout=subprocess.DEVNULL)
-    L = C.CDLL(os.path.join(HERE, "libsimt_learner.so"))
+    L = C.CDLL(hostcheck.build("libsimt_learner.so"))
     L.sl_head.restype = C.c_longlong
     L.sl_head.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_ulonglong, C.c_ulonglong, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p]
     L.sl_head_n.restype = C.c_longlong
