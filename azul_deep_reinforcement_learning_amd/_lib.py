@@ -20,6 +20,7 @@ POOL_RANDOM, POOL_LID = 0, 1
 FIRST_RANDOM = 0
 PERSP_PLAYER0, PERSP_PLAYER1, PERSP_CURRENT = 0, 1, 2
 PERSP_MOVER = 7
+SCORE_ILLEGAL = -2 ** 31              # AZUL_SCORE_ILLEGAL: azul_batch_score_moves' entry of an action that is not legal
 FLAG_END_OF_ROUND, FLAG_END_OF_GAME, FLAG_ENDED_FLAG = 1, 2, 4
 A2C_FLAT_SIZE = 82082          # k-major flat layout of the parameters / gradient / Adam moments (82081 + 1 pad)
 POLICY_ARGMAX = 0xFFFFFFFFFFFFFFFF        # `seed` value: np.argmax instead of sampling (agent.py action_selection="Max")
@@ -117,6 +118,7 @@ SIGNATURES = {
     "azul_discounted_returns_ring": (_i, [_vp, _vp, _vp, C.c_float, _i, C.c_int64, _i, _i, _vp]),
     "azul_batch_sample_mask": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "azul_batch_score_preview": (_i, [_vp, _vp, _vp]),
+    "azul_batch_score_moves": (_i, [_vp, _i, _vp, _vp, _vp, _vp]),
     "azul_batch_mp_runner_init": (_i, [_vp, _vp, _vp, _vp]),
     "azul_batch_mp_runner_reset": (_i, [_vp, _vp, _vp, _vp]),
     "azul_batch_mp_runner_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),

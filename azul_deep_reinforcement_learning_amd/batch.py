@@ -308,6 +308,27 @@ class BatchedAzul:
         L.check(L.lib.azul_batch_score_preview(self._h, _ptr(p), self._stream()))
         return p
 
+    def score_moves(self, perspective=L.PERSP_CURRENT, active=None, scores=None, best=None):
+        """The one-ply table of GameRunner.step's reward in one launch, the games untouched: scores [N][180] int32, for every legal
+        action score[p] - score[1 - p] after move + count_score on a copy of the game (game_runner.py:48-50; p = `perspective`: 0, 1 or
+        PERSP_CURRENT, the player to move), L.SCORE_ILLEGAL elsewhere; best [N] int32, the first legal action with the maximal score
+        (-1: nothing is legal).  `scores` / `best`: preallocated device tensors to write into; rows of games whose `active` is 0 are
+        not written (fresh outputs start as SCORE_ILLEGAL / -1).  Two-player reference batches only.  Returns (scores, best)."""
+        if scores is None:
+            scores = torch.full((self.n, L.NUM_ACTIONS), L.SCORE_ILLEGAL, dtype=torch.int32, device=self.device)
+        if best is None:
+            best = torch.full((self.n,), -1, dtype=torch.int32, device=self.device)
+        L.check(L.lib.azul_batch_score_moves(self._h, int(perspective), _ptr(self._dev(active, torch.uint8)), _ptr(scores), _ptr(best),
+                                             self._stream()))
+        return scores, best
+
+    def greedy_action(self, active=None, out=None):
+        """The one-ply greedy player of the reference's reward: for every game the move that maximises the mover's score difference after
+        move + count_score (score_moves' `best` from the mover's perspective; -1: nothing is legal).  `out`: a preallocated int32 [N]."""
+        best = torch.full((self.n,), -1, dtype=torch.int32, device=self.device) if out is None else out
+        L.check(L.lib.azul_batch_score_moves(self._h, L.PERSP_CURRENT, _ptr(self._dev(active, torch.uint8)), None, _ptr(best), self._stream()))
+        return best
+
     # -- policy-driven self-play (config 3) ----------------------------------------------------------
     def observe_all(self, perspective=L.PERSP_CURRENT, obs=None, mask=None, player=None):
         obs = self._new((self.n, self.obs_size), torch.float32) if obs is None else obs

@@ -989,6 +989,25 @@ int azul_batch_score_preview(azul_batch_t *b, int32_t *potential_dev, void *stre
     return launch_op(b, a, stream);
 }
 
+// every legal move's what-if score difference and the greedy choice (azul_ops2.hpp: score_moves_body2): one launch, the games are only read
+int azul_batch_score_moves(azul_batch_t *b, int perspective, const uint8_t *active_dev, int32_t *scores_dev, int32_t *best_dev, void *stream)
+{
+    BATCH_GUARD(b, stream);
+    if (!b) return fail(AZUL_ERR_INVALID, "batch is NULL");
+    if (b->x) return fail(AZUL_ERR_INVALID, "azul_batch_score_moves: a wide batch (three / four players or extended rules): the table is the "
+                                            "two-player reward of game_runner.py:48-50, two-player reference batches only");
+    if (!scores_dev && !best_dev) return fail(AZUL_ERR_INVALID, "azul_batch_score_moves: scores_dev and best_dev are both NULL");
+    if (perspective != AZUL_PERSP_PLAYER0 && perspective != AZUL_PERSP_PLAYER1 && perspective != AZUL_PERSP_CURRENT)
+        return fail(AZUL_ERR_INVALID, "azul_batch_score_moves: perspective must be 0, 1 or AZUL_PERSP_CURRENT");
+    ScoreMovesArgs a;
+    a.active = active_dev; a.scores = scores_dev; a.best = best_dev; a.persp = perspective;
+    const dim3 grid((b->d.n + 1u) / 2u), block(64);
+    if (b->d.rules.tile_pool == POOL_LID) hipLaunchKernelGGL(azul_score_moves_kernel<true>, grid, block, 0, (hipStream_t)stream, b->d, a);
+    else hipLaunchKernelGGL(azul_score_moves_kernel<false>, grid, block, 0, (hipStream_t)stream, b->d, a);
+    HIP_TRY(hipGetLastError());
+    return AZUL_SUCCESS;
+}
+
 // ---- GameRunner for P seats (azul_rules_x.hpp: runner_body_x): the azul_batch_mp_* entries ------------------------------------------------------
 // One launch over the whole batch, no host synchronisation, no allocation: capturable in a HIP graph.  Wide batches only; a two-player
 // reference batch is refused with the name of its own entry (`twin`).

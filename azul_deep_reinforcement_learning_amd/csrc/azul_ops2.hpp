@@ -271,3 +271,86 @@ AZ_FN void op_body2(const BatchDev &b, const OpArgs &a, u32 pair, u32 (*mt_lds)[
     }
     if (a.player && l == 0u) a.player[oi] = (uint8_t)g.cur;
 }
+
+// ---- azul_score_moves_kernel's body: THE ONE-PLY TABLE OF THE REFERENCE'S OWN REWARD ----------------------------------------------------------
+// For every legal action a of every game, score[p] - score[1 - p] of a copy of the game after move(*nn_deserialize(a)) and count_score() -- the
+// quantity whose change GameRunner.step pays out (game_runner.py:48-50: deepcopy + count_score) -- and the first action that maximises it
+// (np.argmax's rule).  On the rule book above (g2_load, prime2, legal_mask2, action_code2, do_move2): the rule code the other kernels run, not
+// a restatement.  The games are only read: no record, MT19937 word or counter is written, so the body stages no RNG state and no sampler
+// table and uses no LDS.  Reference lines: move azulnet/azul.py:118-161 (the unchecked move: no next_player, no new round, no draw),
+// count_score :192-295, the reward azulnet/game_runner.py:48-50, check_all_valid :113-117.
+struct ScoreMovesArgs {
+    const uint8_t *active;   // [n] in, optional: games with 0 are not looked at and their rows are not written
+    i32 *scores;             // [n][180] out, optional: the table; AZUL_SCORE_ILLEGAL where the legal mask holds 0
+    i32 *best;               // [n] out, optional: first legal action with the maximal score, -1 when nothing is legal
+    int persp;               // 0, 1 or AZUL_PERSP_CURRENT (the player to move)
+};
+
+namespace az2 {
+
+constexpr i32 SCORE_ILLEGAL = (i32)0x80000000u;      // AZUL_SCORE_ILLEGAL (INT32_MIN)
+
+// (score, lowest action) as ONE unsigned key for the half-wave maximum: a score difference lies in (-2^16, 2^16) -- both what-if scores
+// are clamped at 0 and stay below 2^16 (the record keeps scores in 16 bits; the full lines of one round add at most 5 * 29 points) -- so
+// score + 2^16 is a positive 17-bit number; below it 255 - a, so that among equal scores the LOWEST action is the maximum.  0 = no move.
+AZ_FN u32 score_key(i32 score, u32 a) { return ((u32)(score + 65536) << 8) | (255u - a); }
+
+// The table of games 2 pair and 2 pair + 1.  Lane l < 30 of a half keeps the six results of ITS actions l, 30 + l, .. 150 + l in six named
+// registers, as Mask2 keeps the mask rows, and writes them as the mask rows are written.
+// The candidate loop is wave-uniform: 180 trips, a candidate neither half's mask holds is skipped by a ballot (no per-lane branch).  A
+// candidate that only ONE half's mask holds still runs on both: do_move2f is total for every action number -- the source lane, display
+// base, colour (< 5) and row (< 6) it shifts and gathers by are decoded from the ACTION (K2::lcode), never from the state, the gathers stay
+// inside the half, and the state only enters sums, compares and selects -- and the half whose mask lacks the candidate discards the result.
+// Each candidate starts from the loaded game again (`t = g`): a move changes only the mover's line, floor and the source cells, so the
+// copy is those few registers, not a second live game.
+template <bool LID>
+AZ_FN void score_moves_body2(const BatchDev &b, const ScoreMovesArgs &a, u32 pair)
+{
+    const u32 lane = wv::lane(), l = lane & 31u, half = lane >> 5;
+    const u32 gi = 2u * pair + half;
+    if (gi >= b.n) return;                           // odd batch: the last wave serves one game
+    if (a.active && a.active[gi] == 0) return;
+    K2 k;
+    k2_init(k);
+    G2 g;
+    g2_load(g, b.state + (size_t)gi * AZUL_RECORD_BYTES, l);
+    prime2(g, k);
+    Mask2 m;
+    legal_mask2(g, k, m);
+    const u32 me = me2(g);
+    const u32 p = a.persp == AZUL_PERSP_CURRENT ? me : (u32)a.persp;
+    const i32 sign = p == me ? 1 : -1;
+    const i32 base = (me ? g.score1 : g.score0), other = (me ? g.wi0 : g.wi1);       // the opponent's what-if score: a move leaves it alone
+    const u32 wall = me ? g.wall1 : g.wall0;
+    i32 s0 = SCORE_ILLEGAL, s1 = SCORE_ILLEGAL, s2 = SCORE_ILLEGAL, s3 = SCORE_ILLEGAL, s4 = SCORE_ILLEGAL, s5 = SCORE_ILLEGAL;
+    u32 key = 0;
+#pragma unroll 1
+    for (u32 row = 0; row < 6u; row++) {
+        const u32 word = row == 0u ? m.m[0] : row == 1u ? m.m[1] : row == 2u ? m.m[2] : row == 3u ? m.m[3] : row == 4u ? m.m[4] : m.m[5];
+#pragma unroll 1
+        for (u32 ln = 0; ln < 30u; ln++) {
+            const bool legal = ((word >> ln) & 1u) != 0u;
+            if (!wave_any(legal)) continue;
+            const u32 act = 30u * row + ln;
+            G2 t = g;
+            do_move2<LID>(t, action_code2(act, k), g.B, k);                                            // azul.py:118-161
+            const i32 wc = wall_points2(wall, full_lines2(me ? t.cp1 : t.cp0, k), k);                  // :211-290, nothing committed
+            const i32 wi = clamp0(base + floor_penalty(me ? t.floor1 : t.floor0) + wc);                // :200-209, :292-295
+            const i32 v = sign * (wi - other);
+            const bool mine = legal & (l == ln);
+            s0 = (mine & (row == 0u)) ? v : s0; s1 = (mine & (row == 1u)) ? v : s1; s2 = (mine & (row == 2u)) ? v : s2;
+            s3 = (mine & (row == 3u)) ? v : s3; s4 = (mine & (row == 4u)) ? v : s4; s5 = (mine & (row == 5u)) ? v : s5;
+            key = mine ? umax(key, score_key(v, act)) : key;
+        }
+    }
+    if (a.scores && l < 30u) {
+        i32 *out = a.scores + (size_t)gi * AZUL_NUM_ACTIONS + l;
+        out[0] = s0; out[30] = s1; out[60] = s2; out[90] = s3; out[120] = s4; out[150] = s5;
+    }
+    if (a.best) {
+        const u32 top = hmax(key);                   // (lanes 30, 31 and a half without a game hold / read 0)
+        if (l == 0u) a.best[gi] = top ? (i32)(255u - (top & 0xffu)) : -1;
+    }
+}
+
+} // namespace az2

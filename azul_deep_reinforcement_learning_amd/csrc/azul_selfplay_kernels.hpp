@@ -25,6 +25,14 @@ __global__ void __launch_bounds__(64) azul_op_kernel(BatchDev b, OpArgs a)
     op_body2<LID>(b, a, blockIdx.x, mt_lds, tabfs_lds, obs_lds);
 }
 
+// Every legal move's what-if score difference and the greedy choice (azul_ops2.hpp: score_moves_body2), the games untouched:
+// grid = ceil(n / 2) one-wave workgroups, two games per wavefront; no workgroup looks at another's games
+template <bool LID>
+__global__ void __launch_bounds__(64) azul_score_moves_kernel(BatchDev b, ScoreMovesArgs a)
+{
+    az2::score_moves_body2<LID>(b, a, blockIdx.x);
+}
+
 // Discounted returns over the time-major trajectory of one launch window (reference loop: nn_runner.py:70-76,
 // qval = reward + gamma * qval backwards within an episode).  One thread per game walks its column backwards;
 // `done[t][g] != 0` ends an episode at move t; `carry[g]` holds the return flowing in from the NEXT window

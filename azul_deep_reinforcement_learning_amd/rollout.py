@@ -58,6 +58,12 @@ class PolicyRollout:
         inside the window kernel (matrix phases on the second weight set while any game of a workgroup owes a reply); otherwise one launch
         per cut of the protocol and one host synchronisation per reply round (no HIP graph).  `opponent_trace` = R > 0 also records the
         opponent's answers: opp_action / opp_logp [T][R][N], opp_replies [T][N].
+        opponent="greedy" (two-player reference batches only; anything else raises ValueError): the scripted one-ply greedy player of the
+        reference's own reward on the same per-cut protocol -- every opponent_move() (replies, player 1's forced moves, the openings of
+        reset()) is BatchedAzul.greedy_action's answer, the move that maximises the mover's score difference after move + count_score
+        (game_runner.py:48-50), one launch per reply round in place of the network's forward; records as with "random"; `opponent_trace`
+        records opp_action (opp_logp stays 0) and opp_replies; persistent and use_graph resolve to False, ring to 1; at most MAX_REPLY_ROUNDS
+        reply rounds per step or opening (a game with nothing legal would owe its move for ever: RuntimeError).
         `move_limit` > 0 (beyond the reference, off by default): cut an episode at the first end of a round with move_counter >= move_limit
         (done = 3) -- under the reference's rules some games never end and would keep their slot for ever (BatchedAzul.set_move_limit).
         `seed_base` / `game_id_base`: game i of this rollout is global game game_id_base + i (default: seed_base, so that a rank
@@ -130,6 +136,9 @@ class PolicyRollout:
                 raise ValueError("a network opponent for batches of %d players / extended rules must take the batch's observation and give its "
                                  "actions: ActorCritic(%d, %d, any hidden size), got inputs %d / %d and %d actions"
                                  % (self.players, n_obs, n_act, shape[0], shape[1], shape[2]))
+        if isinstance(opponent, str) and opponent == "greedy" and self.wide:
+            raise ValueError("opponent=\"greedy\" maximises the two-player reward of game_runner.py:48-50: two-player reference batches only, "
+                             "not %d players / extended rules" % self.players)
         if self.wide and move_limit:
             raise ValueError("no move limit for batches of three / four players or extended rules")
         self.fused_wide = bool(fused_wide)
@@ -162,25 +171,26 @@ class PolicyRollout:
         self.opp_policy = None
         if net:
             self.opp_policy, opponent = opponent, "net"
-        assert opponent in (None, "random", "net")
+        assert opponent in (None, "random", "net", "greedy")
         self.opponent = opponent
+        self.cut = opponent in ("net", "greedy")               # GameRunner.step cut at its opponent_move() calls (BatchedAzul.net_*)
         self.fused_head = fused_head
         # the one-launch forward (azul_policy_forward) is compiled for the reference's ActorCritic(136, 180, hidden 180)
         self.fused_mlp = bool(fused_mlp and fused_head and not self.wide and policy.critic_linear1.in_features == L.OBS_SIZE and
                               policy.critic_linear1.out_features == 180 and policy.actor_linear2.out_features == L.NUM_ACTIONS)
         # persistent=True: the whole window runs in ONE launch per part (azul_batch_policy_rollout); same results
-        self.persistent = bool(persistent and self.fused_mlp)
+        self.persistent = bool(persistent and self.fused_mlp and self.opponent != "greedy")
         self.ring = int(ring) if self.persistent else (int(wide_ring) if self.fused_wide else 1)
         assert self.ring >= 1
         # Agent.get_ac_output's two modes (agent.py:64-72): sample from the masked softmax, or take its first maximum
         assert action_selection in ("Distribution", "Max") and (fused_head or action_selection == "Distribution")
         self.action_selection = action_selection
         assert opponent_selection in ("Distribution", "Max")
-        self.opp_slots = int(opponent_trace) if self.opponent == "net" else 0
+        self.opp_slots = int(opponent_trace) if self.cut else 0
         assert self.opponent != "net" or self.fused_mlp or self.wide, \
             "the network opponent runs on the library's forward (ActorCritic(136, 180, hidden 180))"
         # one launch per window needs no graph; reply rounds are data-dependent (a capture that fails clears the flag again)
-        self.use_graph = bool(use_graph and not self.persistent and not self.fused_wide and self.opponent != "net")
+        self.use_graph = bool(use_graph and not self.persistent and not self.fused_wide and not self.cut)
 
     def _stage_weights(self, kweights):
         """The k-major weight copies the kernels and GEMMs read.  kweights: tensors owned by someone else (A2CLearner.kweights(): views of
@@ -220,7 +230,7 @@ class PolicyRollout:
               "done": torch.zeros(R, h, dtype=torch.uint8, device=d),
               "value": torch.zeros(R, h, 1, device=d), "log_prob": torch.zeros(R, h, device=d), "entropy": torch.zeros(R, h, device=d),
               "returns": torch.zeros(R, h, device=d), "carry": torch.zeros(h, device=d)}
-        if self.opponent == "net":
+        if self.cut:
             rg["opp_replies"] = torch.zeros(R, h, dtype=torch.uint8, device=d)
             if self.opp_slots:
                 rg["opp_action"] = torch.full((R, self.opp_slots, h), -1, dtype=torch.int32, device=d)
@@ -230,7 +240,7 @@ class PolicyRollout:
         w = {"hidden": torch.zeros(h, 2 * self.H, device=d), "logits": torch.zeros(h, env.num_actions, device=d),
              "status": torch.zeros(h, dtype=torch.uint8, device=d),
              "counter": torch.tensor([0, 0], dtype=torch.int64, device=d)}     # [0] Philox step counter, [1] launch ticket
-        if self.opponent == "net":
+        if self.cut:
             w["net"] = env.net_state()
             w["scratch_f"] = torch.zeros(3, h, device=d)       # the opponent forward's value / entropy (not recorded) and untraced log-prob
             if self.wide:                                      # the opponent's actor half as PyTorch GEMMs (its own hidden size)
@@ -239,8 +249,8 @@ class PolicyRollout:
         self.traj.append(t)
         self.work.append(w)
         with torch.cuda.stream(self.streams[p]):
-            if self.opponent == "net":
-                self._net_reset(p)                             # GameRunner.reset(): the network opponent opens when it starts
+            if self.cut:
+                self._net_reset(p)                             # GameRunner.reset(): the network / greedy opponent opens when it starts
             env.observe_all(self._persp(), t["obs"][T], t["mask"][T], t["player"][T])     # becomes slot 0 of the first window
 
     def _window_views(self, rg, w):
@@ -253,7 +263,7 @@ class PolicyRollout:
         return out
 
     def _persp(self):
-        return 0 if self.opponent in ("random", "net") else L.PERSP_CURRENT     # NNRunner observes with perspective 0 (game_runner.py:56)
+        return 0 if self.opponent in ("random", "net", "greedy") else L.PERSP_CURRENT     # NNRunner observes with perspective 0 (game_runner.py:56)
 
     def _stage(self, get, prefix, names):
         """The k-major copies `names` of the reference's four layers (`get`: parameter name -> tensor) as attributes prefix + name,
@@ -282,6 +292,10 @@ class PolicyRollout:
         what net_step_* left in work["net"], reply j of the step sampled with Philox key opponent_seed + j at the step's counter."""
         w = self.work[p]
         net, sc = w["net"], w["scratch_f"]
+        if self.opponent == "greedy":
+            # the scripted opponent: the best move of every game that owes one, from the mover's perspective (azul_batch_score_moves)
+            self.envs[p].greedy_action(active=net["pending"], out=net["action"])
+            return
         key = self.opponent_seed if self.opponent_seed == L.POLICY_ARGMAX else (self.opponent_seed + j) & 0xFFFFFFFFFFFFFFFF
         if self.wide:
             # forward_actor (model.py:28-41) on the mover-perspective observations net_step_* left; the head samples at the same counter as
@@ -310,7 +324,7 @@ class PolicyRollout:
         env.net_reset_begin(w["net"], w["status"])
         j = 0
         while int(w["net"]["owing"].item()) > 0:
-            if self.wide and j >= self.MAX_REPLY_ROUNDS:
+            if (self.wide or self.opponent == "greedy") and j >= self.MAX_REPLY_ROUNDS:
                 self._reply_loop_failed(p, j, "the opening of reset()")
             self._opp_forward(p, j, w["scratch_f"][2])
             env.net_step_reply(w["net"]["action"], w["net"], None, None, w["status"])
@@ -321,9 +335,10 @@ class PolicyRollout:
         owing = torch.nonzero(net["pending"]).flatten().cpu().tolist()
         st = self.work[p]["status"].cpu()
         ids = [self.game_id_base + p * self.h + i for i in owing]
-        raise RuntimeError("network opponent: games %s (global ids) still owe an opponent_move() after %d reply rounds of %s (round %d); "
-                           "statuses %s -- the opponent keeps answering with moves that are not legal (a forward that is not finite answers -1)"
-                           % (ids[:16], rounds, where, rounds, [int(st[i]) for i in owing[:16]]))
+        raise RuntimeError("%s opponent: games %s (global ids) still owe an opponent_move() after %d reply rounds of %s (round %d); "
+                           "statuses %s -- the opponent keeps answering with moves that are not legal (a forward that is not finite, or a "
+                           "state with nothing legal, answers -1)"
+                           % ("greedy" if self.opponent == "greedy" else "network", ids[:16], rounds, where, rounds, [int(st[i]) for i in owing[:16]]))
 
     def refresh_weights(self):
         """(Re)build the fused first-layer weights from the policy's parameters -- call after every optimiser step.  The
@@ -395,14 +410,14 @@ class PolicyRollout:
 
     def _env_step(self, p, t):
         env, tr, w = self.envs[p], self.traj[p], self.work[p]
-        if self.opponent == "net":
+        if self.cut:
             # GameRunner.step cut at its opponent_move() calls: the agent's move, then reply rounds while any game owes one (one host
             # synchronisation per round: this is the per-move reference structure, the window kernel is the fast path)
             net = w["net"]
             env.net_step_begin(tr["action"][t], net, tr["reward"][t], tr["done"][t], w["status"])
             j = 0
             while int(net["owing"].item()) > 0:
-                if self.wide and j >= self.MAX_REPLY_ROUNDS:
+                if (self.wide or self.opponent == "greedy") and j >= self.MAX_REPLY_ROUNDS:
                     self._reply_loop_failed(p, j, "agent step %d of the window" % t)
                 self._opp_forward(p, j, tr["opp_logp"][t][j] if j < self.opp_slots else w["scratch_f"][2])
                 if j < self.opp_slots:

@@ -43,7 +43,9 @@ class BatchedTrainer:
         exactly once (episodes straddle windows; an episode may span ring - 1 window boundaries), like NNRunner.train.
         opponent: "random" (GameRunner's default RandomAgent, the reference's scripts/training.py), a module (GameRunner(opponent=Agent(...)),
         game_runner.py:27-30: a frozen second net inside the rollout kernel), or "self": a frozen COPY of the policy that is replaced by the
-        current policy every `opponent_refresh` updates (0: never) -- training against a past self.
+        current policy every `opponent_refresh` updates (0: never) -- training against a past self; or "greedy" (two-player reference batches):
+        PolicyRollout's scripted one-ply greedy player of the reward, on the per-cut path (no window kernel, ring 1: the learner takes
+        update_from_windows; the opponent has no state, so checkpoints carry nothing for it).
         move_limit > 0: BatchedAzul.set_move_limit (beyond the reference: a game that would never end is cut, done = 3; its steps are trained like an
         episode that ended there, the return chain starts at the cut).
         players = 3 / 4 (or extended-rule keys in `rules`): PolicyRollout(players=...) on MultiplayerAzul parts -- the policy is

@@ -201,6 +201,17 @@ int azul_batch_random_action(azul_batch_t *b, const uint8_t *active_dev, int32_t
 int azul_batch_sample_mask(azul_batch_t *b, const uint8_t *mask_dev /*[N][180]*/, const uint8_t *active_dev,
                            int32_t *actions_dev, void *stream);
 int azul_batch_score_preview(azul_batch_t *b, int32_t *potential_dev /*[N]*/, void *stream);   /* deepcopy+count_score, score[0]-score[1]  game_runner.py:48-50 */
+/* The one-ply table of that reward, for every legal move of every game in ONE launch, the games untouched (records, MT19937 words and
+ * index, counters).  With p = `perspective` (0, 1, or AZUL_PERSP_CURRENT: the player to move) and a an action azul_batch_legal_mask marks 1:
+ * scores[g][a] = score[p] - score[1 - p] of a copy of game g after move(*nn_deserialize(a)) (azul.py:118-161, the unchecked move: no
+ * next_player, no new round, no draw) and count_score() on that copy (azul.py:192-295) -- what GameRunner.step's deepcopy + count_score
+ * evaluates (game_runner.py:48-50).  Any other a: AZUL_SCORE_ILLEGAL.  best[g]: the first legal action, in action order, with the maximal
+ * score (np.argmax's rule); -1 when nothing is legal (an ended game, every source empty).  active_dev (optional): rows of games with 0
+ * are not written at all.  scores_dev and best_dev are each optional, not both.  AZUL_ERR_INVALID before any launch: both outputs NULL, a
+ * perspective outside {0, 1, AZUL_PERSP_CURRENT}, a wide batch (three / four players or extended rules). */
+#define AZUL_SCORE_ILLEGAL INT32_MIN
+int azul_batch_score_moves(azul_batch_t *b, int perspective, const uint8_t *active_dev, int32_t *scores_dev /*[N][180], optional*/,
+                           int32_t *best_dev /*[N], optional*/, void *stream);
 
 /* ---- GameRunner for P players: batches of 3 / 4 players and extended-rule batches (wide records) ------------------------------
  * The reference's GameRunner (game_runner.py:23-97) on an Azul(players = P): the agent is seat 0 ("player 1"), every other seat answers
