@@ -101,6 +101,7 @@ SIGNATURES = {
     "azul_batch_policy_rollout_returns": (_i, [_vp, _i, _i] + [_vp] * 6 + [_i, _i, _i, _u64, _u64, _vp] + [_vp] * 10 + [_vp, C.c_float, _vp]),
     "azul_batch_policy_rollout_vs": (_i, [_vp, _i, C.POINTER(NetWeights), C.POINTER(NetWeights), _i, _i, _i, _u64, _u64, _u64, _vp,
                                           C.POINTER(RolloutBuffers), C.c_float, _vp]),
+    "azul_batch_policy_rollout_greedy": (_i, [_vp, _i, C.POINTER(NetWeights), _i, _i, _i, _u64, _u64, _vp, C.POINTER(RolloutBuffers), C.c_float, _vp]),
     "azul_batch_mp_policy_rollout": (_i, [_vp, _i, _i, C.POINTER(NetWeights), _i, _i, _i, _u64, _u64, _vp, C.POINTER(RolloutBuffers), C.c_float, _vp]),
     "azul_batch_mp_policy_rollout_vs": (_i, [_vp, _i, C.POINTER(NetWeights), C.POINTER(NetWeights), _i, _i, _i, _u64, _u64, _u64, _vp, _i,
                                              C.POINTER(RolloutBuffers), C.c_float, _vp]),

@@ -373,4 +373,49 @@ AZ_FN void net_reset2(G2 &g, Mask2 &m, u32 first_player, Rng2 &r, u64 margin, Co
     net_settle2<LID>(g, ns, m, first_player, r, margin, cnt, k);
 }
 
+// ---- the one-ply greedy player of the reference's own reward (game_runner.py:48-50; azul_ops2.hpp: score_moves_body2's table) ----------------
+// (score, lowest action) as ONE unsigned key for the half-wave maximum: a score difference lies in (-2^16, 2^16) -- both what-if scores
+// are clamped at 0 and stay below 2^16 (the record keeps scores in 16 bits; the full lines of one round add at most 5 * 29 points) -- so
+// score + 2^16 is a positive 17-bit number; below it 255 - a, so that among equal scores the LOWEST action is the maximum.  0 = no move.
+AZ_FN u32 score_key(i32 score, u32 a) { return ((u32)(score + 65536) << 8) | (255u - a); }
+
+// The mover's what-if score after candidate `act`: score[me] of a copy of the game after move(*nn_deserialize(act)) and count_score()
+// (azul.py:118-161, :192-295; nothing committed).  Total for every action number: do_move2 decodes the source lane, display base, colour
+// and row from the ACTION (K2::lcode), never from the state.  Each candidate starts from the game again (`t = g`): a move changes only the
+// mover's line, floor and the source cells, so the copy is those few registers, not a second live game.
+template <bool LID>
+AZ_FN i32 whatif_after2(const G2 &g, u32 act, u32 me, const K2 &k)
+{
+    G2 t = g;
+    do_move2<LID>(t, action_code2(act, k), g.B, k);                                                   // azul.py:118-161
+    const i32 wc = wall_points2(me ? g.wall1 : g.wall0, full_lines2(me ? t.cp1 : t.cp0, k), k);       // :211-290
+    return clamp0((me ? g.score1 : g.score0) + floor_penalty(me ? t.floor1 : t.floor0) + wc);        // :200-209, :292-295
+}
+
+// The greedy player's answer on a register-resident game and its legal mask `m`, from the MOVER's perspective: the first legal action
+// with the maximal score[p] - score[1 - p] after move + count_score (np.argmax's rule), -1 when nothing is legal.  Reads the game only;
+// draws nothing.  The candidate loop is wave-uniform (a candidate neither half's mask holds is skipped by a ballot; one that only ONE
+// half's mask holds runs on both and the other half discards it): call it with the whole wave active.
+template <bool LID>
+AZ_FN i32 greedy_pick2(const G2 &g, const Mask2 &m, const K2 &k)
+{
+    const u32 me = me2(g);
+    const i32 other = me ? g.wi0 : g.wi1;                // the opponent's what-if score: a move leaves it alone
+    u32 key = 0;
+#pragma unroll 1
+    for (u32 row = 0; row < 6u; row++) {
+        const u32 word = row == 0u ? m.m[0] : row == 1u ? m.m[1] : row == 2u ? m.m[2] : row == 3u ? m.m[3] : row == 4u ? m.m[4] : m.m[5];
+#pragma unroll 1
+        for (u32 ln = 0; ln < 30u; ln++) {
+            const bool legal = ((word >> ln) & 1u) != 0u;
+            if (!wave_any(legal)) continue;
+            const u32 act = 30u * row + ln;
+            const i32 v = whatif_after2<LID>(g, act, me, k) - other;
+            key = (legal & (k.l == ln)) ? umax(key, score_key(v, act)) : key;
+        }
+    }
+    const u32 top = hmax(key);                           // (lanes 30, 31 hold 0)
+    return top ? (i32)(255u - (top & 0xffu)) : -1;
+}
+
 } // namespace az2

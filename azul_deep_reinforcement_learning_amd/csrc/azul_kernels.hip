@@ -687,11 +687,13 @@ static int launch_rollout(azul_batch_t *b, const PolicyWeights &W, const Rollout
     const bool lid = b->d.rules.tile_pool == POOL_LID;
     const dim3 grid2((b->d.n + PF_GAMES - 1) / PF_GAMES), block2(64 * PR2_WAVES);
     if (lid) {
-        if (opp == 2) hipLaunchKernelGGL((azul_policy_rollout2_kernel<true, 2>), grid2, block2, 0, st, b->d, W, a);
+        if (opp == 3) hipLaunchKernelGGL((azul_policy_rollout2_kernel<true, 3>), grid2, block2, 0, st, b->d, W, a);
+        else if (opp == 2) hipLaunchKernelGGL((azul_policy_rollout2_kernel<true, 2>), grid2, block2, 0, st, b->d, W, a);
         else if (opp == 1) hipLaunchKernelGGL((azul_policy_rollout2_kernel<true, 1>), grid2, block2, 0, st, b->d, W, a);
         else hipLaunchKernelGGL((azul_policy_rollout2_kernel<true, 0>), grid2, block2, 0, st, b->d, W, a);
     } else {
-        if (opp == 2) hipLaunchKernelGGL((azul_policy_rollout2_kernel<false, 2>), grid2, block2, 0, st, b->d, W, a);
+        if (opp == 3) hipLaunchKernelGGL((azul_policy_rollout2_kernel<false, 3>), grid2, block2, 0, st, b->d, W, a);
+        else if (opp == 2) hipLaunchKernelGGL((azul_policy_rollout2_kernel<false, 2>), grid2, block2, 0, st, b->d, W, a);
         else if (opp == 1) hipLaunchKernelGGL((azul_policy_rollout2_kernel<false, 1>), grid2, block2, 0, st, b->d, W, a);
         else hipLaunchKernelGGL((azul_policy_rollout2_kernel<false, 0>), grid2, block2, 0, st, b->d, W, a);
     }
@@ -710,7 +712,8 @@ static int fail_in(const char *who, const char *what)
 
 // The one host path of a window launch: every azul_batch_[mp_]policy_rollout* entry packs its arguments and calls this.  `wide` = an _mp_
 // entry (the azul_x_* kernels), otherwise the two-player kernel; opp = 0 the policy moves for every seat, 1 RandomAgent seats, 2 the
-// `opponent` net.  Where the two families differ the condition says so: those differences are behaviour (include/azul_hip.h).
+// `opponent` net, 3 the one-ply greedy player (two-player kernel only).  Where the two families differ the condition says so: those
+// differences are behaviour (include/azul_hip.h).
 static int rollout_window(azul_batch_t *b, const char *who, bool wide, int n_steps, int opp, const azul_net_weights_t *agent,
                           const azul_net_weights_t *opponent, NetShape shape, DrawKeys keys, const azul_rollout_buffers_t *out, float gamma,
                           int max_replies, void *stream)
@@ -718,6 +721,9 @@ static int rollout_window(azul_batch_t *b, const char *who, bool wide, int n_ste
     const bool net = opp == 2;
     if (!b || n_steps < 0 || !agent || !out) return fail_in(who, "bad arguments");
     if (net && !opponent) return fail_in(who, "no opponent (the entry without _vs plays without one)");
+    if (opp == 3 && b->x)
+        return fail_in(who, "a wide batch (three / four players or extended rules): the greedy player maximises the two-player reward of "
+                            "game_runner.py:48-50");
     if (wide != b->x)
         return fail_in(who, wide ? (net ? "a two-player batch of 128-byte records: use azul_batch_policy_rollout_vs"
                                         : "a two-player batch of 128-byte records: use azul_batch_policy_rollout")
@@ -745,7 +751,7 @@ static int rollout_window(azul_batch_t *b, const char *who, bool wide, int n_ste
         if (((uintptr_t)out->obs & 15u) != 0 || ((uintptr_t)out->mask & 3u) != 0)
             return fail_in(who, "obs must be 16-byte aligned, mask 4-byte aligned");
     }
-    if (net && (out->opp_action || out->opp_logp) && out->opp_slots <= 0) return fail_in(who, "opp_slots must be positive with a trace");
+    if ((net || opp == 3) && (out->opp_action || out->opp_logp) && out->opp_slots <= 0) return fail_in(who, "opp_slots must be positive with a trace");
     if (wide && n_steps == 0) return AZUL_SUCCESS;           // (the two-player kernel is launched with an empty window too: it writes slot 0)
     const PolicyWeights W = {agent->w1t, agent->b1, agent->w2c, agent->b2c, agent->w2a_t, agent->b2a};
     // returns: the two-player kernel writes a window of up to 32 steps itself (it keeps the rewards in 32 lanes); the wide kernels never do
@@ -755,6 +761,9 @@ static int rollout_window(azul_batch_t *b, const char *who, bool wide, int n_ste
         a.Wopp = {opponent->w1t, opponent->b1, opponent->w2c, opponent->b2c, opponent->w2a_t, opponent->b2a};
         a.opp_seed = (u64)keys.opp_seed;
         a.opp_action = out->opp_action; a.opp_logp = out->opp_logp; a.opp_replies = out->opp_replies; a.opp_slots = out->opp_slots;
+    }
+    if (opp == 3) {                                          // the greedy player's trace: its answers and their number (opp_logp is never written)
+        a.opp_action = out->opp_action; a.opp_replies = out->opp_replies; a.opp_slots = out->opp_slots;
     }
     if (!wide) {
         const int rc = launch_rollout(b, W, a, opp, stream);
@@ -810,6 +819,15 @@ int azul_batch_policy_rollout_vs(azul_batch_t *b, int n_steps, const azul_net_we
     BATCH_GUARD(b, stream);
     return rollout_window(b, "azul_batch_policy_rollout_vs", false, n_steps, 2, agent, opponent, {num_inputs, hidden_size, num_actions},
                           {seed, opponent_seed, counter, counter_dev}, out, gamma, 0, stream);
+}
+
+/* GameRunner with the one-ply greedy opponent inside the persistent rollout (game_runner.py:37-55, 76-85 answered by az2::greedy_pick2) */
+int azul_batch_policy_rollout_greedy(azul_batch_t *b, int n_steps, const azul_net_weights_t *agent, int num_inputs, int hidden_size, int num_actions,
+                                     uint64_t seed, uint64_t counter, uint64_t *counter_dev, const azul_rollout_buffers_t *out, float gamma, void *stream)
+{
+    BATCH_GUARD(b, stream);
+    return rollout_window(b, "azul_batch_policy_rollout_greedy", false, n_steps, 3, agent, nullptr, {num_inputs, hidden_size, num_actions},
+                          {seed, 0, counter, counter_dev}, out, gamma, 0, stream);
 }
 
 /* GameRunner / flat self-play of wide batches inside one launch per window (azul_x_policy_rollout_kernel) */

@@ -290,19 +290,14 @@ namespace az2 {
 
 constexpr i32 SCORE_ILLEGAL = (i32)0x80000000u;      // AZUL_SCORE_ILLEGAL (INT32_MIN)
 
-// (score, lowest action) as ONE unsigned key for the half-wave maximum: a score difference lies in (-2^16, 2^16) -- both what-if scores
-// are clamped at 0 and stay below 2^16 (the record keeps scores in 16 bits; the full lines of one round add at most 5 * 29 points) -- so
-// score + 2^16 is a positive 17-bit number; below it 255 - a, so that among equal scores the LOWEST action is the maximum.  0 = no move.
-AZ_FN u32 score_key(i32 score, u32 a) { return ((u32)(score + 65536) << 8) | (255u - a); }
-
 // The table of games 2 pair and 2 pair + 1.  Lane l < 30 of a half keeps the six results of ITS actions l, 30 + l, .. 150 + l in six named
 // registers, as Mask2 keeps the mask rows, and writes them as the mask rows are written.
 // The candidate loop is wave-uniform: 180 trips, a candidate neither half's mask holds is skipped by a ballot (no per-lane branch).  A
 // candidate that only ONE half's mask holds still runs on both: do_move2f is total for every action number -- the source lane, display
 // base, colour (< 5) and row (< 6) it shifts and gathers by are decoded from the ACTION (K2::lcode), never from the state, the gathers stay
 // inside the half, and the state only enters sums, compares and selects -- and the half whose mask lacks the candidate discards the result.
-// Each candidate starts from the loaded game again (`t = g`): a move changes only the mover's line, floor and the source cells, so the
-// copy is those few registers, not a second live game.
+// The per-candidate step and the key of the maximum are azul_env2.hpp's (whatif_after2, score_key): the rule greedy_pick2 -- the greedy
+// opponent inside the window kernel -- plays by is this table's, stated once.
 template <bool LID>
 AZ_FN void score_moves_body2(const BatchDev &b, const ScoreMovesArgs &a, u32 pair)
 {
@@ -320,8 +315,7 @@ AZ_FN void score_moves_body2(const BatchDev &b, const ScoreMovesArgs &a, u32 pai
     const u32 me = me2(g);
     const u32 p = a.persp == AZUL_PERSP_CURRENT ? me : (u32)a.persp;
     const i32 sign = p == me ? 1 : -1;
-    const i32 base = (me ? g.score1 : g.score0), other = (me ? g.wi0 : g.wi1);       // the opponent's what-if score: a move leaves it alone
-    const u32 wall = me ? g.wall1 : g.wall0;
+    const i32 other = me ? g.wi0 : g.wi1;            // the opponent's what-if score: a move leaves it alone
     i32 s0 = SCORE_ILLEGAL, s1 = SCORE_ILLEGAL, s2 = SCORE_ILLEGAL, s3 = SCORE_ILLEGAL, s4 = SCORE_ILLEGAL, s5 = SCORE_ILLEGAL;
     u32 key = 0;
 #pragma unroll 1
@@ -332,10 +326,7 @@ AZ_FN void score_moves_body2(const BatchDev &b, const ScoreMovesArgs &a, u32 pai
             const bool legal = ((word >> ln) & 1u) != 0u;
             if (!wave_any(legal)) continue;
             const u32 act = 30u * row + ln;
-            G2 t = g;
-            do_move2<LID>(t, action_code2(act, k), g.B, k);                                            // azul.py:118-161
-            const i32 wc = wall_points2(wall, full_lines2(me ? t.cp1 : t.cp0, k), k);                  // :211-290, nothing committed
-            const i32 wi = clamp0(base + floor_penalty(me ? t.floor1 : t.floor0) + wc);                // :200-209, :292-295
+            const i32 wi = whatif_after2<LID>(g, act, me, k);          // the per-candidate step greedy_pick2 runs (azul_env2.hpp)
             const i32 v = sign * (wi - other);
             const bool mine = legal & (l == ln);
             s0 = (mine & (row == 0u)) ? v : s0; s1 = (mine & (row == 1u)) ? v : s1; s2 = (mine & (row == 2u)) ? v : s2;

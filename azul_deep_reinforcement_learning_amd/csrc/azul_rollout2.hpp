@@ -11,9 +11,10 @@
 // Arithmetic per output element: the same k-ordered v_mfma_f32_16x16x4_f32 chain per hidden unit / logit, the same critic summation and
 // the same head as azul_policy_forward_kernel, and the rules are azul_selfplay2.hpp's: the trajectories are bit-identical to the
 // two-launches-per-move path (tests/test_policy_bridge.py, tests/test_full_size_configs.py).
-// Three opponents (template parameter OPP): 0 the policy moves for both players; 1 GameRunner with its default RandomAgent inside the env
+// Four opponents (template parameter OPP): 0 the policy moves for both players; 1 GameRunner with its default RandomAgent inside the env
 // phase; 2 GameRunner(opponent=Agent(...)) (game_runner.py:27-30) -- a SECOND network: after the agent's move the workgroup runs matrix phases
-// on the opponent's weights while any of its 16 games owes an opponent_move() (azul_env2.hpp: the NET_* protocol).
+// on the opponent's weights while any of its 16 games owes an opponent_move() (azul_env2.hpp: the NET_* protocol); 3 the scripted greedy
+// player of the reference's own reward (azul_env2.hpp: greedy_pick2) on the same protocol, answered inside the env phase by the wave itself.
 // Reference lines: azulnet/azul.py:296-313 (step), azulnet/game_runner.py:27-30, 37-55 (opponent_move, GameRunner.step), :56-72 (get_state),
 // :76-85 (reset), :87-97 (RandomAgent); azulnet/agent.py:64-81; azulnet/nn_runner.py:17-47.
 #pragma once
@@ -180,7 +181,8 @@ __device__ __forceinline__ void pr2_opp_layer1(const __amdgpu_buffer_rsrc_t rso,
     }
 }
 
-// OPP: 0 the policy moves for both players, 1 GameRunner with the RandomAgent opponent, 2 GameRunner with a NETWORK opponent (a.Wopp)
+// OPP: 0 the policy moves for both players, 1 GameRunner with the RandomAgent opponent, 2 GameRunner with a NETWORK opponent (a.Wopp),
+// 3 GameRunner with the one-ply GREEDY opponent (az2::greedy_pick2: no weights, no matrix phase, no draw)
 template <bool LID, int OPP>
 __global__ void __launch_bounds__(64 * PR2_WAVES) azul_policy_rollout2_kernel(BatchDev b, PolicyWeights W, RolloutArgs a)
 {
@@ -290,6 +292,7 @@ __global__ void __launch_bounds__(64 * PR2_WAVES) azul_policy_rollout2_kernel(Ba
         orow[l] = 0.f; orow[l + 32u] = 0.f; orow[l + 64u] = 0.f; orow[l + 96u] = 0.f;
         if (l < 8u) orow[l + 128u] = 0.f;
         if (l == 0u) { maskS[gl][0] = 0; maskS[gl][1] = 0; maskS[gl][2] = 0; }
+        if constexpr (OPP == 3) m = az2::Mask2{};        // (a half without a game offers the greedy player's candidate loop nothing)
     }
 
     // (waves 0..3: lane c owns the FOUR adjacent columns 64w + 4c .. + 3 -- one 16-byte load per k-step; waves 4..7: a pair, 8 bytes)
@@ -412,7 +415,40 @@ __global__ void __launch_bounds__(64 * PR2_WAVES) azul_policy_rollout2_kernel(Ba
         }
         lds_barrier();
         PR2_STAMP(4);                                    // head (incl. barrier)
-        if constexpr (OPP != 2) {
+        if constexpr (OPP == 3) {
+            // GameRunner.step against the GREEDY opponent (game_runner.py:43-55 with :37-42 answered by az2::greedy_pick2): OPP == 1's control
+            // flow -- no extra barrier, no matrix phase -- on OPP == 2's protocol.  The answer is a pure function of the game this half holds,
+            // so the reply rounds stay inside the wave: while EITHER half owes an opponent_move() both halves price their candidates (the loop
+            // is wave-uniform) and only the half that owes plays; its sibling's game, mask, stream and counters are not touched.
+            // ONE env site per pass, as with the network opponent: pass 0 plays the agent's action, pass j > 0 reply j - 1 of the halves that owe it
+#pragma unroll 1
+            for (u32 j = 0; j <= NET_MAX_REPLIES; j++) {
+                const bool go = live && (j == 0u || ns.pending != az2::NET_READY);
+                if (!az2::wave_any(go)) break;
+                i32 av = actS[gl];
+                if (j > 0u) {
+                    av = az2::greedy_pick2<LID>(g, m, k);
+                    if (go && l == 0u && a.opp_action && j - 1u < (u32)a.opp_slots) a.opp_action[((size_t)t * (size_t)a.opp_slots + (j - 1u)) * n + gi] = av;
+                }
+                if (go) az2::net_move2<LID>(g, av, j == 0u, m, b.rules.first_player, r, margin, cnt, k, ns);
+            }
+            pr2_request1(two, rs1, voffA, voffB, preA, preB);    // the next step's layer 1: in flight during the publish
+            if (live) {
+                if (ns.pending != az2::NET_READY) {              // (NET_MAX_REPLIES hit: cannot happen with legal replies; the slot reports it and moves on)
+                    ns.pending = az2::NET_READY;
+                    if (!ns.st) ns.st = ST_STUCK;
+                    az2::legal_mask2(g, k, m);
+                }
+                st_last = ns.st;
+                if (l == 0u) {
+                    a.reward[row_t + gi] = ns.rew; a.done[row_t + gi] = (uint8_t)ns.dn;
+                    if (a.opp_replies) a.opp_replies[row_t + gi] = (uint8_t)(ns.replies < 255u ? ns.replies : 255u);
+                }
+                win_rew = l == ((u32)t & 31u) ? ns.rew : win_rew;
+                win_done = l == ((u32)t & 31u) ? ns.dn : win_done;
+                publish((u32)t + 1u, true);                      // net_settle2 left the mask of this state in `m`
+            }
+        } else if constexpr (OPP != 2) {
             pr2_request1(two, rs1, voffA, voffB, preA, preB);    // the next move's layer 1: in flight during the env step
             if (live) {
                 const i32 av = actS[gl];

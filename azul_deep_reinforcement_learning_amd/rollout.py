@@ -95,7 +95,14 @@ class PolicyRollout:
         and trajectories as the per-cut path, opponent_selection, opponent_trace and set_opponent() included.  The opening of the games at
         construction stays on the per-cut path; openings after episodes that end inside a window are the kernel's.  One difference: a game
         that still owes an opponent_move() after MAX_REPLY_ROUNDS rounds ends its step with status AZUL_STUCK (unless the step already has a
-        status) instead of raising RuntimeError, as the two-player window kernel does -- raising would cost a host synchronisation per window."""
+        status) instead of raising RuntimeError, as the two-player window kernel does -- raising would cost a host synchronisation per window.
+        `fused_opponent=True` with opponent="greedy" (two-player reference batches, ActorCritic(136, 180, hidden 180); another policy shape
+        raises ValueError): the greedy player answers inside the two-player window kernel (azul_batch_policy_rollout_greedy) -- one launch per
+        window and part, no reply launches and no host synchronisation; persistent resolves to True, use_graph to False, `ring` windows
+        (rings >= 2 with one part) feed A2CLearner.update_from_rollout.  The same trajectories, records, streams and counters as the per-cut
+        path, opponent_trace included (opp_action of the slots a step's replies filled; the other slots keep -1).  The opening at
+        construction stays on the per-cut path.  One difference: a game that still owes an opponent_move() after 64 replies of one step
+        ends the step with status AZUL_STUCK (unless the step already has a status) instead of raising RuntimeError."""
         self._check_modes(policy, n_games, parts, rules, window, use_graph, fused_head, opponent, fused_mlp, persistent, action_selection, ring,
                           opponent_selection, opponent_trace, move_limit, players, fused_wide, fused_opponent, wide_ring)
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
@@ -160,10 +167,19 @@ class PolicyRollout:
         if int(wide_ring) >= 2 and (not self.fused_wide or parts != 1):
             raise ValueError("wide_ring >= 2 is the trajectory ring of the wide window kernel: it needs fused_wide=True and parts=1")
         self.fused_opponent = bool(fused_opponent)
-        if self.fused_opponent:
+        self.fused_greedy = bool(self.fused_opponent and isinstance(opponent, str) and opponent == "greedy")      # (wide batches were refused above)
+        if self.fused_greedy:
+            shape = (policy.critic_linear1.in_features, policy.actor_linear1.in_features, policy.critic_linear1.out_features,
+                     policy.actor_linear1.out_features, policy.actor_linear2.out_features)
+            if shape != (L.OBS_SIZE, L.OBS_SIZE, 180, 180, L.NUM_ACTIONS) or not (fused_mlp and fused_head):
+                raise ValueError("fused_opponent=True with opponent=\"greedy\" plays inside the two-player window kernel, compiled for "
+                                 "ActorCritic(136, 180, hidden 180) -- shape (136, 180, 180) -- with fused_mlp and fused_head; got inputs %d / %d, "
+                                 "hidden %d / %d and %d actions; other policies play the greedy opponent on the per-cut path "
+                                 "(fused_opponent=False)" % shape)
+        elif self.fused_opponent:
             if not self.fused_wide or not net:
                 raise ValueError("fused_opponent=True plays a network opponent inside the window kernel of wide batches: it needs fused_wide=True "
-                                 "and opponent=<module>")
+                                 "and opponent=<module> (or opponent=\"greedy\" on a two-player reference batch)")
             if (opponent.critic_linear1.out_features, opponent.actor_linear1.out_features) != (180, 180):
                 raise ValueError("fused_opponent=True is compiled for an opponent of hidden size 180, got %d / %d; other opponents run on the "
                                  "per-cut path (fused_opponent=False, fused_wide=False)"
@@ -179,7 +195,7 @@ class PolicyRollout:
         self.fused_mlp = bool(fused_mlp and fused_head and not self.wide and policy.critic_linear1.in_features == L.OBS_SIZE and
                               policy.critic_linear1.out_features == 180 and policy.actor_linear2.out_features == L.NUM_ACTIONS)
         # persistent=True: the whole window runs in ONE launch per part (azul_batch_policy_rollout); same results
-        self.persistent = bool(persistent and self.fused_mlp and self.opponent != "greedy")
+        self.persistent = bool(self.fused_greedy or (persistent and self.fused_mlp and self.opponent != "greedy"))
         self.ring = int(ring) if self.persistent else (int(wide_ring) if self.fused_wide else 1)
         assert self.ring >= 1
         # Agent.get_ac_output's two modes (agent.py:64-72): sample from the masked softmax, or take its first maximum
@@ -358,8 +374,8 @@ class PolicyRollout:
         return L.NetWeights(*[x.data_ptr() for x in w])
 
     def _buffers(self, tr, w, returns):
-        """azul_rollout_buffers_t of a window's views; the opponent fields only with a network opponent (the trace only when asked for)."""
-        net, trace = self.opponent == "net", self.opp_slots > 0
+        """azul_rollout_buffers_t of a window's views; the opponent fields only with a network / greedy opponent (the trace only when asked for)."""
+        net, trace = self.cut, self.opp_slots > 0           # (a window kernel with a cut protocol plays the opponent itself)
         ptr = lambda k: tr[k].data_ptr()
         return L.RolloutBuffers(ptr("obs"), ptr("mask"), ptr("player"), ptr("action"), ptr("reward"), ptr("done"), ptr("value"), ptr("log_prob"),
                                 ptr("entropy"), w["status"].data_ptr(), returns, ptr("opp_action") if trace else None,
@@ -456,6 +472,8 @@ class PolicyRollout:
             else:
                 L.check(L.lib.azul_batch_policy_rollout_vs(env._h, T, C.byref(wa), C.byref(wo), *shape, self.sample_seed, self.opponent_seed, 0, ctr,
                                                            C.byref(out), C.c_float(gamma), st))
+        elif self.opponent == "greedy":                     # the greedy player's answers inside the env phase
+            L.check(L.lib.azul_batch_policy_rollout_greedy(env._h, T, C.byref(wa), *shape, self.sample_seed, 0, ctr, C.byref(out), C.c_float(gamma), st))
         elif self.wide:
             L.check(L.lib.azul_batch_mp_policy_rollout(env._h, T, rnd, C.byref(wa), *shape, self.sample_seed, 0, ctr, C.byref(out), C.c_float(gamma), st))
         else:                                               # this entry takes the same pointers one by one

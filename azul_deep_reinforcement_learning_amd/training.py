@@ -45,7 +45,10 @@ class BatchedTrainer:
         game_runner.py:27-30: a frozen second net inside the rollout kernel), or "self": a frozen COPY of the policy that is replaced by the
         current policy every `opponent_refresh` updates (0: never) -- training against a past self; or "greedy" (two-player reference batches):
         PolicyRollout's scripted one-ply greedy player of the reward, on the per-cut path (no window kernel, ring 1: the learner takes
-        update_from_windows; the opponent has no state, so checkpoints carry nothing for it).
+        update_from_windows; the opponent has no state, so checkpoints carry nothing for it) -- or, with fused_opponent=True (policy
+        ActorCritic(136, 180, hidden 180)), inside the two-player window kernel (PolicyRollout(opponent="greedy", fused_opponent=True)): a
+        persistent rollout with `ring` windows, the learner on update_from_rollout (every step of every finished episode trained exactly once),
+        checkpoints that carry the ring and still nothing for the opponent.
         move_limit > 0: BatchedAzul.set_move_limit (beyond the reference: a game that would never end is cut, done = 3; its steps are trained like an
         episode that ended there, the return chain starts at the cut).
         players = 3 / 4 (or extended-rule keys in `rules`): PolicyRollout(players=...) on MultiplayerAzul parts -- the policy is

@@ -412,6 +412,25 @@ typedef struct azul_rollout_buffers {
 int azul_batch_policy_rollout_vs(azul_batch_t *b, int n_steps, const azul_net_weights_t *agent, const azul_net_weights_t *opponent, int num_inputs,
                                  int hidden_size, int num_actions, uint64_t seed, uint64_t opponent_seed, uint64_t counter, uint64_t *counter_dev,
                                  const azul_rollout_buffers_t *out, float gamma, void *stream);
+/* ---- GameRunner with the one-ply GREEDY opponent inside the window kernel (game_runner.py:37-55, 76-85) ----------------------------
+ * azul_batch_policy_rollout with opponent_random = 1 whose RandomAgent is replaced by the scripted player of azul_batch_score_moves: every
+ * opponent_move() (game_runner.py:37-42) -- the opponent's replies, player 1's forced moves (:46) and, after an episode end inside the
+ * window, the opening moves of the next episode (:84-85) -- is the first legal action that maximises the MOVER's score[p] - score[1 - p]
+ * after move + count_score (:48-50; `best` of azul_batch_score_moves with AZUL_PERSP_CURRENT).  The answer needs no weights, no matrix
+ * phase and no draw: it is computed inside the env phase by the wave that holds the game, so a window is one launch with no extra
+ * barrier; a reply consumes no MT19937 word (only new rounds and restarts do) and no Philox key.  One record per AGENT step, observations
+ * from perspective 0, returns as azul_batch_policy_rollout_vs (in-kernel for windows of up to 32 steps, the separate scan behind the
+ * kernel otherwise).  Optional trace: out->opp_replies [T][N] gets the opponent moves played inside each step (opening moves of the next
+ * episode included), out->opp_action [T][opp_slots][N] reply j of a step for j < opp_slots (replies beyond opp_slots are played but not
+ * recorded; slots beyond a step's replies are not written); out->opp_logp is never written.  No host synchronisation and no allocation:
+ * the call can be captured in a HIP graph.  Bit-identical to the per-cut entries (azul_batch_net_step_begin / _step_reply) driven with
+ * azul_batch_score_moves' `best`, with one difference: a game that still owes an opponent_move() after 64 replies of one step ends the
+ * step with status AZUL_STUCK (unless the step already has a status), as azul_batch_policy_rollout_vs does.
+ * AZUL_ERR_INVALID before any launch: a wide batch (three / four players or extended rules), a shape other than (136, 180, 180), a NULL
+ * agent or out. */
+int azul_batch_policy_rollout_greedy(azul_batch_t *b, int n_steps, const azul_net_weights_t *agent, int num_inputs, int hidden_size, int num_actions,
+                                     uint64_t seed, uint64_t counter, uint64_t *counter_dev, const azul_rollout_buffers_t *out, float gamma,
+                                     void *stream);
 /* azul_batch_policy_rollout for WIDE batches (three / four players, or any extended rule; two-player reference batches are refused: they
  * have azul_batch_policy_rollout): a whole window of n_steps moves in ONE launch, 16 games per workgroup of eight waves, the env on the
  * vector pipe, ActorCritic(obs_size, hidden 180, num_actions) on the f32 matrix cores, the head of azul_policy_head_n.  opponent_random = 0:
