@@ -124,7 +124,12 @@ AZ_FN i32 clamp0(i32 s) { return s < 0 ? 0 : s; }       // azul.py:294-295
 
 AZ_FN bool any_row_full(u32 w) { return ((w & (w >> 1) & (w >> 2) & (w >> 3) & (w >> 4)) & 0x108421u) != 0u; }     // azul.py:184-191
 
-AZ_FN u32 byte_sum5(u64 v) { return (u32)(((v & 0xffffffffffull) * 0x0101010101ull) >> 32) & 0xffu; }
+AZ_FN u32 byte_sum5(u64 v)
+{
+    // (no eight-bit limit on the sum: a bag refilled from the lid holds five bytes of up to 255 tiles each)
+    const u32 lo = (u32)v, s = (lo & 0x00ff00ffu) + ((lo >> 8) & 0x00ff00ffu);
+    return (s & 0xffffu) + (s >> 16) + ((u32)(v >> 32) & 0xffu);
+}
 
 // compact trajectory record of one move (what the multi-GPU all-gather ships): action (0xff = none) | done << 8 | reward << 16
 AZ_FN u32 pack_move(i32 a, u32 dn, i32 reward) { return ((u32)(a >= 0 ? a : 0xff) & 0xffu) | ((dn & 0xffu) << 8) | (((u32)reward & 0xffffu) << 16); }

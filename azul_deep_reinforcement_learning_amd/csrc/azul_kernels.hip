@@ -250,7 +250,9 @@ static int check_range(const azul_batch_t *b, int first, int count)
     return AZUL_SUCCESS;
 }
 
-// domain the kernels are exact on (documented in DESIGN.md)
+// domain the kernels are exact on (documented in DESIGN.md 4).  Not closed under play -- tiles returned to the lid can make a refilled bag
+// hold more than 255 -- which the deal handles (az::byte_sum5 is a plain sum); the closure bound that would keep a record inside for good is
+// not enforced here: records the deal tests hand in (a box of up to 255 tiles on a dealt table) lie outside it.
 static int record_in_domain(const azul_batch_t *b, const uint8_t *p)
 {
     const u32 P = (u32)b->players;

@@ -439,6 +439,16 @@ AZ_FN void add_tile(u32 &cs0, u32 &cs1, u32 d, u32 colour, u32 l)
     if (Dim<D>::WIDE) cs1 += ((l == cell) & hi) ? 1u : 0u;
 }
 
+// box_0 + .. + box_(l & 3) for my lane and the number of tiles in the bag -- plain sums: a bag refilled from the lid can hold more than 255 tiles
+AZ_FN u32 box_prefix(u64 box, u32 l, u32 &total)
+{
+    const u32 b = (u32)box;
+    const u32 p0 = b & 0xffu, p1 = p0 + ((b >> 8) & 0xffu), p2 = p1 + ((b >> 16) & 0xffu), p3 = p2 + (b >> 24);
+    total = p3 + ((u32)(box >> 32) & 0xffu);
+    const u32 j = l & 3u;
+    return j == 0u ? p0 : j == 1u ? p1 : j == 2u ? p2 : p3;
+}
+
 // the draws of a round one after the other, for the pools whose draws consume a data-dependent number of words: "Random"
 // (_randbelow(5) per tile, azul.py:78) and -- beyond the reference -- the finite bag (_randbelow(tiles left) per tile)
 template <u32 D>
@@ -449,22 +459,19 @@ AZ_FN u32 deal_serial_x(u32 &cs0, u32 &cs1, u64 &box, u64 &lid, u32 &lidp, u32 p
         for (u32 t = 0; t < 4u * D; t++) add_tile<D>(cs0, cs1, t >> 2, rng2_below(r, 5u, 3u, l), l);        // :78 randrange(0,5,1)
         return ST_OK;
     }
-    u64 Pp = ((box & 0xffffffffffull) * 0x0101010101ull) & 0xffffffffffull;     // byte c = box_0 + .. + box_c
 #pragma unroll 1
     for (u32 t = 0; t < 4u * D; t++) {
-        u32 total = (u32)(Pp >> 32) & 0xffu;
+        u32 total;
+        u32 pc = box_prefix(box, l, total);
         if (total == 0u) {                                                           // the bag is empty: refill it from the lid (like :81-83)
             box = lid + lid_fold2(lidp, l); lid = 0; lidp = 0;
-            Pp = ((box & 0xffffffffffull) * 0x0101010101ull) & 0xffffffffffull;
-            total = (u32)(Pp >> 32) & 0xffu;
+            pc = box_prefix(box, l, total);
             if (total == 0u) return short_deal ? (u32)ST_OK : (u32)ST_BOX_EMPTY;     // beyond the reference: the short deal
         }
         // the nth of the `total` tiles left, tiles ordered by colour; random.randrange(total) = _randbelow(total)
         const u32 nth = rng2_below(r, total, 32u - (u32)__builtin_clz(total), l);
-        const u32 pc = ((u32)Pp >> ((l & 3u) * 8u)) & 0xffu;
         const u32 color = (u32)__popc(hb((pc <= nth) & (l < 4u)));
         box -= 1ull << (8u * color);
-        Pp -= (0x0101010101ull << (8u * color)) & 0xffffffffffull;
         add_tile<D>(cs0, cs1, t >> 2, color, l);
     }
     return ST_OK;

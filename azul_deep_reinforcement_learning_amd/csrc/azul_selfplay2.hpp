@@ -688,7 +688,10 @@ AZ_FN void deal_batch2(u32 &cs0, u32 &cs1, u64 &box, Rng2 &r, u64 margin, u32 t0
     const u32 tt = T0 - l;                               // draw t sees T0 - t tiles (valid for l < n <= T0)
     const u32 lo = klo * tt, kthi = khi * tt + __umulhi(klo, tt);
     const u32 mg = (u32)margin;
-    const u32 risky = hb(lo + mg < 2u * mg) & nmask;
+    // T0 > 255 (only a bag refilled from a lid that scoring pushed past 255 tiles: no game gets there, a handed-in record can): the margin
+    // argument above and the byte-wise prefix sums below hold for T <= 255, so such a batch is decided by the literal fp64 code throughout
+    const bool big = T0 > 255u;
+    const u32 risky = big ? nmask : hb(lo + mg < 2u * mg) & nmask;
     u32 col = 0;
     if (risky == 0u) {
         const u32 below = (1u << l) - 1u;
@@ -714,7 +717,7 @@ AZ_FN void deal_batch2(u32 &cs0, u32 &cs1, u64 &box, Rng2 &r, u64 margin, u32 t0
             const u32 Klo = hread(klo, t), Khi = hread(khi, t);
             const u64 KT = (u64)Klo * total + (((u64)Khi * total) << 32);
             u32 color;
-            if (((KT - margin) >> 32) == ((KT + margin) >> 32)) {
+            if (!big && ((KT - margin) >> 32) == ((KT + margin) >> 32)) {
                 const u32 pc = ((u32)Pp >> ((l & 3u) * 8u)) & 0xffu;
                 color = (u32)__popc(hb(((pc << 21) <= (u32)(KT >> 32)) & (l < 4u)));
             } else {

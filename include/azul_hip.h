@@ -167,6 +167,12 @@ void *azul_batch_mtpos_dev(azul_batch_t *b);
 
 /* ---- state / RNG I/O (superset of export_JSON / import_JSON, azul.py:90-117) ------------------ */
 int azul_batch_get_state(azul_batch_t *b, int first, int count, void *records_host, void *stream);
+/* set_state checks every record against the domain the kernels are exact on (AZUL_ERR_RANGE otherwise, nothing of the call lands): player
+ * fields 0..P, floors 0..7, 25-bit walls, box and lid each at most 255 tiles in total, and for a wide record byte 204 = P, byte 205 = the
+ * batch's displays (0 for five).  Play can leave that domain in one way and stays exact there: tiles that scoring returns to the lid can make
+ * the refill of an empty bag find more than 255 tiles; the deal sums the bag without an eight-bit limit.  A record stays inside the limits
+ * for good when box + lid + displays + centre colours + pattern lines <= 255 (not enforced).  One colour's count in box or lid passing 255
+ * is beyond the record format. */
 int azul_batch_set_state(azul_batch_t *b, int first, int count, const void *records_host, void *stream);
 /* random.getstate() / random.setstate() of one game's stream: 624 words + index */
 int azul_batch_get_rng(azul_batch_t *b, int game, uint32_t *mt_host, uint32_t *pos_host, void *stream);
