@@ -126,6 +126,7 @@ SIGNATURES = {
     "azul_batch_mp_agent_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     "azul_batch_mp_policy_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     "azul_batch_mp_score_preview": (_i, [_vp, _vp, _vp]),
+    "azul_batch_mp_score_moves": (_i, [_vp, _i, _vp, _vp, _vp, _vp]),
     "azul_batch_mp_net_step_begin": (_i, [_vp] * 11),
     "azul_batch_mp_net_step_reply": (_i, [_vp] * 11),
     "azul_batch_mp_net_reset_begin": (_i, [_vp] * 8),

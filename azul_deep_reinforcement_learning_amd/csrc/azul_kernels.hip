@@ -1162,6 +1162,25 @@ int azul_batch_mp_net_reset_begin(azul_batch_t *b, const uint8_t *active_dev, ui
                   __func__, "azul_batch_net_reset_begin", stream);
 }
 
+// every legal move's what-if margin and the greedy choice of a wide batch (azul_rules_x.hpp: score_moves_body_x): one launch, the games are
+// only read -- so, unlike the other azul_batch_mp_* entries, a move limit is no reason to refuse
+int azul_batch_mp_score_moves(azul_batch_t *b, int perspective, const uint8_t *active_dev, int32_t *scores_dev, int32_t *best_dev, void *stream)
+{
+    BATCH_GUARD(b, stream);
+    if (!b) return fail(AZUL_ERR_INVALID, "batch is NULL");
+    if (!b->x) return fail(AZUL_ERR_INVALID, "azul_batch_mp_score_moves: a two-player batch of 128-byte records: use azul_batch_score_moves");
+    if (!scores_dev && !best_dev) return fail(AZUL_ERR_INVALID, "azul_batch_mp_score_moves: scores_dev and best_dev are both NULL");
+    if (perspective != AZUL_PERSP_MOVER && (perspective < 0 || perspective >= b->players))
+        return fail(AZUL_ERR_INVALID, "azul_batch_mp_score_moves: perspective must be a seat 0 .. players - 1 or AZUL_PERSP_MOVER");
+    azx::XScoreMoves a;
+    a.active = active_dev; a.scores = scores_dev; a.best = best_dev; a.persp = perspective;
+    const dim3 grid((b->d.n + 1u) / 2u), block(64);
+    const azx::XBatchDev xb = xdev(b);
+    AZ_X_DISPATCH(b, hipLaunchKernelGGL((azul_x_score_moves_kernel<PP, DD>), grid, block, 0, (hipStream_t)stream, xb, a));
+    HIP_TRY(hipGetLastError());
+    return AZUL_SUCCESS;
+}
+
 int azul_policy_head_n(const float *logits_dev, const uint8_t *mask_dev, uint64_t seed, uint64_t counter, const uint64_t *counter_dev,
                        int n_games, int num_actions, uint32_t game_id_base, int32_t *action_dev, float *logp_dev, float *entropy_dev, void *stream)
 {

@@ -406,6 +406,19 @@ AZ_FN void count_score_x(GX<P, D> &g, bool tracked, bool end_bonus, const KX<D> 
     g.over = over ? 1u : 0u;
 }
 
+// ONE seat's chain of count_score_x and only its score: what count_score_x leaves in score[p] for a seat with pattern lines `cells` (the
+// seat's byte of cpk), wall `wall`, `floor` tiles on the floor line and `score` points.  Stated next to it for score_moves_body_x, which
+// prices every candidate move of one seat: the other seats' chains are the same for all candidates.  count_score_x itself is untouched.
+AZ_FN i32 seat_score_x(u32 cells, u32 wall, i32 score, u32 floor, bool end_bonus, const K2 &k)
+{
+    const u32 F = full_lines2(cells, k);                                                   // :216
+    Score2 s;
+    score2(wall | (F & k.pbelow), k, s);                                                   // :219
+    const bool on = ((F >> k.l) & 1u) != 0u;
+    const i32 cnt = (i32)hsum(on ? (end_bonus ? s.pos : s.val) : 0u);                      // :289 (end_bonus: without the line bonuses)
+    return clamp0(score + floor_penalty(floor) + cnt);                                     // :208, :292-295
+}
+
 // beyond the reference: the rulebook's end-of-game bonuses from the final walls -- 2 per complete row, 7 per complete board column,
 // 10 per colour with all five tiles placed -- added once, after the last round's clamp
 AZ_FN i32 wall_bonus(u32 w)
@@ -1225,6 +1238,117 @@ AZ_FN i32 potential_x(const GX<P, D> &g, const RulesX &rules, const KX<D> &K)
 #pragma unroll
     for (u32 p = 2; p < P; p++) best = c.score[p] > best ? c.score[p] : best;
     return c.score[0] - best;
+}
+
+// ---- azul_x_score_moves_kernel's body: THE ONE-PLY TABLE OF THE WIDE RUNNER'S REWARD, the wide twin of az2::score_moves_body2 ------------------
+// For every action a that legal_mask_x marks: s[p] - max_{j != p} s[j], with s the scores of a register copy of the game after
+// do_move_x(decode_action_x(a)) (the unchecked move, azul.py:118-161: no next_player, no new round, no draw) and count_score_x as
+// potential_x calls it; p = a.persp (a seat, or >= P: the seat to move).  At p = 0 that is potential_x of the moved copy, at P = 2 the
+// reference's score[p] - score[1 - p] (game_runner.py:48-50); BEYOND THE REFERENCE for P > 2, like the runner's reward (the margin over
+// the best other seat).  And the first action that maximises it (np.argmax's rule), -1 when nothing is legal.  The games are only read:
+// no record byte, MT19937 word or index and no counter is written; no RNG state, no sampler table, no LDS.
+// A move changes only the mover's pattern lines and floor, the sources and the lid, so every other seat's score after count_score_x is
+// the same for all candidates: count_score_x runs ONCE per game on a copy (potential_x's call) for those, seat_score_x once per
+// candidate for the mover.  Lane l keeps the results of ITS actions Q r + 32 w + l in 6 NW registers, as MaskX keeps the mask bits, and
+// writes them as store_mask_bytes_x writes those.
+// The candidate loop is wave-uniform: NA trips, a candidate neither half's mask holds is skipped by a ballot.  A candidate only ONE
+// half's mask holds still runs on both, and the half that lacks it discards the result.  do_move_x is total for every action number
+// below NA on any in-domain state: source (< S), colour (< 5) and row (< 6) come from the ACTION, so the display base (<= 20), the source
+// lane (< 30) and the line cell (< 25) it gathers and shifts by are in range whatever the state holds; its gathers stay inside the half
+// (the one gather with a wrapped index, `moved`, is only used by the lanes 25..29 whose index is in 0..24); the state only enters sums,
+// compares and selects, and the floor is capped at 7 before floor_penalty sees it.
+struct XScoreMoves {
+    const uint8_t *active;   // [n] in, optional: games with 0 are not looked at and their rows are not written
+    i32 *scores;             // [n][NA] out, optional: the table; AZUL_SCORE_ILLEGAL where the legal mask holds 0
+    i32 *best;               // [n] out, optional: first legal action with the maximal score, -1 when nothing is legal
+    int persp;               // 0 .. P-1, or >= P: the seat to move
+};
+
+// (score, lowest action) as ONE unsigned key for the half-wave maximum, az2::score_key with room for 300 actions: a score lies in
+// (-2^16, 2^16) -- every s[j] is clamped at 0 and stays below 2^16 (the record keeps scores in 16 bits; the full lines of one round add
+// at most 5 * 29 points) -- so score + 2^16 is a positive 17-bit number; below it NINE bits of 511 - a, so that among equal scores the
+// LOWEST action is the maximum.  0 = no move.
+AZ_FN u32 score_key_x(i32 score, u32 a) { return ((u32)(score + 65536) << 9) | (511u - a); }
+
+template <u32 P, u32 D>
+AZ_FN void score_moves_body_x(const XBatchDev &b, const XScoreMoves &a, u32 pair)
+{
+    constexpr u32 S = Dim<D>::S, Q = Dim<D>::Q, NW = Dim<D>::NW;
+    const u32 lane = wv::lane(), l = lane & 31u, half = lane >> 5;
+    const u32 gi = 2u * pair + half;
+    if (gi >= b.n) return;                           // odd batch: the last wave serves one game
+    if (a.active && a.active[gi] == 0) return;
+    KX<D> K;
+    GX<P, D> g;
+    open_game_x(g, K, b.state + (size_t)gi * AZUL_RECORD_BYTES_WIDE, l);
+    MaskX<D> m;
+    legal_mask_x(g, K, m);
+    const bool end_bonus = b.rules.end_bonus != 0u;
+    const u32 me = mex(g);
+    const u32 p = (u32)a.persp < P ? (u32)a.persp : me;
+    // the seats a move leaves alone: s[p] (used when p is not the mover) and the best of the seats that are neither p nor the mover
+    i32 sp, rest = -(1 << 20);                       // (P = 2 from the other seat's view: nobody else -- below every score)
+    {
+        GX<P, D> c = g;
+        count_score_x(c, false, end_bonus, K);
+        sp = pick<P>(c.score, p);
+#pragma unroll
+        for (u32 j = 0; j < P; j++) rest = ((j == p) | (j == me) | (c.score[j] <= rest)) ? rest : c.score[j];
+    }
+    const u32 wall_me = pick<P>(g.wall, me);
+    const i32 score_me = pick<P>(g.score, me);
+    const u32 sh = 8u * me;
+    // (the mask words pass through an empty asm first: a select chain over elements of a struct reached through a reference is folded
+    // into ONE load from a selected address, which pins the struct in scratch memory -- pick_action_x)
+    u32 lo[6], hi[6];
+#pragma unroll
+    for (u32 r = 0; r < 6u; r++) {
+        lo[r] = m.m[r][0]; hi[r] = m.m[r][NW - 1];
+        asm volatile("" : "+v"(lo[r]), "+v"(hi[r]));
+    }
+    i32 sc[6][NW];
+#pragma unroll
+    for (u32 r = 0; r < 6u; r++)
+#pragma unroll
+        for (u32 w = 0; w < NW; w++) sc[r][w] = (i32)AZUL_SCORE_ILLEGAL;
+    u32 key = 0;
+#pragma unroll 1
+    for (u32 row = 0; row < 6u; row++) {
+        u32 wlo = lo[0], whi = hi[0];
+#pragma unroll
+        for (u32 r = 1; r < 6u; r++) { wlo = row == r ? lo[r] : wlo; whi = row == r ? hi[r] : whi; }
+#pragma unroll 1
+        for (u32 c = 0; c < 5u; c++) {
+#pragma unroll 1
+            for (u32 s = 0; s < S; s++) {
+                const u32 q = S * c + s, qw = q >> 5, ql = q & 31u;
+                const bool legal = ((((NW > 1 && qw) ? whi : wlo) >> ql) & 1u) != 0u;
+                if (!wave_any(legal)) continue;
+                GX<P, D> t = g;
+                do_move_x(t, s, c, row, false, K);                                                  // azul.py:118-161
+                const i32 v = seat_score_x((t.cpk >> sh) & 0xffu, wall_me, score_me, (t.floors >> sh) & 0xffu, end_bonus, K.k);
+                const i32 val = p == me ? v - rest : sp - (v > rest ? v : rest);
+                const bool mine = legal & (l == ql);
+#pragma unroll
+                for (u32 r = 0; r < 6u; r++)
+#pragma unroll
+                    for (u32 w = 0; w < NW; w++) sc[r][w] = (mine & (row == r) & (qw == w)) ? val : sc[r][w];
+                key = mine ? umax(key, score_key_x(val, Q * row + q)) : key;
+            }
+        }
+    }
+    if (a.scores) {
+        i32 *out = a.scores + (size_t)gi * Dim<D>::NA + l;
+#pragma unroll
+        for (u32 r = 0; r < 6u; r++) {
+            if (l < (Q < 32u ? Q : 32u)) out[Q * r] = sc[r][0];
+            if (NW > 1) { if (l < Q - 32u) out[Q * r + 32u] = sc[r][NW - 1]; }
+        }
+    }
+    if (a.best) {
+        const u32 top = hmax(key);                   // (a lane without an action holds 0)
+        if (l == 0u) a.best[gi] = top ? (i32)(511u - (top & 511u)) : -1;
+    }
 }
 
 // a fresh Azul(players = P, rules) + new_round(), player_score = move_counter = 0 (game_runner.py:23-36 / :79-82)

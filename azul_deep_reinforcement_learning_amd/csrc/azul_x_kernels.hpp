@@ -49,3 +49,11 @@ __global__ void __launch_bounds__(64) azul_x_net_kernel(azx::XBatchDev b, azx::X
     __shared__ u32 mt_lds[2][624];
     azx::net_body_x<P, D>(b, a, blockIdx.x, mt_lds);
 }
+
+// Every legal move's what-if margin and the greedy choice of wide batches (azx::score_moves_body_x), the games untouched: two games per
+// wavefront, the game in VGPRs, no LDS.  grid = ceil(n / 2) one-wave workgroups.
+template <u32 P, u32 D>
+__global__ void __launch_bounds__(64) azul_x_score_moves_kernel(azx::XBatchDev b, azx::XScoreMoves a)
+{
+    azx::score_moves_body_x<P, D>(b, a, blockIdx.x);
+}

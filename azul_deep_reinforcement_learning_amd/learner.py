@@ -106,6 +106,8 @@ class A2CLearner:
         advantage = qvals.to(values.dtype) - values
         w = torch.ones_like(values) if weight is None else weight.to(values.dtype)
         n = w.sum() if n_total is None else n_total
+        # a window without a finished episode has no sample: the sums are 0, and so are the terms (the fused path's rule), not 0 / 0
+        n = n.clamp(min=1.0) if torch.is_tensor(n) else max(float(n), 1.0)
         actor_loss = (-log_prob * advantage * w).sum() / n
         critic_loss = (advantage.pow(2) * w).sum() / n
         entropy_loss = (entropy * w).sum() / n

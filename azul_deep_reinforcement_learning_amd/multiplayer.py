@@ -52,6 +52,28 @@ class MultiplayerAzul(BatchedAzul):
         L.check(L.lib.azul_batch_mp_score_preview(self._h, _ptr(p), self._stream()))
         return p
 
+    def score_moves(self, perspective=L.PERSP_MOVER, active=None, scores=None, best=None):
+        """The one-ply table of the reward above in one launch (azul_batch_mp_score_moves), the games untouched: scores [N][num_actions]
+        int32, for every legal action s[p] - max_{j != p} s[j] after move + count_score on a copy of the game (p = `perspective`: a seat
+        0 .. P-1, or PERSP_MOVER, the seat to move; at p = 0 phi of the moved copy; beyond the reference for P > 2), L.SCORE_ILLEGAL
+        elsewhere; best [N] int32, the first legal action with the maximal score (-1: nothing is legal).  `scores` / `best`: preallocated
+        device tensors to write into; rows of games whose `active` is 0 are not written (fresh outputs start as SCORE_ILLEGAL / -1).
+        Returns (scores, best)."""
+        if scores is None:
+            scores = torch.full((self.n, self.num_actions), L.SCORE_ILLEGAL, dtype=torch.int32, device=self.device)
+        if best is None:
+            best = torch.full((self.n,), -1, dtype=torch.int32, device=self.device)
+        L.check(L.lib.azul_batch_mp_score_moves(self._h, int(perspective), _ptr(self._dev(active, torch.uint8)), _ptr(scores), _ptr(best),
+                                                self._stream()))
+        return scores, best
+
+    def greedy_action(self, active=None, out=None):
+        """The one-ply greedy seat of that reward: for every game the move that maximises the mover's margin over the best other seat
+        after move + count_score (score_moves' `best` from the mover's perspective; -1: nothing is legal).  `out`: a preallocated int32 [N]."""
+        best = torch.full((self.n,), -1, dtype=torch.int32, device=self.device) if out is None else out
+        L.check(L.lib.azul_batch_mp_score_moves(self._h, L.PERSP_MOVER, _ptr(self._dev(active, torch.uint8)), None, _ptr(best), self._stream()))
+        return best
+
     def observe_all(self, perspective=L.PERSP_MOVER, obs=None, mask=None, player=None):
         return super().observe_all(perspective, obs, mask, player)
 

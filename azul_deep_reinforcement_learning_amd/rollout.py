@@ -64,6 +64,11 @@ class PolicyRollout:
         (game_runner.py:48-50), one launch per reply round in place of the network's forward; records as with "random"; `opponent_trace`
         records opp_action (opp_logp stays 0) and opp_replies; persistent and use_graph resolve to False, ring to 1; at most MAX_REPLY_ROUNDS
         reply rounds per step or opening (a game with nothing legal would owe its move for ever: RuntimeError).
+        opponent="greedy_margin" (wide batches only, on the per-cut path: fused_wide / fused_opponent raise ValueError): the same scripted
+        player for three / four seats and extended rules -- every other seat answers every opponent_move() with
+        MultiplayerAzul.greedy_action, the move that maximises the MOVER's margin over the best other seat after move + count_score
+        (azul_batch_mp_score_moves; beyond the reference for P > 2, like the wide reward), through MultiplayerAzul.net_* exactly as a
+        network opponent's answers: one launch per reply round, no opponent weights, opp_logp stays 0, at most MAX_REPLY_ROUNDS rounds.
         `move_limit` > 0 (beyond the reference, off by default): cut an episode at the first end of a round with move_counter >= move_limit
         (done = 3) -- under the reference's rules some games never end and would keep their slot for ever (BatchedAzul.set_move_limit).
         `seed_base` / `game_id_base`: game i of this rollout is global game game_id_base + i (default: seed_base, so that a rank
@@ -145,7 +150,14 @@ class PolicyRollout:
                                  % (self.players, n_obs, n_act, shape[0], shape[1], shape[2]))
         if isinstance(opponent, str) and opponent == "greedy" and self.wide:
             raise ValueError("opponent=\"greedy\" maximises the two-player reward of game_runner.py:48-50: two-player reference batches only, "
-                             "not %d players / extended rules" % self.players)
+                             "not %d players / extended rules (their scripted opponent is opponent=\"greedy_margin\")" % self.players)
+        margin = isinstance(opponent, str) and opponent == "greedy_margin"
+        if margin and not self.wide:
+            raise ValueError("opponent=\"greedy_margin\" maximises the margin over the best other seat on batches of three / four players or "
+                             "extended rules; a two-player reference batch has opponent=\"greedy\"")
+        if margin and (fused_wide or fused_opponent):
+            raise ValueError("opponent=\"greedy_margin\" answers on the per-cut path (one azul_batch_mp_score_moves launch per reply round): "
+                             "the wide window kernel does not play it (fused_wide=False, fused_opponent=False)")
         if self.wide and move_limit:
             raise ValueError("no move limit for batches of three / four players or extended rules")
         self.fused_wide = bool(fused_wide)
@@ -187,15 +199,16 @@ class PolicyRollout:
         self.opp_policy = None
         if net:
             self.opp_policy, opponent = opponent, "net"
-        assert opponent in (None, "random", "net", "greedy")
+        assert opponent in (None, "random", "net", "greedy", "greedy_margin")
         self.opponent = opponent
-        self.cut = opponent in ("net", "greedy")               # GameRunner.step cut at its opponent_move() calls (BatchedAzul.net_*)
+        self.scripted = opponent in ("greedy", "greedy_margin")        # answers are env.greedy_action's: no weights, no log-probabilities
+        self.cut = opponent == "net" or self.scripted          # GameRunner.step cut at its opponent_move() calls (BatchedAzul.net_*)
         self.fused_head = fused_head
         # the one-launch forward (azul_policy_forward) is compiled for the reference's ActorCritic(136, 180, hidden 180)
         self.fused_mlp = bool(fused_mlp and fused_head and not self.wide and policy.critic_linear1.in_features == L.OBS_SIZE and
                               policy.critic_linear1.out_features == 180 and policy.actor_linear2.out_features == L.NUM_ACTIONS)
         # persistent=True: the whole window runs in ONE launch per part (azul_batch_policy_rollout); same results
-        self.persistent = bool(self.fused_greedy or (persistent and self.fused_mlp and self.opponent != "greedy"))
+        self.persistent = bool(self.fused_greedy or (persistent and self.fused_mlp and not self.scripted))
         self.ring = int(ring) if self.persistent else (int(wide_ring) if self.fused_wide else 1)
         assert self.ring >= 1
         # Agent.get_ac_output's two modes (agent.py:64-72): sample from the masked softmax, or take its first maximum
@@ -259,7 +272,7 @@ class PolicyRollout:
         if self.cut:
             w["net"] = env.net_state()
             w["scratch_f"] = torch.zeros(3, h, device=d)       # the opponent forward's value / entropy (not recorded) and untraced log-prob
-            if self.wide:                                      # the opponent's actor half as PyTorch GEMMs (its own hidden size)
+            if self.wide and self.opponent == "net":           # the opponent's actor half as PyTorch GEMMs (its own hidden size)
                 w["opp_hidden"] = torch.zeros(h, self.ob1.numel() // 2, device=d)
                 w["opp_logits"] = torch.zeros(h, env.num_actions, device=d)
         self.traj.append(t)
@@ -279,7 +292,7 @@ class PolicyRollout:
         return out
 
     def _persp(self):
-        return 0 if self.opponent in ("random", "net", "greedy") else L.PERSP_CURRENT     # NNRunner observes with perspective 0 (game_runner.py:56)
+        return 0 if self.opponent in ("random", "net", "greedy", "greedy_margin") else L.PERSP_CURRENT     # NNRunner observes with perspective 0 (game_runner.py:56)
 
     def _stage(self, get, prefix, names):
         """The k-major copies `names` of the reference's four layers (`get`: parameter name -> tensor) as attributes prefix + name,
@@ -308,8 +321,9 @@ class PolicyRollout:
         what net_step_* left in work["net"], reply j of the step sampled with Philox key opponent_seed + j at the step's counter."""
         w = self.work[p]
         net, sc = w["net"], w["scratch_f"]
-        if self.opponent == "greedy":
-            # the scripted opponent: the best move of every game that owes one, from the mover's perspective (azul_batch_score_moves)
+        if self.scripted:
+            # the scripted opponent: the best move of every game that owes one, from the mover's perspective (azul_batch_score_moves /
+            # azul_batch_mp_score_moves)
             self.envs[p].greedy_action(active=net["pending"], out=net["action"])
             return
         key = self.opponent_seed if self.opponent_seed == L.POLICY_ARGMAX else (self.opponent_seed + j) & 0xFFFFFFFFFFFFFFFF
@@ -340,7 +354,7 @@ class PolicyRollout:
         env.net_reset_begin(w["net"], w["status"])
         j = 0
         while int(w["net"]["owing"].item()) > 0:
-            if (self.wide or self.opponent == "greedy") and j >= self.MAX_REPLY_ROUNDS:
+            if (self.wide or self.scripted) and j >= self.MAX_REPLY_ROUNDS:
                 self._reply_loop_failed(p, j, "the opening of reset()")
             self._opp_forward(p, j, w["scratch_f"][2])
             env.net_step_reply(w["net"]["action"], w["net"], None, None, w["status"])
@@ -354,7 +368,7 @@ class PolicyRollout:
         raise RuntimeError("%s opponent: games %s (global ids) still owe an opponent_move() after %d reply rounds of %s (round %d); "
                            "statuses %s -- the opponent keeps answering with moves that are not legal (a forward that is not finite, or a "
                            "state with nothing legal, answers -1)"
-                           % ("greedy" if self.opponent == "greedy" else "network", ids[:16], rounds, where, rounds, [int(st[i]) for i in owing[:16]]))
+                           % ("greedy" if self.scripted else "network", ids[:16], rounds, where, rounds, [int(st[i]) for i in owing[:16]]))
 
     def refresh_weights(self):
         """(Re)build the fused first-layer weights from the policy's parameters -- call after every optimiser step.  The
@@ -433,7 +447,7 @@ class PolicyRollout:
             env.net_step_begin(tr["action"][t], net, tr["reward"][t], tr["done"][t], w["status"])
             j = 0
             while int(net["owing"].item()) > 0:
-                if (self.wide or self.opponent == "greedy") and j >= self.MAX_REPLY_ROUNDS:
+                if (self.wide or self.scripted) and j >= self.MAX_REPLY_ROUNDS:
                     self._reply_loop_failed(p, j, "agent step %d of the window" % t)
                 self._opp_forward(p, j, tr["opp_logp"][t][j] if j < self.opp_slots else w["scratch_f"][2])
                 if j < self.opp_slots:

@@ -48,7 +48,9 @@ class BatchedTrainer:
         update_from_windows; the opponent has no state, so checkpoints carry nothing for it) -- or, with fused_opponent=True (policy
         ActorCritic(136, 180, hidden 180)), inside the two-player window kernel (PolicyRollout(opponent="greedy", fused_opponent=True)): a
         persistent rollout with `ring` windows, the learner on update_from_rollout (every step of every finished episode trained exactly once),
-        checkpoints that carry the ring and still nothing for the opponent.
+        checkpoints that carry the ring and still nothing for the opponent; or "greedy_margin" (players = 3 / 4 or extended rules): the
+        same scripted player for wide batches (PolicyRollout(players=P, opponent="greedy_margin"): every other seat maximises its margin over
+        the best other seat), on the per-cut path only, the learner on update_from_windows, nothing in the checkpoint for it.
         move_limit > 0: BatchedAzul.set_move_limit (beyond the reference: a game that would never end is cut, done = 3; its steps are trained like an
         episode that ended there, the return chain starts at the cut).
         players = 3 / 4 (or extended-rule keys in `rules`): PolicyRollout(players=...) on MultiplayerAzul parts -- the policy is

@@ -247,6 +247,19 @@ int azul_batch_mp_policy_step(azul_batch_t *b, const int32_t *actions_dev, const
                               uint8_t *done_dev, uint8_t *status_dev, int perspective, float *obs_next_dev,
                               uint8_t *mask_next_dev, uint8_t *player_next_dev, void *stream);
 int azul_batch_mp_score_preview(azul_batch_t *b, int32_t *potential_dev /*[N]*/, void *stream);   /* phi of the current state, game_runner.py:48-50 */
+/* azul_batch_score_moves for wide batches: the one-ply table of the reward above, for every legal move of every game in ONE launch, the
+ * games untouched (records, MT19937 words and index, counters).  With me the seat to move, p = `perspective` (a seat 0 .. P-1, or
+ * AZUL_PERSP_MOVER: me) and a an action azul_batch_legal_mask marks 1: scores[g][a] = s[p] - max_{j != p} s[j], s the scores of a copy of
+ * game g after move(*nn_deserialize(a)) (azul.py:118-161, the unchecked move: no next_player, no new round, no draw) and count_score()
+ * on that copy (azul.py:192-295, with the batch's end-bonus switch).  At p = 0 this is phi of the moved copy, at P = 2 the reference's
+ * score[p] - score[1 - p] (game_runner.py:48-50); BEYOND THE REFERENCE for P > 2, as the reward above is.  Any other a: AZUL_SCORE_ILLEGAL.
+ * best[g]: the first legal action, in action order, with the maximal score (np.argmax's rule); -1 when nothing is legal (an ended game,
+ * every source empty -- e.g. before the first new_round).  active_dev (optional): rows of games with 0 are not written at all.
+ * scores_dev and best_dev are each optional, not both.  AZUL_ERR_INVALID before any launch: a NULL batch, both outputs NULL, a perspective
+ * that is neither a seat nor AZUL_PERSP_MOVER, a two-player batch of 128-byte records (the message names azul_batch_score_moves).  It plays
+ * nothing, so a move limit is not refused. */
+int azul_batch_mp_score_moves(azul_batch_t *b, int perspective, const uint8_t *active_dev,
+                              int32_t *scores_dev /*[N][azul_batch_num_actions], optional*/, int32_t *best_dev /*[N], optional*/, void *stream);
 
 /* ---- one method call of the reference's SINGLE-GAME API on one game of a batch -------------------
  * What the Python facade (Azul / GameRunner / RandomAgent of this package, i.e. BASELINE configs[0]: tests/test_azul.py,
