@@ -8,6 +8,8 @@
 //                                        side of the policy rollout -- two games per 64-lane wavefront, state in VGPRs
 //   azul_rules_x.hpp                     P = 2..4 players, D = 5 or 2 P + 1 displays, the extended rule switches (row N4), built from the
 //                                        same wave primitives (half ballots, LDS-crossbar gathers, wall pricing, parallel factory draw)
+//   azul_runner.hpp                      GameRunner.step / reset, the agent step, the policy self-play move and the network-opponent
+//                                        protocol, ONCE for both shapes: templates over the adaptors az2::Env2 / azx::EnvX
 // The __global__ functions are in headers too (azul_selfplay_kernels.hpp; azul_x_kernels.hpp for the rule kernels of the wide record;
 // azul_policy.hpp, azul_rollout2.hpp, azul_learner.hpp), so that the emulation below compiles the kernels themselves; azul_kernels.hip
 // holds the host side.
@@ -28,6 +30,8 @@ typedef int64_t  i64;
 #endif
 #include <hip/hip_runtime.h>
 #define AZ_FN __device__ __forceinline__
+// (member functions: __device__ spelled as the attribute it is -- the lockstep emulation makes the keyword a storage class, which a member cannot take)
+#define AZ_MEMBER_FN __attribute__((device)) __forceinline__
 #define AZ_UNLIKELY(x) __builtin_expect(!!(x), 0)
 
 namespace wv {

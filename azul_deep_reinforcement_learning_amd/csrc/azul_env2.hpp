@@ -1,12 +1,13 @@
-// azul_env2.hpp -- GameRunner on the two-player rule book: GameRunner.step / GameRunner.reset / GameRunner.get_state /
-// RandomAgent.get_a_output / Azul.step with its legality test, for TWO GAMES PER WAVEFRONT on top of azul_selfplay2.hpp's half-uniform
-// rules (state in VGPRs, one game per 32-lane half).  Two users: the env side of the persistent policy rollout (azul_rollout2.hpp calls
+// azul_env2.hpp -- GameRunner on the two-player rule book: GameRunner.get_state / RandomAgent.get_a_output / Azul.step with its legality
+// test / the fresh game of GameRunner.reset, for TWO GAMES PER WAVEFRONT on top of azul_selfplay2.hpp's half-uniform rules (state in VGPRs,
+// one game per 32-lane half), and Env2, the adaptor through which azul_runner.hpp's GameRunner.step / reset protocol runs on them.  Two users: the env side of the persistent policy rollout (azul_rollout2.hpp calls
 // these between its matrix phases) and the two-player rule entries of the C ABI (azul_ops2.hpp).  tests/hostcheck/simt_env2.cpp and
 // simt_ops2.cpp run THIS FILE, unmodified, lane by lane on the CPU against the oracle.
 // Reference lines: azulnet/azul.py:296-313 (step), azulnet/game_runner.py:43-55 (GameRunner.step), :56-72 (get_state), :76-85 (reset),
 // :87-97 (RandomAgent); azulnet/nn_runner.py:17-47.
 #pragma once
 #include "azul_selfplay2.hpp"
+#include "azul_runner.hpp"
 
 namespace az2 {
 
@@ -167,52 +168,14 @@ AZ_FN u32 reset2(G2 &g, u32 first_player, Rng2 &r, u64 margin, const K2 &k)
     return st;
 }
 
-// One env move of policy-driven self-play on a register-resident game: Azul.step (azul.py:296-313) for the current player, the shaped
-// reward of game_runner.py:48-52 per move, done, statistics and the auto-reset of game_runner.py:76-82 (ONE reset site)
-template <bool LID>
-AZ_FN u32 policy_step2(G2 &g, i32 av, const Mask2 &m /* of the current state: the one that was published */, u32 first_player, Rng2 &r, u64 margin,
-                        Counters2 &cnt, const K2 &k, i32 &rew, u32 &dn)
-{
-    rew = 0; dn = 0;
-    // "no action" is legitimate only when nothing is legal (hazard H3)
-    bool stuck = false;
-    if (AZ_UNLIKELY(wave_any(av < 0))) stuck = (av < 0) & (g.eog == 0u) & (mask_count2(m) == 0u);
-    u32 st = ST_OK;
-    bool restart = false;
-    if (!stuck) {
-        st = checked_step2<LID>(g, av, m, r, margin, k);
-        const bool dirty = !(st == ST_ILLEGAL_MOVE || st == ST_GAME_ENDED || st == ST_BAD_ACTION);
-        if (dirty) {
-            g.moves += 1u;
-            const i32 phi = g.wi0 - g.wi1;                             // game_runner.py:48-50 (the what-if caches are current)
-            rew = phi - g.pscore;
-            g.pscore = phi;
-            dn = g.over ? 1u : (st == ST_TRUNCATED ? 3u : 0u);         // is_end_of_game(): the walls, not the record's flag; 3: cut by the move limit
-            restart = dn && (st == ST_OK || st == ST_TRUNCATED);
-        } else if (st == ST_GAME_ENDED) {                               // a finished game handed in: restart the slot, report done
-            dn = 1u;
-            restart = true;
-        }
-    }
-    if (AZ_UNLIKELY(wave_any(stuck | restart))) {
-        if (stuck | restart) {
-            if (stuck) { cnt.stuck_add += 1u; dn = 2u; }
-            else if (st == ST_TRUNCATED) cnt.stuck_add += 1u;          // (a cut episode is no finished game)
-            else if (st == ST_OK) episode_stats2(g, cnt, k.l);         // (a game handed in finished is not counted: st == ST_GAME_ENDED)
-            const bool cut = st == ST_TRUNCATED;
-            u32 st0 = reset2<LID>(g, first_player, r, margin, k);
-            st = stuck ? (st0 ? st0 : (u32)ST_STUCK) : (cut ? (st0 ? st0 : (u32)ST_TRUNCATED) : st0);
-        }
-    }
-    return st;
-}
-
-// GameRunner's opponent loop (game_runner.py:46-47 / :84)
+// GameRunner's opponent loop (game_runner.py:46-47 / :84), the ONE piece of the step protocol that stays per record shape (Env2's
+// opponent_loop member): here the RandomAgent draws BEFORE the end-of-game test and a loop that hits the guard returns ST_OK; the wide
+// loop (azx::opponent_loop_x) tests first and returns ST_STUCK.
 template <bool LID>
 AZ_FN u32 opponent_loop2(G2 &g, Rng2 &r, const Tab2 &T, u64 margin, const K2 &k, bool until_player1_only)
 {
 #pragma unroll 1
-    for (u32 guard = 0; guard < 4096u; guard++) {
+    for (u32 guard = 0; guard < azr::REPLY_GUARD; guard++) {
         Mask2 m;
         legal_mask2(g, k, m);
         const bool keep = until_player1_only ? (g.cur != 1u) : ((g.cur != 1u || mask_count2(m) < 2u) && !g.over);
@@ -227,151 +190,56 @@ AZ_FN u32 opponent_loop2(G2 &g, Rng2 &r, const Tab2 &T, u64 margin, const K2 &k,
     return ST_OK;
 }
 
-// GameRunner.step (game_runner.py:43-55): the agent's move, the opponent's RandomAgent replies, the shaped reward, done.  No reset.
+// ---- the two-player env adaptor of azul_runner.hpp: GameRunner.step / reset and their cut-at-opponent_move() form (azr::policy_step,
+// runner_step, agent_step, net_settle, net_move, net_reset) on a register-resident G2.  References to what the call site
+// holds; `m` is the legal mask of the current state (in: checked_step tests the action against it; out: net_settle leaves the mask of the
+// state left behind).  GameRunner.player_score / move_counter are the record's own g.pscore / g.moves.
 template <bool LID>
-AZ_FN u32 runner_step2(G2 &g, i32 av, const Mask2 &m /* of the current state */, Rng2 &r, const Tab2 &T, u64 margin, const K2 &k, i32 &rew, u32 &dn)
-{
-    rew = 0;
-    dn = g.over ? 1u : 0u;
-    u32 st = checked_step2<LID>(g, av, m, r, margin, k);                // game_runner.py:44
-    if (!st) {
-        g.moves += 1u;                                                  // :45
-        st = opponent_loop2<LID>(g, r, T, margin, k, false);            // :46-47
-        if (!st) {
-            const i32 phi = g.wi0 - g.wi1;                             // :48-50
-            rew = phi - g.pscore;                                      // :51
-            g.pscore = phi;                                            // :52
-            dn = g.over ? 1u : 0u;                                     // :55
-        }
-    }
-    return st;
-}
+struct Env2 {
+    using Mask = Mask2;
+    static constexpr bool MOVE_LIMIT = true;                 // apply_step2 can cut an episode (ST_TRUNCATED)
+    G2 &g;
+    Mask2 &m;
+    const u32 &first_player;
+    Rng2 &r;
+    const Tab2 &tab;
+    const u64 &margin;
+    Counters2 &cnt;
+    const K2 &k;
 
-// One AGENT step of NNRunner.run_episode (nn_runner.py:24-29): GameRunner.step and, when the episode ends, the GameRunner.reset() that
-// opens the next run_episode (nn_runner.py:20 -> game_runner.py:76-82, incl. the opponent's opening moves), so the observation / mask
-// taken afterwards are the next decision's.
-template <bool LID>
-AZ_FN u32 agent_step2(G2 &g, i32 av, const Mask2 &m /* of the current state */, u32 first_player, Rng2 &r, const Tab2 &T, u64 margin,
-                       Counters2 &cnt, const K2 &k, i32 &rew, u32 &dn)
-{
-    u32 st = runner_step2<LID>(g, av, m, r, T, margin, k, rew, dn);
-    const bool dirty = !(st == ST_ILLEGAL_MOVE || st == ST_BAD_ACTION);
-    if (st == ST_STUCK) { cnt.stuck_add += 1u; dn = 2u; rew = 0; }   // hazard H3: nobody can move
-    else if (st == ST_TRUNCATED) { cnt.stuck_add += 1u; dn = 3u; rew = 0; }       // move limit: the episode was cut at the end of a round
-    else if (st == ST_GAME_ENDED) dn = 1u;
-    else if (st == ST_OK && dn) episode_stats2(g, cnt, k.l);
-    if (dirty && dn) {
-        u32 st2 = reset2<LID>(g, first_player, r, margin, k);
-        if (!st2) st2 = opponent_loop2<LID>(g, r, T, margin, k, true);
-        if (st == ST_OK || (st == ST_TRUNCATED && st2)) st = st2;
-    }
-    return st;
-}
-
-// ---- GameRunner with an EXTERNAL opponent (game_runner.py:27-30: GameRunner(opponent=Agent(...)); scripts/run_batch.py:6-10) --------------
-// The reference's GameRunner.step / reset call opponent.get_a_output(...) in a data-dependent loop (game_runner.py:46-47, :84-85).  When the
-// opponent is a network the answer comes from OUTSIDE the rule code (the matrix phases of the rollout kernel, or a separate launch), so the
-// two methods are cut at their opponent_move() calls into a three-state protocol per game:
-//     NET_REPLY    inside GameRunner.step's loop (:46): the opponent moves while (current_player != 1 or player 1 has fewer than two legal
-//                  moves) and the game is not over -- player 1's FORCED moves are the opponent's too
-//     NET_OPENING  inside GameRunner.reset's loop (:84): the opponent moves while current_player != 1
-//     NET_READY    nothing owed: the agent's next decision
-// net_move2 plays the agent's action (:44-45) or one opponent_move() (:37-42) with the action somebody chose on the mask /
-// perspective-rotated observation net_settle2 left; net_settle2 runs the loop conditions, closes the step (:48-55: shaped reward, done,
-// statistics) and opens the next episode (nn_runner.py:20 -> game_runner.py:76-82) -- agent_step2's bookkeeping, statement for statement,
-// with the RandomAgent's draw replaced by "owed".  `m` is always the legal mask of the state left behind.
-enum : u32 { NET_READY = 0, NET_REPLY = 1, NET_OPENING = 2, NET_RESET = 3 /* internal: the next episode's game is due (never stored) */ };
-
-struct NetStep {
-    u32 pending;     // NET_*
-    u32 replies;     // opponent moves played since the agent's action (opening moves of the next episode included)
-    i32 rew;         // valid once `closed`
-    u32 dn;
-    bool closed;     // the agent step's reward / done are final
-    u32 st;          // first status that was not ST_OK
+    AZ_MEMBER_FN void legal_mask(Mask2 &out) const { legal_mask2(g, k, out); }
+    AZ_MEMBER_FN u32 count(const Mask2 &t) const { return mask_count2(t); }
+    AZ_MEMBER_FN u32 count_current() const { return mask_count2(m); }                  // (`m` is the one that was published)
+    AZ_MEMBER_FN u32 checked_step(i32 a) { return checked_step2<LID>(g, a, m, r, margin, k); }
+    AZ_MEMBER_FN void mask_after_refusal() {}                                          // (state untouched: `m` is still its mask)
+    AZ_MEMBER_FN u32 opponent_loop(bool opening) { return opponent_loop2<LID>(g, r, tab, margin, k, opening); }
+    AZ_MEMBER_FN i32 potential() const { return g.wi0 - g.wi1; }                       // (the what-if caches are current)
+    AZ_MEMBER_FN i32 &phi() { return g.pscore; }
+    AZ_MEMBER_FN u32 &moves() { return g.moves; }
+    AZ_MEMBER_FN u32 fresh_game() { return reset2<LID>(g, first_player, r, margin, k); }
+    AZ_MEMBER_FN void episode_stats() { episode_stats2(g, cnt, k.l); }
 };
 
-// The loop conditions.  Leaves ns.pending = NET_REPLY / NET_OPENING (an opponent_move() is owed on the state and mask left behind) or
-// NET_READY.  ONE site each for the episode reset and the legal mask: the rollout kernel inlines this function once.
+// The entry points the kernels call: each builds the adaptor from its arguments and forwards.  They stay because calling the shared
+// functions from the kernels directly (one adaptor per kernel) changed the instructions of 35 of the 110 kernels, with more scratch in
+// some; through these wrappers every kernel compiles to the parent's instruction stream.  (`tab` / `cnt` / `first_player` that an entry
+// does not take are never read on its path.)
 template <bool LID>
-AZ_FN void net_settle2(G2 &g, NetStep &ns, Mask2 &m, u32 first_player, Rng2 &r, u64 margin, Counters2 &cnt, const K2 &k)
-{
-#pragma unroll 1
-    for (u32 pass = 0; pass < 4u; pass++) {
-        if (ns.pending == NET_RESET) {                                          // the next run_episode: nn_runner.py:20 -> game_runner.py:76-82
-            const u32 st2 = reset2<LID>(g, first_player, r, margin, k);
-            if (!ns.st) ns.st = st2;
-            ns.pending = st2 ? (u32)NET_READY : (u32)NET_OPENING;
-            continue;
-        }
-        legal_mask2(g, k, m);
-        if (ns.pending == NET_READY) break;
-        const u32 legal = mask_count2(m);
-        if (ns.pending == NET_REPLY) {
-            const bool keep = (g.cur != 1u || legal < 2u) && !g.over;          // game_runner.py:46
-            if (keep && legal) break;                                           // :47 -- an opponent_move() is owed
-            ns.closed = true;
-            if (keep) {                                                         // nobody can move (hazard H3; an Agent raises IllegalMask, model.py:33-34)
-                cnt.stuck_add += 1u; ns.dn = 2u; ns.rew = 0;
-                if (!ns.st) ns.st = ST_STUCK;
-            } else {
-                const i32 phi = g.wi0 - g.wi1;                                 // :48-50 (the what-if caches are current)
-                ns.rew = phi - g.pscore;                                       // :51
-                g.pscore = phi;                                                // :52
-                ns.dn = g.over ? 1u : 0u;                                      // :55
-                if (ns.dn) episode_stats2(g, cnt, k.l);                        // :53-54
-            }
-            ns.pending = ns.dn ? (u32)NET_RESET : (u32)NET_READY;
-            if (!ns.dn) break;                                                  // (`m` is the mask of this state: the agent's next decision)
-        } else {                                                                // NET_OPENING
-            if (g.cur != 1u && legal) break;                                    // game_runner.py:84-85 -- an opponent_move() is owed
-            if (g.cur != 1u && !ns.st) ns.st = ST_STUCK;
-            ns.pending = NET_READY;
-            break;
-        }
-    }
-}
-
-// One move of the protocol: the AGENT's action of GameRunner.step (game_runner.py:44-45; `agent`) or one opponent_move() (:37-42) of a game
-// that owes one, then the loop conditions.  `m`: in, the legal mask of the current state; out, of the state left behind.
-// An opponent's answer that is not a legal action leaves the game and the debt as they are (the reference lets IllegalMove escape from
-// GameRunner.step); refused / failed agent moves follow agent_step2's bookkeeping.
+AZ_FN u32 policy_step2(G2 &g, i32 av, Mask2 &m, u32 first_player, Rng2 &r, u64 margin, Counters2 &cnt, const K2 &k, i32 &rew, u32 &dn)
+{ const Tab2 tab = {nullptr}; Env2<LID> e{g, m, first_player, r, tab, margin, cnt, k}; return azr::policy_step(e, av, rew, dn); }
+template <bool LID>
+AZ_FN u32 runner_step2(G2 &g, i32 av, Mask2 &m, Rng2 &r, const Tab2 &T, u64 margin, const K2 &k, i32 &rew, u32 &dn)
+{ Counters2 cnt; const u32 fp = 0; Env2<LID> e{g, m, fp, r, T, margin, cnt, k}; return azr::runner_step(e, av, rew, dn); }
+template <bool LID>
+AZ_FN u32 agent_step2(G2 &g, i32 av, Mask2 &m, u32 first_player, Rng2 &r, const Tab2 &T, u64 margin, Counters2 &cnt, const K2 &k, i32 &rew, u32 &dn)
+{ Env2<LID> e{g, m, first_player, r, T, margin, cnt, k}; return azr::agent_step(e, av, rew, dn); }
+using azr::NetStep; using azr::NET_READY; using azr::NET_REPLY; using azr::NET_OPENING; using azr::NET_RESET;
 template <bool LID>
 AZ_FN void net_move2(G2 &g, i32 av, bool agent, Mask2 &m, u32 first_player, Rng2 &r, u64 margin, Counters2 &cnt, const K2 &k, NetStep &ns)
-{
-    if (agent) { ns.pending = NET_READY; ns.replies = 0; ns.rew = 0; ns.dn = g.over ? 1u : 0u; ns.closed = false; ns.st = ST_OK; }
-    const u32 st = checked_step2<LID>(g, av, m, r, margin, k);                 // :44 / :41
-    if (st == ST_OK) {
-        g.moves += 1u;                                                          // :45 / :42
-        if (agent) ns.pending = NET_REPLY; else ns.replies += 1u;
-    } else {
-        if (!ns.st) ns.st = st;
-        if (st == ST_ILLEGAL_MOVE || st == ST_BAD_ACTION) {                     // state untouched
-            if (agent) ns.closed = true;
-            return;
-        }
-        const bool in_step = agent || ns.pending == NET_REPLY;                  // (runner_step2 returning a status: reward 0, done only for GAME_ENDED)
-        ns.pending = NET_READY;
-        if (in_step) {
-            ns.closed = true; ns.rew = 0;
-            ns.dn = st == ST_GAME_ENDED ? 1u : (st == ST_TRUNCATED ? 3u : (agent ? ns.dn : 0u));
-            if (st == ST_TRUNCATED) {                                           // move limit: the episode was cut at the end of a round
-                cnt.stuck_add += 1u;
-                if (!agent) ns.replies += 1u;                                   // (the opponent's move WAS played: the round it ended is scored)
-            }
-            if (ns.dn) ns.pending = NET_RESET;
-        }
-    }
-    net_settle2<LID>(g, ns, m, first_player, r, margin, cnt, k);
-}
-
-// GameRunner.reset() with an external opponent (game_runner.py:76-85): the fresh game, then the opening loop's condition
+{ const Tab2 tab = {nullptr}; Env2<LID> e{g, m, first_player, r, tab, margin, cnt, k}; azr::net_move(e, av, agent, ns); }
 template <bool LID>
 AZ_FN void net_reset2(G2 &g, Mask2 &m, u32 first_player, Rng2 &r, u64 margin, Counters2 &cnt, const K2 &k, NetStep &ns)
-{
-    ns.pending = NET_RESET; ns.replies = 0; ns.rew = 0; ns.dn = 0; ns.closed = false; ns.st = ST_OK;
-    net_settle2<LID>(g, ns, m, first_player, r, margin, cnt, k);
-}
+{ const Tab2 tab = {nullptr}; Env2<LID> e{g, m, first_player, r, tab, margin, cnt, k}; azr::net_reset(e, ns); }
 
 // ---- the one-ply greedy player of the reference's own reward (game_runner.py:48-50; azul_ops2.hpp: score_moves_body2's table) ----------------
 // (score, lowest action) as ONE unsigned key for the half-wave maximum: a score difference lies in (-2^16, 2^16) -- both what-if scores

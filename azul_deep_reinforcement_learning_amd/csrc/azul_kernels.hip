@@ -5,7 +5,8 @@
 // per workgroup for the policy rollout.  A game's board cells sit in the lanes of its half, everything else is replicated across the
 // half ("half-uniform") and the rules run on the vector pipe; the rare paths (factory draw, scoring, episode reset) are ordinary
 // divergent branches between the halves.  The rules exist ONCE per game shape (azul_common.hpp): azul_selfplay2.hpp + azul_env2.hpp
-// for two players, azul_rules_x.hpp for 3 / 4 players and the extended rules.
+// for two players, azul_rules_x.hpp for 3 / 4 players and the extended rules; GameRunner's step protocol on top of them exists once
+// for both (azul_runner.hpp, on the adaptors az2::Env2 / azx::EnvX).
 //
 // Kernels
 //   azul_seed_kernel            one THREAD per game: CPython init_by_array is a strictly sequential 1247-step recurrence
@@ -581,7 +582,7 @@ int azul_batch_agent_step(azul_batch_t *b, const int32_t *actions_dev, const uin
     return launch_op(b, a, stream);
 }
 
-// GameRunner.step / reset with an EXTERNAL opponent, cut at their opponent_move() calls (azul_env2.hpp: NET_*)
+// GameRunner.step / reset with an EXTERNAL opponent, cut at their opponent_move() calls (azul_runner.hpp: NET_*)
 static int net_op(azul_batch_t *b, int op, const int32_t *actions_dev, const uint8_t *active_dev, uint8_t *pending_dev, uint8_t *replies_dev,
                   int32_t *reward_dev, uint8_t *done_dev, uint8_t *status_dev, float *obs_opp_dev, uint8_t *mask_opp_dev, uint32_t *owing_dev, void *stream)
 {

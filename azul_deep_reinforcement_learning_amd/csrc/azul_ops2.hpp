@@ -32,7 +32,7 @@ struct BatchDev {
 enum {
     OP_QUERY = 0, OP_INIT, OP_NEW_ROUND, OP_MOVE, OP_NEXT_PLAYER, OP_COUNT_SCORE, OP_STEP,
     OP_RUNNER_INIT, OP_RUNNER_RESET, OP_RUNNER_STEP, OP_RANDOM_ACTION, OP_SAMPLE_MASK, OP_POLICY_STEP, OP_AGENT_STEP,
-    OP_NET_BEGIN, OP_NET_REPLY, OP_NET_RESET      // GameRunner.step / reset with an EXTERNAL opponent, cut at opponent_move() (azul_env2.hpp: NET_*)
+    OP_NET_BEGIN, OP_NET_REPLY, OP_NET_RESET      // GameRunner.step / reset with an EXTERNAL opponent, cut at opponent_move() (azul_runner.hpp: NET_*)
 };
 
 struct OpArgs {
@@ -166,7 +166,7 @@ AZ_FN void op_body2(const BatchDev &b, const OpArgs &a, u32 pair, u32 (*mt_lds)[
         case OP_NET_REPLY:
         case OP_NET_RESET: {
             // GameRunner.step / reset with an external opponent (game_runner.py:27-30, 37-47, 84-85), one launch per cut: the agent's move,
-            // or one opponent_move() of the games that owe one, or the fresh game -- then the loop condition (azul_env2.hpp: net_settle2)
+            // or one opponent_move() of the games that owe one, or the fresh game -- then the loop condition (azul_runner.hpp: net_settle)
             Mask2 m;
             NetStep ns;
             if (a.op == OP_NET_RESET) {

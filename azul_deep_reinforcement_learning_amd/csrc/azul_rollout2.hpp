@@ -446,7 +446,7 @@ __global__ void __launch_bounds__(64 * PR2_WAVES) azul_policy_rollout2_kernel(Ba
                 }
                 win_rew = l == ((u32)t & 31u) ? ns.rew : win_rew;
                 win_done = l == ((u32)t & 31u) ? ns.dn : win_done;
-                publish((u32)t + 1u, true);                      // net_settle2 left the mask of this state in `m`
+                publish((u32)t + 1u, true);                      // azr::net_settle left the mask of this state in `m`
             }
         } else if constexpr (OPP != 2) {
             pr2_request1(two, rs1, voffA, voffB, preA, preB);    // the next move's layer 1: in flight during the env step
@@ -546,7 +546,7 @@ __global__ void __launch_bounds__(64 * PR2_WAVES) azul_policy_rollout2_kernel(Ba
                 }
                 win_rew = l == ((u32)t & 31u) ? ns.rew : win_rew;
                 win_done = l == ((u32)t & 31u) ? ns.dn : win_done;
-                publish((u32)t + 1u, true);                      // net_settle2 left the mask of this state in `m`
+                publish((u32)t + 1u, true);                      // azr::net_settle left the mask of this state in `m`
             }
         }
     }

@@ -32,7 +32,7 @@
 // RandomAgent game_runner.py:87-97, check_all_valid :113-117, get_state :56-72.
 #pragma once
 #include "azul_selfplay2.hpp"
-#include "azul_env2.hpp"      // NetStep / NET_*: the external-opponent protocol, shared with the P-seat version below
+#include "azul_env2.hpp"      // (which brings azul_runner.hpp: the GameRunner step protocol that EnvX below adapts to the wide record)
 
 namespace azx {
 using namespace az;
@@ -1164,7 +1164,7 @@ AZ_FN void selfplay_body_x(const XBatchDev &b, const XTraj &t, u32 wave_id, u32 
 //
 // What it is: GameRunner.__init__ / step / reset of the reference (azulnet/game_runner.py:23-36, 43-55, 76-85) statement for statement on an
 // Azul(players = P), the agent in seat 0 ("player 1"), every other seat replying with its own RandomAgent draw (:87-97) from the game's
-// stream; plus agent_step2 / policy_step2 of azul_env2.hpp generalised to P seats.  The reference's code is P-generic in every one of these
+// stream -- azr::runner_step / agent_step / policy_step / opponent_loop of azul_runner.hpp on EnvX.  The reference's code is P-generic in every one of these
 // lines except the shaped reward, score[0] - score[1] (:50).  BEYOND THE REFERENCE for P > 2: the potential is
 //     phi = s[0] - max_{j = 1 .. P-1} s[j]      (s: the scores after count_score() on a copy of the game, :48-49)
 // -- the agent's margin over the best opponent; at P = 2 it is the reference's line exactly.
@@ -1360,14 +1360,24 @@ AZ_FN u32 runner_restart_x(GX<P, D> &g, RunX &s, const RulesX &rules, Rng2 &r, u
     return restart_x(g, rules, r, margin, K);
 }
 
+template <u32 P, u32 D>
+AZ_FN void episode_stats_x(const GX<P, D> &g, Counters2 &cnt, u32 l)
+{
+    double fsum = 0.0;
+#pragma unroll
+    for (u32 p = 0; p < P; p++) fsum += (double)g.fps[p];              // first_player_stats.sum(): left to right
+    counters2_episode(cnt, stat_lane(l, g.score[0], g.score[1], g.turn, (double)g.fps[0] / fsum * 100, g.fpen[0], g.mc[0], g.cl[0]));
+}
+
 // the opponents' RandomAgent moves: GameRunner.step's loop (:46-47, `opening` false) or reset's (:84-85, `opening` true).  ST_STUCK when the
-// seat to move has no legal action (random.choices raises in the reference) or after the 4096-move guard of az2::opponent_loop2.
+// seat to move has no legal action (random.choices raises in the reference) or after azr::REPLY_GUARD moves.  (Per record shape, behind EnvX's opponent_loop
+// member: see az2::opponent_loop2 for what differs.)
 template <u32 P, u32 D>
 AZ_FN u32 opponent_loop_x(GX<P, D> &g, RunX &s, const RulesX &rules, const KX<D> &K, Rng2 &r, const Tab2 &T, u64 margin, bool opening)
 {
     const bool tracked = rules.pool != (u32)XPOOL_RANDOM;
 #pragma unroll 1
-    for (u32 guard = 0; guard < 4096u; guard++) {
+    for (u32 guard = 0; guard < azr::REPLY_GUARD; guard++) {
         MaskX<D> m;
         legal_mask_x(g, K, m);
         const u32 L = mask_count_x<D>(m);
@@ -1386,93 +1396,61 @@ AZ_FN u32 opponent_loop_x(GX<P, D> &g, RunX &s, const RulesX &rules, const KX<D>
     return ST_STUCK;
 }
 
-// GameRunner.step (game_runner.py:43-55): the agent's move, the replies, the shaped reward, done.  No reset.
+// ---- the wide env adaptor of azul_runner.hpp: GameRunner.step / reset and their cut-at-opponent_move() form (azr::policy_step,
+// runner_step, agent_step, net_settle, net_move, net_reset) on a register-resident GX and its runner tail.  References to
+// what the call site holds.  `m` is OUT only: checked_step_x computes the mask it tests against, net_settle / net_move leave the legal mask
+// of the state left behind in it.  The potential is potential_x (beyond the reference for P > 2: the margin over the best opponent).
+template <u32 P, u32 D>
+struct EnvX {
+    using Mask = MaskX<D>;
+    static constexpr bool MOVE_LIMIT = false;                // wide batches have no move limit: no move ends in ST_TRUNCATED
+    GX<P, D> &g;
+    RunX &s;
+    MaskX<D> &m;
+    const RulesX &rules;
+    const KX<D> &K;
+    Rng2 &r;
+    const Tab2 &tab;
+    const u64 &margin;
+    Counters2 &cnt;
+
+    AZ_MEMBER_FN void legal_mask(MaskX<D> &out) const { legal_mask_x(g, K, out); }
+    AZ_MEMBER_FN u32 count(const MaskX<D> &t) const { return mask_count_x<D>(t); }
+    AZ_MEMBER_FN u32 count_current() const
+    {
+        MaskX<D> t;
+        legal_mask_x(g, K, t);
+        return mask_count_x<D>(t);
+    }
+    AZ_MEMBER_FN u32 checked_step(i32 a) { return checked_step_x(g, rules, K, r, margin, a); }
+    AZ_MEMBER_FN void mask_after_refusal() { legal_mask_x(g, K, m); }           // (state untouched; `m` was never its mask)
+    AZ_MEMBER_FN u32 opponent_loop(bool opening) { return opponent_loop_x(g, s, rules, K, r, tab, margin, opening); }
+    AZ_MEMBER_FN i32 potential() const { return potential_x(g, rules, K); }
+    AZ_MEMBER_FN i32 &phi() { return s.phi; }
+    AZ_MEMBER_FN u32 &moves() { return s.moves; }
+    AZ_MEMBER_FN u32 fresh_game() { return runner_restart_x(g, s, rules, r, margin, K); }
+    AZ_MEMBER_FN void episode_stats() { episode_stats_x(g, cnt, K.k.l); }
+};
+
+// The entry points the kernels call: each builds the adaptor and forwards (why they stay: az2's wrappers in azul_env2.hpp)
 template <u32 P, u32 D>
 AZ_FN u32 runner_step_x(GX<P, D> &g, RunX &s, i32 av, const RulesX &rules, const KX<D> &K, Rng2 &r, const Tab2 &T, u64 margin, i32 &rew, u32 &dn)
-{
-    rew = 0;
-    dn = g.over ? 1u : 0u;
-    u32 st = checked_step_x(g, rules, K, r, margin, av);               // :44
-    if (!st) {
-        s.moves += 1u;                                                 // :45
-        st = opponent_loop_x(g, s, rules, K, r, T, margin, false);     // :46-47
-        if (!st) {
-            const i32 phi = potential_x(g, rules, K);                  // :48-50 (beyond the reference for P > 2: margin over the best opponent)
-            rew = phi - s.phi;                                         // :51
-            s.phi = phi;                                               // :52
-            dn = g.over ? 1u : 0u;                                     // :55
-        }
-    }
-    return st;
-}
-
-template <u32 P, u32 D>
-AZ_FN void episode_stats_x(const GX<P, D> &g, Counters2 &cnt, u32 l)
-{
-    double fsum = 0.0;
-#pragma unroll
-    for (u32 p = 0; p < P; p++) fsum += (double)g.fps[p];              // first_player_stats.sum(): left to right
-    counters2_episode(cnt, stat_lane(l, g.score[0], g.score[1], g.turn, (double)g.fps[0] / fsum * 100, g.fpen[0], g.mc[0], g.cl[0]));
-}
-
-// One AGENT step of NNRunner.run_episode (nn_runner.py:24-29) = az2::agent_step2 for P seats: GameRunner.step, and when the episode ends its
-// statistics and the GameRunner.reset() that opens the next one (incl. the opening replies).  done 2: nobody could move (slot restarted).
+{ MaskX<D> m; Counters2 cnt; EnvX<P, D> e{g, s, m, rules, K, r, T, margin, cnt}; return azr::runner_step(e, av, rew, dn); }
 template <u32 P, u32 D>
 AZ_FN u32 agent_step_x(GX<P, D> &g, RunX &s, i32 av, const RulesX &rules, const KX<D> &K, Rng2 &r, const Tab2 &T, u64 margin, Counters2 &cnt,
                        i32 &rew, u32 &dn)
-{
-    u32 st = runner_step_x(g, s, av, rules, K, r, T, margin, rew, dn);
-    const bool dirty = !(st == ST_ILLEGAL_MOVE || st == ST_BAD_ACTION);
-    if (st == ST_STUCK) { cnt.stuck_add += 1u; dn = 2u; rew = 0; }
-    else if (st == ST_GAME_ENDED) dn = 1u;
-    else if (st == ST_OK && dn) episode_stats_x(g, cnt, K.k.l);
-    if (dirty && dn) {
-        u32 st2 = runner_restart_x(g, s, rules, r, margin, K);         // game_runner.py:79-82
-        if (!st2) st2 = opponent_loop_x(g, s, rules, K, r, T, margin, true);      // :84-85
-        if (st == ST_OK) st = st2;
-    }
-    return st;
-}
-
-// One env move of policy-driven self-play (the policy plays every seat) = az2::policy_step2 for P seats: Azul.step for the current player,
-// the per-move shaped reward (seat-0-centric, as above), done, statistics and the auto-reset (a fresh game, no opening replies).
+{ MaskX<D> m; EnvX<P, D> e{g, s, m, rules, K, r, T, margin, cnt}; return azr::agent_step(e, av, rew, dn); }
 template <u32 P, u32 D>
 AZ_FN u32 policy_step_x(GX<P, D> &g, RunX &s, i32 av, const RulesX &rules, const KX<D> &K, Rng2 &r, u64 margin, Counters2 &cnt, i32 &rew, u32 &dn)
-{
-    rew = 0; dn = 0;
-    bool stuck = false;
-    if (AZ_UNLIKELY(wave_any(av < 0))) {                               // "no action" is legitimate only when nothing is legal (hazard H3)
-        MaskX<D> m;
-        legal_mask_x(g, K, m);
-        stuck = (av < 0) & (g.eog == 0u) & (mask_count_x<D>(m) == 0u);
-    }
-    u32 st = ST_OK;
-    bool restart = false;
-    if (!stuck) {
-        st = checked_step_x(g, rules, K, r, margin, av);
-        const bool dirty = !(st == ST_ILLEGAL_MOVE || st == ST_GAME_ENDED || st == ST_BAD_ACTION);
-        if (dirty) {
-            s.moves += 1u;
-            const i32 phi = potential_x(g, rules, K);
-            rew = phi - s.phi;
-            s.phi = phi;
-            dn = g.over ? 1u : 0u;
-            restart = dn && st == ST_OK;
-        } else if (st == ST_GAME_ENDED) {                              // a finished game handed in: restart the slot, report done
-            dn = 1u;
-            restart = true;
-        }
-    }
-    if (AZ_UNLIKELY(wave_any(stuck | restart))) {
-        if (stuck | restart) {
-            if (stuck) { cnt.stuck_add += 1u; dn = 2u; }
-            else if (st == ST_OK) episode_stats_x(g, cnt, K.k.l);
-            const u32 st0 = runner_restart_x(g, s, rules, r, margin, K);
-            st = stuck ? (st0 ? st0 : (u32)ST_STUCK) : st0;
-        }
-    }
-    return st;
-}
+{ MaskX<D> m; const Tab2 tab = {nullptr}; EnvX<P, D> e{g, s, m, rules, K, r, tab, margin, cnt}; return azr::policy_step(e, av, rew, dn); }
+using azr::NetStep; using azr::NET_READY; using azr::NET_REPLY; using azr::NET_OPENING; using azr::NET_RESET;
+template <u32 P, u32 D>
+AZ_FN u32 net_move_x(GX<P, D> &g, RunX &s, i32 av, bool agent, MaskX<D> &m, const RulesX &rules, const KX<D> &K, Rng2 &r, u64 margin,
+                     Counters2 &cnt, NetStep &ns)
+{ const Tab2 tab = {nullptr}; EnvX<P, D> e{g, s, m, rules, K, r, tab, margin, cnt}; return azr::net_move(e, av, agent, ns); }
+template <u32 P, u32 D>
+AZ_FN void net_reset_x(GX<P, D> &g, RunX &s, MaskX<D> &m, const RulesX &rules, const KX<D> &K, Rng2 &r, u64 margin, Counters2 &cnt, NetStep &ns)
+{ const Tab2 tab = {nullptr}; EnvX<P, D> e{g, s, m, rules, K, r, tab, margin, cnt}; azr::net_reset(e, ns); }
 
 // One runner call on games 2 pair, 2 pair + 1 of the batch: the op, the record / tail / stream / counters written back, then the queries
 template <u32 P, u32 D>
@@ -1542,92 +1520,12 @@ AZ_FN void runner_body_x(const XBatchDev &b, const XRun &a, u32 pair, u32 (*mt_l
     if (a.player && l == 0u) a.player[gi] = (uint8_t)g.cur;
 }
 
-// ---- GameRunner for P seats with an EXTERNAL opponent (game_runner.py:27-30, 37-47, 84-85): az2::net_settle2 / net_move2 / net_reset2 of
-// azul_env2.hpp generalised to P seats, statement for statement, on the wide record.  Every seat other than the agent's is the opponent: each
-// opponent_move() -- the other seats' replies, the agent's FORCED moves (:46) and the opening moves of reset() (:84-85) -- is answered
-// outside the rule code (PolicyRollout's PyTorch GEMMs + azul_policy_head_n on the mover-perspective observation) and handed back by the next
-// launch.  The loop conditions are opponent_loop_x's, the potential is potential_x's, restarts and statistics are runner_restart_x /
-// episode_stats_x, and the runner's tail (phi, move counter: bytes 228..231) is kept as runner_body_x keeps it.  No move limit (wide batches
-// have none), no reply guard: the host bounds its reply rounds.  net_body_x is the body of azul_x_net_kernel; tests/hostcheck/simt_net_x.cpp
-// runs it, unmodified, under the lockstep emulation against tests/mp_net_model.py.
-template <u32 P, u32 D>
-AZ_FN void net_settle_x(GX<P, D> &g, RunX &s, NetStep &ns, MaskX<D> &m, const RulesX &rules, const KX<D> &K, Rng2 &r, u64 margin, Counters2 &cnt)
-{
-#pragma unroll 1
-    for (u32 pass = 0; pass < 4u; pass++) {
-        if (ns.pending == NET_RESET) {                                          // the next run_episode: nn_runner.py:20 -> game_runner.py:76-82
-            const u32 st2 = runner_restart_x(g, s, rules, r, margin, K);
-            if (!ns.st) ns.st = st2;
-            ns.pending = st2 ? (u32)NET_READY : (u32)NET_OPENING;
-            continue;
-        }
-        legal_mask_x(g, K, m);
-        if (ns.pending == NET_READY) break;
-        const u32 legal = mask_count_x<D>(m);
-        if (ns.pending == NET_REPLY) {
-            const bool keep = (g.cur != 1u || legal < 2u) && !g.over;          // game_runner.py:46
-            if (keep && legal) break;                                           // :47 -- an opponent_move() is owed
-            ns.closed = true;
-            if (keep) {                                                         // nobody can move (hazard H3)
-                cnt.stuck_add += 1u; ns.dn = 2u; ns.rew = 0;
-                if (!ns.st) ns.st = ST_STUCK;
-            } else {
-                const i32 phi = potential_x(g, rules, K);                      // :48-50 (beyond the reference for P > 2: margin over the best opponent)
-                ns.rew = phi - s.phi;                                          // :51
-                s.phi = phi;                                                   // :52
-                ns.dn = g.over ? 1u : 0u;                                      // :55
-                if (ns.dn) episode_stats_x(g, cnt, K.k.l);                     // :53-54
-            }
-            ns.pending = ns.dn ? (u32)NET_RESET : (u32)NET_READY;
-            if (!ns.dn) break;                                                  // (`m` is the mask of this state: the agent's next decision)
-        } else {                                                                // NET_OPENING
-            if (g.cur != 1u && legal) break;                                    // game_runner.py:84-85 -- an opponent_move() is owed
-            if (g.cur != 1u && !ns.st) ns.st = ST_STUCK;
-            ns.pending = NET_READY;
-            break;
-        }
-    }
-}
-
-// The agent's action of GameRunner.step (:44-45; `agent`) or one opponent_move() (:37-42), then the loop conditions; `m` out: the legal mask
-// of the state left behind.  Returns the status of the move itself: an answer that is not legal (ST_ILLEGAL_MOVE / ST_BAD_ACTION) leaves
-// the game and the debt as they are.
-template <u32 P, u32 D>
-AZ_FN u32 net_move_x(GX<P, D> &g, RunX &s, i32 av, bool agent, MaskX<D> &m, const RulesX &rules, const KX<D> &K, Rng2 &r, u64 margin,
-                     Counters2 &cnt, NetStep &ns)
-{
-    if (agent) { ns.pending = NET_READY; ns.replies = 0; ns.rew = 0; ns.dn = g.over ? 1u : 0u; ns.closed = false; ns.st = ST_OK; }
-    const u32 st = checked_step_x(g, rules, K, r, margin, av);                 // :44 / :41
-    if (st == ST_OK) {
-        s.moves += 1u;                                                          // :45 / :42
-        if (agent) ns.pending = NET_REPLY; else ns.replies += 1u;
-    } else {
-        if (!ns.st) ns.st = st;
-        if (st == ST_ILLEGAL_MOVE || st == ST_BAD_ACTION) {                     // state untouched
-            if (agent) ns.closed = true;
-            legal_mask_x(g, K, m);
-            return st;
-        }
-        const bool in_step = agent || ns.pending == NET_REPLY;                  // (runner_step_x returning a status: reward 0, done only for GAME_ENDED)
-        ns.pending = NET_READY;
-        if (in_step) {
-            ns.closed = true; ns.rew = 0;
-            ns.dn = st == ST_GAME_ENDED ? 1u : (agent ? ns.dn : 0u);
-            if (ns.dn) ns.pending = NET_RESET;
-        }
-    }
-    net_settle_x(g, s, ns, m, rules, K, r, margin, cnt);
-    return st;
-}
-
-// GameRunner.reset() with an external opponent (game_runner.py:76-85): the fresh game, then the opening loop's condition
-template <u32 P, u32 D>
-AZ_FN void net_reset_x(GX<P, D> &g, RunX &s, MaskX<D> &m, const RulesX &rules, const KX<D> &K, Rng2 &r, u64 margin, Counters2 &cnt, NetStep &ns)
-{
-    ns.pending = NET_RESET; ns.replies = 0; ns.rew = 0; ns.dn = 0; ns.closed = false; ns.st = ST_OK;
-    net_settle_x(g, s, ns, m, rules, K, r, margin, cnt);
-}
-
+// ---- GameRunner for P seats with an EXTERNAL opponent (game_runner.py:27-30, 37-47, 84-85): azr::net_settle / net_move / net_reset
+// (azul_runner.hpp) on EnvX, the wide record.  Every seat other than the agent's is the opponent: each opponent_move() -- the other seats'
+// replies, the agent's FORCED moves (:46) and the opening moves of reset() (:84-85) -- is answered outside the rule code (PolicyRollout's
+// PyTorch GEMMs + azul_policy_head_n on the mover-perspective observation) and handed back by the next launch.  The runner's tail (phi, move
+// counter: bytes 228..231) is kept as runner_body_x keeps it.  No reply guard: the host bounds its reply rounds.  net_body_x is the body of
+// azul_x_net_kernel; tests/hostcheck/simt_net_x.cpp runs it, unmodified, under the lockstep emulation against tests/mp_net_model.py.
 enum { XNET_BEGIN = 0, XNET_REPLY, XNET_RESET };
 
 struct XNet {
@@ -1688,7 +1586,7 @@ AZ_FN void net_body_x(const XBatchDev &b, const XNet &a, u32 pair, u32 (*mt_lds)
         }
         owes = ns.pending != NET_READY;
     }
-    // what the opponent is handed: the state and legal mask (left in `m` by net_settle_x) from the mover's perspective (game_runner.py:38-39)
+    // what the opponent is handed: the state and legal mask (left in `m` by azr::net_settle) from the mover's perspective (game_runner.py:38-39)
     if (owes) {
         if (a.mask) store_mask_bytes_x<D>(m, a.mask + (size_t)gi * Dim<D>::NA, l);
         if (a.obs) observe_x(g, mex(g), a.obs + (size_t)gi * obs_size<P, D>(), l);

@@ -1,6 +1,6 @@
 // TEST-ONLY stand-in for <hip/hip_runtime.h> when the product's device headers are compiled by g++ for the lockstep wave
 // emulation (tests/hostcheck/simt/simt.hpp): HIP's device qualifiers become host spellings, the gfx950 builtins the headers
-// call become the emulator's functions.  Only what csrc/azul_common.hpp, azul_tables.hpp, azul_selfplay2.hpp, azul_env2.hpp,
+// call become the emulator's functions.  Only what csrc/azul_common.hpp, azul_tables.hpp, azul_selfplay2.hpp, azul_env2.hpp, azul_runner.hpp,
 // azul_rules_x.hpp, azul_ops2.hpp, azul_policy.hpp, azul_rollout2.hpp and azul_learner.hpp use.
 #pragma once
 #include <math.h>

@@ -160,7 +160,7 @@ def test_product_sources_carry_no_experiment_switches_and_no_kernel_selection_by
             assert names <= allowed, (os.path.basename(f), m.group(0).strip())
     assert sorted(os.path.basename(f) for f in glob.glob(os.path.join(csrc, "*"))) == [
         "azul_common.hpp", "azul_env2.hpp", "azul_kernels.hip", "azul_learner.hpp", "azul_ops2.hpp", "azul_policy.hpp", "azul_rollout2.hpp",
-        "azul_rules_x.hpp", "azul_selfplay2.hpp", "azul_selfplay_kernels.hpp", "azul_tables.hpp", "azul_x_kernels.hpp"]
+        "azul_rules_x.hpp", "azul_runner.hpp", "azul_selfplay2.hpp", "azul_selfplay_kernels.hpp", "azul_tables.hpp", "azul_x_kernels.hpp"]
 
 
 def test_call_block_layout_is_the_headers(tmp_path):

@@ -236,6 +236,7 @@ def run_vs(L, first, pool, n, T, seed0, warm, slots=8, argmax=False, move_limit=
             q = np.float32(o["reward"][t, g]) + np.float32(0.9) * (np.float32(0) if o["done"][t, g] else q)
             want[t] = q
         assert np.array_equal(o["returns"][:, g], want), tag
+    run_vs.last_done = o["done"]
     return (ops, episodes, forced, opening, cuts) if move_limit else (ops, episodes, forced, opening)
 
 
@@ -257,6 +258,20 @@ def test_network_opponent_in_the_rollout_kernel_replays_through_the_oracle():
     assert ops > 5000 and episodes >= 1 and forced >= 1
     ops, episodes, forced, opening = run_vs(L, first, pool, n=16, T=30, seed0=500, warm=50)
     assert episodes >= 10 and forced >= 8 and opening >= 3
+
+
+def test_network_opponent_window_ending_on_an_episode_end_reports_no_status():
+    """The launch status is the LAST step's.  A window whose last step ends an episode also opens the next one (the opponent's opening
+    moves while player 1 is not to move, game_runner.py:84-85): the opening loop that ends with player 1 to move leaves no status --
+    AZUL_STUCK is for an opening in which the seat to move has no legal action.  (run_vs asserts the status of every game.)"""
+    L = load_vs()
+    first, pool = RULES["lid_randomfirst"]
+    run_vs(L, first, pool, n=16, T=30, seed0=500, warm=50)
+    ends = [t for t in range(30) if (run_vs.last_done[t] == 1).any()]
+    assert ends
+    T = ends[0] + 1                                                         # the same window, cut right after its first episode end
+    ops, episodes, forced, opening = run_vs(L, first, pool, n=16, T=T, seed0=500, warm=50)
+    assert episodes >= 1 and (run_vs.last_done[T - 1] == 1).any()
 
 
 def test_network_opponent_argmax_and_the_random_pool():
