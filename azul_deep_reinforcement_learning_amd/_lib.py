@@ -105,6 +105,8 @@ SIGNATURES = {
     "azul_batch_mp_policy_rollout": (_i, [_vp, _i, _i, C.POINTER(NetWeights), _i, _i, _i, _u64, _u64, _vp, C.POINTER(RolloutBuffers), C.c_float, _vp]),
     "azul_batch_mp_policy_rollout_vs": (_i, [_vp, _i, C.POINTER(NetWeights), C.POINTER(NetWeights), _i, _i, _i, _u64, _u64, _u64, _vp, _i,
                                              C.POINTER(RolloutBuffers), C.c_float, _vp]),
+    "azul_batch_mp_policy_rollout_greedy": (_i, [_vp, _i, C.POINTER(NetWeights), _i, _i, _i, _u64, _u64, _vp, _i, C.POINTER(RolloutBuffers),
+                                                 C.c_float, _vp]),
     "azul_batch_net_step_begin": (_i, [_vp] * 11),
     "azul_batch_net_step_reply": (_i, [_vp] * 11),
     "azul_batch_net_reset_begin": (_i, [_vp] * 8),

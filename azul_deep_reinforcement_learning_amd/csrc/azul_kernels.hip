@@ -715,7 +715,7 @@ static int fail_in(const char *who, const char *what)
 
 // The one host path of a window launch: every azul_batch_[mp_]policy_rollout* entry packs its arguments and calls this.  `wide` = an _mp_
 // entry (the azul_x_* kernels), otherwise the two-player kernel; opp = 0 the policy moves for every seat, 1 RandomAgent seats, 2 the
-// `opponent` net, 3 the one-ply greedy player (two-player kernel only).  Where the two families differ the condition says so: those
+// `opponent` net, 3 the one-ply greedy player (az2::greedy_pick2 / the greedy_margin seats of azx::greedy_pick_x).  Where the two families differ the condition says so: those
 // differences are behaviour (include/azul_hip.h).
 static int rollout_window(azul_batch_t *b, const char *who, bool wide, int n_steps, int opp, const azul_net_weights_t *agent,
                           const azul_net_weights_t *opponent, NetShape shape, DrawKeys keys, const azul_rollout_buffers_t *out, float gamma,
@@ -724,11 +724,12 @@ static int rollout_window(azul_batch_t *b, const char *who, bool wide, int n_ste
     const bool net = opp == 2;
     if (!b || n_steps < 0 || !agent || !out) return fail_in(who, "bad arguments");
     if (net && !opponent) return fail_in(who, "no opponent (the entry without _vs plays without one)");
-    if (opp == 3 && b->x)
+    if (opp == 3 && !wide && b->x)
         return fail_in(who, "a wide batch (three / four players or extended rules): the greedy player maximises the two-player reward of "
                             "game_runner.py:48-50");
     if (wide != b->x)
         return fail_in(who, wide ? (net ? "a two-player batch of 128-byte records: use azul_batch_policy_rollout_vs"
+                                        : opp == 3 ? "a two-player batch of 128-byte records: use azul_batch_policy_rollout_greedy"
                                         : "a two-player batch of 128-byte records: use azul_batch_policy_rollout")
                                  : "the policy entries are compiled for the reference's two-player game (ActorCritic(136, 180): 180 actions, 136 "
                                    "observations; game_runner.py:50) -- not for 3 / 4 players or extended rules");
@@ -737,7 +738,7 @@ static int rollout_window(azul_batch_t *b, const char *who, bool wide, int n_ste
         if (shape.hidden != PF_HID) return fail_in(who, "only hidden size 180 is compiled in (agent and opponent)");
         if (shape.inputs != azul_batch_obs_size(b) || shape.actions != azul_batch_num_actions(b))
             return fail_in(who, "num_inputs / num_actions must be the batch's azul_batch_obs_size / azul_batch_num_actions");
-        if (net && max_replies < 1) return fail_in(who, "max_replies must be at least 1");
+        if ((net || opp == 3) && max_replies < 1) return fail_in(who, "max_replies must be at least 1");
     } else if (shape.inputs != PF_IN || shape.hidden != PF_HID || shape.actions != PF_ACT)
         return fail_in(who, "only ActorCritic(136, 180, hidden 180) is compiled in");
     if (!agent->w1t || !agent->b1 || !agent->w2c || !agent->b2c || !agent->w2a_t || !agent->b2a || !out->obs || !out->mask || !out->player ||
@@ -777,6 +778,8 @@ static int rollout_window(azul_batch_t *b, const char *who, bool wide, int n_ste
         const azx::XBatchDev xb = xdev(b);
         const u32 id_base = b->d.id_base;
         if (net) AZ_X_DISPATCH(b, hipLaunchKernelGGL((azul_x_policy_rollout_vs_kernel<PP, DD>), grid, block, 0, st, xb, W, a, id_base, (u32)max_replies));
+        else if (opp == 3)
+            AZ_X_DISPATCH(b, hipLaunchKernelGGL((azul_x_policy_rollout_kernel<PP, DD, 3>), grid, block, 0, st, xb, W, a, id_base, (u32)max_replies));
         else if (opp) AZ_X_DISPATCH(b, hipLaunchKernelGGL((azul_x_policy_rollout_kernel<PP, DD, 1>), grid, block, 0, st, xb, W, a, id_base));
         else AZ_X_DISPATCH(b, hipLaunchKernelGGL((azul_x_policy_rollout_kernel<PP, DD, 0>), grid, block, 0, st, xb, W, a, id_base));
         HIP_TRY(hipGetLastError());
@@ -851,6 +854,16 @@ int azul_batch_mp_policy_rollout_vs(azul_batch_t *b, int n_steps, const azul_net
     BATCH_GUARD(b, stream);
     return rollout_window(b, "azul_batch_mp_policy_rollout_vs", true, n_steps, 2, agent, opponent, {num_inputs, hidden_size, num_actions},
                           {seed, opp_seed, counter, counter_dev}, out, gamma, max_replies, stream);
+}
+
+/* GameRunner with greedy_margin seats for wide batches inside one launch per window (azul_x_policy_rollout_kernel<P, D, 3>) */
+int azul_batch_mp_policy_rollout_greedy(azul_batch_t *b, int n_steps, const azul_net_weights_t *agent, int num_inputs, int hidden_size, int num_actions,
+                                        uint64_t seed, uint64_t counter, uint64_t *counter_dev, int max_replies, const azul_rollout_buffers_t *out,
+                                        float gamma, void *stream)
+{
+    BATCH_GUARD(b, stream);
+    return rollout_window(b, "azul_batch_mp_policy_rollout_greedy", true, n_steps, 3, agent, nullptr, {num_inputs, hidden_size, num_actions},
+                          {seed, 0, counter, counter_dev}, out, gamma, max_replies, stream);
 }
 
 /* the wide shapes of azul_learner.hpp: (obs_size, num_actions) of p3_d5, p4_d5, p3_d7, p4_d9; hidden 180 */

@@ -607,7 +607,8 @@ __global__ void __launch_bounds__(64 * PR2_WAVES) azul_policy_rollout2_kernel(Ba
 // in its 32-lane halves, the same waves run the network on the f32 matrix cores between the env phases -- on azul_rules_x.hpp's P-seat
 // GameRunner.  Per move: env phase -> layer 1 -> layer 2 -> head (+ critic, trajectory stores) -> env phase.
 //   env       OPP 0: azx::policy_step_x (the policy moves for every seat, observation from the mover); OPP 1: azx::agent_step_x (GameRunner with
-//             RandomAgent seats, observation from seat 0); OPP 2: GameRunner with a NETWORK opponent (azx::net_move_x, see there).  The game is loaded from / stored to its 256-byte record in LDS around each env
+//             RandomAgent seats, observation from seat 0); OPP 2: GameRunner with a NETWORK opponent (azx::net_move_x, see there); OPP 3: the same
+//             protocol answered by azx::greedy_pick_x inside the wave.  The game is loaded from / stored to its 256-byte record in LDS around each env
 //             phase exactly as runner_body_x does around each launch (stored only when the step touched it), so nothing of the game is live
 //             across the matrix phases; the MT19937 stream (LDS) and the counters stay open for the window.
 //   matrix    hidden = relu(obs @ w1t + b1) over 23 column tiles of 16 (360 columns), K = obs_size zero-padded in LDS to a multiple of 32;
@@ -697,7 +698,8 @@ AZ_FN void px_chain(const float *ap, const float *const (&bp)[NT], u32 bstride, 
 
 // One window of T moves for the workgroup's 16 games (blockIdx.x); 512 threads.  OPP: 0 the policy moves for every seat, 1 GameRunner with
 // RandomAgent seats, 2 GameRunner with a network opponent (a.Wopp; O: PXOpp in LDS, max_replies: reply rounds per step before the loop gives
-// up).  The returns are not written here (azul_batch_mp_policy_rollout / _vs run azul_discounted_returns behind the launch).
+// up), 3 GameRunner with greedy_margin seats (azx::greedy_pick_x: no weights, no matrix phase, no draw, no PXOpp; max_replies as OPP 2).
+// The returns are not written here (azul_batch_mp_policy_rollout / _vs / _greedy run azul_discounted_returns behind the launch).
 template <u32 P, u32 D, int OPP>
 AZ_FN void x_policy_rollout_body(const azx::XBatchDev &b, const PolicyWeights &W, const RolloutArgs &a, u32 id_base, PXShared<P, D> &S,
                                  PXOpp<D> *O = nullptr, u32 max_replies = 0)
@@ -986,6 +988,56 @@ AZ_FN void x_policy_rollout_body(const azx::XBatchDev &b, const PolicyWeights &W
                 st_last = ns.st;
                 publish(g, K, (u32)t + 1u);
             }
+        } else if constexpr (OPP == 3) {
+            // GameRunner.step against GREEDY_MARGIN seats (game_runner.py:43-55 with :37-42 answered by azx::greedy_pick_x), as
+            // azul_policy_rollout2_kernel<LID, 3> does it: OPP 1's control flow -- no barrier, no matrix phase -- on OPP 2's protocol.  The
+            // answer is a pure function of the game this half holds, so the reply rounds stay inside the wave and the game, its runner tail
+            // and its NetStep stay in registers for the step: loaded from LDS once, stored once.  Pass 0 plays the agent's action, pass
+            // j > 0 reply j - 1: while EITHER half owes an opponent_move() both halves price their candidates (the loop is wave-uniform; a
+            // half without a game holds an empty mask) and only the half that owes plays; its sibling's game, stream and counters are not
+            // touched.  A wave without a live game skips all of it.
+            if (az2::wave_any(live)) {
+                azx::KX<D> K;
+                azx::kx_init(K);
+                azx::GX<P, D> g;
+                azx::gx_load(g, rec, l);                 // (a half without a game: a row of zeros)
+                azx::prime_x(g, K);
+                azx::RunX s;
+                azx::runx_load(s, rec);
+                az2::NetStep ns = {az2::NET_READY, 0u, 0, 0u, false, (u32)ST_OK};
+                const bool end_bonus = b.rules.end_bonus != 0u;
+                bool touched = false;                    // a refused move leaves the record as it was (OPP 2)
+#pragma unroll 1
+                for (u32 j = 0; j <= max_replies; j++) {
+                    const bool go = live && (j == 0u || ns.pending != az2::NET_READY);
+                    if (!az2::wave_any(go)) break;
+                    i32 av = S.act[gl];
+                    azx::MaskX<D> m;                     // (per pass: a mask carried through the move would cost its registers there)
+                    if (j > 0u) {
+                        azx::legal_mask_x(g, K, m);      // the mask net_move_x left; a half without a game is handed an empty one
+                        if (!live) m = azx::MaskX<D>{};
+                        av = azx::greedy_pick_x(g, m, K, end_bonus);
+                        if (go && l == 0u && a.opp_action && j - 1u < (u32)a.opp_slots)
+                            a.opp_action[((size_t)t * (size_t)a.opp_slots + (j - 1u)) * n + gi] = av;
+                    }
+                    if (go) {
+                        const u32 st = azx::net_move_x(g, s, av, j == 0u, m, b.rules, K, r, b.draw_margin, cnt, ns);
+                        touched = touched | !(st == ST_ILLEGAL_MOVE || st == ST_BAD_ACTION);
+                    }
+                }
+                if (live) {
+                    // close the step: a game still owing at the cap gives up as azul_x_policy_rollout_vs_kernel does (AZUL_STUCK unless the
+                    // step already has a status; the debt ends with the step's NetStep); then slot t + 1 from perspective 0
+                    if (ns.pending != az2::NET_READY && !ns.st) ns.st = ST_STUCK;
+                    if (touched) azx::store_runner_x(g, s, rec, l);
+                    if (l == 0u) {
+                        a.reward[row_t + gi] = ns.rew; a.done[row_t + gi] = (uint8_t)ns.dn;
+                        if (a.opp_replies) a.opp_replies[row_t + gi] = (uint8_t)(ns.replies < 255u ? ns.replies : 255u);
+                    }
+                    st_last = ns.st;
+                    publish(g, K, (u32)t + 1u);
+                }
+            }
         } else if (live) {
             // one runner call of azul_x_runner_kernel (XRUN_AGENT_STEP / XRUN_POLICY_STEP) on the record in LDS
             azx::KX<D> K;
@@ -1030,11 +1082,13 @@ AZ_FN void x_policy_rollout_body(const azx::XBatchDev &b, const PolicyWeights &W
 
 // The persistent policy rollout for wide batches (azul_batch_mp_policy_rollout; x_policy_rollout_body above): 16 games per
 // workgroup of eight waves for a whole window, the workgroup's LDS declared here.
+// OPP 3 (azul_batch_mp_policy_rollout_greedy): max_replies bounds the reply rounds of a step; the other two do not read it.
 template <u32 P, u32 D, int OPP>
-__global__ void __launch_bounds__(64 * PR2_WAVES) azul_x_policy_rollout_kernel(azx::XBatchDev b, PolicyWeights W, RolloutArgs a, u32 id_base)
+__global__ void __launch_bounds__(64 * PR2_WAVES) azul_x_policy_rollout_kernel(azx::XBatchDev b, PolicyWeights W, RolloutArgs a, u32 id_base,
+                                                                                u32 max_replies = 0)
 {
     __shared__ PXShared<P, D> S;
-    x_policy_rollout_body<P, D, OPP>(b, W, a, id_base, S);
+    x_policy_rollout_body<P, D, OPP>(b, W, a, id_base, S, nullptr, max_replies);
 }
 
 // ... with a NETWORK opponent (azul_batch_mp_policy_rollout_vs; OPP 2 of x_policy_rollout_body): the reply rounds inside the window, the

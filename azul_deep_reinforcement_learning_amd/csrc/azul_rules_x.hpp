@@ -1270,6 +1270,29 @@ struct XScoreMoves {
 // LOWEST action is the maximum.  0 = no move.
 AZ_FN u32 score_key_x(i32 score, u32 a) { return ((u32)(score + 65536) << 9) | (511u - a); }
 
+// The two steps score_moves_body_x and greedy_pick_x share (az2: whatif_after2).  rest_scores_x: the seats a move by `me` leaves alone,
+// ONCE per game -- s[p] after count_score_x on a copy (potential_x's call; read when p is not the mover) and the best of the seats that are
+// neither p nor the mover (P = 2 from the other seat's view: nobody else -- below every score).  whatif_after_x: the mover's score after
+// ONE candidate, do_move_x on `t`, a copy of the game the CALLER makes per candidate (azul.py:118-161: a move changes only the mover's
+// lines and floor, the sources and the lid, so the copy is those few registers; made inside this function it costs the table kernel one
+// VGPR per shape), and its own chain of count_score_x.
+template <u32 P, u32 D>
+AZ_FN void rest_scores_x(const GX<P, D> &g, u32 p, u32 me, bool end_bonus, const KX<D> &K, i32 &sp, i32 &rest)
+{
+    rest = -(1 << 20);
+    GX<P, D> c = g;
+    count_score_x(c, false, end_bonus, K);
+    sp = pick<P>(c.score, p);
+#pragma unroll
+    for (u32 j = 0; j < P; j++) rest = ((j == p) | (j == me) | (c.score[j] <= rest)) ? rest : c.score[j];
+}
+template <u32 P, u32 D>
+AZ_FN i32 whatif_after_x(GX<P, D> &t, u32 s, u32 c, u32 row, u32 sh /* 8 me */, u32 wall_me, i32 score_me, bool end_bonus, const KX<D> &K)
+{
+    do_move_x(t, s, c, row, false, K);                                                              // azul.py:118-161
+    return seat_score_x((t.cpk >> sh) & 0xffu, wall_me, score_me, (t.floors >> sh) & 0xffu, end_bonus, K.k);
+}
+
 template <u32 P, u32 D>
 AZ_FN void score_moves_body_x(const XBatchDev &b, const XScoreMoves &a, u32 pair)
 {
@@ -1286,15 +1309,8 @@ AZ_FN void score_moves_body_x(const XBatchDev &b, const XScoreMoves &a, u32 pair
     const bool end_bonus = b.rules.end_bonus != 0u;
     const u32 me = mex(g);
     const u32 p = (u32)a.persp < P ? (u32)a.persp : me;
-    // the seats a move leaves alone: s[p] (used when p is not the mover) and the best of the seats that are neither p nor the mover
-    i32 sp, rest = -(1 << 20);                       // (P = 2 from the other seat's view: nobody else -- below every score)
-    {
-        GX<P, D> c = g;
-        count_score_x(c, false, end_bonus, K);
-        sp = pick<P>(c.score, p);
-#pragma unroll
-        for (u32 j = 0; j < P; j++) rest = ((j == p) | (j == me) | (c.score[j] <= rest)) ? rest : c.score[j];
-    }
+    i32 sp, rest;
+    rest_scores_x(g, p, me, end_bonus, K, sp, rest);
     const u32 wall_me = pick<P>(g.wall, me);
     const i32 score_me = pick<P>(g.score, me);
     const u32 sh = 8u * me;
@@ -1325,8 +1341,7 @@ AZ_FN void score_moves_body_x(const XBatchDev &b, const XScoreMoves &a, u32 pair
                 const bool legal = ((((NW > 1 && qw) ? whi : wlo) >> ql) & 1u) != 0u;
                 if (!wave_any(legal)) continue;
                 GX<P, D> t = g;
-                do_move_x(t, s, c, row, false, K);                                                  // azul.py:118-161
-                const i32 v = seat_score_x((t.cpk >> sh) & 0xffu, wall_me, score_me, (t.floors >> sh) & 0xffu, end_bonus, K.k);
+                const i32 v = whatif_after_x(t, s, c, row, sh, wall_me, score_me, end_bonus, K);
                 const i32 val = p == me ? v - rest : sp - (v > rest ? v : rest);
                 const bool mine = legal & (l == ql);
 #pragma unroll
@@ -1349,6 +1364,50 @@ AZ_FN void score_moves_body_x(const XBatchDev &b, const XScoreMoves &a, u32 pair
         const u32 top = hmax(key);                   // (a lane without an action holds 0)
         if (l == 0u) a.best[gi] = top ? (i32)(511u - (top & 511u)) : -1;
     }
+}
+
+// The greedy_margin seat's answer on a register-resident game and its legal mask `m`, the wide twin of az2::greedy_pick2: the first legal
+// action with the maximal s[mover] - max_{j != mover} s[j] after do_move_x + count_score_x -- score_moves_body_x's table at persp >= P,
+// through the same per-candidate step, untouched-seat scores and key -- and -1 when nothing is legal.  Reads the game and `m` only; draws
+// nothing.  The candidate loop is wave-uniform (a candidate neither half's mask holds is skipped by a ballot; one that only ONE half's
+// mask holds runs on both and the other half discards it): call it with the whole wave active, a half without a game with an empty mask.
+template <u32 P, u32 D>
+AZ_FN i32 greedy_pick_x(const GX<P, D> &g, const MaskX<D> &m, const KX<D> &K, bool end_bonus)
+{
+    constexpr u32 S = Dim<D>::S, Q = Dim<D>::Q, NW = Dim<D>::NW;
+    const u32 l = K.k.l, me = mex(g);
+    i32 sp, rest;
+    rest_scores_x(g, me, me, end_bonus, K, sp, rest);
+    const u32 wall_me = pick<P>(g.wall, me);
+    const i32 score_me = pick<P>(g.score, me);
+    const u32 sh = 8u * me;
+    u32 lo[6], hi[6];                                // (through an empty asm: see score_moves_body_x)
+#pragma unroll
+    for (u32 r = 0; r < 6u; r++) {
+        lo[r] = m.m[r][0]; hi[r] = m.m[r][NW - 1];
+        asm volatile("" : "+v"(lo[r]), "+v"(hi[r]));
+    }
+    u32 key = 0;
+#pragma unroll 1
+    for (u32 row = 0; row < 6u; row++) {
+        u32 wlo = lo[0], whi = hi[0];
+#pragma unroll
+        for (u32 r = 1; r < 6u; r++) { wlo = row == r ? lo[r] : wlo; whi = row == r ? hi[r] : whi; }
+#pragma unroll 1
+        for (u32 c = 0; c < 5u; c++) {
+#pragma unroll 1
+            for (u32 s = 0; s < S; s++) {
+                const u32 q = S * c + s, qw = q >> 5, ql = q & 31u;
+                const bool legal = ((((NW > 1 && qw) ? whi : wlo) >> ql) & 1u) != 0u;
+                if (!wave_any(legal)) continue;
+                GX<P, D> t = g;
+                const i32 v = whatif_after_x(t, s, c, row, sh, wall_me, score_me, end_bonus, K);
+                key = (legal & (l == ql)) ? umax(key, score_key_x(v - rest, Q * row + q)) : key;
+            }
+        }
+    }
+    const u32 top = hmax(key);                       // (a lane without an action holds 0)
+    return top ? (i32)(511u - (top & 511u)) : -1;
 }
 
 // a fresh Azul(players = P, rules) + new_round(), player_score = move_counter = 0 (game_runner.py:23-36 / :79-82)

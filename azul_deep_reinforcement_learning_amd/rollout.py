@@ -46,7 +46,8 @@ class PolicyRollout:
     def __init__(self, policy, n_games=4096, parts=1, rules={"first_player": "Random", "tile_pool": "Lid"}, seed_base=0,
                  device=None, window=32, use_graph=True, fused_head=True, sample_seed=0x5EED, opponent=None, fused_mlp=True, persistent=False,
                  action_selection="Distribution", kweights=None, game_id_base=None, ring=1, opponent_selection="Distribution",
-                 opponent_seed=None, opponent_trace=0, move_limit=0, players=2, fused_wide=False, fused_opponent=False, wide_ring=1):
+                 opponent_seed=None, opponent_trace=0, move_limit=0, players=2, fused_wide=False, fused_opponent=False, wide_ring=1,
+                 fused_seats=False):
         """opponent=None: the policy moves for both players (flat self-play, one record per env move).
         opponent="random": the reference's training setup -- the policy is player 1 of GameRunner, the opponent a RandomAgent
         inside the env step (game_runner.py:43-47); one record per AGENT step, observations from the agent's perspective.
@@ -64,7 +65,8 @@ class PolicyRollout:
         (game_runner.py:48-50), one launch per reply round in place of the network's forward; records as with "random"; `opponent_trace`
         records opp_action (opp_logp stays 0) and opp_replies; persistent and use_graph resolve to False, ring to 1; at most MAX_REPLY_ROUNDS
         reply rounds per step or opening (a game with nothing legal would owe its move for ever: RuntimeError).
-        opponent="greedy_margin" (wide batches only, on the per-cut path: fused_wide / fused_opponent raise ValueError): the same scripted
+        opponent="greedy_margin" (wide batches only; on the per-cut path unless fused_seats=True, see there: fused_wide / fused_opponent
+        without it raise ValueError): the same scripted
         player for three / four seats and extended rules -- every other seat answers every opponent_move() with
         MultiplayerAzul.greedy_action, the move that maximises the MOVER's margin over the best other seat after move + count_score
         (azul_batch_mp_score_moves; beyond the reference for P > 2, like the wide reward), through MultiplayerAzul.net_* exactly as a
@@ -107,9 +109,18 @@ class PolicyRollout:
         (rings >= 2 with one part) feed A2CLearner.update_from_rollout.  The same trajectories, records, streams and counters as the per-cut
         path, opponent_trace included (opp_action of the slots a step's replies filled; the other slots keep -1).  The opening at
         construction stays on the per-cut path.  One difference: a game that still owes an opponent_move() after 64 replies of one step
-        ends the step with status AZUL_STUCK (unless the step already has a status) instead of raising RuntimeError."""
+        ends the step with status AZUL_STUCK (unless the step already has a status) instead of raising RuntimeError.
+        `fused_seats=True` (opponent="greedy_margin" on a wide batch, with fused_wide=True, fused_head and ActorCritic(env.obs_size,
+        env.num_actions, hidden 180); anything else, fused_opponent included, raises ValueError): the greedy_margin seats answer inside the
+        wide window kernel (azul_batch_mp_policy_rollout_greedy) -- one launch per window and part, no reply launches, no host
+        synchronisation and no opponent weights; use_graph resolves to False, wide_ring and opponent_trace work as with the other wide
+        window kernels (opp_action of the slots a step's replies filled; the other slots keep -1, opp_logp stays 0).  The same
+        trajectories, records, streams and counters as the per-cut path.  The opening at construction stays on the per-cut path; openings
+        after episodes that end inside a window are the kernel's.  One difference, the window kernels' usual one: a game that still owes an
+        opponent_move() after MAX_REPLY_ROUNDS replies of one step ends the step with status AZUL_STUCK (unless the step already has a
+        status) instead of raising RuntimeError."""
         self._check_modes(policy, n_games, parts, rules, window, use_graph, fused_head, opponent, fused_mlp, persistent, action_selection, ring,
-                          opponent_selection, opponent_trace, move_limit, players, fused_wide, fused_opponent, wide_ring)
+                          opponent_selection, opponent_trace, move_limit, players, fused_wide, fused_opponent, wide_ring, fused_seats)
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         self.policy = policy.to(self.device).eval()
         self.windows_played = 0
@@ -133,7 +144,7 @@ class PolicyRollout:
                 torch.cuda.synchronize(self.device)
 
     def _check_modes(self, policy, n_games, parts, rules, window, use_graph, fused_head, opponent, fused_mlp, persistent, action_selection, ring,
-                     opponent_selection, opponent_trace, move_limit, players, fused_wide, fused_opponent, wide_ring):
+                     opponent_selection, opponent_trace, move_limit, players, fused_wide, fused_opponent, wide_ring, fused_seats=False):
         """Every refusal of the constructor, and the flags the modes resolve to -- from the arguments and the modules' shapes alone: no
         device and no library call, so nothing is allocated before a refusal."""
         assert n_games % parts == 0
@@ -155,9 +166,20 @@ class PolicyRollout:
         if margin and not self.wide:
             raise ValueError("opponent=\"greedy_margin\" maximises the margin over the best other seat on batches of three / four players or "
                              "extended rules; a two-player reference batch has opponent=\"greedy\"")
-        if margin and (fused_wide or fused_opponent):
+        self.fused_seats = bool(fused_seats)
+        if self.fused_seats:
+            if not margin:
+                raise ValueError("fused_seats=True plays the greedy_margin seats of a wide batch inside its window kernel: it needs "
+                                 "opponent=\"greedy_margin\" (three / four players or extended rules)")
+            if fused_opponent:
+                raise ValueError("fused_seats=True has no opponent network: fused_opponent=True is the network opponent's switch (or the "
+                                 "two-player opponent=\"greedy\")")
+            if not fused_wide:
+                raise ValueError("fused_seats=True answers inside the wide window kernel: it needs fused_wide=True")
+        elif margin and (fused_wide or fused_opponent):
             raise ValueError("opponent=\"greedy_margin\" answers on the per-cut path (one azul_batch_mp_score_moves launch per reply round): "
-                             "the wide window kernel does not play it (fused_wide=False, fused_opponent=False)")
+                             "the wide window kernel does not play it (fused_wide=False, fused_opponent=False) unless fused_seats=True asks "
+                             "for it (with fused_wide=True)")
         if self.wide and move_limit:
             raise ValueError("no move limit for batches of three / four players or extended rules")
         self.fused_wide = bool(fused_wide)
@@ -488,6 +510,9 @@ class PolicyRollout:
                                                            C.byref(out), C.c_float(gamma), st))
         elif self.opponent == "greedy":                     # the greedy player's answers inside the env phase
             L.check(L.lib.azul_batch_policy_rollout_greedy(env._h, T, C.byref(wa), *shape, self.sample_seed, 0, ctr, C.byref(out), C.c_float(gamma), st))
+        elif self.opponent == "greedy_margin":              # the greedy_margin seats' answers inside the env phase (fused_seats)
+            L.check(L.lib.azul_batch_mp_policy_rollout_greedy(env._h, T, C.byref(wa), *shape, self.sample_seed, 0, ctr, int(self.MAX_REPLY_ROUNDS),
+                                                              C.byref(out), C.c_float(gamma), st))
         elif self.wide:
             L.check(L.lib.azul_batch_mp_policy_rollout(env._h, T, rnd, C.byref(wa), *shape, self.sample_seed, 0, ctr, C.byref(out), C.c_float(gamma), st))
         else:                                               # this entry takes the same pointers one by one

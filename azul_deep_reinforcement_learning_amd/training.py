@@ -38,7 +38,7 @@ class BatchedTrainer:
     def __init__(self, policy, n_games=4096, window=32, parts=1, learning_rate=3e-4, gamma=0.99, seed_base=0, sample_seed=0x5EED,
                  rules={"first_player": "Random", "tile_pool": "Lid"}, device=None, use_graph=True, persistent=True, results_dir="results",
                  ring=3, opponent="random", opponent_refresh=0, move_limit=0, players=2, fused_wide=False,
-                 fused_opponent=False, fused_learner=False):
+                 fused_opponent=False, fused_learner=False, fused_seats=False):
         """ring: trajectory windows kept (persistent rollout with one part): with ring >= 2 every step of every episode is trained
         exactly once (episodes straddle windows; an episode may span ring - 1 window boundaries), like NNRunner.train.
         opponent: "random" (GameRunner's default RandomAgent, the reference's scripts/training.py), a module (GameRunner(opponent=Agent(...)),
@@ -50,7 +50,10 @@ class BatchedTrainer:
         persistent rollout with `ring` windows, the learner on update_from_rollout (every step of every finished episode trained exactly once),
         checkpoints that carry the ring and still nothing for the opponent; or "greedy_margin" (players = 3 / 4 or extended rules): the
         same scripted player for wide batches (PolicyRollout(players=P, opponent="greedy_margin"): every other seat maximises its margin over
-        the best other seat), on the per-cut path only, the learner on update_from_windows, nothing in the checkpoint for it.
+        the best other seat), on the per-cut path, the learner on update_from_windows, nothing in the checkpoint for it -- or, with
+        fused_wide=True and fused_seats=True (hidden 180), inside the wide window kernel (PolicyRollout(fused_seats=True)): one launch per
+        window, the learner as for any fused_wide rollout (fused_learner=True trains whole episodes from the ring), still nothing in the
+        checkpoint for the opponent.
         move_limit > 0: BatchedAzul.set_move_limit (beyond the reference: a game that would never end is cut, done = 3; its steps are trained like an
         episode that ended there, the return chain starts at the cut).
         players = 3 / 4 (or extended-rule keys in `rules`): PolicyRollout(players=...) on MultiplayerAzul parts -- the policy is
@@ -86,7 +89,8 @@ class BatchedTrainer:
                                      kweights=None if (wide and not wide_fused) else self.learner.kweights(dev),
                                      ring=ring if (persistent and parts == 1) else 1,
                                      move_limit=move_limit, players=players, fused_wide=fused_wide,
-                                     fused_opponent=fused_opponent, wide_ring=ring if (wide_fused and parts == 1) else 1)
+                                     fused_opponent=fused_opponent, wide_ring=ring if (wide_fused and parts == 1) else 1,
+                                     fused_seats=fused_seats)
         self.gamma = gamma
         self.results_dir = results_dir
         self.batch = 0

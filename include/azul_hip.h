@@ -445,8 +445,8 @@ int azul_batch_policy_rollout_vs(azul_batch_t *b, int n_steps, const azul_net_we
  * the call can be captured in a HIP graph.  Bit-identical to the per-cut entries (azul_batch_net_step_begin / _step_reply) driven with
  * azul_batch_score_moves' `best`, with one difference: a game that still owes an opponent_move() after 64 replies of one step ends the
  * step with status AZUL_STUCK (unless the step already has a status), as azul_batch_policy_rollout_vs does.
- * AZUL_ERR_INVALID before any launch: a wide batch (three / four players or extended rules), a shape other than (136, 180, 180), a NULL
- * agent or out. */
+ * AZUL_ERR_INVALID before any launch: a wide batch (three / four players or extended rules: those play their greedy_margin seats inside
+ * the window through azul_batch_mp_policy_rollout_greedy), a shape other than (136, 180, 180), a NULL agent or out. */
 int azul_batch_policy_rollout_greedy(azul_batch_t *b, int n_steps, const azul_net_weights_t *agent, int num_inputs, int hidden_size, int num_actions,
                                      uint64_t seed, uint64_t counter, uint64_t *counter_dev, const azul_rollout_buffers_t *out, float gamma,
                                      void *stream);
@@ -484,6 +484,23 @@ int azul_batch_mp_policy_rollout(azul_batch_t *b, int n_steps, int opponent_rand
 int azul_batch_mp_policy_rollout_vs(azul_batch_t *b, int n_steps, const azul_net_weights_t *agent, const azul_net_weights_t *opponent,
                                     int num_inputs, int hidden_size, int num_actions, uint64_t seed, uint64_t opp_seed, uint64_t counter,
                                     uint64_t *counter_dev, int max_replies, const azul_rollout_buffers_t *out, float gamma, void *stream);
+/* azul_batch_mp_policy_rollout with GREEDY_MARGIN seats (azul_batch_policy_rollout_greedy for wide batches): the protocol of
+ * azul_batch_mp_policy_rollout_vs with every opponent_move() -- the other seats' replies, the agent's forced moves, after an episode end the
+ * next episode's openings -- answered by `best` of azul_batch_mp_score_moves at AZUL_PERSP_MOVER: the first legal action that maximises the
+ * MOVER's s[me] - max_{j != me} s[j] after move + count_score (beyond the reference for P > 2, as the reward is).  The answer needs no
+ * weights, no matrix phase and no draw: the wave that holds the game computes it inside the env phase, so the reply rounds of a step cost
+ * no barrier and no launch; a reply consumes no MT19937 word (only new rounds and restarts do) and no Philox key.  A game that still owes
+ * after max_replies replies of one step gives up as in azul_batch_mp_policy_rollout_vs: the step ends with status AZUL_STUCK unless it
+ * already has a status, and the window goes on.  Layouts, the agent's draw and the returns as azul_batch_mp_policy_rollout; trace:
+ * out->opp_replies [T][N] (optional) the opponent moves played inside each step, saturated at 255, out->opp_action [T][opp_slots][N]
+ * (optional) reply j of a step for j < opp_slots of the games that owed it (slots beyond a step's replies are not written); out->opp_logp is
+ * never written.  No host synchronisation and no allocation.  Results: bit-identical to the per-cut path (azul_batch_mp_net_step_begin /
+ * _step_reply driven with azul_batch_mp_score_moves' best) wherever the agent network's sums are exact.  AZUL_ERR_INVALID before any launch:
+ * a two-player batch of 128-byte records (the message names azul_batch_policy_rollout_greedy), a move limit, hidden_size != 180,
+ * num_inputs / num_actions not the batch's, obs or mask not 4-byte aligned, max_replies < 1, a trace with opp_slots <= 0. */
+int azul_batch_mp_policy_rollout_greedy(azul_batch_t *b, int n_steps, const azul_net_weights_t *agent, int num_inputs, int hidden_size,
+                                        int num_actions, uint64_t seed, uint64_t counter, uint64_t *counter_dev, int max_replies,
+                                        const azul_rollout_buffers_t *out, float gamma, void *stream);
 /* The same protocol one launch per cut, for opponents evaluated OUTSIDE the library (any network as PyTorch modules, or azul_policy_forward
  * on a second weight set): GameRunner.step / reset are cut at their opponent_move() calls.  pending_dev (uint8 [N], in / out) holds per
  * game 0 = nothing owed (the agent's next decision), 1 = an opponent_move() is owed inside GameRunner.step's loop (game_runner.py:46-47),
