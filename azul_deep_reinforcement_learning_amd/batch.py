@@ -8,6 +8,8 @@ azulnet/azul.py), every call is one kernel launch over all games through the C A
 PyTorch is used for device memory and streams only.
 """
 import ctypes as C
+import functools
+import types
 
 import numpy as np
 import torch
@@ -105,7 +107,18 @@ def _dev_view(ptr, shape, typestr, device):
     return torch.as_tensor(_DevArray(ptr, shape, typestr), device=device)
 
 
+@functools.lru_cache(maxsize=None)
+def _runner_family(prefix):
+    """The GameRunner / net-protocol entries of one family (`prefix` + name), bound once: the per-move path looks nothing up by name."""
+    return types.SimpleNamespace(**{k: getattr(L.lib, prefix + k) for k in (
+        "runner_init", "runner_reset", "runner_step", "score_preview", "score_moves", "policy_step", "agent_step", "net_step_begin",
+        "net_step_reply", "net_reset_begin")})
+
+
 class BatchedAzul:
+    ENTRY_PREFIX = "azul_batch_"          # the GameRunner family of this class in the C ABI (MultiplayerAzul: "azul_batch_mp_")
+    PERSP_TO_MOVE = L.PERSP_CURRENT       # "whoever moves", as this family's entries spell it (MultiplayerAzul: PERSP_MOVER)
+
     def __init__(self, n_games, rules={"first_player": "Random", "tile_pool": "Lid"}, device=None, seed=None, players=2, ext_rules=None):
         """players = 3 or 4: the reference's Azul(players=...) (five displays, azul.py:19).  Extended rules (beyond the reference,
         "parity unpinned") through the rules dict (parse_ext_rules: "displays": "2P+1", "bonuses": "end", "short_deal", "finite_bag")
@@ -125,6 +138,7 @@ class BatchedAzul:
         self.rules.update(ext_rules_dict(self.ext))
         self.wide = self.players != 2 or self.ext != 0
         self.record_dtype = RECORD_NP_DTYPE if self.wide else RECORD_DTYPE
+        self._gr = _runner_family(self.ENTRY_PREFIX)
         self._h = C.c_void_p()
         with torch.cuda.device(self.device):
             L.check(L.lib.azul_batch_create_rules(C.byref(self._h), self.n, self.players, first, pool, self.ext))
@@ -260,23 +274,31 @@ class BatchedAzul:
         return s
 
     # -- GameRunner methods, batched --------------------------------------------------------------
+    # The entries of this family (runner_*, score_*, policy_step / agent_step, net_*) are the class's: ENTRY_PREFIX + name, bound once in
+    # __init__ (self._gr).  The prefix belongs to the CLASS, not to self.wide: a plain BatchedAzul keeps calling the two-player entries for a
+    # wide batch and the library refuses them in its own words; MultiplayerAzul is the P-seat family.
+    def _status(self):
+        return torch.zeros(self.n, dtype=torch.uint8, device=self.device)
+
     def runner_init(self, active=None):
-        st = torch.zeros(self.n, dtype=torch.uint8, device=self.device)
-        L.check(L.lib.azul_batch_runner_init(self._h, _ptr(self._dev(active, torch.uint8)), _ptr(st), self._stream()))
+        """GameRunner.__init__ (game_runner.py:23-36): a fresh Azul + new_round(), player_score = move_counter = 0."""
+        st = self._status()
+        L.check(self._gr.runner_init(self._h, _ptr(self._dev(active, torch.uint8)), _ptr(st), self._stream()))
         return st
 
     def reset(self, active=None):
-        st = torch.zeros(self.n, dtype=torch.uint8, device=self.device)
-        L.check(L.lib.azul_batch_runner_reset(self._h, _ptr(self._dev(active, torch.uint8)), _ptr(st), self._stream()))
+        """GameRunner.reset (game_runner.py:76-85): a fresh game, then the opponent (every other seat) moves while current_player != 1."""
+        st = self._status()
+        L.check(self._gr.runner_reset(self._h, _ptr(self._dev(active, torch.uint8)), _ptr(st), self._stream()))
         return st
 
     def step(self, actions, active=None):
-        """GameRunner.step for every game -> (reward int32[N], done bool[N], status uint8[N])."""
+        """GameRunner.step (game_runner.py:43-55) for every game -> (reward int32[N], done bool[N], status uint8[N])."""
         a = self._dev(actions, torch.int32)
         reward = torch.zeros(self.n, dtype=torch.int32, device=self.device)
         done = torch.zeros(self.n, dtype=torch.uint8, device=self.device)
-        st = torch.zeros(self.n, dtype=torch.uint8, device=self.device)
-        L.check(L.lib.azul_batch_runner_step(self._h, _ptr(a), _ptr(self._dev(active, torch.uint8)), _ptr(reward), _ptr(done), _ptr(st), self._stream()))
+        st = self._status()
+        L.check(self._gr.runner_step(self._h, _ptr(a), _ptr(self._dev(active, torch.uint8)), _ptr(reward), _ptr(done), _ptr(st), self._stream()))
         return reward, done.bool(), st
 
     def get_state(self, perspective=0, out=None):
@@ -304,29 +326,32 @@ class BatchedAzul:
         return a
 
     def score_preview(self):
+        """The reward's potential (phi) of the current state for every game (int32[N])."""
         p = self._new((self.n,), torch.int32)
-        L.check(L.lib.azul_batch_score_preview(self._h, _ptr(p), self._stream()))
+        L.check(self._gr.score_preview(self._h, _ptr(p), self._stream()))
         return p
 
-    def score_moves(self, perspective=L.PERSP_CURRENT, active=None, scores=None, best=None):
-        """The one-ply table of GameRunner.step's reward in one launch, the games untouched: scores [N][180] int32, for every legal
-        action score[p] - score[1 - p] after move + count_score on a copy of the game (game_runner.py:48-50; p = `perspective`: 0, 1 or
-        PERSP_CURRENT, the player to move), L.SCORE_ILLEGAL elsewhere; best [N] int32, the first legal action with the maximal score
-        (-1: nothing is legal).  `scores` / `best`: preallocated device tensors to write into; rows of games whose `active` is 0 are
-        not written (fresh outputs start as SCORE_ILLEGAL / -1).  Two-player reference batches only.  Returns (scores, best)."""
+    def score_moves(self, perspective=None, active=None, scores=None, best=None):
+        """The one-ply table of GameRunner.step's reward in one launch, the games untouched: scores [N][num_actions] int32, for every legal
+        action score[p] - score[1 - p] after move + count_score on a copy of the game (game_runner.py:48-50; p = `perspective`: a seat, or
+        PERSP_TO_MOVE -- the default -- the player to move), L.SCORE_ILLEGAL elsewhere; best [N] int32, the first legal action with the
+        maximal score (-1: nothing is legal).  `scores` / `best`: preallocated device tensors to write into; rows of games whose `active`
+        is 0 are not written (fresh outputs start as SCORE_ILLEGAL / -1).  This class: two-player reference batches only (MultiplayerAzul:
+        the margin s[p] - max_{j != p} s[j], p a seat 0 .. P-1).  Returns (scores, best)."""
         if scores is None:
-            scores = torch.full((self.n, L.NUM_ACTIONS), L.SCORE_ILLEGAL, dtype=torch.int32, device=self.device)
+            scores = torch.full((self.n, self.num_actions), L.SCORE_ILLEGAL, dtype=torch.int32, device=self.device)
         if best is None:
             best = torch.full((self.n,), -1, dtype=torch.int32, device=self.device)
-        L.check(L.lib.azul_batch_score_moves(self._h, int(perspective), _ptr(self._dev(active, torch.uint8)), _ptr(scores), _ptr(best),
-                                             self._stream()))
+        L.check(self._gr.score_moves(self._h, int(self.PERSP_TO_MOVE if perspective is None else perspective),
+                                     _ptr(self._dev(active, torch.uint8)), _ptr(scores), _ptr(best), self._stream()))
         return scores, best
 
     def greedy_action(self, active=None, out=None):
-        """The one-ply greedy player of the reference's reward: for every game the move that maximises the mover's score difference after
-        move + count_score (score_moves' `best` from the mover's perspective; -1: nothing is legal).  `out`: a preallocated int32 [N]."""
+        """The one-ply greedy player of that reward: for every game the move that maximises the mover's score difference (MultiplayerAzul:
+        its margin over the best other seat) after move + count_score (score_moves' `best` from the mover's perspective; -1: nothing is
+        legal).  `out`: a preallocated int32 [N]."""
         best = torch.full((self.n,), -1, dtype=torch.int32, device=self.device) if out is None else out
-        L.check(L.lib.azul_batch_score_moves(self._h, L.PERSP_CURRENT, _ptr(self._dev(active, torch.uint8)), None, _ptr(best), self._stream()))
+        L.check(self._gr.score_moves(self._h, self.PERSP_TO_MOVE, _ptr(self._dev(active, torch.uint8)), None, _ptr(best), self._stream()))
         return best
 
     # -- policy-driven self-play (config 3) ----------------------------------------------------------
@@ -339,23 +364,23 @@ class BatchedAzul:
         L.check(L.lib.azul_batch_observe_all(self._h, int(perspective), _ptr(obs), _ptr(mask), _ptr(player), self._stream()))
         return obs, mask, player
 
-    def policy_step(self, actions, reward, done, status, obs_next, mask_next, player_next, perspective=L.PERSP_CURRENT, active=None):
-        """One fused env move with caller-chosen actions (all arguments are preallocated device tensors)."""
-        L.check(L.lib.azul_batch_policy_step(self._h, _ptr(actions), _ptr(self._dev(active, torch.uint8)), _ptr(reward), _ptr(done),
-                                             _ptr(status), int(perspective), _ptr(obs_next), _ptr(mask_next), _ptr(player_next),
-                                             self._stream()))
+    def policy_step(self, actions, reward, done, status, obs_next, mask_next, player_next, perspective=None, active=None):
+        """One fused env move for the player to move with caller-chosen actions (the policy plays every seat): reward, done, statistics and
+        auto-reset, then the next observation (default: from whoever moves next), mask and player; all preallocated device tensors."""
+        L.check(self._gr.policy_step(self._h, _ptr(actions), _ptr(self._dev(active, torch.uint8)), _ptr(reward), _ptr(done), _ptr(status),
+                                     int(self.PERSP_TO_MOVE if perspective is None else perspective), _ptr(obs_next), _ptr(mask_next),
+                                     _ptr(player_next), self._stream()))
 
     def agent_step(self, actions, reward, done, status, obs_next, mask_next, player_next=None, perspective=0, active=None):
-        """One AGENT step of NNRunner.run_episode (GameRunner.step incl. the opponent's replies; GameRunner.reset() when
-        the episode ends) + the next decision's observation / mask; all arguments are preallocated device tensors."""
-        L.check(L.lib.azul_batch_agent_step(self._h, _ptr(actions), _ptr(self._dev(active, torch.uint8)), _ptr(reward), _ptr(done),
-                                            _ptr(status), int(perspective), _ptr(obs_next), _ptr(mask_next), _ptr(player_next),
-                                            self._stream()))
+        """One AGENT step of NNRunner.run_episode (GameRunner.step incl. the opponent's replies; at the end of an episode its statistics and
+        GameRunner.reset() with the opening replies) + the next decision's observation / mask / player; all preallocated device tensors."""
+        L.check(self._gr.agent_step(self._h, _ptr(actions), _ptr(self._dev(active, torch.uint8)), _ptr(reward), _ptr(done), _ptr(status),
+                                    int(perspective), _ptr(obs_next), _ptr(mask_next), _ptr(player_next), self._stream()))
 
     # -- GameRunner with an external (network) opponent, cut at its opponent_move() calls (game_runner.py:27-30, 37-47, 84-85) ------
     def net_state(self):
         """Preallocated device tensors of the protocol: pending / replies [N] u8, owing [1] (int32 view of the ABI's uint32), the
-        opponent's observation [N][136] / mask [N][180] and its answer [N]."""
+        opponent's observation [N][obs_size] / mask [N][num_actions] and its answer [N]."""
         d = self.device
         return {"pending": torch.zeros(self.n, dtype=torch.uint8, device=d), "replies": torch.zeros(self.n, dtype=torch.uint8, device=d),
                 "owing": torch.zeros(1, dtype=torch.int32, device=d), "obs": torch.zeros(self.n, self.obs_size, device=d),
@@ -365,18 +390,18 @@ class BatchedAzul:
     def net_step_begin(self, actions, net, reward, done, status):
         """The agent's move of GameRunner.step (game_runner.py:44-45) for every game, then the loop condition (:46): net["pending"] says
         who owes an opponent_move(), net["obs"] / net["mask"] what it is handed, net["owing"] how many games owe one."""
-        L.check(L.lib.azul_batch_net_step_begin(self._h, _ptr(actions), _ptr(net["pending"]), _ptr(net["replies"]), _ptr(reward), _ptr(done),
-                                                _ptr(status), _ptr(net["obs"]), _ptr(net["mask"]), _ptr(net["owing"]), self._stream()))
+        L.check(self._gr.net_step_begin(self._h, _ptr(actions), _ptr(net["pending"]), _ptr(net["replies"]), _ptr(reward), _ptr(done),
+                                        _ptr(status), _ptr(net["obs"]), _ptr(net["mask"]), _ptr(net["owing"]), self._stream()))
 
     def net_step_reply(self, opp_actions, net, reward, done, status):
         """One opponent_move() (game_runner.py:37-42) with `opp_actions` for every game that owes one, then the loop condition again."""
-        L.check(L.lib.azul_batch_net_step_reply(self._h, _ptr(opp_actions), _ptr(net["pending"]), _ptr(net["replies"]), _ptr(reward), _ptr(done),
-                                                _ptr(status), _ptr(net["obs"]), _ptr(net["mask"]), _ptr(net["owing"]), self._stream()))
+        L.check(self._gr.net_step_reply(self._h, _ptr(opp_actions), _ptr(net["pending"]), _ptr(net["replies"]), _ptr(reward), _ptr(done),
+                                        _ptr(status), _ptr(net["obs"]), _ptr(net["mask"]), _ptr(net["owing"]), self._stream()))
 
     def net_reset_begin(self, net, status, active=None):
         """GameRunner.reset() (game_runner.py:76-85) up to its first opponent_move()."""
-        L.check(L.lib.azul_batch_net_reset_begin(self._h, _ptr(self._dev(active, torch.uint8)), _ptr(net["pending"]), _ptr(status), _ptr(net["obs"]),
-                                                 _ptr(net["mask"]), _ptr(net["owing"]), self._stream()))
+        L.check(self._gr.net_reset_begin(self._h, _ptr(self._dev(active, torch.uint8)), _ptr(net["pending"]), _ptr(status), _ptr(net["obs"]),
+                                         _ptr(net["mask"]), _ptr(net["owing"]), self._stream()))
 
     # -- flat self-play rollout -------------------------------------------------------------------
     def selfplay(self, n_steps, mask=None, action=None, reward=None, done=None, records=None, maskbits=None, packed=None):

@@ -19,6 +19,7 @@ Per (move t, game g) the record holds what the reference's run_episode keeps per
 observation, legal mask, action, reward, done, value, log-prob of the action and the entropy term
 `-mean(log p over legal actions)` (nn_runner.py:36-40), plus the player who moved and the discounted returns.
 """
+import collections
 import ctypes as C
 import operator
 
@@ -37,6 +38,28 @@ def _p(t):
 _WEIGHT_FIELDS = operator.attrgetter(*[k for k, _ in L.NetWeights._fields_])
 _FLAT_BUFFER_FIELDS = operator.attrgetter(*[k for k, _ in L.RolloutBuffers._fields_[:11]])
 
+# The window kernels, one row per (wide batch, opponent kind) that has one: the C entry that plays a whole window of a part in one launch,
+# the constructor switch that asks for it, and the hidden size it is compiled for -- the policy must be ActorCritic(obs_size, num_actions,
+# hidden) of the batch; opp_hidden: the same for a network opponent whose shape the mode checks vouch for (None: nothing to check there).
+# "persistent" is the one switch that gives way quietly: a policy the one-launch forward does not fit plays move by move.
+_WindowKernel = collections.namedtuple("_WindowKernel", "entry switch hidden opp_hidden")
+_WINDOW_KERNELS = {
+    (False, None): _WindowKernel("azul_batch_policy_rollout_returns", "persistent", 180, None),
+    (False, "random"): _WindowKernel("azul_batch_policy_rollout_returns", "persistent", 180, None),
+    (False, "net"): _WindowKernel("azul_batch_policy_rollout_vs", "persistent", 180, None),
+    (False, "greedy"): _WindowKernel("azul_batch_policy_rollout_greedy", "fused_opponent", 180, None),
+    (True, None): _WindowKernel("azul_batch_mp_policy_rollout", "fused_wide", 180, None),
+    (True, "random"): _WindowKernel("azul_batch_mp_policy_rollout", "fused_wide", 180, None),
+    (True, "net"): _WindowKernel("azul_batch_mp_policy_rollout_vs", "fused_opponent", 180, 180),
+    (True, "greedy_margin"): _WindowKernel("azul_batch_mp_policy_rollout_greedy", "fused_seats", 180, None),
+}
+
+
+def _layer_sizes(net):
+    """(inputs of the critic / of the actor, hidden of the critic / of the actor, actions) of a module with the reference's four layers."""
+    return (net.critic_linear1.in_features, net.actor_linear1.in_features, net.critic_linear1.out_features, net.actor_linear1.out_features,
+            net.actor_linear2.out_features)
+
 
 class PolicyRollout:
     # reply rounds per agent step / opening on the wide path before the loop gives up: a legal opponent ends a step within about two rounds
@@ -48,77 +71,89 @@ class PolicyRollout:
                  action_selection="Distribution", kweights=None, game_id_base=None, ring=1, opponent_selection="Distribution",
                  opponent_seed=None, opponent_trace=0, move_limit=0, players=2, fused_wide=False, fused_opponent=False, wide_ring=1,
                  fused_seats=False):
-        """opponent=None: the policy moves for both players (flat self-play, one record per env move).
-        opponent="random": the reference's training setup -- the policy is player 1 of GameRunner, the opponent a RandomAgent
-        inside the env step (game_runner.py:43-47); one record per AGENT step, observations from the agent's perspective.
+        """Who answers GameRunner's opponent_move(), and what plays a window.  "window kernel": ONE launch per window and part (_WINDOW_KERNELS),
+        asked for by the switch in brackets; "per move" / "per cut": the launches of _window_moves.  Two-player reference batches (players=2, no
+        extended-rule key in `rules`) and wide batches (`players` = 3 / 4 or extended rules) admit:
+
+            opponent           two-player reference batch                           wide batch
+            None, "random"     per move, HIP graph                                  per move, HIP graph
+                               azul_batch_policy_rollout_returns [persistent]       azul_batch_mp_policy_rollout [fused_wide]
+            <module>           per cut                                              per cut
+                               azul_batch_policy_rollout_vs [persistent]            azul_batch_mp_policy_rollout_vs [fused_wide, fused_opponent]
+            "greedy"           per cut                                              ValueError
+                               azul_batch_policy_rollout_greedy [fused_opponent]
+            "greedy_margin"    ValueError                                           per cut
+                                                                                    azul_batch_mp_policy_rollout_greedy [fused_wide, fused_seats]
+
+        Every other combination of an opponent with fused_wide / fused_opponent / fused_seats raises ValueError, before anything is allocated.
+        A window kernel computes what the per-move / per-cut path computes: the same trajectories, records, streams and counters (wide
+        kernels add the network's sums in another order: the same bits wherever they are exact).  With an opponent inside, the opening of the
+        games at construction stays on the per-cut path (openings after episodes that end inside a window are the kernel's), and a game that
+        still owes an opponent_move() after MAX_REPLY_ROUNDS replies of one step (the two-player kernels: 64) ends the step with status AZUL_STUCK
+        (unless the step already has a status) instead of raising RuntimeError -- raising would cost a host synchronisation per window.
+
+        The opponents:
+        opponent=None: the policy moves for both players / every seat (flat self-play, one record per env move).
+        opponent="random": the reference's training setup -- the policy is player 1 of GameRunner, the opponent a RandomAgent inside the env
+        step (game_runner.py:43-47); one record per AGENT step, observations from the agent's perspective.
         opponent=<a second BatchedActorCritic / any module with the reference's four layers>: GameRunner(opponent=Agent(...))
-        (game_runner.py:27-30; scripts/run_batch.py:6-10) -- every opponent_move(), i.e. the opponent's replies, player 1's FORCED moves
-        (:46) and the opening moves of reset() (:84-85), is sampled from that net's forward_actor on the observation from the mover's
-        perspective (:38; agent.py:73-81), `opponent_selection` = its action_selection; records as with "random".  Its weights are copied
-        at construction; set_opponent() installs new ones (e.g. a frozen past self of the policy being trained).  persistent=True plays it
-        inside the window kernel (matrix phases on the second weight set while any game of a workgroup owes a reply); otherwise one launch
-        per cut of the protocol and one host synchronisation per reply round (no HIP graph).  `opponent_trace` = R > 0 also records the
-        opponent's answers: opp_action / opp_logp [T][R][N], opp_replies [T][N].
-        opponent="greedy" (two-player reference batches only; anything else raises ValueError): the scripted one-ply greedy player of the
-        reference's own reward on the same per-cut protocol -- every opponent_move() (replies, player 1's forced moves, the openings of
-        reset()) is BatchedAzul.greedy_action's answer, the move that maximises the mover's score difference after move + count_score
-        (game_runner.py:48-50), one launch per reply round in place of the network's forward; records as with "random"; `opponent_trace`
-        records opp_action (opp_logp stays 0) and opp_replies; persistent and use_graph resolve to False, ring to 1; at most MAX_REPLY_ROUNDS
-        reply rounds per step or opening (a game with nothing legal would owe its move for ever: RuntimeError).
-        opponent="greedy_margin" (wide batches only; on the per-cut path unless fused_seats=True, see there: fused_wide / fused_opponent
-        without it raise ValueError): the same scripted
-        player for three / four seats and extended rules -- every other seat answers every opponent_move() with
+        (game_runner.py:27-30; scripts/run_batch.py:6-10) -- every opponent_move(), i.e. the opponent's replies, player 1's FORCED moves (:46)
+        and the opening moves of reset() (:84-85), is sampled from that net's forward_actor on the observation from the mover's perspective
+        (:38; agent.py:73-81), `opponent_selection` = its action_selection, `opponent_seed` its Philox seed; records as with "random".  Its
+        weights are copied at construction; set_opponent() installs new ones (e.g. a frozen past self of the policy being trained).  Per cut:
+        one launch per cut of the protocol (BatchedAzul.net_*) and one host synchronisation per reply round, no HIP graph; the window kernel
+        runs matrix phases on the second weight set while any game of a workgroup owes a reply.  Two-player: the library's forward,
+        ActorCritic(136, 180, hidden 180).  Wide: the module's shape must match the batch (ActorCritic(env.obs_size, env.num_actions), any
+        hidden size: anything else raises ValueError); its actor half runs as PyTorch GEMMs + azul_policy_head_n with the two-player path's
+        Philox keys, through MultiplayerAzul.net_* (azul_batch_mp_net_*); at most MAX_REPLY_ROUNDS reply rounds per step or opening -- an
+        opponent that keeps answering with moves that are not legal raises RuntimeError.
+        opponent="greedy": the scripted one-ply greedy player of the reference's own reward on the same per-cut protocol -- every
+        opponent_move() is BatchedAzul.greedy_action's answer, the move that maximises the mover's score difference after move + count_score
+        (game_runner.py:48-50), one launch per reply round in place of the network's forward; records as with "random"; persistent and
+        use_graph resolve to False, ring to 1; at most MAX_REPLY_ROUNDS reply rounds per step or opening (a game with nothing legal would owe
+        its move for ever: RuntimeError).
+        opponent="greedy_margin": the same scripted player for three / four seats and extended rules -- every other seat answers with
         MultiplayerAzul.greedy_action, the move that maximises the MOVER's margin over the best other seat after move + count_score
-        (azul_batch_mp_score_moves; beyond the reference for P > 2, like the wide reward), through MultiplayerAzul.net_* exactly as a
-        network opponent's answers: one launch per reply round, no opponent weights, opp_logp stays 0, at most MAX_REPLY_ROUNDS rounds.
-        `move_limit` > 0 (beyond the reference, off by default): cut an episode at the first end of a round with move_counter >= move_limit
-        (done = 3) -- under the reference's rules some games never end and would keep their slot for ever (BatchedAzul.set_move_limit).
-        `seed_base` / `game_id_base`: game i of this rollout is global game game_id_base + i (default: seed_base, so that a rank
-        passes the id of its first game once); its CPython stream is random.seed(seed_base + i) and its sampling stream is
-        Philox(sample_seed, step, global id) -- both independent of how the games are sharded over GPUs or split into parts.
-        `ring` (persistent=True only): the trajectory buffers hold the last `ring` windows (a ring of ring * window time slots);
-        run_window fills the next window of the ring and re-chains the discounted returns backwards through the older windows, so
-        that the opening steps of an episode that ends in a LATER window get their exact Monte-Carlo return too
-        (A2CLearner.update_from_rollout trains every step of every episode exactly once, like NNRunner.train).
+        (azul_batch_mp_score_moves; beyond the reference for P > 2, like the wide reward), through MultiplayerAzul.net_* exactly as a network
+        opponent's answers: one launch per reply round, no opponent weights, at most MAX_REPLY_ROUNDS rounds.
+
+        The switches:
+        `persistent=True` (two-player; the policy must fit the one-launch forward, see fused_mlp -- otherwise it quietly plays per move): the
+        window kernel keeps every game in registers for the whole window.  With opponent="greedy" it resolves to False unless fused_opponent.
+        `fused_wide=True` (wide batches; ActorCritic(env.obs_size, env.num_actions, hidden 180) and fused_head, anything else raises
+        ValueError): env, network on the f32 matrix cores and azul_policy_head_n's draw inside one kernel instead of the per-move GEMMs + head
+        + env launches.  opponent=None | "random"; a network opponent needs fused_opponent=True too, greedy_margin seats fused_seats=True.
+        `fused_opponent=True`: with fused_wide=True and opponent=<module>, itself of hidden size 180 (other opponents run per cut), the network
+        opponent's reply rounds run inside the wide window kernel -- the same keys, counters and answers, opponent_selection, opponent_trace and
+        set_opponent() included.  With opponent="greedy" (two-player, ActorCritic(136, 180, hidden 180) with fused_mlp and fused_head; another
+        policy raises ValueError) the greedy player answers inside the two-player window kernel: persistent resolves to True.
+        `fused_seats=True` (opponent="greedy_margin" with fused_wide=True; anything else, fused_opponent included, raises ValueError): the
+        greedy_margin seats answer inside the wide window kernel -- no reply launches, no host synchronisation and no opponent weights.
+        `use_graph`: a window of per-move launches is captured once into a HIP graph per part; resolves to False with a window kernel (one
+        launch needs no graph) and on the per-cut path (reply rounds are data-dependent).
+        `fused_mlp` / `fused_head`: fused_mlp=False, a wide batch, or a policy other than ActorCritic(136, 180, hidden 180) runs the network as
+        PyTorch GEMMs + azul_policy_head (azul_policy_head_n on env.num_actions logits; trajectory buffers are env.obs_size / env.num_actions
+        wide); fused_head=False keeps the all-PyTorch sampling path (action_selection="Distribution" only).
+
+        The other arguments:
+        `opponent_trace` = R > 0 (any opponent but "random") also records the opponent's answers: opp_action / opp_logp [T][R][N] (a scripted
+        opponent leaves opp_logp 0; a window kernel fills the slots a step's replies used, the others keep -1), opp_replies [T][N].
+        `move_limit` > 0 (beyond the reference, off by default; two-player reference batches only): cut an episode at the first end of a round
+        with move_counter >= move_limit (done = 3) -- under the reference's rules some games never end and would keep their slot for ever
+        (BatchedAzul.set_move_limit).
+        `seed_base` / `game_id_base`: game i of this rollout is global game game_id_base + i (default: seed_base, so that a rank passes the id
+        of its first game once); its CPython stream is random.seed(seed_base + i) and its sampling stream is Philox(sample_seed, step, global
+        id) -- both independent of how the games are sharded over GPUs or split into parts.
+        `ring` (two-player window kernels; rings >= 2 with one part feed A2CLearner.update_from_rollout): the trajectory buffers hold the
+        last `ring` windows (a ring of ring * window time slots); run_window fills the next window of the ring and re-chains the discounted returns
+        backwards through the older windows (azul_discounted_returns_ring), so that the opening steps of an episode that ends in a LATER window
+        get their exact Monte-Carlo return too (A2CLearner.update_from_rollout trains every step of every episode exactly once, like
+        NNRunner.train).  `wide_ring` = k >= 2 (wide window kernels, one part) is the same ring for wide batches (`ring` becomes k; the default
+        k = 1 keeps it at 1).
         `players` = 3 / 4, or extended-rule keys in `rules` (the wide records): the games are MultiplayerAzul parts (GameRunner for P seats,
-        azul_batch_mp_*; the shaped reward is the margin over the best opponent, beyond the reference for P > 2), the network runs as
-        PyTorch GEMMs + azul_policy_head_n on env.num_actions logits, trajectory buffers are env.obs_size / env.num_actions wide;
-        opponent=None | "random" with both action_selection modes, HIP graphs and parts as on the two-player PyTorch path; opponent=<module>
-        when its shape matches the batch (ActorCritic(env.obs_size, env.num_actions), any hidden size: anything else raises ValueError):
-        every other seat's opponent_move() goes through MultiplayerAzul.net_* (azul_batch_mp_net_*), answered by the module's actor half as
-        PyTorch GEMMs + azul_policy_head_n with the two-player path's Philox keys; no HIP graph, and at most MAX_REPLY_ROUNDS reply rounds
-        per step or opening -- an opponent that keeps answering with moves that are not legal raises RuntimeError.
-        `fused_wide=True` (wide batches, opponent=None | "random", ActorCritic(env.obs_size, env.num_actions, hidden 180), fused_head): each
-        window is ONE launch per part (azul_batch_mp_policy_rollout: env, network on the f32 matrix cores and azul_policy_head_n's draw inside
-        one kernel) instead of the per-move GEMMs + head + env launches; the same trajectories (the network's sums in another order: the same
-        bits wherever they are exact).  Anything else with fused_wide=True raises ValueError.
-        `wide_ring` = k >= 2 (fused_wide=True, one part): the ring of the two-player persistent path for wide batches -- each window kernel
-        writes the next window of a ring of k windows (`ring` = k), and azul_discounted_returns_ring chains the returns back through it, so
-        that A2CLearner.update_from_rollout trains every step of every episode once.  The default k = 1 keeps `ring` at 1.
-        `kweights` with fused_wide=True: the k-major weights of a fused A2CLearner of the policy's shape (A2CLearner.kweights(): one copy
-        serves rollout and learner); other wide rollouts ignore it.
-        `fused_opponent=True` (with fused_wide=True and opponent=<module>, itself ActorCritic(env.obs_size, env.num_actions, hidden 180)): the
-        network opponent's reply rounds run inside the window kernel too (azul_batch_mp_policy_rollout_vs) -- the same keys, counters, answers
-        and trajectories as the per-cut path, opponent_selection, opponent_trace and set_opponent() included.  The opening of the games at
-        construction stays on the per-cut path; openings after episodes that end inside a window are the kernel's.  One difference: a game
-        that still owes an opponent_move() after MAX_REPLY_ROUNDS rounds ends its step with status AZUL_STUCK (unless the step already has a
-        status) instead of raising RuntimeError, as the two-player window kernel does -- raising would cost a host synchronisation per window.
-        `fused_opponent=True` with opponent="greedy" (two-player reference batches, ActorCritic(136, 180, hidden 180); another policy shape
-        raises ValueError): the greedy player answers inside the two-player window kernel (azul_batch_policy_rollout_greedy) -- one launch per
-        window and part, no reply launches and no host synchronisation; persistent resolves to True, use_graph to False, `ring` windows
-        (rings >= 2 with one part) feed A2CLearner.update_from_rollout.  The same trajectories, records, streams and counters as the per-cut
-        path, opponent_trace included (opp_action of the slots a step's replies filled; the other slots keep -1).  The opening at
-        construction stays on the per-cut path.  One difference: a game that still owes an opponent_move() after 64 replies of one step
-        ends the step with status AZUL_STUCK (unless the step already has a status) instead of raising RuntimeError.
-        `fused_seats=True` (opponent="greedy_margin" on a wide batch, with fused_wide=True, fused_head and ActorCritic(env.obs_size,
-        env.num_actions, hidden 180); anything else, fused_opponent included, raises ValueError): the greedy_margin seats answer inside the
-        wide window kernel (azul_batch_mp_policy_rollout_greedy) -- one launch per window and part, no reply launches, no host
-        synchronisation and no opponent weights; use_graph resolves to False, wide_ring and opponent_trace work as with the other wide
-        window kernels (opp_action of the slots a step's replies filled; the other slots keep -1, opp_logp stays 0).  The same
-        trajectories, records, streams and counters as the per-cut path.  The opening at construction stays on the per-cut path; openings
-        after episodes that end inside a window are the kernel's.  One difference, the window kernels' usual one: a game that still owes an
-        opponent_move() after MAX_REPLY_ROUNDS replies of one step ends the step with status AZUL_STUCK (unless the step already has a
-        status) instead of raising RuntimeError."""
+        azul_batch_mp_*; the shaped reward is the margin over the best opponent, beyond the reference for P > 2).
+        `kweights` (two-player, or a wide window kernel; other wide rollouts ignore it): the k-major weights of a fused A2CLearner of the
+        policy's shape (A2CLearner.kweights(): one copy serves rollout and learner)."""
         self._check_modes(policy, n_games, parts, rules, window, use_graph, fused_head, opponent, fused_mlp, persistent, action_selection, ring,
                           opponent_selection, opponent_trace, move_limit, players, fused_wide, fused_opponent, wide_ring, fused_seats)
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
@@ -145,30 +180,34 @@ class PolicyRollout:
 
     def _check_modes(self, policy, n_games, parts, rules, window, use_graph, fused_head, opponent, fused_mlp, persistent, action_selection, ring,
                      opponent_selection, opponent_trace, move_limit, players, fused_wide, fused_opponent, wide_ring, fused_seats=False):
-        """Every refusal of the constructor, and the flags the modes resolve to -- from the arguments and the modules' shapes alone: no
-        device and no library call, so nothing is allocated before a refusal."""
+        """Every refusal of the constructor, then the resolution of the modes -- from the arguments and the modules' shapes alone: no device
+        and no library call, so nothing is allocated before a refusal.  Three facts come out: the record family (`wide`), who answers
+        opponent_move() (`opponent`, one of the kinds below) and what plays a window (`window_entry`: a row of _WINDOW_KERNELS, or None for
+        the move-by-move path); the other flags restate them."""
         assert n_games % parts == 0
         self.n, self.parts, self.h, self.T = n_games, parts, n_games // parts, window
         self.players = int(players)
         self.wide = self.players != 2 or parse_ext_rules(rules, self.players) != 0
-        net = opponent is not None and not isinstance(opponent, str)
+        kind = opponent if opponent is None or isinstance(opponent, str) else "net"       # None | "random" | "net" | "greedy" | "greedy_margin"
         n_obs, n_act = batch_shape(self.players, rules)          # azul_batch_obs_size / azul_batch_num_actions
-        if self.wide and net:
+        # (a kind the assert below turns away is checked as self-play until then)
+        row = _WINDOW_KERNELS.get((self.wide, kind), _WINDOW_KERNELS[self.wide, None])
+        compiled_for = (n_obs, n_obs, row.hidden, row.hidden, n_act)
+        # -- the refusals, in the order in which they win
+        if self.wide and kind == "net":
             shape = (opponent.critic_linear1.in_features, opponent.actor_linear1.in_features, opponent.actor_linear2.out_features)
             if shape != (n_obs, n_obs, n_act):
                 raise ValueError("a network opponent for batches of %d players / extended rules must take the batch's observation and give its "
                                  "actions: ActorCritic(%d, %d, any hidden size), got inputs %d / %d and %d actions"
                                  % (self.players, n_obs, n_act, shape[0], shape[1], shape[2]))
-        if isinstance(opponent, str) and opponent == "greedy" and self.wide:
+        if kind == "greedy" and self.wide:
             raise ValueError("opponent=\"greedy\" maximises the two-player reward of game_runner.py:48-50: two-player reference batches only, "
                              "not %d players / extended rules (their scripted opponent is opponent=\"greedy_margin\")" % self.players)
-        margin = isinstance(opponent, str) and opponent == "greedy_margin"
-        if margin and not self.wide:
+        if kind == "greedy_margin" and not self.wide:
             raise ValueError("opponent=\"greedy_margin\" maximises the margin over the best other seat on batches of three / four players or "
                              "extended rules; a two-player reference batch has opponent=\"greedy\"")
-        self.fused_seats = bool(fused_seats)
-        if self.fused_seats:
-            if not margin:
+        if fused_seats:
+            if kind != "greedy_margin":
                 raise ValueError("fused_seats=True plays the greedy_margin seats of a wide batch inside its window kernel: it needs "
                                  "opponent=\"greedy_margin\" (three / four players or extended rules)")
             if fused_opponent:
@@ -176,77 +215,71 @@ class PolicyRollout:
                                  "two-player opponent=\"greedy\")")
             if not fused_wide:
                 raise ValueError("fused_seats=True answers inside the wide window kernel: it needs fused_wide=True")
-        elif margin and (fused_wide or fused_opponent):
+        elif kind == "greedy_margin" and (fused_wide or fused_opponent):
             raise ValueError("opponent=\"greedy_margin\" answers on the per-cut path (one azul_batch_mp_score_moves launch per reply round): "
                              "the wide window kernel does not play it (fused_wide=False, fused_opponent=False) unless fused_seats=True asks "
                              "for it (with fused_wide=True)")
         if self.wide and move_limit:
             raise ValueError("no move limit for batches of three / four players or extended rules")
-        self.fused_wide = bool(fused_wide)
-        if self.fused_wide:
+        if fused_wide:
             if not self.wide:
                 raise ValueError("fused_wide=True is the window kernel of batches of three / four players or extended rules; two-player reference "
                                  "batches have persistent=True")
-            if net and not fused_opponent:
+            if kind == "net" and not fused_opponent:
                 raise ValueError("fused_wide=True plays opponent=None or \"random\"; a network opponent runs on the per-cut path (fused_wide=False)")
             if not fused_head:
                 raise ValueError("fused_wide=True samples with azul_policy_head_n's draw: fused_head=False is the PyTorch sampling path")
-            shape = (policy.critic_linear1.in_features, policy.actor_linear1.in_features, policy.critic_linear1.out_features,
-                     policy.actor_linear1.out_features, policy.actor_linear2.out_features)
-            if shape != (n_obs, n_obs, 180, 180, n_act):
+            if _layer_sizes(policy) != compiled_for:
                 raise ValueError("fused_wide=True is compiled for ActorCritic(%d, %d, hidden 180) on this batch, got inputs %d / %d, hidden %d / %d "
-                                 "and %d actions" % ((n_obs, n_act) + shape))
+                                 "and %d actions" % ((n_obs, n_act) + _layer_sizes(policy)))
         if int(wide_ring) < 1:
             raise ValueError("wide_ring must be >= 1")
-        if int(wide_ring) >= 2 and (not self.fused_wide or parts != 1):
+        if int(wide_ring) >= 2 and (not fused_wide or parts != 1):
             raise ValueError("wide_ring >= 2 is the trajectory ring of the wide window kernel: it needs fused_wide=True and parts=1")
-        self.fused_opponent = bool(fused_opponent)
-        self.fused_greedy = bool(self.fused_opponent and isinstance(opponent, str) and opponent == "greedy")      # (wide batches were refused above)
-        if self.fused_greedy:
-            shape = (policy.critic_linear1.in_features, policy.actor_linear1.in_features, policy.critic_linear1.out_features,
-                     policy.actor_linear1.out_features, policy.actor_linear2.out_features)
-            if shape != (L.OBS_SIZE, L.OBS_SIZE, 180, 180, L.NUM_ACTIONS) or not (fused_mlp and fused_head):
+        if fused_opponent and kind == "greedy":                  # (wide batches were refused above)
+            if _layer_sizes(policy) != compiled_for or not (fused_mlp and fused_head):
                 raise ValueError("fused_opponent=True with opponent=\"greedy\" plays inside the two-player window kernel, compiled for "
                                  "ActorCritic(136, 180, hidden 180) -- shape (136, 180, 180) -- with fused_mlp and fused_head; got inputs %d / %d, "
                                  "hidden %d / %d and %d actions; other policies play the greedy opponent on the per-cut path "
-                                 "(fused_opponent=False)" % shape)
-        elif self.fused_opponent:
-            if not self.fused_wide or not net:
+                                 "(fused_opponent=False)" % _layer_sizes(policy))
+        elif fused_opponent:
+            if not fused_wide or kind != "net":
                 raise ValueError("fused_opponent=True plays a network opponent inside the window kernel of wide batches: it needs fused_wide=True "
                                  "and opponent=<module> (or opponent=\"greedy\" on a two-player reference batch)")
-            if (opponent.critic_linear1.out_features, opponent.actor_linear1.out_features) != (180, 180):
+            if (opponent.critic_linear1.out_features, opponent.actor_linear1.out_features) != (row.opp_hidden, row.opp_hidden):
                 raise ValueError("fused_opponent=True is compiled for an opponent of hidden size 180, got %d / %d; other opponents run on the "
                                  "per-cut path (fused_opponent=False, fused_wide=False)"
                                  % (opponent.critic_linear1.out_features, opponent.actor_linear1.out_features))
-        self.opp_policy = None
-        if net:
-            self.opp_policy, opponent = opponent, "net"
-        assert opponent in (None, "random", "net", "greedy", "greedy_margin")
-        self.opponent = opponent
-        self.scripted = opponent in ("greedy", "greedy_margin")        # answers are env.greedy_action's: no weights, no log-probabilities
-        self.cut = opponent == "net" or self.scripted          # GameRunner.step cut at its opponent_move() calls (BatchedAzul.net_*)
+        assert kind in (None, "random", "net", "greedy", "greedy_margin")
+        # -- the resolution
+        self.opponent, self.opp_policy = kind, (opponent if kind == "net" else None)
+        self.scripted = kind in ("greedy", "greedy_margin")    # answers are env.greedy_action's: no weights, no log-probabilities
+        self.cut = kind == "net" or self.scripted              # GameRunner.step cut at its opponent_move() calls (BatchedAzul.net_*)
         self.fused_head = fused_head
         # the one-launch forward (azul_policy_forward) is compiled for the reference's ActorCritic(136, 180, hidden 180)
         self.fused_mlp = bool(fused_mlp and fused_head and not self.wide and policy.critic_linear1.in_features == L.OBS_SIZE and
                               policy.critic_linear1.out_features == 180 and policy.actor_linear2.out_features == L.NUM_ACTIONS)
-        # persistent=True: the whole window runs in ONE launch per part (azul_batch_policy_rollout); same results
-        self.persistent = bool(self.fused_greedy or (persistent and self.fused_mlp and not self.scripted))
-        self.ring = int(ring) if self.persistent else (int(wide_ring) if self.fused_wide else 1)
+        asked = {"persistent": persistent and self.fused_mlp, "fused_wide": fused_wide, "fused_opponent": fused_opponent, "fused_seats": fused_seats}
+        self.window_entry = row.entry if asked[row.switch] else None          # the whole window in ONE launch per part; same results
+        self.fused_wide, self.fused_opponent, self.fused_seats = bool(fused_wide), bool(fused_opponent), bool(fused_seats)
+        self.fused_greedy = self.fused_opponent and kind == "greedy"
+        self.persistent = self.window_entry is not None and not self.wide
+        self.ring = (int(wide_ring) if self.wide else int(ring)) if self.window_entry else 1
         assert self.ring >= 1
         # Agent.get_ac_output's two modes (agent.py:64-72): sample from the masked softmax, or take its first maximum
         assert action_selection in ("Distribution", "Max") and (fused_head or action_selection == "Distribution")
         self.action_selection = action_selection
         assert opponent_selection in ("Distribution", "Max")
         self.opp_slots = int(opponent_trace) if self.cut else 0
-        assert self.opponent != "net" or self.fused_mlp or self.wide, \
+        assert kind != "net" or self.fused_mlp or self.wide, \
             "the network opponent runs on the library's forward (ActorCritic(136, 180, hidden 180))"
         # one launch per window needs no graph; reply rounds are data-dependent (a capture that fails clears the flag again)
-        self.use_graph = bool(use_graph and not self.persistent and not self.fused_wide and not self.cut)
+        self.use_graph = bool(use_graph and self.window_entry is None and not self.cut)
 
     def _stage_weights(self, kweights):
         """The k-major weight copies the kernels and GEMMs read.  kweights: tensors owned by someone else (A2CLearner.kweights(): views of
         its flat master copy, kept current by the optimiser kernel) -- then nothing is copied here and refresh_weights() has nothing to do."""
-        if self.wide and not self.fused_wide:
+        if self.wide and self.window_entry is None:
             kweights = None                                # (the PyTorch-GEMM path keeps its own copies)
         self._external_kweights = kweights is not None
         self.H = self.policy.critic_linear1.out_features
@@ -314,7 +347,7 @@ class PolicyRollout:
         return out
 
     def _persp(self):
-        return 0 if self.opponent in ("random", "net", "greedy", "greedy_margin") else L.PERSP_CURRENT     # NNRunner observes with perspective 0 (game_runner.py:56)
+        return 0 if self.opponent is not None else L.PERSP_CURRENT     # with any opponent NNRunner observes with perspective 0 (game_runner.py:56)
 
     def _stage(self, get, prefix, names):
         """The k-major copies `names` of the reference's four layers (`get`: parameter name -> tensor) as attributes prefix + name,
@@ -372,14 +405,25 @@ class PolicyRollout:
     def _net_reset(self, p):
         """GameRunner.reset() with the network opponent for every game of part p (game_runner.py:76-85); its opening moves draw at the
         counter before the first step."""
+        w = self.work[p]
+        self.envs[p].net_reset_begin(w["net"], w["status"])
+        self._reply_rounds(p, "the opening of reset()", None, None)
+
+    def _reply_rounds(self, p, where, reward, done, trace=None):
+        """opponent_move() while any game of part p owes one: per round the opponent's answers, one net_step_reply launch and one host
+        synchronisation (the loop condition).  `reward` / `done`: the step's slots (None for an opening); `trace`: the step's (opp_action,
+        opp_logp) [R][N], whose first opp_slots rounds are recorded.  Wide and scripted opponents give up after MAX_REPLY_ROUNDS rounds."""
         env, w = self.envs[p], self.work[p]
-        env.net_reset_begin(w["net"], w["status"])
+        net = w["net"]
         j = 0
-        while int(w["net"]["owing"].item()) > 0:
+        while int(net["owing"].item()) > 0:
             if (self.wide or self.scripted) and j >= self.MAX_REPLY_ROUNDS:
-                self._reply_loop_failed(p, j, "the opening of reset()")
-            self._opp_forward(p, j, w["scratch_f"][2])
-            env.net_step_reply(w["net"]["action"], w["net"], None, None, w["status"])
+                self._reply_loop_failed(p, j, where)
+            traced = trace is not None and j < self.opp_slots
+            self._opp_forward(p, j, trace[1][j] if traced else w["scratch_f"][2])
+            if traced:
+                trace[0][j].copy_(net["action"])
+            env.net_step_reply(net["action"], net, reward, done, w["status"])
             j += 1
 
     def _reply_loop_failed(self, p, rounds, where):
@@ -467,15 +511,8 @@ class PolicyRollout:
             # synchronisation per round: this is the per-move reference structure, the window kernel is the fast path)
             net = w["net"]
             env.net_step_begin(tr["action"][t], net, tr["reward"][t], tr["done"][t], w["status"])
-            j = 0
-            while int(net["owing"].item()) > 0:
-                if (self.wide or self.scripted) and j >= self.MAX_REPLY_ROUNDS:
-                    self._reply_loop_failed(p, j, "agent step %d of the window" % t)
-                self._opp_forward(p, j, tr["opp_logp"][t][j] if j < self.opp_slots else w["scratch_f"][2])
-                if j < self.opp_slots:
-                    tr["opp_action"][t][j].copy_(net["action"])
-                env.net_step_reply(net["action"], net, tr["reward"][t], tr["done"][t], w["status"])
-                j += 1
+            self._reply_rounds(p, "agent step %d of the window" % t, tr["reward"][t], tr["done"][t],
+                               (tr["opp_action"][t], tr["opp_logp"][t]) if self.opp_slots else None)
             tr["opp_replies"][t].copy_(net["replies"])
             env.observe_all(0, tr["obs"][t + 1], tr["mask"][t + 1], tr["player"][t + 1])
         elif self.opponent == "random":
@@ -484,40 +521,36 @@ class PolicyRollout:
             env.policy_step(tr["action"][t], tr["reward"][t], tr["done"][t], w["status"], tr["obs"][t + 1], tr["mask"][t + 1], tr["player"][t + 1])
 
     def _window(self, p, gamma):
-        if self.persistent or self.fused_wide:
+        if self.window_entry:
             self._window_kernel(p, gamma)
         else:
             self._window_moves(p, gamma)
 
     def _window_kernel(self, p, gamma):
-        """The whole window of part p in one launch (+ the returns scan behind it): the two-player kernel (persistent) or the wide one
-        (fused_wide), with the opponent inside.  The only place a window kernel is launched from."""
+        """The whole window of part p in one launch of `window_entry` (+ the returns scan behind it), the opponent inside.  The only place a
+        window kernel is launched from.  The entries share one argument order (include/azul_hip.h); what differs is said where it is added."""
         T, env, w = self.T, self.envs[p], self.work[p]
         if self.ring > 1:
             self.traj[p] = self._window_views(self.rings[p], self.windows_played % self.ring)     # (run_window advances windows_played after all parts)
         tr = self.traj[p]
         st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        wa = self._net_weights()
         out = self._buffers(tr, w, tr["returns"].data_ptr() if self.ring == 1 else None)          # ring: the chain below writes the returns
-        shape, ctr, rnd = (self.obs_size, self.H, self.num_actions), _p(w["counter"]), 1 if self.opponent == "random" else 0
-        if self.opponent == "net":                          # the reply rounds inside the kernel
-            wo = self._net_weights(opponent=True)
-            if self.wide:
-                L.check(L.lib.azul_batch_mp_policy_rollout_vs(env._h, T, C.byref(wa), C.byref(wo), *shape, self.sample_seed, self.opponent_seed, 0, ctr,
-                                                              int(self.MAX_REPLY_ROUNDS), C.byref(out), C.c_float(gamma), st))
-            else:
-                L.check(L.lib.azul_batch_policy_rollout_vs(env._h, T, C.byref(wa), C.byref(wo), *shape, self.sample_seed, self.opponent_seed, 0, ctr,
-                                                           C.byref(out), C.c_float(gamma), st))
-        elif self.opponent == "greedy":                     # the greedy player's answers inside the env phase
-            L.check(L.lib.azul_batch_policy_rollout_greedy(env._h, T, C.byref(wa), *shape, self.sample_seed, 0, ctr, C.byref(out), C.c_float(gamma), st))
-        elif self.opponent == "greedy_margin":              # the greedy_margin seats' answers inside the env phase (fused_seats)
-            L.check(L.lib.azul_batch_mp_policy_rollout_greedy(env._h, T, C.byref(wa), *shape, self.sample_seed, 0, ctr, int(self.MAX_REPLY_ROUNDS),
-                                                              C.byref(out), C.c_float(gamma), st))
-        elif self.wide:
-            L.check(L.lib.azul_batch_mp_policy_rollout(env._h, T, rnd, C.byref(wa), *shape, self.sample_seed, 0, ctr, C.byref(out), C.c_float(gamma), st))
-        else:                                               # this entry takes the same pointers one by one
-            L.check(L.lib.azul_batch_policy_rollout_returns(env._h, T, rnd, *_WEIGHT_FIELDS(wa), *shape, self.sample_seed, 0, ctr,
-                                                            *_FLAT_BUFFER_FIELDS(out), C.c_float(gamma), st))
+        vs, flat = self.opponent == "net", self.window_entry == "azul_batch_policy_rollout_returns"
+        wa, wo = self._net_weights(), self._net_weights(opponent=True) if vs else None
+        args = [env._h, T]
+        if not self.cut:
+            args.append(1 if self.opponent == "random" else 0)                  # opponent_random: the entries without reply rounds play both
+        args += _WEIGHT_FIELDS(wa) if flat else [C.byref(wa)]                   # (_returns takes the structs' pointers one by one)
+        if vs:
+            args.append(C.byref(wo))                                            # the reply rounds run on the opponent's weights
+        args += [self.obs_size, self.H, self.num_actions, self.sample_seed]
+        if vs:
+            args.append(self.opponent_seed)
+        args += [0, _p(w["counter"])]
+        if self.wide and self.cut:
+            args.append(int(self.MAX_REPLY_ROUNDS))                             # max_replies: the wide kernels' bound on one step's reply rounds
+        args += _FLAT_BUFFER_FIELDS(out) if flat else [C.byref(out)]
+        L.check(getattr(L.lib, self.window_entry)(*args, C.c_float(gamma), st))
         if self.ring > 1:
             # returns of the new window and, chained backwards through the ring, of the older windows: the value flowing out of a
             # window's first step flows into the window before it (nn_runner.py:70-76 across window boundaries) -- one launch

@@ -286,7 +286,6 @@ def test_wrong_shapes_and_two_player_batches_are_refused():
     for name, fn in calls.items():
         assert fn() == L.ERR_INVALID
         assert name in L.lib.azul_last_error_string().decode()
-    with pytest.raises(L.AzulHipError):                    # the two-player entries keep refusing wide batches
-        from azul_deep_reinforcement_learning_amd import MultiplayerAzul
-        wide = MultiplayerAzul(8, players=3, device="cuda:0")
-        BatchedAzul.net_reset_begin(wide, wide.net_state(), torch.zeros(8, dtype=torch.uint8, device="cuda:0"))
+    with pytest.raises(L.AzulHipError, match="GameRunner is two-player"):      # the two-player entries keep refusing wide batches
+        wide = BatchedAzul(8, players=3, device="cuda:0")  # (the family is the class's: a plain BatchedAzul calls azul_batch_net_*)
+        wide.net_reset_begin(wide.net_state(), torch.zeros(8, dtype=torch.uint8, device="cuda:0"))

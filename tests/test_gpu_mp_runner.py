@@ -212,3 +212,31 @@ def test_two_player_batches_are_refused_with_the_name_of_their_entry():
         MultiplayerAzul(8, players=2, device="cuda:0")
     with pytest.raises(L.AzulHipError):                    # ... and the two-player entries keep refusing wide batches
         BatchedAzul(8, players=3, device="cuda:0", seed=1).reset()
+
+
+def test_a_plain_wide_batch_keeps_the_two_player_family_and_its_refusals():
+    """The GameRunner family belongs to the class, not to the record shape: a plain BatchedAzul of three players calls azul_batch_runner_* /
+    azul_batch_net_* / azul_batch_score_moves, and every one of them is refused by the library in its own words (csrc/azul_kernels.hip:
+    launch_op_x, net_op, azul_batch_score_moves) before anything is launched -- the games are not touched."""
+    from azul_deep_reinforcement_learning_amd import BatchedAzul
+    from azul_deep_reinforcement_learning_amd import _lib as L
+    env = BatchedAzul(4, players=3, seed=1)
+    assert (env.ENTRY_PREFIX, env.PERSP_TO_MOVE, env.wide) == ("azul_batch_", L.PERSP_CURRENT, True)
+    env.init()
+    env.new_round()
+    before, (mt0, pos0) = env.get_records().tobytes(), env.get_rng_range()
+    b, net, act = bufs(env), env.net_state(), torch.zeros(4, dtype=torch.int32, device=env.device)
+    step_args = (act, b["reward"], b["done"], b["status"], b["obs"], b["mask"], b["player"])
+    runner, protocol, table = "mirrors GameRunner's two-player step", "GameRunner is two-player", "two-player reference batches only"
+    calls = [(runner, env.runner_init), (runner, env.reset), (runner, lambda: env.step(act)), (runner, env.score_preview),
+             (runner, lambda: env.policy_step(*step_args)), (runner, lambda: env.agent_step(*step_args)),
+             (protocol, lambda: env.net_step_begin(act, net, b["reward"], b["done"], b["status"])),
+             (protocol, lambda: env.net_step_reply(act, net, b["reward"], b["done"], b["status"])),
+             (protocol, lambda: env.net_reset_begin(net, b["status"])),
+             (table, env.score_moves), (table, env.greedy_action)]
+    for fragment, call in calls:
+        with pytest.raises(L.AzulHipError, match=fragment):
+            call()
+    torch.cuda.synchronize()
+    mt1, pos1 = env.get_rng_range()
+    assert env.get_records().tobytes() == before and np.array_equal(mt0, mt1) and np.array_equal(pos0, pos1)
