@@ -119,6 +119,7 @@ SIGNATURES = {
     "azul_select_complete_samples": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp]),
     "azul_discounted_returns": (_i, [_vp, _vp, _vp, _vp, C.c_float, _i, _i, _vp]),
     "azul_discounted_returns_ring": (_i, [_vp, _vp, _vp, C.c_float, _i, C.c_int64, _i, _i, _vp]),
+    "azul_lambda_returns_ring": (_i, [_vp, _vp, _vp, _vp, _vp, C.c_float, C.c_float, _i, C.c_int64, _i, _i, _vp]),
     "azul_batch_sample_mask": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "azul_batch_score_preview": (_i, [_vp, _vp, _vp]),
     "azul_batch_score_moves": (_i, [_vp, _i, _vp, _vp, _vp, _vp]),

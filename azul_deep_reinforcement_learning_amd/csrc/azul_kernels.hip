@@ -651,6 +651,23 @@ int azul_discounted_returns_ring(const int32_t *reward_ring_dev, const uint8_t *
     return AZUL_SUCCESS;
 }
 
+int azul_lambda_returns_ring(const int32_t *reward_ring_dev, const uint8_t *done_ring_dev, const float *value_ring_dev, const float *tail_value_dev,
+                             float *returns_ring_dev, float gamma, float lambda, int ring_steps, int64_t steps_played, int span_steps, int n_games,
+                             void *stream)
+{
+    // (the comparisons are written so that a NaN fails them)
+    if (!reward_ring_dev || !done_ring_dev || !value_ring_dev || !returns_ring_dev || ring_steps < 1 || span_steps < 1 || span_steps > ring_steps ||
+        steps_played < span_steps || n_games < 1 || (uint64_t)ring_steps * (uint64_t)n_games >= (1ull << 32) || !(lambda >= 0.f && lambda <= 1.f) ||
+        !(gamma - gamma == 0.f))
+        return fail(AZUL_ERR_INVALID, "azul_lambda_returns_ring: bad arguments");
+    STREAM_GUARD(stream);
+    hipLaunchKernelGGL(azul_lambda_returns_ring_kernel, dim3(((u32)n_games + 63u) / 64u), dim3(64), 0, (hipStream_t)stream, reward_ring_dev,
+                       done_ring_dev, value_ring_dev, tail_value_dev, returns_ring_dev, gamma, lambda, ring_steps,
+                       (int)(steps_played % ring_steps == 0 ? ring_steps : steps_played % ring_steps), span_steps, (u32)n_games);
+    HIP_TRY(hipGetLastError());
+    return AZUL_SUCCESS;
+}
+
 int azul_policy_head(const float *logits_dev, const uint8_t *mask_dev, uint64_t seed, uint64_t counter, const uint64_t *counter_dev,
                      int n_games, uint32_t game_id_base, int32_t *action_dev, float *logp_dev, float *entropy_dev, void *stream)
 {

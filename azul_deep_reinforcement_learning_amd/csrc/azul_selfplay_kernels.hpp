@@ -86,6 +86,47 @@ __global__ void __launch_bounds__(64) azul_returns_ring_kernel(const i32 *__rest
     }
 }
 
+// The TD(lambda) return over the same ring (include/azul_hip.h: azul_lambda_returns_ring states the float32 contract statement for
+// statement): G[s] = r[s] + gamma * ((1 - lambda) * V[s+1] + lambda * G[s+1]) inside an episode, G[s] = r[s] at its end; `tail` [n] (or
+// null: 0) is the critic's value of the state after the newest step and flows into it as both V and G.  The walk, the batched reads and
+// the addressing are azul_returns_ring_kernel's; each step adds one 4-byte read (the recorded value) and three operations to the chain.
+__global__ void __launch_bounds__(64) azul_lambda_returns_ring_kernel(const i32 *__restrict__ reward, const uint8_t *__restrict__ done,
+                                                                      const float *__restrict__ value, const float *__restrict__ tail,
+                                                                      float *__restrict__ out, float gamma, float lambda, int ring_steps,
+                                                                      int s_end, int span, u32 n)
+{
+    u32 g = blockIdx.x * 64u + threadIdx.x;
+    if (g >= n) return;
+    const float oml = 1.f - lambda;
+    float v_next = tail ? tail[g] : 0.f;
+    float q = v_next;
+    int slot = (s_end - 1) % ring_steps;
+    constexpr int RB = 16;
+#pragma unroll 1
+    for (int j = 0; j < span; j += RB) {
+        i32 r[RB];
+        float v[RB];
+        u32 d[RB], at[RB];
+#pragma unroll
+        for (int b = 0; b < RB; b++) {
+            at[b] = (u32)slot * n + g;
+            r[b] = reward[at[b]];
+            d[b] = done[at[b]];
+            v[b] = value[at[b]];
+            if (j + b + 1 < span) slot = slot == 0 ? ring_steps - 1 : slot - 1;
+        }
+#pragma unroll
+        for (int b = 0; b < RB; b++) {
+            if (j + b < span) {
+                const float mix = oml * v_next + lambda * q;
+                q = d[b] ? (float)r[b] : (float)r[b] + gamma * mix;
+                out[at[b]] = q;
+                v_next = v[b];
+            }
+        }
+    }
+}
+
 // DIAGNOSTIC: the shader clock the device really runs at, measured ON the device: one wave runs a fixed chain of dependent vector operations
 // between two readings of s_memtime (shader-clock cycles) and s_memrealtime (a constant 100 MHz counter); out[0] / out[1] x 100 MHz is the
 // clock the wave saw.  bench.py launches it between the blocks of its sustained phase, beside the driver's reported clock.

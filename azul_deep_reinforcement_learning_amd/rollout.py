@@ -70,7 +70,7 @@ class PolicyRollout:
                  device=None, window=32, use_graph=True, fused_head=True, sample_seed=0x5EED, opponent=None, fused_mlp=True, persistent=False,
                  action_selection="Distribution", kweights=None, game_id_base=None, ring=1, opponent_selection="Distribution",
                  opponent_seed=None, opponent_trace=0, move_limit=0, players=2, fused_wide=False, fused_opponent=False, wide_ring=1,
-                 fused_seats=False):
+                 fused_seats=False, gae_lambda=None, bootstrap_tail=False):
         """Who answers GameRunner's opponent_move(), and what plays a window.  "window kernel": ONE launch per window and part (_WINDOW_KERNELS),
         asked for by the switch in brackets; "per move" / "per cut": the launches of _window_moves.  Two-player reference batches (players=2, no
         extended-rule key in `rules`) and wide batches (`players` = 3 / 4 or extended rules) admit:
@@ -153,9 +153,26 @@ class PolicyRollout:
         `players` = 3 / 4, or extended-rule keys in `rules` (the wide records): the games are MultiplayerAzul parts (GameRunner for P seats,
         azul_batch_mp_*; the shaped reward is the margin over the best opponent, beyond the reference for P > 2).
         `kweights` (two-player, or a wide window kernel; other wide rollouts ignore it): the k-major weights of a fused A2CLearner of the
-        policy's shape (A2CLearner.kweights(): one copy serves rollout and learner)."""
+        policy's shape (A2CLearner.kweights(): one copy serves rollout and learner).
+        `gae_lambda` (any opponent but None; every path): None, or 1.0 without bootstrap_tail, leaves `returns` the reference's Monte-Carlo
+        return q[t] = r[t] + gamma * q[t+1] and runs exactly the launches it ran before.  A float in [0, 1): after each window `returns` holds
+        the TD(lambda) return G[t] = r[t] + gamma * ((1 - lambda) * V[t+1] + lambda * G[t+1]) (G[t] = r[t] at an episode end), V the recorded
+        `value` -- one azul_lambda_returns_ring launch per window and part over the steps the buffers hold (min(ring * window, played); the
+        window kernels then write no returns themselves, the move-by-move path launches it in place of azul_discounted_returns); lambda = 0
+        is the one-step TD target.  A2CLearner forms returns - V itself, so the learner paths need no change.  Nothing flows into the newest
+        step unless bootstrap_tail; the values of a ring's older windows were recorded under older weights and are used as recorded; a step
+        recorded without an action (action -1) carries the critic's value of its observation like any other (every path writes it), the scan
+        makes no exception.  Flat self-play (opponent=None) raises ValueError: consecutive records there belong to different seats observed
+        with PERSP_CURRENT, so V[t+1] would be another seat's value.  Like gamma, lambda is baked into a captured graph.
+        `bootstrap_tail=True` (ring 1, any opponent but None; gae_lambda then defaults to 1.0): after the window's moves the critic's value
+        of slot T -- the state after the window -- is computed by PyTorch on the part's stream from the weights the kernels read (one GEMM
+        pair per window), kept in the trajectory dict as "tail_value" [N] and handed to the scan, where it flows into the newest step: every
+        step of the window then has a proper target at once, episodes still open included (n-step A2C:
+        A2CLearner.update_from_windows(traj, complete_only=False)).  A ring of two or more windows trains whole episodes, nothing is open
+        there: ValueError."""
         self._check_modes(policy, n_games, parts, rules, window, use_graph, fused_head, opponent, fused_mlp, persistent, action_selection, ring,
-                          opponent_selection, opponent_trace, move_limit, players, fused_wide, fused_opponent, wide_ring, fused_seats)
+                          opponent_selection, opponent_trace, move_limit, players, fused_wide, fused_opponent, wide_ring, fused_seats,
+                          gae_lambda, bootstrap_tail)
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         self.policy = policy.to(self.device).eval()
         self.windows_played = 0
@@ -179,7 +196,8 @@ class PolicyRollout:
                 torch.cuda.synchronize(self.device)
 
     def _check_modes(self, policy, n_games, parts, rules, window, use_graph, fused_head, opponent, fused_mlp, persistent, action_selection, ring,
-                     opponent_selection, opponent_trace, move_limit, players, fused_wide, fused_opponent, wide_ring, fused_seats=False):
+                     opponent_selection, opponent_trace, move_limit, players, fused_wide, fused_opponent, wide_ring, fused_seats=False,
+                     gae_lambda=None, bootstrap_tail=False):
         """Every refusal of the constructor, then the resolution of the modes -- from the arguments and the modules' shapes alone: no device
         and no library call, so nothing is allocated before a refusal.  Three facts come out: the record family (`wide`), who answers
         opponent_move() (`opponent`, one of the kinds below) and what plays a window (`window_entry`: a row of _WINDOW_KERNELS, or None for
@@ -250,6 +268,12 @@ class PolicyRollout:
                 raise ValueError("fused_opponent=True is compiled for an opponent of hidden size 180, got %d / %d; other opponents run on the "
                                  "per-cut path (fused_opponent=False, fused_wide=False)"
                                  % (opponent.critic_linear1.out_features, opponent.actor_linear1.out_features))
+        lam = None if gae_lambda is None else float(gae_lambda)
+        if lam is not None and not 0.0 <= lam <= 1.0:            # (a NaN fails the comparison too)
+            raise ValueError("gae_lambda must lie in [0, 1] (1: the Monte-Carlo return, 0: the one-step TD target), got %r" % (gae_lambda,))
+        if kind is None and (bootstrap_tail or (lam is not None and lam < 1.0)):
+            raise ValueError("gae_lambda < 1 and bootstrap_tail need the records of ONE seat (any opponent but None): consecutive records of "
+                             "flat self-play belong to different seats observed with PERSP_CURRENT, so V(s_{t+1}) is another seat's value")
         assert kind in (None, "random", "net", "greedy", "greedy_margin")
         # -- the resolution
         self.opponent, self.opp_policy = kind, (opponent if kind == "net" else None)
@@ -266,6 +290,12 @@ class PolicyRollout:
         self.persistent = self.window_entry is not None and not self.wide
         self.ring = (int(wide_ring) if self.wide else int(ring)) if self.window_entry else 1
         assert self.ring >= 1
+        if bootstrap_tail and self.ring >= 2:                    # (the last refusal: it needs the resolved ring; still nothing allocated)
+            raise ValueError("bootstrap_tail=True gives the open episodes of ONE window a target; a ring of %d windows trains whole episodes, "
+                             "nothing is open there (ring=1 / wide_ring=1)" % self.ring)
+        # None: the Monte-Carlo return and the launches of a rollout without these switches; a float: azul_lambda_returns_ring writes `returns`
+        self.bootstrap_tail = bool(bootstrap_tail)
+        self.gae_lambda = (1.0 if lam is None else lam) if (self.bootstrap_tail or (lam is not None and lam < 1.0)) else None
         # Agent.get_ac_output's two modes (agent.py:64-72): sample from the masked softmax, or take its first maximum
         assert action_selection in ("Distribution", "Max") and (fused_head or action_selection == "Distribution")
         self.action_selection = action_selection
@@ -330,6 +360,9 @@ class PolicyRollout:
             if self.wide and self.opponent == "net":           # the opponent's actor half as PyTorch GEMMs (its own hidden size)
                 w["opp_hidden"] = torch.zeros(h, self.ob1.numel() // 2, device=d)
                 w["opp_logits"] = torch.zeros(h, env.num_actions, device=d)
+        if self.bootstrap_tail:                                # the critic's value of slot T, and the hidden layer it is formed from
+            w["tail_hidden"], w["tail_value"] = torch.zeros(h, self.H, device=d), torch.zeros(h, 1, device=d)
+            t["tail_value"] = w["tail_value"].view(h)
         self.traj.append(t)
         self.work.append(w)
         with torch.cuda.stream(self.streams[p]):
@@ -534,7 +567,8 @@ class PolicyRollout:
             self.traj[p] = self._window_views(self.rings[p], self.windows_played % self.ring)     # (run_window advances windows_played after all parts)
         tr = self.traj[p]
         st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        out = self._buffers(tr, w, tr["returns"].data_ptr() if self.ring == 1 else None)          # ring: the chain below writes the returns
+        # (a ring, or a lambda-return: the scan below writes the returns)
+        out = self._buffers(tr, w, tr["returns"].data_ptr() if self.ring == 1 and self.gae_lambda is None else None)
         vs, flat = self.opponent == "net", self.window_entry == "azul_batch_policy_rollout_returns"
         wa, wo = self._net_weights(), self._net_weights(opponent=True) if vs else None
         args = [env._h, T]
@@ -551,12 +585,32 @@ class PolicyRollout:
             args.append(int(self.MAX_REPLY_ROUNDS))                             # max_replies: the wide kernels' bound on one step's reply rounds
         args += _FLAT_BUFFER_FIELDS(out) if flat else [C.byref(out)]
         L.check(getattr(L.lib, self.window_entry)(*args, C.c_float(gamma), st))
-        if self.ring > 1:
+        if self.gae_lambda is not None:
+            self._lambda_returns(p, gamma)
+        elif self.ring > 1:
             # returns of the new window and, chained backwards through the ring, of the older windows: the value flowing out of a
             # window's first step flows into the window before it (nn_runner.py:70-76 across window boundaries) -- one launch
             rg, R, played = self.rings[p], self.ring * T, (self.windows_played + 1) * T
             L.check(L.lib.azul_discounted_returns_ring(_p(rg["reward"]), _p(rg["done"]), _p(rg["returns"]), C.c_float(gamma), R,
                                                        played % (1 << 40), min(R, played), self.h, st))
+
+    def _lambda_returns(self, p, gamma):
+        """The TD(lambda) returns of every step part p's buffers hold, on the current stream: one azul_lambda_returns_ring launch from the
+        newest step backwards (a single window is a ring of its T slots) -- with bootstrap_tail behind the critic's forward on slot T (the
+        two GEMMs of forward_critic, model.py:22-26, on the staged weights the kernels read), whose value flows into the newest step."""
+        T, w = self.T, self.work[p]
+        rg, R = self.rings[p], self.ring * T
+        played = (self.windows_played + 1) * T if self.ring > 1 else T     # (run_window advances windows_played after all parts)
+        tail = None
+        if self.bootstrap_tail:
+            H, tail = self.H, w["tail_value"]
+            with torch.no_grad():
+                torch.addmm(self.b1[:H], self.traj[p]["obs"][T], self.w1t[:, :H], out=w["tail_hidden"])
+                w["tail_hidden"].relu_()
+                torch.addmm(self.policy.critic_linear2.bias, w["tail_hidden"], self.w2c_t, out=tail)
+        L.check(L.lib.azul_lambda_returns_ring(_p(rg["reward"]), _p(rg["done"]), _p(rg["value"]), None if tail is None else _p(tail),
+                                               _p(rg["returns"]), C.c_float(gamma), C.c_float(self.gae_lambda), R, played % (1 << 40),
+                                               min(R, played), self.h, C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
 
     def _window_moves(self, p, gamma):
         """The window of part p move by move (what a HIP graph captures): slot T of the last window becomes slot 0, T moves, the returns scan."""
@@ -566,6 +620,8 @@ class PolicyRollout:
         tr["player"][0].copy_(tr["player"][T])
         for t in range(T):
             self._move(p, t)
+        if self.gae_lambda is not None:
+            return self._lambda_returns(p, gamma)
         L.check(L.lib.azul_discounted_returns(_p(tr["reward"]), _p(tr["done"]), _p(tr["returns"]), None, C.c_float(gamma), T, self.h,
                                               C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
 
@@ -582,11 +638,15 @@ class PolicyRollout:
             self.graphs.append(g)
         torch.cuda.synchronize(self.device)
 
-    def run_window(self, gamma=0.99):
+    def run_window(self, gamma=0.99, gae_lambda=None):
         """Advance every game by `window` moves; returns the per-part trajectory dicts (views into static buffers;
-        `obs`, `mask`, `player` have T+1 slots: slot t is what the policy saw at move t)."""
+        `obs`, `mask`, `player` have T+1 slots: slot t is what the policy saw at move t).  `gae_lambda` is the constructor's: given here,
+        it must name the same returns."""
         if self.use_graph and gamma != getattr(self, "gamma", gamma):
             raise ValueError("gamma is baked into the captured graph")
+        if gae_lambda is not None and float(gae_lambda) != (1.0 if self.gae_lambda is None else self.gae_lambda):
+            raise ValueError("gae_lambda is the constructor's (and baked into a captured graph): this rollout was built with %r"
+                             % (1.0 if self.gae_lambda is None else self.gae_lambda))
         cur = torch.cuda.current_stream(self.device)
         for p in range(self.parts):
             self.streams[p].wait_stream(cur)             # e.g. the optimiser step / refresh_weights enqueued by the caller

@@ -38,7 +38,7 @@ class BatchedTrainer:
     def __init__(self, policy, n_games=4096, window=32, parts=1, learning_rate=3e-4, gamma=0.99, seed_base=0, sample_seed=0x5EED,
                  rules={"first_player": "Random", "tile_pool": "Lid"}, device=None, use_graph=True, persistent=True, results_dir="results",
                  ring=3, opponent="random", opponent_refresh=0, move_limit=0, players=2, fused_wide=False,
-                 fused_opponent=False, fused_learner=False, fused_seats=False):
+                 fused_opponent=False, fused_learner=False, fused_seats=False, gae_lambda=None, bootstrap_tail=False):
         """ring: trajectory windows kept (persistent rollout with one part): with ring >= 2 every step of every episode is trained
         exactly once (episodes straddle windows; an episode may span ring - 1 window boundaries), like NNRunner.train.
         opponent: "random" (GameRunner's default RandomAgent, the reference's scripts/training.py), a module (GameRunner(opponent=Agent(...)),
@@ -67,12 +67,27 @@ class BatchedTrainer:
         two-player one -- PolicyRollout(wide_ring=ring) keeps the last `ring` windows, the learner is A2CLearner(fused=True) (gradients and
         Adam on the f32 matrix cores, azul_a2c_gradients / azul_a2c_apply_adam_n) reading the ring through azul_select_episode_samples,
         so every step of every episode is trained once, and rollout and learner share the learner's k-major weight copy.  Checkpoints then
-        carry the ring, the learner's books and the fused moments.  Default False: the wide learner stays on its PyTorch path."""
+        carry the ring, the learner's books and the fused moments.  Default False: the wide learner stays on its PyTorch path.
+        gae_lambda / bootstrap_tail: PolicyRollout's switches of the same names, handed on.  gae_lambda in [0, 1) trains on the TD(lambda)
+        return with critic bootstrap (the learner forms returns - V as before, on whichever path it takes); None or 1.0: the Monte-Carlo
+        return, the launches of before.  bootstrap_tail=True (needs ring=1): the critic's value of the state after the window flows into its
+        newest step and run_batch trains EVERY recorded step that carries an action, open episodes included
+        (A2CLearner.update_from_windows(traj, complete_only=False)): n-step A2C.  Both need an opponent; a resumed run replays the next
+        window's returns bit for bit (the values are in the ring a checkpoint carries, the tail is recomputed from the restored weights)."""
         from .batch import parse_ext_rules
         wide = int(players) != 2 or parse_ext_rules(rules, int(players)) != 0
         fused_learner = bool(fused_learner)
         if fused_learner and wide and not fused_wide:
             raise ValueError("fused_learner=True trains a wide batch from the ring of its window kernel: it needs fused_wide=True")
+        # (PolicyRollout refuses the same before it allocates; here the learner's buffers would already exist)
+        if gae_lambda is not None and not 0.0 <= float(gae_lambda) <= 1.0:
+            raise ValueError("gae_lambda must lie in [0, 1] (1: the Monte-Carlo return, 0: the one-step TD target), got %r" % (gae_lambda,))
+        if opponent is None and (bootstrap_tail or (gae_lambda is not None and float(gae_lambda) < 1.0)):
+            raise ValueError("gae_lambda < 1 and bootstrap_tail need the records of one seat: an opponent other than None")
+        if bootstrap_tail and parts == 1 and int(ring) >= 2 and (persistent or (wide and fused_learner)):
+            raise ValueError("bootstrap_tail=True gives the open episodes of one window a target: it needs ring=1 (a ring of %d windows "
+                             "trains whole episodes, nothing is open there)" % int(ring))
+        self.bootstrap_tail = bool(bootstrap_tail)
         dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         policy = policy.to(dev)
         wide_fused = wide and fused_learner
@@ -90,7 +105,7 @@ class BatchedTrainer:
                                      ring=ring if (persistent and parts == 1) else 1,
                                      move_limit=move_limit, players=players, fused_wide=fused_wide,
                                      fused_opponent=fused_opponent, wide_ring=ring if (wide_fused and parts == 1) else 1,
-                                     fused_seats=fused_seats)
+                                     fused_seats=fused_seats, gae_lambda=gae_lambda, bootstrap_tail=bootstrap_tail)
         self.gamma = gamma
         self.results_dir = results_dir
         self.batch = 0
@@ -126,7 +141,10 @@ class BatchedTrainer:
         GameStatistics buffers between two get_stats() calls (game_runner.py:17-22)."""
         tr = self.rollout.run_window(self.gamma)
         self.rollout.join()                              # device-side dependency: the host keeps enqueueing
-        out = self.learner.update_from_rollout(self.rollout)
+        if self.bootstrap_tail:                          # every recorded step has its target: the open episodes' steps are samples too
+            out = self.learner.update_from_windows(tr, complete_only=False)
+        else:
+            out = self.learner.update_from_rollout(self.rollout)
         self.rollout.refresh_weights()
         self.batch += 1
         if self._self_opponent and self.opponent_refresh and self.batch % self.opponent_refresh == 0:

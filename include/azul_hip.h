@@ -612,6 +612,27 @@ int azul_discounted_returns(const int32_t *reward_dev, const uint8_t *done_dev, 
  * window-by-window calls chained through the carry. */
 int azul_discounted_returns_ring(const int32_t *reward_ring_dev, const uint8_t *done_ring_dev, float *returns_ring_dev, float gamma,
                                  int ring_steps, int64_t steps_played, int span_steps, int n_games, void *stream);
+/* The TD(lambda) return (the lambda-return / GAE target) with critic bootstrap over the same ring, in ONE launch:
+ *     G[s] = r[s] + gamma * ((1 - lambda) * V[s+1] + lambda * G[s+1])        inside an episode,        G[s] = r[s]  at its end,
+ * V = value_ring_dev (what the rollout recorded for each agent step, time-major like the rewards), tail_value_dev [n_games] (optional)
+ * the critic's value of the state AFTER the newest step: it flows into the newest step as both V and G; NULL: 0 flows in.  The ring
+ * addressing is azul_discounted_returns_ring's: absolute step s lives in slot s % ring_steps, the scan walks from steps_played - 1 back
+ * over span_steps steps, slots outside the span keep their bits; a single window of T steps is ring_steps = span_steps = T.
+ * The contract, in float32, statement for statement (no contraction, no fast-math: ONE result):
+ *     oml = 1.0f - lambda                                                       (one float32 subtraction)
+ *     v_next = tail_value_dev ? tail_value_dev[g] : 0.0f ;  q_next = v_next
+ *     for s = steps_played - 1 down to steps_played - span_steps:
+ *         slot = s % ring_steps ;  r = (float)reward[slot][g] ;  v = value[slot][g]
+ *         if done[slot][g] != 0:  q = r
+ *         else:                   mix = fl(fl(oml * v_next) + fl(lambda * q_next)) ;  q = fl(r + fl(gamma * mix))
+ *         returns[slot][g] = q ;  q_next = q ;  v_next = v
+ * lambda == 1 with finite values: the bits of azul_discounted_returns_ring (0 * v + 1 * q is exact); lambda == 0: r + gamma * V[s+1].
+ * The scan makes no exception for a step recorded without an action (action -1): its value is read like any other.
+ * AZUL_ERR_INVALID before any launch: a NULL array (tail_value_dev excepted), ring_steps < 1, span_steps outside 1 .. ring_steps,
+ * steps_played < span_steps, n_games < 1, ring_steps * n_games >= 2^32, lambda outside [0, 1], gamma or lambda not finite. */
+int azul_lambda_returns_ring(const int32_t *reward_ring_dev, const uint8_t *done_ring_dev, const float *value_ring_dev,
+                             const float *tail_value_dev /* [n_games], optional */, float *returns_ring_dev, float gamma, float lambda,
+                             int ring_steps, int64_t steps_played, int span_steps, int n_games, void *stream);
 
 /* The C1 WIRE RECORD of the trajectory all-gather BASELINE configs[4] names: one window of a policy rollout (the time-major arrays of
  * azul_batch_policy_rollout*, [n_steps][n_games]...) packed to 184 bytes per agent step -- what NNRunner.run_episode keeps per step
