@@ -111,6 +111,8 @@ SIGNATURES = {
     "azul_batch_net_step_reply": (_i, [_vp] * 11),
     "azul_batch_net_reset_begin": (_i, [_vp] * 8),
     "azul_a2c_gradients": (_i, [_vp, _vp, _vp, _vp, _i, C.c_float] + [_vp] * 7 + [_i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "azul_ppo_gradients": (_i, [_vp] * 6 + [_i, C.c_float, C.c_float, C.c_float, C.c_float] + [_vp] * 7 +
+                           [_i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "azul_a2c_apply_adam": (_i, [_vp, _vp, _vp, _vp, C.c_float, C.c_float, C.c_float, C.c_float, _i] + [_vp] * 8 + [_vp, _vp, C.c_float, _vp, _vp]),
     "azul_a2c_flat_size": (_i, [_i, _i, _i]),
     "azul_a2c_apply_adam_n": (_i, [_vp, _vp, _vp, _vp, C.c_float, C.c_float, C.c_float, C.c_float, _i, _i, _i, _i] + [_vp] * 8 +

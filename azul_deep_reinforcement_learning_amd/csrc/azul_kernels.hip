@@ -896,21 +896,24 @@ int azul_a2c_flat_size(int num_inputs, int hidden_size, int num_actions)
 #define AZ_LN_DISPATCH(IN_, A_, launch) \
     if (num_inputs == IN_ && num_actions == A_) { constexpr int LN_IN = IN_, LN_A = A_; launch; }
 
-int azul_a2c_gradients(const float *obs_dev, const uint8_t *mask_dev, const int32_t *action_dev, const float *qvals_dev, int n_samples,
-                       float inv_n_total, const float *w1t_dev, const float *b1_dev, const float *w2c_dev, const float *b2c_dev,
-                       const float *w2a_t_dev, const float *b2a_dev, const float *w2a_dev, int num_inputs, int hidden_size, int num_actions,
-                       float *workspace_dev, int workspace_parts, float *grad_dev, const int32_t *index_dev, const int32_t *n_samples_dev,
-                       const float *inv_n_total_dev, void *stream)
+// the one host body behind azul_a2c_gradients (obj 0) and azul_ppo_gradients (obj 1: LearnerArgs' PPO fields are read); `who`: the entry called
+static int a2c_gradients(const char *who, int obj, LearnerArgs a, const PolicyWeights &W, int n_samples, int num_inputs, int hidden_size,
+                         int num_actions, int workspace_parts, float *grad_dev, void *stream)
 {
     const bool reference = num_inputs == PF_IN && hidden_size == PF_HID && num_actions == PF_ACT;
     if (azul_a2c_flat_size(num_inputs, hidden_size, num_actions) < 0)
-        return fail(AZUL_ERR_INVALID, "azul_a2c_gradients: compiled shapes are ActorCritic(136, 180), (188, 180), (240, 180), (198, 240) "
-                                      "and (260, 300), hidden 180");
-    if (!w1t_dev || !b1_dev || !w2c_dev || !b2c_dev || !w2a_t_dev || !b2a_dev || !w2a_dev || !workspace_dev || !grad_dev || n_samples < 0 ||
-        workspace_parts <= 0 || (n_samples > 0 && (!obs_dev || !mask_dev || !action_dev || !qvals_dev)))
-        return fail(AZUL_ERR_INVALID, "azul_a2c_gradients: bad arguments");
-    if (reference && (((uintptr_t)w2a_t_dev & 7u) != 0 || ((uintptr_t)w2a_dev & 7u) != 0 || ((uintptr_t)mask_dev & 3u) != 0))
-        return fail(AZUL_ERR_INVALID, "azul_a2c_gradients: weights must be 8-byte aligned, mask_dev 4-byte aligned");
+        return fail_in(who, "compiled shapes are ActorCritic(136, 180), (188, 180), (240, 180), (198, 240) and (260, 300), hidden 180");
+    if (!W.w1t || !W.b1 || !W.w2c || !W.b2c || !W.w2a_t || !W.b2a || !a.w2a || !a.partial || !grad_dev || n_samples < 0 ||
+        workspace_parts <= 0 || (n_samples > 0 && (!a.obs || !a.mask || !a.action || !a.qvals)))
+        return fail_in(who, "bad arguments");
+    if (obj == 1) {
+        if (n_samples > 0 && (!a.old_logp || !a.advantage)) return fail_in(who, "old_log_prob_dev / advantage_dev are NULL");
+        if (!(a.clip_eps > 0.f) || std::isinf(a.clip_eps)) return fail_in(who, "clip_eps must lie in (0, +inf)");
+        if (!(a.value_coeff >= 0.f) || std::isinf(a.value_coeff) || !(a.entropy_coeff >= 0.f) || std::isinf(a.entropy_coeff))
+            return fail_in(who, "value_coeff / entropy_coeff must be finite and >= 0");
+    }
+    if (reference && (((uintptr_t)W.w2a_t & 7u) != 0 || ((uintptr_t)a.w2a & 7u) != 0 || ((uintptr_t)a.mask & 3u) != 0))
+        return fail_in(who, "weights must be 8-byte aligned, mask_dev 4-byte aligned");
     STREAM_GUARD(stream);
     const hipStream_t st = (hipStream_t)stream;
     const u32 total = a2c_shape_n((u32)num_inputs, (u32)num_actions).params + 4u;
@@ -918,20 +921,50 @@ int azul_a2c_gradients(const float *obs_dev, const uint8_t *mask_dev, const int3
     const u32 tiles = ((u32)n_samples + per_pass - 1) / per_pass;
     const u32 parts = tiles < (u32)workspace_parts ? tiles : (u32)workspace_parts;
     if (parts == 0) { HIP_TRY(hipMemsetAsync(grad_dev, 0, sizeof(float) * total, st)); return AZUL_SUCCESS; }
-    PolicyWeights W = {w1t_dev, b1_dev, w2c_dev, b2c_dev, w2a_t_dev, b2a_dev};
-    LearnerArgs a = {obs_dev, mask_dev, action_dev, qvals_dev, (u32)n_samples, inv_n_total, w2a_dev, workspace_dev, index_dev, n_samples_dev,
-                     inv_n_total_dev};
-    if (reference) hipLaunchKernelGGL(azul_a2c_grad_kernel, dim3(parts), dim3(64 * LG_WAVES), 0, st, W, a);
     const dim3 grid(parts, 3), block(64 * LN_WAVES);      // the wide shapes: three workgroup roles per part (azul_learner.hpp)
-    AZ_LN_DISPATCH(188, 180, hipLaunchKernelGGL((azul_a2c_grad_n_kernel<LN_IN, LN_A>), grid, block, 0, st, W, a))
-    AZ_LN_DISPATCH(240, 180, hipLaunchKernelGGL((azul_a2c_grad_n_kernel<LN_IN, LN_A>), grid, block, 0, st, W, a))
-    AZ_LN_DISPATCH(198, 240, hipLaunchKernelGGL((azul_a2c_grad_n_kernel<LN_IN, LN_A>), grid, block, 0, st, W, a))
-    AZ_LN_DISPATCH(260, 300, hipLaunchKernelGGL((azul_a2c_grad_n_kernel<LN_IN, LN_A>), grid, block, 0, st, W, a))
+    if (obj == 0) {
+        if (reference) hipLaunchKernelGGL(azul_a2c_grad_kernel<0>, dim3(parts), dim3(64 * LG_WAVES), 0, st, W, a);
+        AZ_LN_DISPATCH(188, 180, hipLaunchKernelGGL((azul_a2c_grad_n_kernel<LN_IN, LN_A, 0>), grid, block, 0, st, W, a))
+        AZ_LN_DISPATCH(240, 180, hipLaunchKernelGGL((azul_a2c_grad_n_kernel<LN_IN, LN_A, 0>), grid, block, 0, st, W, a))
+        AZ_LN_DISPATCH(198, 240, hipLaunchKernelGGL((azul_a2c_grad_n_kernel<LN_IN, LN_A, 0>), grid, block, 0, st, W, a))
+        AZ_LN_DISPATCH(260, 300, hipLaunchKernelGGL((azul_a2c_grad_n_kernel<LN_IN, LN_A, 0>), grid, block, 0, st, W, a))
+    } else {
+        if (reference) hipLaunchKernelGGL(azul_a2c_grad_kernel<1>, dim3(parts), dim3(64 * LG_WAVES), 0, st, W, a);
+        AZ_LN_DISPATCH(188, 180, hipLaunchKernelGGL((azul_a2c_grad_n_kernel<LN_IN, LN_A, 1>), grid, block, 0, st, W, a))
+        AZ_LN_DISPATCH(240, 180, hipLaunchKernelGGL((azul_a2c_grad_n_kernel<LN_IN, LN_A, 1>), grid, block, 0, st, W, a))
+        AZ_LN_DISPATCH(198, 240, hipLaunchKernelGGL((azul_a2c_grad_n_kernel<LN_IN, LN_A, 1>), grid, block, 0, st, W, a))
+        AZ_LN_DISPATCH(260, 300, hipLaunchKernelGGL((azul_a2c_grad_n_kernel<LN_IN, LN_A, 1>), grid, block, 0, st, W, a))
+    }
     const dim3 rgrid((total + 255) / 256), rblock(256);
-    if (reference) hipLaunchKernelGGL(azul_a2c_reduce_kernel, rgrid, rblock, 0, st, (const float *)workspace_dev, parts, grad_dev);
-    else hipLaunchKernelGGL(azul_a2c_reduce_n_kernel, rgrid, rblock, 0, st, (const float *)workspace_dev, parts, total, grad_dev);
+    if (reference) hipLaunchKernelGGL(azul_a2c_reduce_kernel, rgrid, rblock, 0, st, (const float *)a.partial, parts, grad_dev);
+    else hipLaunchKernelGGL(azul_a2c_reduce_n_kernel, rgrid, rblock, 0, st, (const float *)a.partial, parts, total, grad_dev);
     HIP_TRY(hipGetLastError());
     return AZUL_SUCCESS;
+}
+
+int azul_a2c_gradients(const float *obs_dev, const uint8_t *mask_dev, const int32_t *action_dev, const float *qvals_dev, int n_samples,
+                       float inv_n_total, const float *w1t_dev, const float *b1_dev, const float *w2c_dev, const float *b2c_dev,
+                       const float *w2a_t_dev, const float *b2a_dev, const float *w2a_dev, int num_inputs, int hidden_size, int num_actions,
+                       float *workspace_dev, int workspace_parts, float *grad_dev, const int32_t *index_dev, const int32_t *n_samples_dev,
+                       const float *inv_n_total_dev, void *stream)
+{
+    const LearnerArgs a = {obs_dev, mask_dev, action_dev, qvals_dev, (u32)n_samples, inv_n_total, w2a_dev, workspace_dev, index_dev, n_samples_dev,
+                           inv_n_total_dev};
+    return a2c_gradients("azul_a2c_gradients", 0, a, {w1t_dev, b1_dev, w2c_dev, b2c_dev, w2a_t_dev, b2a_dev}, n_samples, num_inputs, hidden_size,
+                         num_actions, workspace_parts, grad_dev, stream);
+}
+
+int azul_ppo_gradients(const float *obs_dev, const uint8_t *mask_dev, const int32_t *action_dev, const float *returns_dev,
+                       const float *old_log_prob_dev, const float *advantage_dev, int n_samples, float inv_n_total, float clip_eps,
+                       float value_coeff, float entropy_coeff, const float *w1t_dev, const float *b1_dev, const float *w2c_dev,
+                       const float *b2c_dev, const float *w2a_t_dev, const float *b2a_dev, const float *w2a_dev, int num_inputs, int hidden_size,
+                       int num_actions, float *workspace_dev, int workspace_parts, float *grad_dev, const int32_t *index_dev,
+                       const int32_t *n_samples_dev, const float *inv_n_total_dev, float *log_prob_out_dev, void *stream)
+{
+    const LearnerArgs a = {obs_dev, mask_dev, action_dev, returns_dev, (u32)n_samples, inv_n_total, w2a_dev, workspace_dev, index_dev, n_samples_dev,
+                           inv_n_total_dev, old_log_prob_dev, advantage_dev, clip_eps, value_coeff, entropy_coeff, log_prob_out_dev};
+    return a2c_gradients("azul_ppo_gradients", 1, a, {w1t_dev, b1_dev, w2c_dev, b2c_dev, w2a_t_dev, b2a_dev}, n_samples, num_inputs, hidden_size,
+                         num_actions, workspace_parts, grad_dev, stream);
 }
 
 #if defined(AZ_LG_PROFILE)

@@ -21,6 +21,23 @@
 // | (1 pad) | dw2a_t [180][180] | db2a [180]  = 82082 floats, followed by the four loss sums (actor, critic, entropy, count of
 // samples used).  The same layout holds the k-major master copy of the parameters and Adam's moments (azul_a2c_apply_kernel).
 // The wide shapes use it with their own `IN` inputs and `A` actions: a2c_shape_n below is its one definition.
+//
+// A second objective, OBJ = 1 of both gradient kernels (azul_ppo_gradients): PPO's clipped surrogate with the true entropy.  Only the
+// per-sample head differs; forward, dh GEMM, weight-gradient tiles, partial vectors and the reduce are the code of OBJ = 0.  Per sample
+// (old_logp and Adv are INPUTS: detached by construction; eps, c_v, c_e from LearnerArgs; all f32 with __expf / __logf like the head above):
+//     logp_k = z_k - logS,  p_k = e_k / S                  (legal k; 0 otherwise)
+//     r      = exp(logp[a] - old_logp)
+//     L_pi   = -min(r Adv, clamp(r, 1 - eps, 1 + eps) Adv)
+//     H      = -sum_k p_k logp_k                           (the true entropy: one more row reduction)
+//     L_i    = ( L_pi + c_v (q - v)^2 - c_e H ) / n
+// hence   dL/dv       = -2 c_v (q - v) / n
+//         dL/dlogp_a  = g_a = clipped ? 0 : -Adv r,   clipped = (Adv > 0 and r > 1 + eps) or (Adv < 0 and r < 1 - eps)
+//         dH/dlogit_k = -p_k (logp_k + H)                  (from dp_j/dlogit_k = p_j ([j == k] - p_k) and sum_j p_j = 1)
+//         dL/dlogit_k = ( g_a ([k == a] - p_k) + c_e p_k (logp_k + H) ) / n                  (legal k; 0 otherwise)
+// which is autograd's gradient of torch.min(r * Adv, torch.clamp(r, 1 - eps, 1 + eps) * Adv): inside the bounds AND on a bound both
+// arguments of the min are equal, the tie splits the gradient in halves and clamp passes its half (its range is closed), so the sum is
+// Adv dr; strictly outside, the clamped argument is the smaller one exactly when `clipped` holds and its gradient is 0; with Adv == 0
+// every branch gives 0.  The four loss sums keep their slots: sum L_pi, sum (q - v)^2 (raw, without c_v), sum H, count.
 #pragma once
 
 // The one definition of the flat layout, for every shape (in, act) with hidden 180 (azul_a2c_flat_size lists the compiled ones)
@@ -57,6 +74,11 @@ struct LearnerArgs {
     const i32 *index;        // optional [n]: sample s lives in row index[s] of obs / mask / action / qvals (a device-built selection)
     const i32 *n_dev;        // optional: the sample count in device memory (overrides n; no host round trip to learn it)
     const float *inv_n_dev;  // optional: 1 / (samples of the whole batch) in device memory (overrides inv_n)
+    // read by OBJ = 1 only (azul_a2c_gradients' aggregate initialisation leaves them zero)
+    const float *old_logp;   // [n] per source row (through `index` like qvals): log-probability of the action under the behaviour policy
+    const float *advantage;  // [n] per source row
+    float clip_eps, value_coeff, entropy_coeff;
+    float *logp_out;         // optional [n]: sample s (launch order, NOT source row) receives the recomputed logp[a]; rows without a sample: nothing
 };
 
 // One 180-deep GEMM pass of the gradient kernel: NT column tiles of this wave (NT == 2: columns col0, col0 + 1 of a lane, one 8-byte
@@ -110,6 +132,7 @@ __device__ unsigned long long lg_prof_dev[16];
 #define LG_STAMP(i) do { } while (0)
 #endif
 
+template <int OBJ = 0>                                   // the objective of the head (P3): 0 the reference's A2C loss, 1 PPO's clipped surrogate
 __global__ void __launch_bounds__(64 * LG_WAVES) azul_a2c_grad_kernel(PolicyWeights W, LearnerArgs a)
 {
     __shared__ float obsS[LG_M * PF_OBS_STRIDE];         // x      [32][136 (+pad, zero)]
@@ -312,6 +335,7 @@ __global__ void __launch_bounds__(64 * LG_WAVES) azul_a2c_grad_kernel(PolicyWeig
             float mine_lpa = 0.f;
             for (int j = 0; j < HEAD_PER_LANE; j++) if (j == aj && ((okbits >> j) & 1u)) mine_lpa = z[j] - logS;
             const float logp_a = row_sum(mine_lpa);
+            if constexpr (OBJ == 0) {
             const float adv = hq - valS[row];
             const float ent_w = 0.1f / (float)(cnt ? cnt : 1u);
             const float G = -adv - 0.1f;                           // sum_j dL/dlogp_j (times n)
@@ -332,6 +356,43 @@ __global__ void __launch_bounds__(64 * LG_WAVES) azul_a2c_grad_kernel(PolicyWeig
                     lossS[2][row] += -(zsum / (float)cnt - logS);
                     lossS[3][row] += 1.f;
                 }
+            }
+            } else {
+            // PPO (header comment): e becomes p in place; logp_k = z_k - logS is formed twice, for H from z and for the gradient from
+            // the logits still in LDS (the same two subtractions: the same bits), so that z is dead where the gradient loop runs.  Its
+            // two inputs are requested here, not before layer 2 like the return.  (Scratch: 20 bytes per lane beside OBJ = 0's 8)
+            const float hold = a.old_logp[hsc], hadv = a.advantage[hsc];
+            const float invS = 1.0f / S;
+            float hs = 0.f;
+            for (int j = 0; j < HEAD_PER_LANE; j++) {
+                bool ok = (okbits >> j) & 1u;
+                e[j] *= invS;
+                hs -= e[j] * (ok ? z[j] - logS : 0.f);
+            }
+            const float H = row_sum(hs);
+            const float ratio = __expf(logp_a - hold), lo = 1.0f - a.clip_eps, hi = 1.0f + a.clip_eps;
+            const bool clipped = (hadv > 0.f && ratio > hi) || (hadv < 0.f && ratio < lo);
+            const float ga = clipped ? 0.f : -hadv * ratio;        // dL/dlogp_a (times n)
+            const float ce = a.entropy_coeff;
+            for (int j = 0; j < HEAD_PER_LANE; j++) {
+                bool ok = (okbits >> j) & 1u;
+                float lpj = ok ? (lg[j] - m) - logS : 0.f;
+                float d = (ga * ((j == aj ? 1.f : 0.f) - e[j]) + ce * e[j] * (lpj + H)) * inv_n;
+                lg[j] = (use && ok) ? d : 0.f;
+            }
+            if (c == 0u) {
+                const float td = hq - valS[row];
+                const float dv = use ? -2.0f * a.value_coeff * td * inv_n : 0.f;
+                dvS[row] = dv;
+                lossS[4][row] += dv;                     // (slot `row` belongs to this lane alone: fixed summation order)
+                if (use) {
+                    lossS[0][row] += -fminf(ratio * hadv, fminf(fmaxf(ratio, lo), hi) * hadv);
+                    lossS[1][row] += td * td;
+                    lossS[2][row] += H;
+                    lossS[3][row] += 1.f;
+                    if (a.logp_out) a.logp_out[tile * LG_M + row] = logp_a;
+                }
+            }
             }
             if (tid < (u32)LG_M) idxS[par ^ 1u][tid] = nidx;
         }
@@ -761,7 +822,7 @@ __device__ __forceinline__ float ln_max32(float v)
     return v;
 }
 
-template <int IN, int A>
+template <int IN, int A, int OBJ = 0>                    // OBJ: the objective of the head (P3), as in azul_a2c_grad_kernel
 __global__ void __launch_bounds__(64 * LN_WAVES) azul_a2c_grad_n_kernel(PolicyWeights W, LearnerArgs a)
 {
     using Cf = LnCfg<IN, A>;
@@ -901,6 +962,7 @@ __global__ void __launch_bounds__(64 * LN_WAVES) azul_a2c_grad_n_kernel(PolicyWe
                 if ((i32)(l + 32u * (u32)i) == act && ((okbits >> i) & 1u)) mine_lpa = x[i] - logS;
             const float logp_a = ln_sum32(mine_lpa);
             const bool use = valid && cnt > 0.f;                   // rows without a legal action carry no sample
+            if constexpr (OBJ == 0) {
             const float adv = a.qvals[sc] - valS[s];
             const float ent_w = 0.1f / (cnt > 0.f ? cnt : 1.f);
             const float G = -adv - 0.1f;
@@ -922,6 +984,43 @@ __global__ void __launch_bounds__(64 * LN_WAVES) azul_a2c_grad_n_kernel(PolicyWe
                     lossS[2][s] += -(zsum / cnt - logS);
                     lossS[3][s] += 1.f;
                 }
+            }
+            } else {
+            // PPO (header comment): e becomes p in place; logp_k = z_k - logS is formed for H from x (= z) and again for the gradient from
+            // the logits still in LDS (the same subtractions: the same bits), so that x is dead where the gradient loop runs
+            const float invS = 1.0f / S;
+            const float hadv = a.advantage[sc], hold = a.old_logp[sc];
+            float hs = 0.f;
+            for (int i = 0; i < NJ; i++) {
+                const bool ok = (okbits >> i) & 1u;
+                e[i] *= invS;
+                hs -= e[i] * (ok ? x[i] - logS : 0.f);
+            }
+            const float H = ln_sum32(hs);
+            const float ratio = __expf(logp_a - hold), lo = 1.0f - a.clip_eps, hi = 1.0f + a.clip_eps;
+            const bool clipped = (hadv > 0.f && ratio > hi) || (hadv < 0.f && ratio < lo);
+            const float ga = clipped ? 0.f : -hadv * ratio;        // dL/dlogp_a (times n)
+            const float ce = a.entropy_coeff;
+            for (int i = 0; i < NJ; i++) {
+                const u32 j = l + 32u * (u32)i;
+                const bool ok = (okbits >> i) & 1u;
+                const float lpj = ok ? (lgS[s * AS + j] - m) - logS : 0.f;
+                const float d = (ga * (((i32)j == act ? 1.f : 0.f) - e[i]) + ce * e[i] * (lpj + H)) * inv_n;
+                if (j < (u32)A) lgS[s * AS + j] = (use && ok) ? d : 0.f;
+            }
+            if (l == 0u) {
+                const float td = a.qvals[sc] - valS[s];
+                const float dv = use ? -2.0f * a.value_coeff * td * inv_n : 0.f;
+                dvS[s] = dv;
+                lossS[4][s] += dv;                                 // (slot s belongs to this lane alone: fixed summation order)
+                if (use) {
+                    lossS[0][s] += -fminf(ratio * hadv, fminf(fmaxf(ratio, lo), hi) * hadv);
+                    lossS[1][s] += td * td;
+                    lossS[2][s] += H;
+                    lossS[3][s] += 1.f;
+                    if (role == 2u && a.logp_out) a.logp_out[tile * LN_M + s] = logp_a;     // (one of the three roles: one writer per sample)
+                }
+            }
             }
         }
         __syncthreads();

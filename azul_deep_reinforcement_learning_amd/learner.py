@@ -86,8 +86,24 @@ class A2CLearner:
     def loss_terms(self, obs, mask, action, qvals, weight=None, n_total=None):
         """obs [n,136] f32, mask [n,180] bool/u8, action [n] int, qvals [n] -> the four loss terms of agent.py:51-57.
         `weight` [n] (0/1) drops samples without changing shapes; `n_total` is the divisor (default: the local count)."""
-        pol = self.policy
         legal = mask.bool()
+        values, logp = self._values_logp(obs, legal)
+        log_prob = logp.gather(1, action.long().clamp(min=0).unsqueeze(1)).squeeze(1)                 # nn_runner.py:32
+        entropy = -(torch.where(legal, logp, torch.zeros_like(logp)).sum(dim=1) / legal.sum(dim=1).clamp(min=1))   # :36-40
+        advantage = qvals.to(values.dtype) - values
+        w = torch.ones_like(values) if weight is None else weight.to(values.dtype)
+        n = w.sum() if n_total is None else n_total
+        # a window without a finished episode has no sample: the sums are 0, and so are the terms (the fused path's rule), not 0 / 0
+        n = n.clamp(min=1.0) if torch.is_tensor(n) else max(float(n), 1.0)
+        actor_loss = (-log_prob * advantage * w).sum() / n
+        critic_loss = (advantage.pow(2) * w).sum() / n
+        entropy_loss = (entropy * w).sum() / n
+        ac_loss = ACTOR_COEFF * actor_loss + CRITIC_COEFF * critic_loss + ENTROPY_COEFF * entropy_loss
+        return actor_loss, critic_loss, entropy_loss, ac_loss
+
+    def _values_logp(self, obs, legal):
+        """The network on a batch with autograd: values [n], masked log-probabilities [n, A] (-inf where illegal)."""
+        pol = self.policy
         if hasattr(pol, "critic_linear1") and hasattr(pol, "actor_linear1"):
             # same arithmetic as forward_critic / forward_actor (model.py:22-41) with both first layers in ONE GEMM (and one
             # weight-gradient GEMM in the backward pass): autograd splits the concatenated gradient back onto the two modules
@@ -101,18 +117,7 @@ class A2CLearner:
         else:
             values = pol.forward_critic(obs).squeeze(1)
             _, logp = pol.forward_actor(obs, legal)
-        log_prob = logp.gather(1, action.long().clamp(min=0).unsqueeze(1)).squeeze(1)                 # nn_runner.py:32
-        entropy = -(torch.where(legal, logp, torch.zeros_like(logp)).sum(dim=1) / legal.sum(dim=1).clamp(min=1))   # :36-40
-        advantage = qvals.to(values.dtype) - values
-        w = torch.ones_like(values) if weight is None else weight.to(values.dtype)
-        n = w.sum() if n_total is None else n_total
-        # a window without a finished episode has no sample: the sums are 0, and so are the terms (the fused path's rule), not 0 / 0
-        n = n.clamp(min=1.0) if torch.is_tensor(n) else max(float(n), 1.0)
-        actor_loss = (-log_prob * advantage * w).sum() / n
-        critic_loss = (advantage.pow(2) * w).sum() / n
-        entropy_loss = (entropy * w).sum() / n
-        ac_loss = ACTOR_COEFF * actor_loss + CRITIC_COEFF * critic_loss + ENTROPY_COEFF * entropy_loss
-        return actor_loss, critic_loss, entropy_loss, ac_loss
+        return values, logp
 
     # ---- hand-written gradient / optimiser path -------------------------------------------------------------------------
     # One flat k-major vector holds the master copy of the parameters (layout of azul_a2c_gradients' gradient; flat_layout()):
@@ -409,3 +414,202 @@ class A2CLearner:
         one = len(trajectories) == 1
         return self.update(obs[0] if one else torch.cat(obs), mask[0] if one else torch.cat(mask),
                            action[0] if one else torch.cat(action), ret[0] if one else torch.cat(ret))
+
+
+class PPOLearner(A2CLearner):
+    """PPO on the windows of a PolicyRollout: `epochs` passes of `minibatches` optimiser steps over the steps of ONE window, made safe
+    by the clipped importance ratio.  Reuses A2CLearner's flat k-major master copy, kweights(), Adam (_finish_fused) and statistics ring;
+    the gradients come from azul_ppo_gradients (the A2C gradient kernels with a second head, csrc/azul_learner.hpp) on the fused path
+    and from autograd of loss_terms_ppo otherwise.
+
+    Objective per sample, over the n samples of a minibatch (old_logp = the rollout's recorded log_prob, Adv an input: detached):
+        r = exp(logp[a] - old_logp),   L_pi = -min(r Adv, clamp(r, 1 - clip_eps, 1 + clip_eps) Adv),   H = -sum_k p_k logp_k
+        loss = mean(L_pi) + value_coeff * mean((returns - V)^2) - entropy_coeff * mean(H)
+    Adv = returns - value from the rollout's recorded `value` (with PolicyRollout(gae_lambda=...) that is the GAE advantage), normalised
+    over the selected samples of the window when normalize_advantage: (A - mean) / (std + 1e-8), population std, f32.
+
+    Statistics, one entry per OPTIMISER STEP, under A2CLearner's keys with PPO's meaning: actor_loss = mean L_pi, critic_loss =
+    mean (returns - V)^2 (without the coefficient), entropy_loss = mean H (the true entropy, which the loss SUBTRACTS), ac_loss = actor +
+    value_coeff * critic - entropy_coeff * H, samples = the minibatch size; and two more: clip_fraction = mean(|r - 1| > clip_eps) and
+    approx_kl = mean(old_logp - logp[a]), both of the policy BEFORE the step."""
+
+    def __init__(self, policy, learning_rate=3e-4, gamma=0.99, clip_eps=0.2, value_coeff=0.5, entropy_coeff=0.01, epochs=4, minibatches=4,
+                 normalize_advantage=True, shuffle_seed=0, fused=None, stat_history=4096, distributed=None):
+        self.check_arguments(clip_eps, value_coeff, entropy_coeff, epochs, minibatches, distributed)
+        super().__init__(policy, learning_rate=learning_rate, gamma=gamma, distributed=False, fused=fused, stat_history=stat_history)
+        self.clip_eps, self.value_coeff, self.entropy_coeff = float(clip_eps), float(value_coeff), float(entropy_coeff)
+        self.epochs, self.minibatches = int(epochs), int(minibatches)
+        self.normalize_advantage = bool(normalize_advantage)
+        self.shuffle_seed = int(shuffle_seed)
+        self.u = 0                        # update_from_windows calls so far: with the epoch it keys the minibatch permutation
+        for k in ("clip_fraction", "approx_kl"):
+            self.statistics[k] = collections.deque(maxlen=stat_history)
+        self._step_extras = None
+
+    @staticmethod
+    def check_arguments(clip_eps, value_coeff, entropy_coeff, epochs, minibatches, distributed=None):
+        """The refusals of the constructor (ValueError), before anything is allocated; BatchedTrainer asks them before it builds anything."""
+        if distributed or (distributed is None and dist.is_available() and dist.is_initialized()):
+            raise ValueError("PPOLearner is single-process: its minibatch permutations are not sharded over ranks (distributed=True refused)")
+        if int(epochs) < 1 or int(minibatches) < 1:
+            raise ValueError("epochs and minibatches must be >= 1, got %r and %r" % (epochs, minibatches))
+        if not float(clip_eps) > 0.0 or float(clip_eps) == float("inf"):
+            raise ValueError("clip_eps must lie in (0, +inf), got %r" % (clip_eps,))
+        if not (0.0 <= float(value_coeff) < float("inf") and 0.0 <= float(entropy_coeff) < float("inf")):
+            raise ValueError("value_coeff and entropy_coeff must be finite and >= 0, got %r and %r" % (value_coeff, entropy_coeff))
+
+    def loss_terms_ppo(self, obs, mask, action, returns, old_log_prob, advantage, n_total=None):
+        """The objective of the class docstring in PyTorch (any shape, CPU or GPU): (actor_loss, critic_loss, entropy, loss, log_prob) with
+        actor_loss = sum L_pi / n, critic_loss = sum (returns - V)^2 / n, entropy = sum H / n, loss = actor + value_coeff * critic -
+        entropy_coeff * entropy, and log_prob [rows] = logp[a] (attached).  `n_total`: the divisor (default: the number of rows).  Rows
+        without a legal action carry no sample but stay in the divisor, as in the kernels."""
+        legal = mask.bool()
+        live = legal.any(dim=1)
+        legal = legal | ~live.unsqueeze(1)               # (a dead row is evaluated as if every action were legal, then weighted out: no NaN)
+        values, logp = self._values_logp(obs, legal)
+        log_prob = logp.gather(1, action.long().clamp(min=0).unsqueeze(1)).squeeze(1)
+        lp0 = torch.where(legal, logp, torch.zeros_like(logp))
+        entropy = -(lp0.exp() * legal * lp0).sum(dim=1)
+        adv = advantage.to(values.dtype).detach()
+        ratio = torch.exp(log_prob - old_log_prob.to(values.dtype).detach())
+        surrogate = torch.min(ratio * adv, torch.clamp(ratio, 1.0 - self.clip_eps, 1.0 + self.clip_eps) * adv)
+        w = live.to(values.dtype)
+        n = float(obs.shape[0]) if n_total is None else n_total
+        n = n.clamp(min=1.0) if torch.is_tensor(n) else max(float(n), 1.0)
+        actor_loss = (torch.where(live, -surrogate, torch.zeros_like(surrogate))).sum() / n
+        critic_loss = ((returns.to(values.dtype) - values).pow(2) * w).sum() / n
+        entropy_mean = (entropy * w).sum() / n
+        loss = actor_loss + self.value_coeff * critic_loss - self.entropy_coeff * entropy_mean
+        return actor_loss, critic_loss, entropy_mean, loss, log_prob
+
+    def optimizer_state(self):
+        """A2CLearner's state plus `u`, the count of update_from_windows calls: a resumed run draws the same permutations."""
+        st = super().optimizer_state()
+        st["ppo"] = {"u": int(self.u)}
+        return st
+
+    def load_optimizer_state(self, st):
+        super().load_optimizer_state(st)
+        if "ppo" in st:
+            self.u = int(st["ppo"]["u"])
+
+    def _record(self, out):
+        """The entry of one optimiser step: ac_loss from the three terms with PPO's coefficients (the Adam kernel's slot holds the
+        reference's 1 / 0.5 / 0.1 combination), plus the ratio diagnostics of the step."""
+        clip_fraction, approx_kl = self._step_extras
+        out = dict(out, ac_loss=out["actor_loss"] + self.value_coeff * out["critic_loss"] - self.entropy_coeff * out["entropy_loss"],
+                   clip_fraction=clip_fraction, approx_kl=approx_kl)
+        return super()._record(out)
+
+    def _ratio_stats(self, log_prob, old_log_prob):
+        d = old_log_prob - log_prob
+        return ((torch.exp(-d) - 1.0).abs() > self.clip_eps).to(torch.float32).mean(), d.mean()
+
+    def _permutations(self, rows, u, device):
+        """[epochs, rows] on `device`: row e is the order in which epoch e of call `u` visits the `rows` rows of the window -- a function of
+        (shuffle_seed, u, e) only, drawn on the CPU.  A draw of 131072 rows takes the host about 1 ms, so the caller asks BEFORE the
+        selection's host synchronisation: the draws then overlap the device's work on the window (pinned staging buffer, asynchronous
+        copy; the synchronisation that follows completes the copy before the buffer is written again)."""
+        pin = getattr(self, "_perm_pin", None)
+        if pin is None or tuple(pin.shape) != (self.epochs, rows) or pin.is_pinned() != (device.type == "cuda"):
+            pin = self._perm_pin = torch.empty(self.epochs, rows, dtype=torch.int64, pin_memory=device.type == "cuda")
+        g = torch.Generator()
+        for e in range(self.epochs):
+            g.manual_seed(((self.shuffle_seed * 1000003 + u) * 1000003 + e) % (1 << 63))
+            torch.randperm(rows, generator=g, out=pin[e])
+        return pin.to(device, non_blocking=True) if device.type == "cuda" else pin.clone()
+
+    def _fused_gradients(self, src, chunk, adv_rows):
+        """One azul_ppo_gradients launch on the rows `chunk` (int32, device) of the window's buffers, read in place; the flat gradient and
+        the four sums land in the workspace's `grad`, the recomputed logp[a] of the chunk is returned.  -> (None, n_host) for _finish_fused."""
+        import ctypes as C
+        from . import _lib as L
+        pol, dev = self.policy, src["obs"].device
+        ws = self._ensure_flat(dev)
+        kw = self.kweights(dev)
+        n = int(chunk.numel())
+        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        with torch.no_grad():
+            logp = src["log_prob"].index_select(0, chunk)              # (rows without a sample keep the old value: ratio 1 in the diagnostics)
+            L.check(L.lib.azul_ppo_gradients(p(src["obs"]), p(src["mask"]), p(src["action"]), p(src["returns"]), p(src["log_prob"]), p(adv_rows),
+                                             n, C.c_float(1.0 / n), C.c_float(self.clip_eps), C.c_float(self.value_coeff),
+                                             C.c_float(self.entropy_coeff), p(kw["w1t"]), p(kw["b1"]), p(kw["w2c"]), p(kw["b2c"]), p(kw["w2a_t"]),
+                                             p(kw["b2a"]), p(pol.actor_linear2.weight), *self.shape, p(ws["ws"]), 256, p(ws["grad"]), p(chunk),
+                                             None, None, p(logp), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        return (None, float(n)), logp
+
+    def update_from_rollout(self, rollout):
+        """PPO trains the newest window (the ring of whole episodes is A2C's): update_from_windows(rollout.traj)."""
+        return self.update_from_windows(rollout.traj)
+
+    def update_from_windows(self, trajectories, complete_only=True):
+        """epochs x minibatches optimiser steps on the steps of the window(s) that carry an action -- and whose episode ends inside the
+        window unless complete_only=False (PolicyRollout(bootstrap_tail=True) gives every recorded step a target).  The selection is ONE
+        torch.nonzero, i.e. one host synchronisation per call: the minibatch sizes are host numbers, and the price is paid once per
+        epochs x minibatches optimiser steps.  Epoch e of the u-th call visits the selected rows in the order a permutation of the window's
+        rows gives them -- a function of (shuffle_seed, u, e) only, drawn on the CPU before that synchronisation -- cut into `minibatches`
+        near-equal chunks; on the fused path (one part) every chunk is one azul_ppo_gradients launch reading the window's
+        buffers in place through the chunk as index list (no compaction copies) and one Adam step; otherwise the chunks go through
+        loss_terms_ppo and optimizer.step().  Several parts are compacted and concatenated first.  An empty selection performs no step and
+        records one entry of zeros.  Returns the statistics of the last step."""
+        keys = ("obs", "mask", "action", "returns", "log_prob", "value")
+        u, one = self.u, len(trajectories) == 1
+        self.u += 1
+        flat, perms = [], None
+        for tr in trajectories:
+            T = tr["action"].shape[0]
+            keep = complete_episode_samples(tr["done"]) if complete_only else torch.ones_like(tr["done"], dtype=torch.bool)
+            keep = (keep & (tr["action"] >= 0)).reshape(-1)
+            rows = {"obs": tr["obs"][:T].reshape(-1, tr["obs"].shape[-1]), "mask": tr["mask"][:T].reshape(-1, tr["mask"].shape[-1])}
+            rows.update({k: tr[k].reshape(-1) for k in keys[2:]})
+            if one:                                      # drawn while the device still works on the window: before the synchronisation
+                perms = self._permutations(keep.numel(), u, keep.device)
+            flat.append((rows, keep, torch.nonzero(keep).squeeze(1)))
+        if one:
+            src, keep, sel = flat[0]
+        else:
+            src = {k: torch.cat([rows[k].index_select(0, idx) for rows, _, idx in flat]) for k in keys}
+            keep, sel = None, torch.arange(src["action"].shape[0], device=src["action"].device)
+        dev = src["obs"].device
+        n = int(sel.numel())
+        if n == 0:
+            zero = torch.zeros((), device=dev)
+            self._step_extras = (zero, zero)
+            return self._record({"actor_loss": zero, "critic_loss": zero, "entropy_loss": zero, "ac_loss": zero, "samples": zero})
+        if perms is None:
+            perms = self._permutations(n, u, dev)
+        fused = self._use_fused(src["obs"])
+        with torch.no_grad():
+            adv = src["returns"].index_select(0, sel).float() - src["value"].index_select(0, sel).float()
+            if self.normalize_advantage:
+                adv = (adv - adv.mean()) / (adv.std(unbiased=False) + 1e-8)
+            adv_rows = torch.zeros(src["action"].shape[0], device=dev).index_copy_(0, sel, adv)      # per source row, like the buffers
+            if fused:
+                src = {"obs": src["obs"].contiguous().float(), "mask": src["mask"].contiguous().to(torch.uint8),
+                       "action": src["action"].contiguous().to(torch.int32), "returns": src["returns"].contiguous().float(),
+                       "log_prob": src["log_prob"].contiguous().float()}                  # (the rollout's buffers as they are: no copies)
+        out = None
+        for e in range(self.epochs):
+            order = perms[e]
+            if keep is not None:                         # the selected rows in the permutation's order (a stable sort brings them to the
+                order = order[torch.argsort((~keep[order]).to(torch.uint8), stable=True)[:n]]       # front: no second host round trip)
+            for rows in torch.tensor_split(order, self.minibatches):
+                if rows.numel() == 0:
+                    continue
+                if fused:
+                    chunk = rows.to(torch.int32)
+                    nn, logp = self._fused_gradients(src, chunk, adv_rows)
+                    self._step_extras = self._ratio_stats(logp, src["log_prob"].index_select(0, rows))
+                    out = self._finish_fused(*nn)
+                else:
+                    a, c, h, loss, logp = self.loss_terms_ppo(*(src[k].index_select(0, rows) for k in keys[:5]), adv_rows.index_select(0, rows))
+                    self.optimizer.zero_grad(set_to_none=False)
+                    loss.backward()
+                    self.optimizer.step()
+                    with torch.no_grad():
+                        old = src["log_prob"].index_select(0, rows).float()
+                        live = src["mask"].index_select(0, rows).bool().any(dim=1)         # (a row without a sample: ratio 1, as on the fused path)
+                        self._step_extras = self._ratio_stats(torch.where(live, logp.detach(), old), old)
+                    out = self._record({"actor_loss": a.detach(), "critic_loss": c.detach(), "entropy_loss": h.detach(),
+                                        "ac_loss": loss.detach(), "samples": torch.full((), float(rows.numel()), device=dev)})
+        return out

@@ -27,7 +27,7 @@ import os
 import numpy as np
 import torch
 
-from .learner import A2CLearner, complete_episode_samples
+from .learner import A2CLearner, PPOLearner, complete_episode_samples
 from .records import STAT_KEYS
 from .rollout import PolicyRollout
 
@@ -38,7 +38,8 @@ class BatchedTrainer:
     def __init__(self, policy, n_games=4096, window=32, parts=1, learning_rate=3e-4, gamma=0.99, seed_base=0, sample_seed=0x5EED,
                  rules={"first_player": "Random", "tile_pool": "Lid"}, device=None, use_graph=True, persistent=True, results_dir="results",
                  ring=3, opponent="random", opponent_refresh=0, move_limit=0, players=2, fused_wide=False,
-                 fused_opponent=False, fused_learner=False, fused_seats=False, gae_lambda=None, bootstrap_tail=False):
+                 fused_opponent=False, fused_learner=False, fused_seats=False, gae_lambda=None, bootstrap_tail=False, algorithm="a2c",
+                 clip_eps=0.2, value_coeff=0.5, entropy_coeff=0.01, epochs=4, minibatches=4, normalize_advantage=True):
         """ring: trajectory windows kept (persistent rollout with one part): with ring >= 2 every step of every episode is trained
         exactly once (episodes straddle windows; an episode may span ring - 1 window boundaries), like NNRunner.train.
         opponent: "random" (GameRunner's default RandomAgent, the reference's scripts/training.py), a module (GameRunner(opponent=Agent(...)),
@@ -73,7 +74,14 @@ class BatchedTrainer:
         return, the launches of before.  bootstrap_tail=True (needs ring=1): the critic's value of the state after the window flows into its
         newest step and run_batch trains EVERY recorded step that carries an action, open episodes included
         (A2CLearner.update_from_windows(traj, complete_only=False)): n-step A2C.  Both need an opponent; a resumed run replays the next
-        window's returns bit for bit (the values are in the ring a checkpoint carries, the tail is recomputed from the restored weights)."""
+        window's returns bit for bit (the values are in the ring a checkpoint carries, the tail is recomputed from the restored weights).
+        algorithm: "a2c" (default: everything above, launch for launch) or "ppo": the learner is a PPOLearner(clip_eps, value_coeff,
+        entropy_coeff, epochs, minibatches, normalize_advantage) -- `fused` decided as for the A2C learner -- and run_batch makes
+        epochs x minibatches optimiser steps on the newest window through update_from_windows(traj, complete_only=not bootstrap_tail): the
+        clipped surrogate on returns - value (the GAE advantage with gae_lambda), gradients from azul_ppo_gradients on the fused path.  PPO
+        trains one window: it needs ring=1 and an opponent other than None (ValueError otherwise, as for an unknown algorithm).  The five
+        agent columns of the CSV carry PPOLearner's meanings, averaged over the optimiser steps since the last logged row; checkpoints
+        carry the learner's call count, which keys the minibatch permutations."""
         from .batch import parse_ext_rules
         wide = int(players) != 2 or parse_ext_rules(rules, int(players)) != 0
         fused_learner = bool(fused_learner)
@@ -87,12 +95,24 @@ class BatchedTrainer:
         if bootstrap_tail and parts == 1 and int(ring) >= 2 and (persistent or (wide and fused_learner)):
             raise ValueError("bootstrap_tail=True gives the open episodes of one window a target: it needs ring=1 (a ring of %d windows "
                              "trains whole episodes, nothing is open there)" % int(ring))
+        if algorithm not in ("a2c", "ppo"):
+            raise ValueError("algorithm must be \"a2c\" or \"ppo\", got %r" % (algorithm,))
+        if algorithm == "ppo" and (int(ring) != 1 or opponent is None):
+            raise ValueError("algorithm=\"ppo\" trains the newest window of one seat's records: it needs ring=1 and an opponent other than None")
+        if algorithm == "ppo":
+            PPOLearner.check_arguments(clip_eps, value_coeff, entropy_coeff, epochs, minibatches)
+        self.algorithm = algorithm
         self.bootstrap_tail = bool(bootstrap_tail)
         dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         policy = policy.to(dev)
         wide_fused = wide and fused_learner
-        self.learner = A2CLearner(policy, learning_rate=learning_rate, gamma=gamma,
-                                  fused=(True if wide_fused else False) if wide else (True if fused_learner else None))
+        fused = (True if wide_fused else False) if wide else (True if fused_learner else None)
+        if algorithm == "ppo":
+            self.learner = PPOLearner(policy, learning_rate=learning_rate, gamma=gamma, clip_eps=clip_eps, value_coeff=value_coeff,
+                                      entropy_coeff=entropy_coeff, epochs=epochs, minibatches=minibatches,
+                                      normalize_advantage=normalize_advantage, shuffle_seed=sample_seed, fused=fused)
+        else:
+            self.learner = A2CLearner(policy, learning_rate=learning_rate, gamma=gamma, fused=fused)
         # rollout kernels and learner share ONE k-major copy of the weights (the learner's flat master copy)
         self.opponent_refresh = int(opponent_refresh)
         self._self_opponent = opponent == "self"
@@ -141,7 +161,9 @@ class BatchedTrainer:
         GameStatistics buffers between two get_stats() calls (game_runner.py:17-22)."""
         tr = self.rollout.run_window(self.gamma)
         self.rollout.join()                              # device-side dependency: the host keeps enqueueing
-        if self.bootstrap_tail:                          # every recorded step has its target: the open episodes' steps are samples too
+        if self.algorithm == "ppo":                      # epochs x minibatches steps on the newest window
+            out = self.learner.update_from_windows(tr, complete_only=not self.bootstrap_tail)
+        elif self.bootstrap_tail:                        # every recorded step has its target: the open episodes' steps are samples too
             out = self.learner.update_from_windows(tr, complete_only=False)
         else:
             out = self.learner.update_from_rollout(self.rollout)

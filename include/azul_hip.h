@@ -554,6 +554,24 @@ int azul_a2c_gradients(const float *obs_dev, const uint8_t *mask_dev, const int3
                        const float *w2a_t_dev, const float *b2a_dev, const float *w2a_dev, int num_inputs, int hidden_size, int num_actions,
                        float *workspace_dev, int workspace_parts, float *grad_dev, const int32_t *index_dev, const int32_t *n_samples_dev,
                        const float *inv_n_total_dev, void *stream);
+/* PPO's gradients for the same samples, shapes, layouts, workspace, alignment rules, optional device-side inputs and launch rule
+ * (min(tiles, workspace_parts) parts, fixed reduction order: bit-reproducible; no tile: grad_dev is zeroed) as azul_a2c_gradients --
+ * the same kernels with a second head.  Per sample, all in f32 (device exp / log like azul_a2c_gradients):
+ *     r = exp(logp[a] - old_log_prob),   L_pi = -min(r Adv, clamp(r, 1 - clip_eps, 1 + clip_eps) Adv),   H = -sum_{k legal} p_k logp_k
+ *     L = mean_i( L_pi + value_coeff * (returns - V)^2 - entropy_coeff * H )
+ * old_log_prob_dev and advantage_dev (per source row, through index_dev like returns_dev) are inputs: nothing flows back through them.
+ * The gradient is autograd's of torch.min(r * Adv, torch.clamp(r, 1 - clip_eps, 1 + clip_eps) * Adv), r exactly on a bound and
+ * Adv == 0 included.  The four sums after the flat gradient differ from azul_a2c_gradients': sum L_pi, sum (returns - V)^2 (raw: without
+ * value_coeff), sum H (the true entropy), count of samples used.  log_prob_out_dev (optional, [n_samples]): sample s in launch order
+ * (not its source row) receives the recomputed logp[a]; rows without a sample (past the count, no legal action) are not written.
+ * AZUL_ERR_INVALID before any HIP call: a shape that is not compiled, NULL old_log_prob_dev / advantage_dev with n_samples > 0,
+ * clip_eps outside (0, +inf) (+inf refused; a huge finite value such as 1e30 never clips), negative or non-finite coefficients. */
+int azul_ppo_gradients(const float *obs_dev, const uint8_t *mask_dev, const int32_t *action_dev, const float *returns_dev,
+                       const float *old_log_prob_dev, const float *advantage_dev, int n_samples, float inv_n_total, float clip_eps,
+                       float value_coeff, float entropy_coeff, const float *w1t_dev, const float *b1_dev, const float *w2c_dev,
+                       const float *b2c_dev, const float *w2a_t_dev, const float *b2a_dev, const float *w2a_dev, int num_inputs, int hidden_size,
+                       int num_actions, float *workspace_dev, int workspace_parts, float *grad_dev, const int32_t *index_dev,
+                       const int32_t *n_samples_dev, const float *inv_n_total_dev, float *log_prob_out_dev, void *stream);
 #define AZUL_A2C_FLAT_SIZE 82082      /* 82081 parameters of ActorCritic(136, 180, 180) in the k-major layout above + 1 pad float */
 /* azul_a2c_apply_adam_n (below) for ActorCritic(136, 180, 180): the same call with the shape filled in.
  * torch.optim.Adam's step (defaults: betas 0.9 / 0.999, eps 1e-8, no weight decay; same arithmetic) on the flat k-major master copy of
