@@ -23,6 +23,7 @@ PERSP_MOVER = 7
 SCORE_ILLEGAL = -2 ** 31              # AZUL_SCORE_ILLEGAL: azul_batch_score_moves' entry of an action that is not legal
 FLAG_END_OF_ROUND, FLAG_END_OF_GAME, FLAG_ENDED_FLAG = 1, 2, 4
 A2C_FLAT_SIZE = 82082          # k-major flat layout of the parameters / gradient / Adam moments (82081 + 1 pad)
+LEAGUE_GROUP_GAMES = 16                   # AZUL_LEAGUE_GROUP_GAMES: the games of one workgroup of the window kernels play one pool member
 POLICY_ARGMAX = 0xFFFFFFFFFFFFFFFF        # `seed` value: np.argmax instead of sampling (agent.py action_selection="Max")
 
 _vp, _i, _u64, _u32 = C.c_void_p, C.c_int, C.c_uint64, C.c_uint32
@@ -105,6 +106,11 @@ SIGNATURES = {
     "azul_batch_mp_policy_rollout": (_i, [_vp, _i, _i, C.POINTER(NetWeights), _i, _i, _i, _u64, _u64, _vp, C.POINTER(RolloutBuffers), C.c_float, _vp]),
     "azul_batch_mp_policy_rollout_vs": (_i, [_vp, _i, C.POINTER(NetWeights), C.POINTER(NetWeights), _i, _i, _i, _u64, _u64, _u64, _vp, _i,
                                              C.POINTER(RolloutBuffers), C.c_float, _vp]),
+    "azul_batch_policy_rollout_league": (_i, [_vp, _i, C.POINTER(NetWeights), C.POINTER(NetWeights), _i, _vp, _i, _i, _i, _u64, _u64, _u64, _vp,
+                                              C.POINTER(RolloutBuffers), C.c_float, _vp]),
+    "azul_batch_mp_policy_rollout_league": (_i, [_vp, _i, C.POINTER(NetWeights), C.POINTER(NetWeights), _i, _vp, _i, _i, _i, _u64, _u64, _u64, _vp,
+                                                 _i, C.POINTER(RolloutBuffers), C.c_float, _vp]),
+    "azul_league_tally": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
     "azul_batch_mp_policy_rollout_greedy": (_i, [_vp, _i, C.POINTER(NetWeights), _i, _i, _i, _u64, _u64, _vp, _i, C.POINTER(RolloutBuffers),
                                                  C.c_float, _vp]),
     "azul_batch_net_step_begin": (_i, [_vp] * 11),

@@ -723,6 +723,8 @@ static int launch_rollout(azul_batch_t *b, const PolicyWeights &W, const Rollout
 
 struct NetShape { int inputs, hidden, actions; };
 struct DrawKeys { uint64_t seed, opp_seed, counter; uint64_t *counter_dev; };
+struct League { int pool_size; const uint8_t *member_dev; };     // azul_batch_[mp_]policy_rollout_league: the pool behind `opponent`
+static_assert(AZUL_LEAGUE_GROUP_GAMES == PF_GAMES, "a league group is the 16 games of one workgroup of the window kernels");
 
 static int fail_in(const char *who, const char *what)
 {
@@ -736,16 +738,21 @@ static int fail_in(const char *who, const char *what)
 // differences are behaviour (include/azul_hip.h).
 static int rollout_window(azul_batch_t *b, const char *who, bool wide, int n_steps, int opp, const azul_net_weights_t *agent,
                           const azul_net_weights_t *opponent, NetShape shape, DrawKeys keys, const azul_rollout_buffers_t *out, float gamma,
-                          int max_replies, void *stream)
+                          int max_replies, void *stream, const League *league = nullptr)
 {
     const bool net = opp == 2;
     if (!b || n_steps < 0 || !agent || !out) return fail_in(who, "bad arguments");
+    if (league) {                                            // `opponent` is the stacked pool (include/azul_hip.h)
+        if (league->pool_size < 1 || league->pool_size > 255) return fail_in(who, "pool_size must be in 1..255 (a member is one byte per group)");
+        if (!opponent || !league->member_dev) return fail_in(who, "NULL pool or member_dev");
+    }
     if (net && !opponent) return fail_in(who, "no opponent (the entry without _vs plays without one)");
     if (opp == 3 && !wide && b->x)
         return fail_in(who, "a wide batch (three / four players or extended rules): the greedy player maximises the two-player reward of "
                             "game_runner.py:48-50");
     if (wide != b->x)
-        return fail_in(who, wide ? (net ? "a two-player batch of 128-byte records: use azul_batch_policy_rollout_vs"
+        return fail_in(who, wide ? (league ? "a two-player batch of 128-byte records: use azul_batch_policy_rollout_league"
+                                    : net ? "a two-player batch of 128-byte records: use azul_batch_policy_rollout_vs"
                                         : opp == 3 ? "a two-player batch of 128-byte records: use azul_batch_policy_rollout_greedy"
                                         : "a two-player batch of 128-byte records: use azul_batch_policy_rollout")
                                  : "the policy entries are compiled for the reference's two-player game (ActorCritic(136, 180): 180 actions, 136 "
@@ -782,6 +789,7 @@ static int rollout_window(azul_batch_t *b, const char *who, bool wide, int n_ste
         a.Wopp = {opponent->w1t, opponent->b1, opponent->w2c, opponent->b2c, opponent->w2a_t, opponent->b2a};
         a.opp_seed = (u64)keys.opp_seed;
         a.opp_action = out->opp_action; a.opp_logp = out->opp_logp; a.opp_replies = out->opp_replies; a.opp_slots = out->opp_slots;
+        if (league) { a.opp_member = league->member_dev; a.opp_pool = (u32)league->pool_size; }      // a base offset per workgroup, nothing else
     }
     if (opp == 3) {                                          // the greedy player's trace: its answers and their number (opp_logp is never written)
         a.opp_action = out->opp_action; a.opp_replies = out->opp_replies; a.opp_slots = out->opp_slots;
@@ -794,7 +802,9 @@ static int rollout_window(azul_batch_t *b, const char *who, bool wide, int n_ste
         const hipStream_t st = (hipStream_t)stream;
         const azx::XBatchDev xb = xdev(b);
         const u32 id_base = b->d.id_base;
-        if (net) AZ_X_DISPATCH(b, hipLaunchKernelGGL((azul_x_policy_rollout_vs_kernel<PP, DD>), grid, block, 0, st, xb, W, a, id_base, (u32)max_replies));
+        if (net && league)
+            AZ_X_DISPATCH(b, hipLaunchKernelGGL((azul_x_policy_rollout_vs_kernel<PP, DD, true>), grid, block, 0, st, xb, W, a, id_base, (u32)max_replies));
+        else if (net) AZ_X_DISPATCH(b, hipLaunchKernelGGL((azul_x_policy_rollout_vs_kernel<PP, DD>), grid, block, 0, st, xb, W, a, id_base, (u32)max_replies));
         else if (opp == 3)
             AZ_X_DISPATCH(b, hipLaunchKernelGGL((azul_x_policy_rollout_kernel<PP, DD, 3>), grid, block, 0, st, xb, W, a, id_base, (u32)max_replies));
         else if (opp) AZ_X_DISPATCH(b, hipLaunchKernelGGL((azul_x_policy_rollout_kernel<PP, DD, 1>), grid, block, 0, st, xb, W, a, id_base));
@@ -871,6 +881,43 @@ int azul_batch_mp_policy_rollout_vs(azul_batch_t *b, int n_steps, const azul_net
     BATCH_GUARD(b, stream);
     return rollout_window(b, "azul_batch_mp_policy_rollout_vs", true, n_steps, 2, agent, opponent, {num_inputs, hidden_size, num_actions},
                           {seed, opp_seed, counter, counter_dev}, out, gamma, max_replies, stream);
+}
+
+/* _vs against a pool of network opponents, one member per 16-game workgroup (RolloutArgs::opp_member; the same kernels, the same host path) */
+int azul_batch_policy_rollout_league(azul_batch_t *b, int n_steps, const azul_net_weights_t *agent, const azul_net_weights_t *pool, int pool_size,
+                                     const uint8_t *member_dev, int num_inputs, int hidden_size, int num_actions, uint64_t seed,
+                                     uint64_t opponent_seed, uint64_t counter, uint64_t *counter_dev, const azul_rollout_buffers_t *out, float gamma,
+                                     void *stream)
+{
+    BATCH_GUARD(b, stream);
+    const League lg = {pool_size, member_dev};
+    return rollout_window(b, "azul_batch_policy_rollout_league", false, n_steps, 2, agent, pool, {num_inputs, hidden_size, num_actions},
+                          {seed, opponent_seed, counter, counter_dev}, out, gamma, 0, stream, &lg);
+}
+
+int azul_batch_mp_policy_rollout_league(azul_batch_t *b, int n_steps, const azul_net_weights_t *agent, const azul_net_weights_t *pool, int pool_size,
+                                        const uint8_t *member_dev, int num_inputs, int hidden_size, int num_actions, uint64_t seed,
+                                        uint64_t opponent_seed, uint64_t counter, uint64_t *counter_dev, int max_replies,
+                                        const azul_rollout_buffers_t *out, float gamma, void *stream)
+{
+    BATCH_GUARD(b, stream);
+    const League lg = {pool_size, member_dev};
+    return rollout_window(b, "azul_batch_mp_policy_rollout_league", true, n_steps, 2, agent, pool, {num_inputs, hidden_size, num_actions},
+                          {seed, opponent_seed, counter, counter_dev}, out, gamma, max_replies, stream, &lg);
+}
+
+/* the league's per-member results since the marks, one launch (azul_league_tally_kernel) */
+int azul_league_tally(const uint64_t *episodes_dev, const double *stat_sums_dev, uint64_t *mark_episodes_dev, double *mark_sums_dev,
+                      const uint8_t *member_dev, int n_games, int pool_size, double *results_dev, void *stream)
+{
+    if (!episodes_dev || !stat_sums_dev || !mark_episodes_dev || !mark_sums_dev || !member_dev || !results_dev || n_games < 1 || pool_size < 1 ||
+        pool_size > 255)
+        return fail(AZUL_ERR_INVALID, "azul_league_tally: bad arguments");
+    STREAM_GUARD(stream);
+    hipLaunchKernelGGL(azul_league_tally_kernel, dim3((u32)pool_size), dim3(64), 0, (hipStream_t)stream, (const u64 *)episodes_dev, stat_sums_dev,
+                       (u64 *)mark_episodes_dev, mark_sums_dev, member_dev, (u32)n_games, (u32)pool_size, results_dev);
+    HIP_TRY(hipGetLastError());
+    return AZUL_SUCCESS;
 }
 
 /* GameRunner with greedy_margin seats for wide batches inside one launch per window (azul_x_policy_rollout_kernel<P, D, 3>) */

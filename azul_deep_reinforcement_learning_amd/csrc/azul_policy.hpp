@@ -431,4 +431,65 @@ struct RolloutArgs {
     float *opp_logp;     // optional [T][opp_slots][N]: log-probability of each answer under the opponent's masked softmax
     uint8_t *opp_replies;// optional [T][N]: opponent moves played inside the step (the next episode's opening moves included)
     int opp_slots;
+    // ---- league: a POOL of network opponents, one member per 16-game workgroup (the OPP == 2 kernels; azul_batch_[mp_]policy_rollout_league) ----
+    const uint8_t *opp_member;   // optional [ceil(N / 16)]: the pool member workgroup blockIdx.x plays against.  NULL: no pool, Wopp is ONE net.
+                                 // Set: Wopp holds `opp_pool` nets STACKED array by array (league_member below).  A value >= opp_pool is read as
+                                 // opp_pool - 1: the kernel never reads outside the pool.
+    u32 opp_pool;                // K >= 1 when opp_member is set
 };
+
+// Member m of a stacked pool: every array of `W` begins at W.x + m * size(x), the sizes following from the compiled shape -- w1t IN x 360,
+// b1 360, w2c 180, b2c 1, w2a_t 180 x NA, b2a NA.  The arrays the opponent's forward_actor reads (w1t, b1, w2a_t, b2a) keep their 16-byte
+// alignment for every member: their sizes in bytes are multiples of 16 for (IN, NA) of all compiled shapes (b2c's 4 bytes are not, and
+// nothing of the opponent's critic is ever read).  `m` is wave-uniform (one byte per workgroup), so the offsets stay in scalar registers.
+template <u32 IN, u32 NA>
+__device__ __forceinline__ PolicyWeights league_member(const PolicyWeights &W, u32 m)
+{
+    static_assert((IN * (u32)PF_H2 * 4u) % 16u == 0u && ((u32)PF_H2 * 4u) % 16u == 0u && ((u32)PF_HID * 4u) % 16u == 0u &&
+                  ((u32)PF_HID * NA * 4u) % 16u == 0u && (NA * 4u) % 16u == 0u, "a pool member's arrays stay 16-byte aligned");
+    return {W.w1t + (size_t)m * (IN * (u32)PF_H2), W.b1 + (size_t)m * (u32)PF_H2, W.w2c + (size_t)m * (u32)PF_HID, W.b2c + m,
+            W.w2a_t + (size_t)m * ((u32)PF_HID * NA), W.b2a + (size_t)m * NA};
+}
+
+// the pool member of workgroup blockIdx.x (RolloutArgs::opp_member, clamped into the pool), made wave-uniform for the compiler
+__device__ __forceinline__ u32 league_member_of_block(const RolloutArgs &a)
+{
+    const u32 m = (u32)a.opp_member[blockIdx.x];
+    const u32 top = a.opp_pool ? a.opp_pool - 1u : 0u;
+    return (u32)__builtin_amdgcn_readfirstlane((int)(m < top ? m : top));
+}
+
+// ---- league book-keeping: per pool member, what its groups' games finished since the marks (azul_league_tally) -------------------------
+// One workgroup (one wave) per member m, lane j < 11 owns column j of results[m] (0: episodes, 1..10: the ten statistic sums).  The lane
+// walks the 16-game groups in ascending order and, for the groups assigned to m (values >= K read as K - 1, as the rollout kernels read
+// them), adds counter - mark game by game in ascending order: plain fp64 additions in one fixed order, no atomics -- the same bits on every
+// run.  Then it moves the mark up.  Every game belongs to exactly one member, so no two workgroups touch the same mark.
+constexpr u32 LEAGUE_COLS = 11;
+__global__ void __launch_bounds__(64) azul_league_tally_kernel(const u64 *episodes, const double *stat_sums, u64 *mark_episodes, double *mark_sums,
+                                                               const uint8_t *opp_member, u32 n, u32 K, double *results)
+{
+    const u32 m = blockIdx.x, j = threadIdx.x;
+    if (m >= K || j >= LEAGUE_COLS) return;
+    const u32 groups = (n + (u32)PF_GAMES - 1u) / (u32)PF_GAMES;
+    double acc = results[(size_t)m * LEAGUE_COLS + j];
+    bool any = false;
+    for (u32 grp = 0; grp < groups; grp++) {
+        const u32 mg = (u32)opp_member[grp];
+        if ((mg < K - 1u ? mg : K - 1u) != m) continue;
+        any = true;
+        const u32 g1 = (grp + 1u) * (u32)PF_GAMES < n ? (grp + 1u) * (u32)PF_GAMES : n;
+        for (u32 g = grp * (u32)PF_GAMES; g < g1; g++) {
+            if (j == 0u) {
+                const u64 e = episodes[g];
+                acc += (double)(e - mark_episodes[g]);
+                mark_episodes[g] = e;
+            } else {
+                const size_t i = (size_t)g * (LEAGUE_COLS - 1u) + (j - 1u);
+                const double s = stat_sums[i];
+                acc += s - mark_sums[i];
+                mark_sums[i] = s;
+            }
+        }
+    }
+    if (any) results[(size_t)m * LEAGUE_COLS + j] = acc;      // (a member without a group: its row is not written)
+}

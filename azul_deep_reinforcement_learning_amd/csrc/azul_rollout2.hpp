@@ -210,9 +210,13 @@ __global__ void __launch_bounds__(64 * PR2_WAVES) azul_policy_rollout2_kernel(Ba
     if (OPP == 1) {
         for (u32 i = tid; i < (u32)T_PAIRS; i += 64u * PR2_WAVES) tabfs_lds[i] = b.tab[i];
     }
+    // the opponent's net (OPP == 2): a.Wopp itself, or with a league (a.opp_member) the pool member of this workgroup's 16 games -- a base
+    // offset per array chosen once, wave-uniform; everything the workgroup reads of the opponent goes through Wo
+    PolicyWeights Wo = OPP == 2 ? a.Wopp : W;
     if (OPP == 2) {
-        if (tid < (u32)(PF_HID + 12)) b1oS[tid] = tid < (u32)PF_HID ? a.Wopp.b1[PF_HID + tid] : 0.f;
-        if (tid < (u32)(PF_ACT + 12)) b2aoS[tid] = tid < (u32)PF_ACT ? a.Wopp.b2a[tid] : 0.f;
+        if (a.opp_member) Wo = league_member<(u32)PF_IN, (u32)PF_ACT>(a.Wopp, league_member_of_block(a));
+        if (tid < (u32)(PF_HID + 12)) b1oS[tid] = tid < (u32)PF_HID ? Wo.b1[PF_HID + tid] : 0.f;
+        if (tid < (u32)(PF_ACT + 12)) b2aoS[tid] = tid < (u32)PF_ACT ? Wo.b2a[tid] : 0.f;
         if (tid < (u32)PF_GAMES) oweS[tid] = 0u;
     }
     const float b2c_v = W.b2c[0];
@@ -303,8 +307,8 @@ __global__ void __launch_bounds__(64 * PR2_WAVES) azul_policy_rollout2_kernel(Ba
     float2 preA[PR2_HOIST1], preB[PR2_HOIST1], pre2[PR2_HOIST2];
     pr2_request1(two, rs1, voffA, voffB, preA, preB);
     // the opponent's matrices (OPP == 2): the actor half of its layer 1 and its layer 2, both in layer 2's column mapping
-    const __amdgpu_buffer_rsrc_t rso1 = __builtin_amdgcn_make_buffer_rsrc((void *)(OPP == 2 ? a.Wopp.w1t : W.w1t), 0, PF_IN * PF_H2 * 4, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rso2 = __builtin_amdgcn_make_buffer_rsrc((void *)(OPP == 2 ? a.Wopp.w2a_t : W.w2a_t), 0, PF_HID * PF_ACT * 4, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rso1 = __builtin_amdgcn_make_buffer_rsrc((void *)Wo.w1t, 0, PF_IN * PF_H2 * 4, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rso2 = __builtin_amdgcn_make_buffer_rsrc((void *)Wo.w2a_t, 0, PF_HID * PF_ACT * 4, 0x00020000);
     const u32 voffo1 = ((u32)PF_HID + (PR2_L2COL0 < (u32)PF_HID ? PR2_L2COL0 : 0u) + q * (u32)PF_H2) * 4u;
     float2 preo[PR2_HOISTO];
     az2::NetStep ns;
@@ -700,7 +704,11 @@ AZ_FN void px_chain(const float *ap, const float *const (&bp)[NT], u32 bstride, 
 // RandomAgent seats, 2 GameRunner with a network opponent (a.Wopp; O: PXOpp in LDS, max_replies: reply rounds per step before the loop gives
 // up), 3 GameRunner with greedy_margin seats (azx::greedy_pick_x: no weights, no matrix phase, no draw, no PXOpp; max_replies as OPP 2).
 // The returns are not written here (azul_batch_mp_policy_rollout / _vs / _greedy run azul_discounted_returns behind the launch).
-template <u32 P, u32 D, int OPP>
+// LEAGUE (OPP 2 only): a.opp_member picks the workgroup's member of a stacked pool behind a.Wopp.  A template flag, not a null check as in the
+// two-player kernel: the null check in the one instantiation moved the register allocation of the existing azul_x_policy_rollout_vs_kernel
+// (private segment +8 bytes for <2, 5>, or +4 for <4, 9> with only the member index kept live), so the single-opponent kernels compile
+// exactly as before and the league has its own.
+template <u32 P, u32 D, int OPP, bool LEAGUE = false>
 AZ_FN void x_policy_rollout_body(const azx::XBatchDev &b, const PolicyWeights &W, const RolloutArgs &a, u32 id_base, PXShared<P, D> &S,
                                  PXOpp<D> *O = nullptr, u32 max_replies = 0)
 {
@@ -718,9 +726,14 @@ AZ_FN void x_policy_rollout_body(const azx::XBatchDev &b, const PolicyWeights &W
     for (u32 i = tid; i < NA; i += 64u * PR2_WAVES) S.b2a[i] = W.b2a[i];
     if (OPP == 1)
         for (u32 i = tid; i < azx::Dim<D>::TROWS * (u32)T_STRIDE; i += 64u * PR2_WAVES) S.tab[i] = b.tab[i];
+    // the opponent's net (OPP == 2): a.Wopp itself, or with a league (a.opp_member) the pool member of this workgroup's 16 games.  Only the
+    // member (one scalar register, 0 without a pool) lives across the window: the arrays' bases are formed from it where they are read
+    u32 lm = 0;
     if constexpr (OPP == 2) {
-        for (u32 i = tid; i < (u32)PF_HID; i += 64u * PR2_WAVES) O->b1[i] = a.Wopp.b1[PF_HID + i];
-        for (u32 i = tid; i < NA; i += 64u * PR2_WAVES) O->b2a[i] = a.Wopp.b2a[i];
+        if constexpr (LEAGUE) { if (a.opp_member) lm = league_member_of_block(a); }
+        const PolicyWeights Wo = LEAGUE ? league_member<IN, NA>(a.Wopp, lm) : a.Wopp;
+        for (u32 i = tid; i < (u32)PF_HID; i += 64u * PR2_WAVES) O->b1[i] = Wo.b1[PF_HID + i];
+        for (u32 i = tid; i < NA; i += 64u * PR2_WAVES) O->b2a[i] = Wo.b2a[i];
         if (tid < PF_GAMES) {
             O->ns[tid] = {az2::NET_READY, 0u, 0, 0u, false, (u32)ST_OK};
             O->owe[tid] = 0u;
@@ -904,7 +917,7 @@ AZ_FN void x_policy_rollout_body(const azx::XBatchDev &b, const PolicyWeights &W
 #pragma unroll
                     for (u32 i = 0; i < Sh::NTO; i++) {
                         const u32 col = 16u * (w + PR2_WAVES * i) + c;
-                        bpo[i] = a.Wopp.w1t + PF_HID + (col < (u32)PF_HID ? col : 0u);
+                        bpo[i] = (LEAGUE ? league_member<IN, NA>(a.Wopp, lm).w1t : a.Wopp.w1t) + PF_HID + (col < (u32)PF_HID ? col : 0u);
                     }
                     pf_f32x4 acc[Sh::NTO];
 #pragma unroll
@@ -924,7 +937,10 @@ AZ_FN void x_policy_rollout_body(const azx::XBatchDev &b, const PolicyWeights &W
                 {
                     const float *bp2[Sh::NT2];
 #pragma unroll
-                    for (u32 i = 0; i < Sh::NT2; i++) { const u32 col = 16u * (w + PR2_WAVES * i) + c; bp2[i] = a.Wopp.w2a_t + (col < NA ? col : 0u); }
+                    for (u32 i = 0; i < Sh::NT2; i++) {
+                        const u32 col = 16u * (w + PR2_WAVES * i) + c;
+                        bp2[i] = (LEAGUE ? league_member<IN, NA>(a.Wopp, lm).w2a_t : a.Wopp.w2a_t) + (col < NA ? col : 0u);
+                    }
                     pf_f32x4 acc[Sh::NT2];
 #pragma unroll
                     for (u32 i = 0; i < Sh::NT2; i++) acc[i] = (pf_f32x4){0.f, 0.f, 0.f, 0.f};
@@ -1092,12 +1108,13 @@ __global__ void __launch_bounds__(64 * PR2_WAVES) azul_x_policy_rollout_kernel(a
 }
 
 // ... with a NETWORK opponent (azul_batch_mp_policy_rollout_vs; OPP 2 of x_policy_rollout_body): the reply rounds inside the window, the
-// opponent's biases and the games' reply-loop state in LDS next to PXShared
-template <u32 P, u32 D>
+// opponent's biases and the games' reply-loop state in LDS next to PXShared.  LEAGUE (azul_batch_mp_policy_rollout_league): a pool of opponents
+// behind a.Wopp, one member per workgroup (RolloutArgs::opp_member)
+template <u32 P, u32 D, bool LEAGUE = false>
 __global__ void __launch_bounds__(64 * PR2_WAVES) azul_x_policy_rollout_vs_kernel(azx::XBatchDev b, PolicyWeights W, RolloutArgs a, u32 id_base,
                                                                                    u32 max_replies)
 {
     __shared__ PXShared<P, D> S;
     __shared__ PXOpp<D> O;
-    x_policy_rollout_body<P, D, 2>(b, W, a, id_base, S, &O, max_replies);
+    x_policy_rollout_body<P, D, 2, LEAGUE>(b, W, a, id_base, S, &O, max_replies);
 }

@@ -47,10 +47,12 @@ _WINDOW_KERNELS = {
     (False, None): _WindowKernel("azul_batch_policy_rollout_returns", "persistent", 180, None),
     (False, "random"): _WindowKernel("azul_batch_policy_rollout_returns", "persistent", 180, None),
     (False, "net"): _WindowKernel("azul_batch_policy_rollout_vs", "persistent", 180, None),
+    (False, "league"): _WindowKernel("azul_batch_policy_rollout_league", "persistent", 180, None),
     (False, "greedy"): _WindowKernel("azul_batch_policy_rollout_greedy", "fused_opponent", 180, None),
     (True, None): _WindowKernel("azul_batch_mp_policy_rollout", "fused_wide", 180, None),
     (True, "random"): _WindowKernel("azul_batch_mp_policy_rollout", "fused_wide", 180, None),
     (True, "net"): _WindowKernel("azul_batch_mp_policy_rollout_vs", "fused_opponent", 180, 180),
+    (True, "league"): _WindowKernel("azul_batch_mp_policy_rollout_league", "fused_opponent", 180, 180),
     (True, "greedy_margin"): _WindowKernel("azul_batch_mp_policy_rollout_greedy", "fused_seats", 180, None),
 }
 
@@ -80,6 +82,8 @@ class PolicyRollout:
                                azul_batch_policy_rollout_returns [persistent]       azul_batch_mp_policy_rollout [fused_wide]
             <module>           per cut                                              per cut
                                azul_batch_policy_rollout_vs [persistent]            azul_batch_mp_policy_rollout_vs [fused_wide, fused_opponent]
+            [<module>, ...]    per cut                                              per cut
+                               azul_batch_policy_rollout_league [persistent]        azul_batch_mp_policy_rollout_league [fused_wide, fused_opponent]
             "greedy"           per cut                                              ValueError
                                azul_batch_policy_rollout_greedy [fused_opponent]
             "greedy_margin"    ValueError                                           per cut
@@ -107,6 +111,16 @@ class PolicyRollout:
         hidden size: anything else raises ValueError); its actor half runs as PyTorch GEMMs + azul_policy_head_n with the two-player path's
         Philox keys, through MultiplayerAzul.net_* (azul_batch_mp_net_*); at most MAX_REPLY_ROUNDS reply rounds per step or opening -- an
         opponent that keeps answering with moves that are not legal raises RuntimeError.
+        opponent=[net0, net1, ...] (a list or tuple of 1..255 such modules of ONE shape): a LEAGUE -- a pool of network opponents.  The games
+        of a part are taken in groups of 16 (L.LEAGUE_GROUP_GAMES: the games of one workgroup of the window kernels; the last group may be
+        ragged) and every group plays one member of the pool: assignment() / set_assignment(), default group i -> member i % pool_size.
+        Everything said of a single network opponent holds per member -- the shape refusals, opponent_selection, opponent_seed,
+        opponent_trace, the switches (`persistent` two-player; fused_wide with fused_opponent wide), rings, gae_lambda, the fused learner --
+        and a game's trajectory is keyed by its global id, so the games of a group assigned to member m play exactly what they would play
+        against opponent=<member m> alone.  The window kernels read the member once per workgroup (a base offset into the stacked weights);
+        the per-cut path runs the opponent's forward once per member present in the part's assignment and keeps, per game, the answer of
+        its group's member.  set_pool_member(i, ...) installs a member's weights in place; league_results() gives per member the episodes
+        finished against it and the means of the game statistics over them (azul_league_tally: reduced on the device).
         opponent="greedy": the scripted one-ply greedy player of the reference's own reward on the same per-cut protocol -- every
         opponent_move() is BatchedAzul.greedy_action's answer, the move that maximises the mover's score difference after move + count_score
         (game_runner.py:48-50), one launch per reply round in place of the network's forward; records as with "random"; persistent and
@@ -206,14 +220,25 @@ class PolicyRollout:
         self.n, self.parts, self.h, self.T = n_games, parts, n_games // parts, window
         self.players = int(players)
         self.wide = self.players != 2 or parse_ext_rules(rules, self.players) != 0
-        kind = opponent if opponent is None or isinstance(opponent, str) else "net"       # None | "random" | "net" | "greedy" | "greedy_margin"
+        # None | "random" | "net" | "league" | "greedy" | "greedy_margin"
+        kind = opponent if opponent is None or isinstance(opponent, str) else ("league" if isinstance(opponent, (list, tuple)) else "net")
+        members = list(opponent) if kind == "league" else ([opponent] if kind == "net" else [])      # the network opponents, one or a pool
+        netopp = kind in ("net", "league")
         n_obs, n_act = batch_shape(self.players, rules)          # azul_batch_obs_size / azul_batch_num_actions
         # (a kind the assert below turns away is checked as self-play until then)
         row = _WINDOW_KERNELS.get((self.wide, kind), _WINDOW_KERNELS[self.wide, None])
         compiled_for = (n_obs, n_obs, row.hidden, row.hidden, n_act)
         # -- the refusals, in the order in which they win
-        if self.wide and kind == "net":
-            shape = (opponent.critic_linear1.in_features, opponent.actor_linear1.in_features, opponent.actor_linear2.out_features)
+        if kind == "league":
+            if not 1 <= len(members) <= 255:
+                raise ValueError("a league is a pool of 1..255 network opponents (a group's member is one byte), got %d" % len(members))
+            if any(isinstance(m, str) or m is None for m in members):
+                raise ValueError("the members of a league are modules with the reference's four layers, not opponent kinds")
+            if any(_layer_sizes(m) != _layer_sizes(members[0]) for m in members):
+                raise ValueError("the members of a league must have ONE shape (their weights are stacked array by array), got %s"
+                                 % sorted(set(_layer_sizes(m) for m in members)))
+        for net in (members if self.wide else []):                # (every member of a pool: the refusals of a single network opponent)
+            shape = (net.critic_linear1.in_features, net.actor_linear1.in_features, net.actor_linear2.out_features)
             if shape != (n_obs, n_obs, n_act):
                 raise ValueError("a network opponent for batches of %d players / extended rules must take the batch's observation and give its "
                                  "actions: ActorCritic(%d, %d, any hidden size), got inputs %d / %d and %d actions"
@@ -243,7 +268,7 @@ class PolicyRollout:
             if not self.wide:
                 raise ValueError("fused_wide=True is the window kernel of batches of three / four players or extended rules; two-player reference "
                                  "batches have persistent=True")
-            if kind == "net" and not fused_opponent:
+            if netopp and not fused_opponent:
                 raise ValueError("fused_wide=True plays opponent=None or \"random\"; a network opponent runs on the per-cut path (fused_wide=False)")
             if not fused_head:
                 raise ValueError("fused_wide=True samples with azul_policy_head_n's draw: fused_head=False is the PyTorch sampling path")
@@ -261,24 +286,27 @@ class PolicyRollout:
                                  "hidden %d / %d and %d actions; other policies play the greedy opponent on the per-cut path "
                                  "(fused_opponent=False)" % _layer_sizes(policy))
         elif fused_opponent:
-            if not fused_wide or kind != "net":
+            if not fused_wide or not netopp:
                 raise ValueError("fused_opponent=True plays a network opponent inside the window kernel of wide batches: it needs fused_wide=True "
                                  "and opponent=<module> (or opponent=\"greedy\" on a two-player reference batch)")
-            if (opponent.critic_linear1.out_features, opponent.actor_linear1.out_features) != (row.opp_hidden, row.opp_hidden):
+            hidden = [(net.critic_linear1.out_features, net.actor_linear1.out_features) for net in members]
+            if any(hd != (row.opp_hidden, row.opp_hidden) for hd in hidden):
                 raise ValueError("fused_opponent=True is compiled for an opponent of hidden size 180, got %d / %d; other opponents run on the "
                                  "per-cut path (fused_opponent=False, fused_wide=False)"
-                                 % (opponent.critic_linear1.out_features, opponent.actor_linear1.out_features))
+                                 % [hd for hd in hidden if hd != (row.opp_hidden, row.opp_hidden)][0])
         lam = None if gae_lambda is None else float(gae_lambda)
         if lam is not None and not 0.0 <= lam <= 1.0:            # (a NaN fails the comparison too)
             raise ValueError("gae_lambda must lie in [0, 1] (1: the Monte-Carlo return, 0: the one-step TD target), got %r" % (gae_lambda,))
         if kind is None and (bootstrap_tail or (lam is not None and lam < 1.0)):
             raise ValueError("gae_lambda < 1 and bootstrap_tail need the records of ONE seat (any opponent but None): consecutive records of "
                              "flat self-play belong to different seats observed with PERSP_CURRENT, so V(s_{t+1}) is another seat's value")
-        assert kind in (None, "random", "net", "greedy", "greedy_margin")
+        assert kind in (None, "random", "net", "league", "greedy", "greedy_margin")
         # -- the resolution
-        self.opponent, self.opp_policy = kind, (opponent if kind == "net" else None)
+        self.opponent, self.opp_policy = kind, (members[0] if kind == "net" else None)
+        self.netopp, self.league = netopp, kind == "league"    # a network answers (one net, or a pool of them: opp_pool)
+        self.opp_pool = members if self.league else None
         self.scripted = kind in ("greedy", "greedy_margin")    # answers are env.greedy_action's: no weights, no log-probabilities
-        self.cut = kind == "net" or self.scripted              # GameRunner.step cut at its opponent_move() calls (BatchedAzul.net_*)
+        self.cut = netopp or self.scripted                     # GameRunner.step cut at its opponent_move() calls (BatchedAzul.net_*)
         self.fused_head = fused_head
         # the one-launch forward (azul_policy_forward) is compiled for the reference's ActorCritic(136, 180, hidden 180)
         self.fused_mlp = bool(fused_mlp and fused_head and not self.wide and policy.critic_linear1.in_features == L.OBS_SIZE and
@@ -301,7 +329,7 @@ class PolicyRollout:
         self.action_selection = action_selection
         assert opponent_selection in ("Distribution", "Max")
         self.opp_slots = int(opponent_trace) if self.cut else 0
-        assert kind != "net" or self.fused_mlp or self.wide, \
+        assert not netopp or self.fused_mlp or self.wide, \
             "the network opponent runs on the library's forward (ActorCritic(136, 180, hidden 180))"
         # one launch per window needs no graph; reply rounds are data-dependent (a capture that fails clears the flag again)
         self.use_graph = bool(use_graph and self.window_entry is None and not self.cut)
@@ -320,6 +348,19 @@ class PolicyRollout:
         if self.opponent == "net":
             self.opp_policy = self.opp_policy.to(self.device).eval()
             self.set_opponent(self.opp_policy)
+        elif self.league:
+            # the pool STACKED array by array ([K][...] each, member m at m * size: include/azul_hip.h), the default assignment group i ->
+            # member i % K for every part, and the per-member results with their per-game marks (azul_league_tally)
+            K, G = len(self.opp_pool), (self.h + L.LEAGUE_GROUP_GAMES - 1) // L.LEAGUE_GROUP_GAMES
+            staged = [dict(self._kmajor(m.state_dict().__getitem__, self._OPP_ARRAYS)) for m in self.opp_pool]
+            for k in self._OPP_ARRAYS:
+                setattr(self, "o" + k, torch.stack([st[k] for st in staged]).contiguous())
+            self.opp_pool = None                               # (the weights are copied: the modules are not kept)
+            self._pool_size = K
+            self._assign_host = (torch.arange(G, dtype=torch.int64) % K).to(torch.uint8).repeat(self.parts, 1).numpy()
+            self._assign = torch.from_numpy(self._assign_host.copy()).to(self.device)
+            self._lg_results = torch.zeros(self.parts, K, 1 + L.NUM_STATS, dtype=torch.float64, device=self.device)
+            self._lg_marks = []
 
     def _alloc_part(self, p, rules, seed_base, move_limit):
         """Part p: its games (opened as GameRunner opens them), its stream, its trajectory ring and work buffers."""
@@ -357,9 +398,14 @@ class PolicyRollout:
         if self.cut:
             w["net"] = env.net_state()
             w["scratch_f"] = torch.zeros(3, h, device=d)       # the opponent forward's value / entropy (not recorded) and untraced log-prob
-            if self.wide and self.opponent == "net":           # the opponent's actor half as PyTorch GEMMs (its own hidden size)
-                w["opp_hidden"] = torch.zeros(h, self.ob1.numel() // 2, device=d)
+            if self.wide and self.netopp:                      # the opponent's actor half as PyTorch GEMMs (its own hidden size)
+                w["opp_hidden"] = torch.zeros(h, self.ob1.shape[-1] // 2, device=d)
                 w["opp_logits"] = torch.zeros(h, env.num_actions, device=d)
+            if self.league:                                    # per game its group's member; one member's answers before they are taken
+                w["game_member"] = self._assign[p].to(torch.int64).repeat_interleave(L.LEAGUE_GROUP_GAMES)[:h].contiguous()
+                w["lg_action"], w["lg_logp"] = torch.zeros(h, dtype=torch.int32, device=d), torch.zeros(h, device=d)
+                c = env.counters_dev()
+                self._lg_marks.append({"episodes": c["episodes"].clone(), "stat_sums": c["stat_sums"].clone()})
         if self.bootstrap_tail:                                # the critic's value of slot T, and the hidden layer it is formed from
             w["tail_hidden"], w["tail_value"] = torch.zeros(h, self.H, device=d), torch.zeros(h, 1, device=d)
             t["tail_value"] = w["tail_value"].view(h)
@@ -382,9 +428,10 @@ class PolicyRollout:
     def _persp(self):
         return 0 if self.opponent is not None else L.PERSP_CURRENT     # with any opponent NNRunner observes with perspective 0 (game_runner.py:56)
 
-    def _stage(self, get, prefix, names):
-        """The k-major copies `names` of the reference's four layers (`get`: parameter name -> tensor) as attributes prefix + name,
-        updated IN PLACE once they exist: captured HIP graphs and whoever shares kweights() keep reading the same addresses."""
+    _OPP_ARRAYS = ("w1t", "b1", "w2c", "b2c", "w2a_t", "b2a")       # azul_net_weights_t, in its order
+
+    def _kmajor(self, get, names):
+        """[(name, tensor)]: the k-major copies `names` of the reference's four layers (`get`: parameter name -> tensor), contiguous."""
         with torch.no_grad():
             g = lambda k: get(k).detach().to(self.device, torch.float32)
             build = {"w1t": lambda: torch.cat([g("critic_linear1.weight"), g("actor_linear1.weight")], dim=0).t(),
@@ -392,17 +439,126 @@ class PolicyRollout:
                      "w2c": lambda: g("critic_linear2.weight").reshape(-1), "w2c_t": lambda: g("critic_linear2.weight").t(),
                      "b2c": lambda: g("critic_linear2.bias").reshape(-1),
                      "w2a_t": lambda: g("actor_linear2.weight").t(), "b2a": lambda: g("actor_linear2.bias")}
-            for name, v in [(prefix + k, build[k]()) for k in names]:
+            return [(k, build[k]().contiguous()) for k in names]
+
+    def _stage(self, get, prefix, names):
+        """The k-major copies `names` as attributes prefix + name, updated IN PLACE once they exist: captured HIP graphs and whoever shares
+        kweights() keep reading the same addresses."""
+        with torch.no_grad():
+            for k, v in self._kmajor(get, names):
+                name = prefix + k
                 if hasattr(self, name):
                     getattr(self, name).copy_(v)
                 else:
-                    setattr(self, name, v.contiguous().clone())
+                    setattr(self, name, v.clone())
 
     def set_opponent(self, policy_or_state_dict):
         """Install the network opponent's weights (k-major copies, updated IN PLACE): a module with the reference's four layers or its
         state_dict -- e.g. `ro.set_opponent(policy)` every so many updates trains against a frozen past self."""
         sd = policy_or_state_dict.state_dict() if hasattr(policy_or_state_dict, "state_dict") else policy_or_state_dict
-        self._stage(sd.__getitem__, "o", ("w1t", "b1", "w2c", "b2c", "w2a_t", "b2a"))
+        if self.league:
+            raise ValueError("this rollout plays a league: set_pool_member(i, ...) installs the weights of one member")
+        self._stage(sd.__getitem__, "o", self._OPP_ARRAYS)
+
+    # ---- the league (opponent=[net0, net1, ...]) --------------------------------------------------------------------------------
+    @property
+    def pool_size(self):
+        """Members of the league's pool (0 without a league)."""
+        return self._pool_size if self.league else 0
+
+    def _need_league(self):
+        if not self.league:
+            raise ValueError("this rollout plays no league (opponent=[net0, net1, ...])")
+
+    def set_pool_member(self, i, policy_or_state_dict):
+        """Install the weights of pool member i (its slice of the stacked k-major copies, updated IN PLACE like set_opponent): a module
+        with the reference's four layers, of the pool's shape, or its state_dict."""
+        self._need_league()
+        if not 0 <= int(i) < self._pool_size:
+            raise ValueError("pool member %r outside 0..%d" % (i, self._pool_size - 1))
+        sd = policy_or_state_dict.state_dict() if hasattr(policy_or_state_dict, "state_dict") else policy_or_state_dict
+        with torch.no_grad():
+            for k, v in self._kmajor(sd.__getitem__, self._OPP_ARRAYS):
+                getattr(self, "o" + k)[int(i)].copy_(v)
+
+    def assignment(self):
+        """The pool member of every 16-game group: a uint8 array [parts][ceil(h / 16)] (a host copy)."""
+        self._need_league()
+        return self._assign_host.copy()
+
+    def set_assignment(self, members):
+        """Assign the groups anew: an int array [parts][ceil(h / 16)] of pool members, refused if any value is >= pool_size.  The tally runs
+        first, so that the episodes finished so far are booked to the members they were played against; then the array is copied IN PLACE
+        on the parts' streams, behind the windows in flight."""
+        import numpy as np
+        self._need_league()
+        a = np.asarray(members)
+        if a.shape != self._assign_host.shape or a.dtype.kind not in "iu":
+            raise ValueError("the assignment is an int array of shape [parts][ceil(h / 16)] = %s, got %s %s"
+                             % (self._assign_host.shape, a.dtype, a.shape))
+        if a.size and (int(a.min()) < 0 or int(a.max()) >= self._pool_size):
+            raise ValueError("the assignment names pool members 0..%d, got values in %d..%d" % (self._pool_size - 1, int(a.min()), int(a.max())))
+        self._league_tally()
+        self._assign_host = np.ascontiguousarray(a, dtype=np.uint8)
+        for p in range(self.parts):
+            with torch.cuda.stream(self.streams[p]):
+                self._assign[p].copy_(torch.from_numpy(self._assign_host[p]).to(self.device))
+                self.work[p]["game_member"].copy_(self._assign[p].to(torch.int64).repeat_interleave(L.LEAGUE_GROUP_GAMES)[:self.h])
+
+    def _league_tally(self):
+        """azul_league_tally for every part on its stream: what each member's groups finished since the marks goes to the part's results."""
+        for p, env in enumerate(self.envs):
+            with torch.cuda.stream(self.streams[p]):
+                c, mk = env.counters_dev(), self._lg_marks[p]
+                L.check(L.lib.azul_league_tally(_p(c["episodes"]), _p(c["stat_sums"]), _p(mk["episodes"]), _p(mk["stat_sums"]), _p(self._assign[p]),
+                                                self.h, self._pool_size, _p(self._lg_results[p]), C.c_void_p(self.streams[p].cuda_stream)))
+
+    def league_results(self, reset=False):
+        """Per pool member what the games assigned to it finished since construction (or the last reset): a list of pool_size dicts with
+        `episodes` and the means over them of the ten STAT_KEYS (win_percent among them; NaN without an episode).  Reduced on the device,
+        in a fixed order: pool_size x 11 doubles per part cross to the host.  reset=True zeroes the results behind the read."""
+        from .records import STAT_KEYS
+        self._need_league()
+        self._league_tally()
+        self.synchronize()
+        tot = self._lg_results.cpu().numpy().sum(axis=0)       # (parts added in part order)
+        if reset:
+            self._lg_results.zero_()
+        return [dict([("episodes", int(tot[m, 0]))] + [(k, float(tot[m, 1 + i]) / tot[m, 0] if tot[m, 0] else float("nan"))
+                                                       for i, k in enumerate(STAT_KEYS)]) for m in range(self._pool_size)]
+
+    def reset_member_results(self, i):
+        """Zero the results of pool member i (what it finished so far is booked first and dropped with the rest)."""
+        self._need_league()
+        self._league_tally()
+        for p in range(self.parts):
+            with torch.cuda.stream(self.streams[p]):
+                self._lg_results[p, int(i)].zero_()
+
+    def league_state(self):
+        """What a checkpoint carries of the league besides the stacked weights: the assignment, the results, their marks and the per-game
+        counters the marks refer to (host copies).  The counters travel because one of the statistics (percent_first_player) is not a
+        whole number: the results are sums of counter - mark, and only the same counters give the same sums bit for bit."""
+        self._need_league()
+        self.synchronize()
+        return {"assignment": self._assign_host.copy(), "results": self._lg_results.cpu(),
+                "marks": [{k: v.cpu() for k, v in mk.items()} for mk in self._lg_marks],
+                "counters": [{k: v.cpu() for k, v in env.counters_dev().items() if k != "keys"} for env in self.envs]}
+
+    def load_league_state(self, st):
+        self._need_league()
+        self.synchronize()
+        self._assign_host = st["assignment"].copy()
+        self._assign.copy_(torch.from_numpy(self._assign_host))
+        for p in range(self.parts):
+            self.work[p]["game_member"].copy_(self._assign[p].to(torch.int64).repeat_interleave(L.LEAGUE_GROUP_GAMES)[:self.h])
+            c = self.envs[p].counters_dev()                     # (zero-copy views of the batch's per-game counters)
+            for k, v in st["counters"][p].items():
+                c[k].copy_(v)
+            for k, v in st["marks"][p].items():
+                self._lg_marks[p][k].copy_(v)
+        self._lg_results.copy_(st["results"])
+        torch.cuda.synchronize(self.device)
 
     def _opp_forward(self, p, j, logp_out):
         """The opponent's get_a_output (agent.py:73-81) for the games of part p that owe an opponent_move(): forward_actor of its net on
@@ -415,24 +571,40 @@ class PolicyRollout:
             self.envs[p].greedy_action(active=net["pending"], out=net["action"])
             return
         key = self.opponent_seed if self.opponent_seed == L.POLICY_ARGMAX else (self.opponent_seed + j) & 0xFFFFFFFFFFFFFFFF
+        if self.league:
+            # the forward once per member present in the part's assignment (all of the part's games through that member's weights), then per
+            # game the answer of its group's member: exact, because the head draws per row by the game's global id
+            for m in sorted(set(int(x) for x in self._assign_host[p])):
+                self._opp_forward_net(p, key, [getattr(self, "o" + k)[m] for k in self._OPP_ARRAYS], w["lg_action"], w["lg_logp"])
+                mine = w["game_member"] == m
+                torch.where(mine, w["lg_action"], net["action"], out=net["action"])
+                torch.where(mine, w["lg_logp"], logp_out, out=logp_out)
+            return
+        self._opp_forward_net(p, key, [getattr(self, "o" + k) for k in self._OPP_ARRAYS], net["action"], logp_out)
+
+    def _opp_forward_net(self, p, key, weights, action_out, logp_out):
+        """forward_actor + the sampling head of ONE opponent net (`weights`: its six k-major arrays) for all games of part p."""
+        w = self.work[p]
+        net, sc = w["net"], w["scratch_f"]
+        ow1t, ob1, ow2c, ob2c, ow2a_t, ob2a = weights
         if self.wide:
             # forward_actor (model.py:28-41) on the mover-perspective observations net_step_* left; the head samples at the same counter as
             # the two-player path (counter_dev - 1: the value the agent's draw of this step used; before the first step, 2^64 - 1)
             Ho = w["opp_hidden"].shape[1]
             with torch.no_grad():
-                torch.addmm(self.ob1[Ho:], net["obs"], self.ow1t[:, Ho:], out=w["opp_hidden"])
+                torch.addmm(ob1[Ho:], net["obs"], ow1t[:, Ho:], out=w["opp_hidden"])
                 w["opp_hidden"].relu_()
-                torch.addmm(self.ob2a, w["opp_hidden"], self.ow2a_t, out=w["opp_logits"])
+                torch.addmm(ob2a, w["opp_hidden"], ow2a_t, out=w["opp_logits"])
             L.check(L.lib.azul_policy_head_n(_p(w["opp_logits"]), _p(net["mask"]), key, 0xFFFFFFFFFFFFFFFF, _p(w["counter"]), self.h, self.num_actions,
-                                             self.game_id_base + p * self.h, _p(net["action"]), _p(logp_out), _p(sc[1]),
+                                             self.game_id_base + p * self.h, _p(action_out), _p(logp_out), _p(sc[1]),
                                              C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
             # a forward that is not finite has no distribution to sample (np.random.choice raises on NaN probabilities, agent.py:76):
             # its answer is -1, which the env refuses -- the game keeps owing the move and the bounded reply loop reports it
-            net["action"].masked_fill_(~torch.isfinite(w["opp_logits"].sum(dim=1)), -1)
+            action_out.masked_fill_(~torch.isfinite(w["opp_logits"].sum(dim=1)), -1)
             return
-        L.check(L.lib.azul_policy_forward(_p(net["obs"]), _p(net["mask"]), _p(self.ow1t), _p(self.ob1), _p(self.ow2c), _p(self.ob2c), _p(self.ow2a_t),
-                                          _p(self.ob2a), L.OBS_SIZE, self.H, L.NUM_ACTIONS, key, 0xFFFFFFFFFFFFFFFF, _p(w["counter"]), 0, self.h,
-                                          self.game_id_base + p * self.h, _p(sc[0]), _p(net["action"]), _p(logp_out), _p(sc[1]), None,
+        L.check(L.lib.azul_policy_forward(_p(net["obs"]), _p(net["mask"]), _p(ow1t), _p(ob1), _p(ow2c), _p(ob2c), _p(ow2a_t),
+                                          _p(ob2a), L.OBS_SIZE, self.H, L.NUM_ACTIONS, key, 0xFFFFFFFFFFFFFFFF, _p(w["counter"]), 0, self.h,
+                                          self.game_id_base + p * self.h, _p(sc[0]), _p(action_out), _p(logp_out), _p(sc[1]), None,
                                           C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
 
     def _net_reset(self, p):
@@ -569,7 +741,7 @@ class PolicyRollout:
         st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
         # (a ring, or a lambda-return: the scan below writes the returns)
         out = self._buffers(tr, w, tr["returns"].data_ptr() if self.ring == 1 and self.gae_lambda is None else None)
-        vs, flat = self.opponent == "net", self.window_entry == "azul_batch_policy_rollout_returns"
+        vs, flat = self.netopp, self.window_entry == "azul_batch_policy_rollout_returns"
         wa, wo = self._net_weights(), self._net_weights(opponent=True) if vs else None
         args = [env._h, T]
         if not self.cut:
@@ -577,6 +749,8 @@ class PolicyRollout:
         args += _WEIGHT_FIELDS(wa) if flat else [C.byref(wa)]                   # (_returns takes the structs' pointers one by one)
         if vs:
             args.append(C.byref(wo))                                            # the reply rounds run on the opponent's weights
+        if self.league:
+            args += [self._pool_size, _p(self._assign[p])]                      # ... of the pool member each 16-game group is assigned
         args += [self.obs_size, self.H, self.num_actions, self.sample_seed]
         if vs:
             args.append(self.opponent_seed)

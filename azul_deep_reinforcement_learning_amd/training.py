@@ -34,12 +34,52 @@ from .rollout import PolicyRollout
 AGENT_STAT_KEYS = ("reward", "actor_loss", "critic_loss", "entropy_loss", "ac_loss")          # agent.py:13
 
 
+# ---- the league's sampler: host functions of a few numbers per pool member (BatchedTrainer(opponent="league")) ------------------------
+def league_probabilities(episodes, win_rate, sampling="uniform", power=2.0):
+    """The probability with which a 16-game group is given each pool member.  "uniform": 1 / K each.  "pfsp" (prioritised fictitious
+    self-play): proportional to (1 - win_rate_m) ** power, the learner's win rate against member m over the `episodes[m]` episodes finished
+    against it -- the members it still loses to are played more; a member without episodes counts as win rate 0.5; weights that are all
+    zero (every member beaten every time) fall back to uniform."""
+    ep = np.asarray(episodes, dtype=np.float64)
+    K = ep.size
+    if K < 1:
+        raise ValueError("a league has at least one member")
+    if sampling not in ("uniform", "pfsp"):
+        raise ValueError("league_sampling must be \"uniform\" or \"pfsp\", got %r" % (sampling,))
+    if sampling == "uniform":
+        return np.full(K, 1.0 / K)
+    wr = np.asarray(win_rate, dtype=np.float64)
+    wr = np.clip(np.where((ep > 0) & np.isfinite(wr), wr, 0.5), 0.0, 1.0)
+    w = (1.0 - wr) ** float(power)
+    return w / w.sum() if w.sum() > 0.0 else np.full(K, 1.0 / K)
+
+
+def league_group_counts(probabilities, groups):
+    """How many of `groups` groups each member gets: the largest-remainder apportionment of the probabilities (floor of the quotas, the
+    groups left over to the largest fractional parts, ties to the lower member).  A member of probability 0 gets none."""
+    q = np.asarray(probabilities, dtype=np.float64) * int(groups)
+    counts = np.floor(q).astype(np.int64)
+    left = int(groups) - int(counts.sum())
+    order = np.argsort(-(q - counts), kind="stable")
+    counts[order[:left]] += 1
+    return counts
+
+
+def league_redraw(probabilities, groups, seed):
+    """One part's assignment, uint8 [groups]: league_group_counts' members in an order drawn by a NumPy generator seeded with the tuple
+    `seed` -- (sample_seed, redraw count, part) in the trainer: a pure function of the checkpointed state."""
+    counts = league_group_counts(probabilities, groups)
+    members = np.repeat(np.arange(counts.size, dtype=np.uint8), counts)
+    return members[np.random.default_rng([int(x) for x in seed]).permutation(int(groups))]
+
+
 class BatchedTrainer:
     def __init__(self, policy, n_games=4096, window=32, parts=1, learning_rate=3e-4, gamma=0.99, seed_base=0, sample_seed=0x5EED,
                  rules={"first_player": "Random", "tile_pool": "Lid"}, device=None, use_graph=True, persistent=True, results_dir="results",
                  ring=3, opponent="random", opponent_refresh=0, move_limit=0, players=2, fused_wide=False,
                  fused_opponent=False, fused_learner=False, fused_seats=False, gae_lambda=None, bootstrap_tail=False, algorithm="a2c",
-                 clip_eps=0.2, value_coeff=0.5, entropy_coeff=0.01, epochs=4, minibatches=4, normalize_advantage=True):
+                 clip_eps=0.2, value_coeff=0.5, entropy_coeff=0.01, epochs=4, minibatches=4, normalize_advantage=True, league_size=4,
+                 league_sampling="uniform", pfsp_power=2.0):
         """ring: trajectory windows kept (persistent rollout with one part): with ring >= 2 every step of every episode is trained
         exactly once (episodes straddle windows; an episode may span ring - 1 window boundaries), like NNRunner.train.
         opponent: "random" (GameRunner's default RandomAgent, the reference's scripts/training.py), a module (GameRunner(opponent=Agent(...)),
@@ -55,6 +95,14 @@ class BatchedTrainer:
         fused_wide=True and fused_seats=True (hidden 180), inside the wide window kernel (PolicyRollout(fused_seats=True)): one launch per
         window, the learner as for any fused_wide rollout (fused_learner=True trains whole episodes from the ring), still nothing in the
         checkpoint for the opponent.
+        opponent="league" (league_size=K in 1..255, opponent_refresh=k, league_sampling="uniform" | "pfsp", pfsp_power): a POOL of K frozen past
+        selves (PolicyRollout(opponent=[...]): every 16-game group plays one member, inside the window kernels where a single network opponent
+        plays there).  The pool starts as K copies of the initial policy; every k updates the current policy is written into slot
+        snapshots % K, that slot's results are zeroed and the assignment is redrawn: member probabilities league_probabilities (uniform, or
+        pfsp from the win rates of rollout.league_results()), group counts by largest remainder, their order from a NumPy generator seeded
+        with (sample_seed, redraw count, part).  Checkpoints carry the stacked pool, the assignment, the snapshot and redraw counts and the
+        results with their marks and the per-game counters the marks refer to: a resumed run equals the uninterrupted one.  Wide batches, algorithm="ppo" and gae_lambda combine with it
+        as with any network opponent.
         move_limit > 0: BatchedAzul.set_move_limit (beyond the reference: a game that would never end is cut, done = 3; its steps are trained like an
         episode that ended there, the return chain starts at the cut).
         players = 3 / 4 (or extended-rule keys in `rules`): PolicyRollout(players=...) on MultiplayerAzul parts -- the policy is
@@ -101,6 +149,10 @@ class BatchedTrainer:
             raise ValueError("algorithm=\"ppo\" trains the newest window of one seat's records: it needs ring=1 and an opponent other than None")
         if algorithm == "ppo":
             PPOLearner.check_arguments(clip_eps, value_coeff, entropy_coeff, epochs, minibatches)
+        if isinstance(opponent, str) and opponent == "league":
+            if not 1 <= int(league_size) <= 255:
+                raise ValueError("league_size must be in 1..255, got %r" % (league_size,))
+            league_probabilities([0], [0.5], league_sampling, pfsp_power)      # (refuses an unknown league_sampling)
         self.algorithm = algorithm
         self.bootstrap_tail = bool(bootstrap_tail)
         dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
@@ -115,10 +167,16 @@ class BatchedTrainer:
             self.learner = A2CLearner(policy, learning_rate=learning_rate, gamma=gamma, fused=fused)
         # rollout kernels and learner share ONE k-major copy of the weights (the learner's flat master copy)
         self.opponent_refresh = int(opponent_refresh)
-        self._self_opponent = opponent == "self"
+        self._self_opponent = isinstance(opponent, str) and opponent == "self"
+        self._league = isinstance(opponent, str) and opponent == "league"
         if self._self_opponent:
             import copy
             opponent = copy.deepcopy(policy)
+        if self._league:
+            import copy
+            opponent = [copy.deepcopy(policy) for _ in range(int(league_size))]
+            self.league_sampling, self.pfsp_power, self._sample_seed = league_sampling, float(pfsp_power), int(sample_seed)
+            self.snapshots = self.redraws = 0
         self.rollout = PolicyRollout(policy, n_games=n_games, parts=parts, rules=rules, seed_base=seed_base, device=dev, window=window,
                                      use_graph=use_graph, sample_seed=sample_seed, opponent=opponent, persistent=persistent,
                                      kweights=None if (wide and not wide_fused) else self.learner.kweights(dev),
@@ -171,6 +229,8 @@ class BatchedTrainer:
         self.batch += 1
         if self._self_opponent and self.opponent_refresh and self.batch % self.opponent_refresh == 0:
             self.rollout.set_opponent(self.rollout.policy)         # the frozen past self moves up to the present (weights copied in place)
+        if self._league and self.opponent_refresh and self.batch % self.opponent_refresh == 0:
+            self._league_refresh()
         r = sum(part["reward"].sum() for part in tr)
         self._reward_acc = r if getattr(self, "_reward_acc", None) is None else self._reward_acc + r
         if not collect_stats:
@@ -188,6 +248,21 @@ class BatchedTrainer:
         for k, v in row.items():
             self.history[k].append(v)
         return row
+
+    def _league_refresh(self):
+        """The current policy becomes pool member snapshots % K (weights copied in place), that slot's results are zeroed, and the groups are
+        dealt anew from the results so far (one host synchronisation per refresh: K x 11 doubles per part)."""
+        ro = self.rollout
+        res = ro.league_results()                            # booked under the assignment the episodes were played with
+        slot = self.snapshots % ro.pool_size
+        ro.set_pool_member(slot, ro.policy)
+        ro.reset_member_results(slot)
+        self.snapshots += 1
+        episodes = [0 if m == slot else r["episodes"] for m, r in enumerate(res)]
+        probs = league_probabilities(episodes, [r["win_percent"] for r in res], self.league_sampling, self.pfsp_power)
+        groups = ro.assignment().shape[1]
+        ro.set_assignment(np.stack([league_redraw(probs, groups, (self._sample_seed, self.redraws, p)) for p in range(ro.parts)]))
+        self.redraws += 1
 
     def train(self, net_name=None, batches=1000, log_every=None, checkpoint_every=1000, checkpoint_ring=False):
         """nn_runner.py:49-84: `batches` updates; with a `net_name` the CSV log and the checkpoints go to results_dir.
@@ -261,7 +336,9 @@ class BatchedTrainer:
         ck = {"policy": ro.policy.state_dict(), "optimizer": self.learner.optimizer_state(), "envs": envs,
               "batch": self.batch, "n_games": ro.n, "parts": ro.parts, "window": ro.T, "game_id_base": ro.game_id_base,
               "windows_played": ro.windows_played, "ring": ro.ring, "ring_saved": bool(save_ring and ro.ring > 1)}
-        if ro.opponent == "net":                         # the network opponent's (frozen) weights: a resumed run plays against the same net
+        if ro.league:                                    # the assignment, the results and their marks, the snapshot and redraw counts
+            ck["league"] = dict(ro.league_state(), snapshots=getattr(self, "snapshots", 0), redraws=getattr(self, "redraws", 0))
+        if ro.netopp:                                    # the network opponent's (frozen) weights, a league's stacked: a resumed run plays the same nets
             ck["opponent"] = {k: getattr(ro, k).cpu() for k in ("ow1t", "ob1", "ow2c", "ob2c", "ow2a_t", "ob2a")}
         if save_ring and ro.ring > 1:
             ck["ring_buffers"] = [{k: v.cpu() for k, v in rg.items()} for rg in ro.rings]
@@ -316,10 +393,13 @@ class BatchedTrainer:
                               "was written are not trained, their tails count as whole episodes -- the resumed run does not equal the "
                               "uninterrupted one (save_checkpoint(save_ring=True) / train(checkpoint_ring=True) for an exact resume)" % path)
             self.learner.load_ring_state(ro, None)
-        if ro.opponent == "net" and "opponent" in ck:
+        if ro.netopp and "opponent" in ck:
             with torch.no_grad():
                 for k, v in ck["opponent"].items():
                     getattr(ro, k).copy_(v.to(ro.device))
+        if ro.league and "league" in ck:
+            ro.load_league_state(ck["league"])
+            self.snapshots, self.redraws = int(ck["league"]["snapshots"]), int(ck["league"]["redraws"])
         torch.cuda.synchronize(ro.device)
         self.batch = int(ck["batch"])
         self._stat_base = self._stat_totals()

@@ -501,6 +501,37 @@ int azul_batch_mp_policy_rollout_vs(azul_batch_t *b, int n_steps, const azul_net
 int azul_batch_mp_policy_rollout_greedy(azul_batch_t *b, int n_steps, const azul_net_weights_t *agent, int num_inputs, int hidden_size,
                                         int num_actions, uint64_t seed, uint64_t counter, uint64_t *counter_dev, int max_replies,
                                         const azul_rollout_buffers_t *out, float gamma, void *stream);
+/* ---- a LEAGUE: a pool of network opponents inside the window kernels -------------------------------------------------------------------
+ * azul_batch_policy_rollout_vs / azul_batch_mp_policy_rollout_vs whose opponent is chosen per GROUP of AZUL_LEAGUE_GROUP_GAMES consecutive
+ * games (the 16 games of one workgroup): group i, games 16 i .. 16 i + 15 of the batch (the last group may be ragged), plays against
+ * member member_dev[i] of the pool.  `pool` holds pool_size nets STACKED array by array: member m's w1t, b1, w2c, b2c, w2a_t and b2a begin
+ * at pool->x + m * size(x), the sizes following from the shape -- num_inputs * 360, 360, 180, 1, 180 * num_actions, num_actions floats (only
+ * forward_actor's half is read: w2c and b2c may be NULL); the alignment _vs asks of the opponent's arrays is asked of the pool's, and holds
+ * for every member because these sizes are multiples of 16 bytes for every compiled shape.  member_dev: uint8 [ceil(N / 16)] on the device,
+ * read once per workgroup at launch; a value >= pool_size is read as pool_size - 1, so the kernel never reads outside the pool.
+ * Everything else -- agent, keys, counters, layouts, trace, returns, the reply cap -- is _vs's.  A game's trajectory is keyed by its global id
+ * (its Philox draws, its MT19937 stream) and does not depend on what its neighbours play against: for the games of a group assigned to
+ * member m every output, record, stream and counter is bit-identical to _vs with member m's weights on the same batch.  No allocation
+ * and no host synchronisation.  AZUL_ERR_INVALID before any launch: everything _vs refuses (a wide batch for the two-player entry and the
+ * reverse included), pool_size outside 1..255, a NULL pool or member_dev. */
+#define AZUL_LEAGUE_GROUP_GAMES 16
+int azul_batch_policy_rollout_league(azul_batch_t *b, int n_steps, const azul_net_weights_t *agent, const azul_net_weights_t *pool, int pool_size,
+                                     const uint8_t *member_dev, int num_inputs, int hidden_size, int num_actions, uint64_t seed,
+                                     uint64_t opponent_seed, uint64_t counter, uint64_t *counter_dev, const azul_rollout_buffers_t *out, float gamma,
+                                     void *stream);
+int azul_batch_mp_policy_rollout_league(azul_batch_t *b, int n_steps, const azul_net_weights_t *agent, const azul_net_weights_t *pool, int pool_size,
+                                        const uint8_t *member_dev, int num_inputs, int hidden_size, int num_actions, uint64_t seed,
+                                        uint64_t opponent_seed, uint64_t counter, uint64_t *counter_dev, int max_replies,
+                                        const azul_rollout_buffers_t *out, float gamma, void *stream);
+/* The league's book-keeping in ONE launch: for every member m, over the games of the groups assigned to m (member_dev as above, the same
+ * clamp), results_dev[m][0] += episodes - mark_episodes and results_dev[m][1 + k] += stat_sums[.][k] - mark_sums[.][k] (k < 10: the sums
+ * of azul_batch_statistics' keys), game by game in ascending order -- plain fp64 additions in one fixed order, no atomics: the same bits on
+ * every run -- and then the marks move up to the counters.  episodes_dev / stat_sums_dev: the per-game counters of a batch
+ * (azul_batch_counters_dev: uint64 [N], double [N][10]); mark_*_dev: the caller's arrays of the same shapes; results_dev: double
+ * [pool_size][11], the row of a member without a group is not written.  No host synchronisation: eleven doubles per member are what a caller
+ * copies back.  AZUL_ERR_INVALID: a NULL pointer, n_games < 1, pool_size outside 1..255. */
+int azul_league_tally(const uint64_t *episodes_dev, const double *stat_sums_dev, uint64_t *mark_episodes_dev, double *mark_sums_dev,
+                      const uint8_t *member_dev, int n_games, int pool_size, double *results_dev, void *stream);
 /* The same protocol one launch per cut, for opponents evaluated OUTSIDE the library (any network as PyTorch modules, or azul_policy_forward
  * on a second weight set): GameRunner.step / reset are cut at their opponent_move() calls.  pending_dev (uint8 [N], in / out) holds per
  * game 0 = nothing owed (the agent's next decision), 1 = an opponent_move() is owed inside GameRunner.step's loop (game_runner.py:46-47),

@@ -1,0 +1,189 @@
+"""The league without a device: the book-keeping kernel azul_league_tally_kernel (csrc/azul_policy.hpp, compiled UNMODIFIED by g++ under the
+lockstep emulation: tests/hostcheck/simt_league_tally.cpp) against a NumPy restatement; the trainer's sampler (league_probabilities, the
+largest-remainder group counts, the seeded redraw); PolicyRollout's mode checks for opponent=[net0, net1, ...]; and the three C entries
+(declared, exported, bound, refusing their arguments on the host)."""
+import ctypes as C
+import os
+import re
+
+import numpy as np
+import pytest
+
+from tests.hostcheck import hostcheck
+from tests.test_mp_score_moves_model import _modes
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ENTRIES = ("azul_batch_policy_rollout_league", "azul_batch_mp_policy_rollout_league", "azul_league_tally")
+GROUP = 16
+
+
+# ---- 3. the tally kernel ------------------------------------------------------------------------------------------------------------
+def load_tally():
+    L = C.CDLL(hostcheck.build("libsimt_league_tally.so"))
+    L.slt_tally.restype = C.c_longlong
+    L.slt_tally.argtypes = [C.c_void_p] * 5 + [C.c_int, C.c_int, C.c_void_p]
+    return L
+
+
+def ptr(a):
+    return a.ctypes.data_as(C.c_void_p)
+
+
+def tally_ref(ep, ss, mark_ep, mark_ss, member, K, results):
+    """The kernel restated: per member, games in ascending order, one fp64 addition per game and column; then the marks move up."""
+    results, mark_ep, mark_ss = results.copy(), mark_ep.copy(), mark_ss.copy()
+    for m in range(K):
+        for grp, mg in enumerate(member):
+            if min(int(mg), K - 1) != m:
+                continue
+            for g in range(grp * GROUP, min(len(ep), (grp + 1) * GROUP)):
+                results[m, 0] = results[m, 0] + np.float64(int(ep[g]) - int(mark_ep[g]))
+                for j in range(10):
+                    results[m, 1 + j] = results[m, 1 + j] + (ss[g, j] - mark_ss[g, j])
+                mark_ep[g] = ep[g]
+                mark_ss[g] = ss[g]
+    return results, mark_ep, mark_ss
+
+
+@pytest.mark.parametrize("n", [1, 16, 17, 35])
+def test_tally_kernel_matches_the_numpy_restatement(n):
+    L = load_tally()
+    rs = np.random.RandomState(n)
+    K, groups = 4, (n + GROUP - 1) // GROUP
+    member = rs.randint(0, 3, groups).astype(np.uint8)                   # member 3 has no group: its row must stay as it is
+    if groups == 3:
+        member[:] = [2, 0, 9]                                            # ... and a value past the pool is read as K - 1 = 3
+    ep = rs.randint(0, 50, n).astype(np.uint64)
+    ss = rs.randn(n, 10) * 100.0                                         # general doubles: the ORDER of the additions shows in the bits
+    mark_ep, mark_ss = np.zeros(n, np.uint64), np.zeros((n, 10))
+    results = rs.randn(K, 11)                                            # what earlier calls left
+    sentinel = results.copy()
+    want, wme, wms = tally_ref(ep, ss, mark_ep, mark_ss, member, K, results)
+    assert L.slt_tally(ptr(ep), ptr(ss), ptr(mark_ep), ptr(mark_ss), ptr(member), n, K, ptr(results)) > 0
+    assert results.tobytes() == want.tobytes()
+    assert np.array_equal(mark_ep, ep) and mark_ss.tobytes() == ss.tobytes() and wme.tobytes() == mark_ep.tobytes() and wms.tobytes() == mark_ss.tobytes()
+    used = set(min(int(m), K - 1) for m in member)
+    for m in set(range(K)) - used:
+        assert results[m].tobytes() == sentinel[m].tobytes()             # an unused member's row is untouched
+    # a second call with counters that have not moved adds nothing
+    before = results.copy()
+    assert L.slt_tally(ptr(ep), ptr(ss), ptr(mark_ep), ptr(mark_ss), ptr(member), n, K, ptr(results)) > 0
+    assert results.tobytes() == before.tobytes()
+    # a partial advance: only some games move, and only the change since the marks is booked -- to the member of the NEW assignment
+    moved = rs.rand(n) < 0.5
+    moved[0] = True
+    ep2 = ep + moved.astype(np.uint64) * rs.randint(1, 4, n).astype(np.uint64)
+    ss2 = ss + moved[:, None] * rs.randn(n, 10)
+    member2 = ((member.astype(np.int64) + 1) % 3).astype(np.uint8)
+    want, _, _ = tally_ref(ep2, ss2, mark_ep, mark_ss, member2, K, results)
+    assert L.slt_tally(ptr(ep2), ptr(ss2), ptr(mark_ep), ptr(mark_ss), ptr(member2), n, K, ptr(results)) > 0
+    assert results.tobytes() == want.tobytes()
+    assert np.isclose(results[:, 0].sum() - before[:, 0].sum(), float((ep2 - ep).sum()), atol=1e-9)
+    assert np.array_equal(mark_ep, ep2) and mark_ss.tobytes() == ss2.tobytes()
+
+
+# ---- 4. the sampler -------------------------------------------------------------------------------------------------------------------
+def test_league_probabilities_and_the_redraw():
+    from azul_deep_reinforcement_learning_amd.training import league_group_counts, league_probabilities, league_redraw
+    assert np.array_equal(league_probabilities([5, 0, 9], [0.1, 0.2, 0.9], "uniform"), np.full(3, 1 / 3))
+    p = league_probabilities([10, 10, 0], [1.0, 0.5, 0.123], "pfsp", 2.0)       # beaten every time / half the time / no episodes: 0.5
+    assert p[0] == 0.0 and p[1] == p[2] == 0.5
+    p = league_probabilities([10, 10], [0.0, 0.5], "pfsp", 2.0)
+    assert np.allclose(p, [0.8, 0.2])
+    assert np.array_equal(league_probabilities([3, 4], [1.0, 1.0], "pfsp"), [0.5, 0.5])          # all-zero weights: uniform
+    assert np.array_equal(league_probabilities([3, 0], [float("nan"), 0.0], "pfsp", 1.0), [0.5, 0.5])
+    with pytest.raises(ValueError, match="league_sampling"):
+        league_probabilities([1], [0.5], "elo")
+    for probs, groups in (([1 / 3] * 3, 8), ([0.8, 0.2], 3), ([0.0, 0.5, 0.5], 7), ([0.25] * 4, 256), ([1.0], 5), ([0.5, 0.5], 1)):
+        counts = league_group_counts(probs, groups)
+        assert counts.sum() == groups and (counts >= 0).all()
+        assert all(abs(c - q * groups) < 1.0 for c, q in zip(counts, probs))                     # within one of the quota
+        assert all(c == 0 for c, q in zip(counts, probs) if q == 0.0)
+        a = league_redraw(probs, groups, (0x5EED, 3, 0))
+        assert a.dtype == np.uint8 and a.shape == (groups,) and np.array_equal(np.bincount(a, minlength=len(probs)), counts)
+    # a member with win rate 1 gets no group under pfsp while another has weight
+    p = league_probabilities([20, 20, 20], [1.0, 0.4, 0.7], "pfsp", 2.0)
+    assert league_group_counts(p, 256)[0] == 0 and (league_redraw(p, 256, (1, 2, 3)) != 0).all()
+    # deterministic in the seed tuple, and every element of the tuple matters
+    probs = [0.4, 0.35, 0.25]
+    a = league_redraw(probs, 64, (0x5EED, 1, 0))
+    assert np.array_equal(a, league_redraw(probs, 64, (0x5EED, 1, 0)))
+    for other in ((0x5EEE, 1, 0), (0x5EED, 2, 0), (0x5EED, 1, 1)):
+        assert not np.array_equal(a, league_redraw(probs, 64, other))
+
+
+# ---- 5. the mode checks and the C entries ---------------------------------------------------------------------------------------------
+def _net(obs=136, act=180, hidden=180):
+    from azul_deep_reinforcement_learning_amd import BatchedActorCritic
+    return BatchedActorCritic(obs, act, hidden)
+
+
+def test_check_modes_resolves_a_list_of_modules_to_the_league():
+    two = dict(players=2, rules={"first_player": "Random", "tile_pool": "Lid"})
+    for pool in ([_net(), _net()], (_net(),)):
+        ro = _modes(opponent=pool, persistent=True, opponent_trace=4, ring=3, **two)
+        assert ro.opponent == "league" and ro.league and ro.netopp and ro.cut and not ro.scripted and not ro.wide
+        assert ro.window_entry == "azul_batch_policy_rollout_league" and ro.persistent and ro.ring == 3 and ro.opp_slots == 4 and not ro.use_graph
+        ro = _modes(opponent=pool, persistent=False, **two)
+        assert ro.opponent == "league" and ro.window_entry is None and not ro.persistent and ro.ring == 1 and not ro.use_graph
+    wide = [_net(188), _net(188), _net(188)]
+    ro = _modes(3, opponent=wide, fused_wide=True, fused_opponent=True, wide_ring=2)
+    assert ro.league and ro.wide and ro.window_entry == "azul_batch_mp_policy_rollout_league" and ro.fused_opponent and ro.ring == 2
+    ro = _modes(3, opponent=[_net(188, hidden=64)], hidden=64)               # per cut: any hidden size
+    assert ro.league and ro.window_entry is None
+    ro = _modes(opponent=_net(), persistent=True, **two)                     # a single module is still kind "net"
+    assert ro.opponent == "net" and not ro.league and ro.netopp and ro.window_entry == "azul_batch_policy_rollout_vs"
+
+
+def test_league_refusals_come_before_any_allocation():
+    from azul_deep_reinforcement_learning_amd.rollout import PolicyRollout
+    from azul_deep_reinforcement_learning_amd.training import BatchedTrainer
+    with pytest.raises(ValueError, match="pool of 1..255"):
+        PolicyRollout(_net(), n_games=8, opponent=[])
+    with pytest.raises(ValueError, match="pool of 1..255"):
+        PolicyRollout(_net(), n_games=8, opponent=[_net()] * 256)
+    with pytest.raises(ValueError, match="ONE shape"):
+        PolicyRollout(_net(), n_games=8, opponent=[_net(), _net(hidden=64)])
+    with pytest.raises(ValueError, match="not opponent kinds"):
+        PolicyRollout(_net(), n_games=8, opponent=[_net(), "random"])
+    # the refusals of a single network opponent, applied to every member
+    with pytest.raises(ValueError, match="must take the batch's observation"):
+        PolicyRollout(_net(188), n_games=8, players=3, opponent=[_net(136), _net(136)])
+    with pytest.raises(ValueError, match="fused_wide=True plays opponent=None"):
+        PolicyRollout(_net(188), n_games=8, players=3, opponent=[_net(188)], fused_wide=True)
+    with pytest.raises(ValueError, match="opponent of hidden size 180, got 64 / 64"):
+        PolicyRollout(_net(188), n_games=8, players=3, opponent=[_net(188, hidden=64)] * 2, fused_wide=True, fused_opponent=True)
+    with pytest.raises(ValueError, match="fused_opponent=True plays a network opponent"):
+        PolicyRollout(_net(), n_games=8, opponent=[_net()], fused_opponent=True)
+    with pytest.raises(ValueError, match="fused_seats=True.*greedy_margin"):
+        PolicyRollout(_net(188), n_games=8, players=3, opponent=[_net(188)], fused_seats=True)
+    # the trainer's own
+    with pytest.raises(ValueError, match="league_size must be in 1..255"):
+        BatchedTrainer(_net(), n_games=8, opponent="league", league_size=0)
+    with pytest.raises(ValueError, match="league_sampling"):
+        BatchedTrainer(_net(), n_games=8, opponent="league", league_size=2, league_sampling="elo")
+
+
+def test_league_entries_are_declared_exported_bound_and_refuse_on_the_host():
+    from azul_deep_reinforcement_learning_amd import _lib as L
+    from azul_deep_reinforcement_learning_amd.rollout import _WINDOW_KERNELS
+    header = open(os.path.join(ROOT, "include", "azul_hip.h")).read()
+    assert re.search(r"#define\s+AZUL_LEAGUE_GROUP_GAMES\s+16\b", header) and L.LEAGUE_GROUP_GAMES == 16
+    for name in ENTRIES:
+        assert re.search(r"\bint\s+%s\s*\(" % name, header) and name in L.SIGNATURES and hasattr(L.lib, name)
+    assert _WINDOW_KERNELS[False, "league"][:2] == ("azul_batch_policy_rollout_league", "persistent")
+    assert _WINDOW_KERNELS[True, "league"][:2] == ("azul_batch_mp_policy_rollout_league", "fused_opponent")
+    one, f32 = C.c_void_p(16), C.c_float
+    wts, bufs = L.NetWeights(*[one] * 6), L.RolloutBuffers(*[one] * 14, 0)
+    wr, br = C.byref(wts), C.byref(bufs)
+    # without a batch nothing else is looked at, under the entry's own name
+    assert L.lib.azul_batch_policy_rollout_league(None, 4, wr, wr, 2, one, 136, 180, 180, 1, 2, 0, None, br, f32(0.9), None) == L.ERR_INVALID
+    assert L.lib.azul_last_error_string().decode().startswith("azul_batch_policy_rollout_league")
+    assert L.lib.azul_batch_mp_policy_rollout_league(None, 4, wr, wr, 2, one, 188, 180, 180, 1, 2, 0, None, 8, br, f32(0.9), None) == L.ERR_INVALID
+    assert L.lib.azul_last_error_string().decode().startswith("azul_batch_mp_policy_rollout_league")
+    ok = (one, one, one, one, one, 35, 3, one, None)
+    for i, bad in ((0, None), (1, None), (2, None), (3, None), (4, None), (7, None), (5, 0), (6, 0), (6, 256)):
+        args = list(ok)
+        args[i] = bad
+        assert L.lib.azul_league_tally(*args) == L.ERR_INVALID
+        assert L.lib.azul_last_error_string().decode().startswith("azul_league_tally")
