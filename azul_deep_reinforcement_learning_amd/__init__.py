@@ -12,5 +12,6 @@ from .game_runner import GameRunner, RandomAgent, check_all_valid  # noqa: F401
 from .policy import BatchedActorCritic, IllegalMask  # noqa: F401
 from .multiplayer import MultiplayerAzul  # noqa: F401
 from .rollout import PolicyRollout  # noqa: F401
+from .arena import Arena, bradley_terry, round_robin_pairs  # noqa: F401
 from .learner import A2CLearner  # noqa: F401
 from .training import BatchedTrainer  # noqa: F401

@@ -111,6 +111,11 @@ SIGNATURES = {
     "azul_batch_mp_policy_rollout_league": (_i, [_vp, _i, C.POINTER(NetWeights), C.POINTER(NetWeights), _i, _vp, _i, _i, _i, _u64, _u64, _u64, _vp,
                                                  _i, C.POINTER(RolloutBuffers), C.c_float, _vp]),
     "azul_league_tally": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
+    "azul_batch_policy_rollout_arena": (_i, [_vp, _i, C.POINTER(NetWeights), _i, _vp, _vp, _i, _i, _i, _u64, _u64, _u64, _vp,
+                                             C.POINTER(RolloutBuffers), C.c_float, _vp]),
+    "azul_batch_mp_policy_rollout_arena": (_i, [_vp, _i, C.POINTER(NetWeights), _i, _vp, _vp, _i, _i, _i, _u64, _u64, _u64, _vp,
+                                                _i, C.POINTER(RolloutBuffers), C.c_float, _vp]),
+    "azul_arena_tally": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
     "azul_batch_mp_policy_rollout_greedy": (_i, [_vp, _i, C.POINTER(NetWeights), _i, _i, _i, _u64, _u64, _vp, _i, C.POINTER(RolloutBuffers),
                                                  C.c_float, _vp]),
     "azul_batch_net_step_begin": (_i, [_vp] * 11),

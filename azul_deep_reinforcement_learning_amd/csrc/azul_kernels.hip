@@ -701,12 +701,15 @@ int azul_policy_forward(const float *obs_dev, const uint8_t *mask_dev, const flo
     return AZUL_SUCCESS;
 }
 
-static int launch_rollout(azul_batch_t *b, const PolicyWeights &W, const RolloutArgs &a, int opp, void *stream)
+static int launch_rollout(azul_batch_t *b, const PolicyWeights &W, const RolloutArgs &a, int opp, void *stream, bool arena = false)
 {
     const hipStream_t st = (hipStream_t)stream;
     const bool lid = b->d.rules.tile_pool == POOL_LID;
     const dim3 grid2((b->d.n + PF_GAMES - 1) / PF_GAMES), block2(64 * PR2_WAVES);
-    if (lid) {
+    if (arena) {                                             // (opp == 2: W is the stacked pool, a.agent_member picks from it)
+        if (lid) hipLaunchKernelGGL((azul_policy_rollout2_kernel<true, 2, true>), grid2, block2, 0, st, b->d, W, a);
+        else hipLaunchKernelGGL((azul_policy_rollout2_kernel<false, 2, true>), grid2, block2, 0, st, b->d, W, a);
+    } else if (lid) {
         if (opp == 3) hipLaunchKernelGGL((azul_policy_rollout2_kernel<true, 3>), grid2, block2, 0, st, b->d, W, a);
         else if (opp == 2) hipLaunchKernelGGL((azul_policy_rollout2_kernel<true, 2>), grid2, block2, 0, st, b->d, W, a);
         else if (opp == 1) hipLaunchKernelGGL((azul_policy_rollout2_kernel<true, 1>), grid2, block2, 0, st, b->d, W, a);
@@ -723,7 +726,9 @@ static int launch_rollout(azul_batch_t *b, const PolicyWeights &W, const Rollout
 
 struct NetShape { int inputs, hidden, actions; };
 struct DrawKeys { uint64_t seed, opp_seed, counter; uint64_t *counter_dev; };
-struct League { int pool_size; const uint8_t *member_dev; };     // azul_batch_[mp_]policy_rollout_league: the pool behind `opponent`
+// azul_batch_[mp_]policy_rollout_league: the pool behind `opponent`.  agent_member_dev (azul_batch_[mp_]policy_rollout_arena): the same pool is
+// behind `agent` too, one member per group for the agent seat
+struct League { int pool_size; const uint8_t *member_dev; const uint8_t *agent_member_dev; bool arena; };
 static_assert(AZUL_LEAGUE_GROUP_GAMES == PF_GAMES, "a league group is the 16 games of one workgroup of the window kernels");
 
 static int fail_in(const char *who, const char *what)
@@ -741,9 +746,12 @@ static int rollout_window(azul_batch_t *b, const char *who, bool wide, int n_ste
                           int max_replies, void *stream, const League *league = nullptr)
 {
     const bool net = opp == 2;
-    if (!b || n_steps < 0 || !agent || !out) return fail_in(who, "bad arguments");
+    const bool arena = league && league->arena;              // `agent` and `opponent` are the one stacked pool
+    if (!b || n_steps < 0 || (!agent && !arena) || !out) return fail_in(who, "bad arguments");
     if (league) {                                            // `opponent` is the stacked pool (include/azul_hip.h)
         if (league->pool_size < 1 || league->pool_size > 255) return fail_in(who, "pool_size must be in 1..255 (a member is one byte per group)");
+        if (arena && (!agent || !opponent || !league->member_dev || !league->agent_member_dev))
+            return fail_in(who, "NULL pool, agent_member_dev or opp_member_dev");
         if (!opponent || !league->member_dev) return fail_in(who, "NULL pool or member_dev");
     }
     if (net && !opponent) return fail_in(who, "no opponent (the entry without _vs plays without one)");
@@ -751,10 +759,12 @@ static int rollout_window(azul_batch_t *b, const char *who, bool wide, int n_ste
         return fail_in(who, "a wide batch (three / four players or extended rules): the greedy player maximises the two-player reward of "
                             "game_runner.py:48-50");
     if (wide != b->x)
-        return fail_in(who, wide ? (league ? "a two-player batch of 128-byte records: use azul_batch_policy_rollout_league"
+        return fail_in(who, wide ? (arena ? "a two-player batch of 128-byte records: use azul_batch_policy_rollout_arena"
+                                    : league ? "a two-player batch of 128-byte records: use azul_batch_policy_rollout_league"
                                     : net ? "a two-player batch of 128-byte records: use azul_batch_policy_rollout_vs"
                                         : opp == 3 ? "a two-player batch of 128-byte records: use azul_batch_policy_rollout_greedy"
                                         : "a two-player batch of 128-byte records: use azul_batch_policy_rollout")
+                                 : arena ? "a wide batch (three / four players or extended rules): use azul_batch_mp_policy_rollout_arena"
                                  : "the policy entries are compiled for the reference's two-player game (ActorCritic(136, 180): 180 actions, 136 "
                                    "observations; game_runner.py:50) -- not for 3 / 4 players or extended rules");
     if (wide) {                                              // the wide kernels: no move limit, the batch's own sizes, a bound on the reply rounds
@@ -790,19 +800,22 @@ static int rollout_window(azul_batch_t *b, const char *who, bool wide, int n_ste
         a.opp_seed = (u64)keys.opp_seed;
         a.opp_action = out->opp_action; a.opp_logp = out->opp_logp; a.opp_replies = out->opp_replies; a.opp_slots = out->opp_slots;
         if (league) { a.opp_member = league->member_dev; a.opp_pool = (u32)league->pool_size; }      // a base offset per workgroup, nothing else
+        if (arena) { a.agent_member = league->agent_member_dev; a.agent_pool = (u32)league->pool_size; }
     }
     if (opp == 3) {                                          // the greedy player's trace: its answers and their number (opp_logp is never written)
         a.opp_action = out->opp_action; a.opp_replies = out->opp_replies; a.opp_slots = out->opp_slots;
     }
     if (!wide) {
-        const int rc = launch_rollout(b, W, a, opp, stream);
+        const int rc = launch_rollout(b, W, a, opp, stream, arena);
         if (rc != AZUL_SUCCESS) return rc;
     } else {
         const dim3 grid((b->d.n + PF_GAMES - 1) / PF_GAMES), block(64 * PR2_WAVES);
         const hipStream_t st = (hipStream_t)stream;
         const azx::XBatchDev xb = xdev(b);
         const u32 id_base = b->d.id_base;
-        if (net && league)
+        if (net && arena)
+            AZ_X_DISPATCH(b, hipLaunchKernelGGL((azul_x_policy_rollout_vs_kernel<PP, DD, true, true>), grid, block, 0, st, xb, W, a, id_base, (u32)max_replies));
+        else if (net && league)
             AZ_X_DISPATCH(b, hipLaunchKernelGGL((azul_x_policy_rollout_vs_kernel<PP, DD, true>), grid, block, 0, st, xb, W, a, id_base, (u32)max_replies));
         else if (net) AZ_X_DISPATCH(b, hipLaunchKernelGGL((azul_x_policy_rollout_vs_kernel<PP, DD>), grid, block, 0, st, xb, W, a, id_base, (u32)max_replies));
         else if (opp == 3)
@@ -890,7 +903,7 @@ int azul_batch_policy_rollout_league(azul_batch_t *b, int n_steps, const azul_ne
                                      void *stream)
 {
     BATCH_GUARD(b, stream);
-    const League lg = {pool_size, member_dev};
+    const League lg = {pool_size, member_dev, nullptr, false};
     return rollout_window(b, "azul_batch_policy_rollout_league", false, n_steps, 2, agent, pool, {num_inputs, hidden_size, num_actions},
                           {seed, opponent_seed, counter, counter_dev}, out, gamma, 0, stream, &lg);
 }
@@ -901,7 +914,7 @@ int azul_batch_mp_policy_rollout_league(azul_batch_t *b, int n_steps, const azul
                                         const azul_rollout_buffers_t *out, float gamma, void *stream)
 {
     BATCH_GUARD(b, stream);
-    const League lg = {pool_size, member_dev};
+    const League lg = {pool_size, member_dev, nullptr, false};
     return rollout_window(b, "azul_batch_mp_policy_rollout_league", true, n_steps, 2, agent, pool, {num_inputs, hidden_size, num_actions},
                           {seed, opponent_seed, counter, counter_dev}, out, gamma, max_replies, stream, &lg);
 }
@@ -916,6 +929,44 @@ int azul_league_tally(const uint64_t *episodes_dev, const double *stat_sums_dev,
     STREAM_GUARD(stream);
     hipLaunchKernelGGL(azul_league_tally_kernel, dim3((u32)pool_size), dim3(64), 0, (hipStream_t)stream, (const u64 *)episodes_dev, stat_sums_dev,
                        (u64 *)mark_episodes_dev, mark_sums_dev, member_dev, (u32)n_games, (u32)pool_size, results_dev);
+    HIP_TRY(hipGetLastError());
+    return AZUL_SUCCESS;
+}
+
+/* an ARENA: both seats are members of one stacked pool, a pair per 16-game workgroup (RolloutArgs::agent_member / opp_member; the ARENA
+ * instantiations of the same kernels, the same host path) */
+int azul_batch_policy_rollout_arena(azul_batch_t *b, int n_steps, const azul_net_weights_t *pool, int pool_size, const uint8_t *agent_member_dev,
+                                    const uint8_t *opp_member_dev, int num_inputs, int hidden_size, int num_actions, uint64_t seed,
+                                    uint64_t opponent_seed, uint64_t counter, uint64_t *counter_dev, const azul_rollout_buffers_t *out, float gamma,
+                                    void *stream)
+{
+    BATCH_GUARD(b, stream);
+    const League lg = {pool_size, opp_member_dev, agent_member_dev, true};
+    return rollout_window(b, "azul_batch_policy_rollout_arena", false, n_steps, 2, pool, pool, {num_inputs, hidden_size, num_actions},
+                          {seed, opponent_seed, counter, counter_dev}, out, gamma, 0, stream, &lg);
+}
+
+int azul_batch_mp_policy_rollout_arena(azul_batch_t *b, int n_steps, const azul_net_weights_t *pool, int pool_size, const uint8_t *agent_member_dev,
+                                       const uint8_t *opp_member_dev, int num_inputs, int hidden_size, int num_actions, uint64_t seed,
+                                       uint64_t opponent_seed, uint64_t counter, uint64_t *counter_dev, int max_replies,
+                                       const azul_rollout_buffers_t *out, float gamma, void *stream)
+{
+    BATCH_GUARD(b, stream);
+    const League lg = {pool_size, opp_member_dev, agent_member_dev, true};
+    return rollout_window(b, "azul_batch_mp_policy_rollout_arena", true, n_steps, 2, pool, pool, {num_inputs, hidden_size, num_actions},
+                          {seed, opponent_seed, counter, counter_dev}, out, gamma, max_replies, stream, &lg);
+}
+
+/* the arena's per-pair results since the marks, one launch (azul_arena_tally_kernel) */
+int azul_arena_tally(const uint64_t *episodes_dev, const double *stat_sums_dev, uint64_t *mark_episodes_dev, double *mark_sums_dev,
+                     const uint8_t *agent_member_dev, const uint8_t *opp_member_dev, int n_games, int pool_size, double *results_dev, void *stream)
+{
+    if (!episodes_dev || !stat_sums_dev || !mark_episodes_dev || !mark_sums_dev || !agent_member_dev || !opp_member_dev || !results_dev ||
+        n_games < 1 || pool_size < 1 || pool_size > 255)
+        return fail(AZUL_ERR_INVALID, "azul_arena_tally: bad arguments");
+    STREAM_GUARD(stream);
+    hipLaunchKernelGGL(azul_arena_tally_kernel, dim3((u32)pool_size), dim3(64), 0, (hipStream_t)stream, (const u64 *)episodes_dev, stat_sums_dev,
+                       (u64 *)mark_episodes_dev, mark_sums_dev, agent_member_dev, opp_member_dev, (u32)n_games, (u32)pool_size, results_dev);
     HIP_TRY(hipGetLastError());
     return AZUL_SUCCESS;
 }

@@ -436,6 +436,10 @@ struct RolloutArgs {
                                  // Set: Wopp holds `opp_pool` nets STACKED array by array (league_member below).  A value >= opp_pool is read as
                                  // opp_pool - 1: the kernel never reads outside the pool.
     u32 opp_pool;                // K >= 1 when opp_member is set
+    // ---- arena: the AGENT is a pool member too (the ARENA instantiations of the OPP == 2 kernels; azul_batch_[mp_]policy_rollout_arena) ----
+    const uint8_t *agent_member; // [ceil(N / 16)]: the pool member that plays the agent seat of workgroup blockIdx.x.  Set: the kernel's W holds
+                                 // `agent_pool` nets stacked as Wopp's pool is (all six arrays, the critic's included); clamped as opp_member is.
+    u32 agent_pool;              // K >= 1 when agent_member is set
 };
 
 // Member m of a stacked pool: every array of `W` begins at W.x + m * size(x), the sizes following from the compiled shape -- w1t IN x 360,
@@ -456,6 +460,14 @@ __device__ __forceinline__ u32 league_member_of_block(const RolloutArgs &a)
 {
     const u32 m = (u32)a.opp_member[blockIdx.x];
     const u32 top = a.opp_pool ? a.opp_pool - 1u : 0u;
+    return (u32)__builtin_amdgcn_readfirstlane((int)(m < top ? m : top));
+}
+
+// the pool member that plays the agent seat of workgroup blockIdx.x (RolloutArgs::agent_member), clamped and made wave-uniform the same way
+__device__ __forceinline__ u32 arena_agent_of_block(const RolloutArgs &a)
+{
+    const u32 m = (u32)a.agent_member[blockIdx.x];
+    const u32 top = a.agent_pool ? a.agent_pool - 1u : 0u;
     return (u32)__builtin_amdgcn_readfirstlane((int)(m < top ? m : top));
 }
 
@@ -492,4 +504,38 @@ __global__ void __launch_bounds__(64) azul_league_tally_kernel(const u64 *episod
         }
     }
     if (any) results[(size_t)m * LEAGUE_COLS + j] = acc;      // (a member without a group: its row is not written)
+}
+
+// ---- arena book-keeping: azul_league_tally_kernel for ORDERED PAIRS (azul_arena_tally) ---------------------------------------------------
+// results [K][K][11]: cell [a][o] gains what the games of the groups assigned agent a, opponent o finished since the marks.  One workgroup
+// (one wave) per agent member a, lane j < 11 owns column j of every cell of row a.  The lane walks the groups in ascending order; for a
+// group of its row it takes the cell's value, adds counter - mark game by game in ascending order and puts the value back -- so within a
+// cell the games are added in ascending order, plain fp64 additions, no atomics: the same bits on every run.  Then the mark moves up.
+// Both bytes are clamped as the rollout kernels clamp them.  A cell whose pair has no group is not written; every game belongs to one row.
+__global__ void __launch_bounds__(64) azul_arena_tally_kernel(const u64 *episodes, const double *stat_sums, u64 *mark_episodes, double *mark_sums,
+                                                              const uint8_t *agent_member, const uint8_t *opp_member, u32 n, u32 K, double *results)
+{
+    const u32 am = blockIdx.x, j = threadIdx.x;
+    if (am >= K || j >= LEAGUE_COLS) return;
+    const u32 groups = (n + (u32)PF_GAMES - 1u) / (u32)PF_GAMES;
+    for (u32 grp = 0; grp < groups; grp++) {
+        const u32 ag = (u32)agent_member[grp], og = (u32)opp_member[grp];
+        if ((ag < K - 1u ? ag : K - 1u) != am) continue;
+        double *cell = results + ((size_t)am * K + (og < K - 1u ? og : K - 1u)) * LEAGUE_COLS + j;
+        double acc = *cell;
+        const u32 g1 = (grp + 1u) * (u32)PF_GAMES < n ? (grp + 1u) * (u32)PF_GAMES : n;
+        for (u32 g = grp * (u32)PF_GAMES; g < g1; g++) {
+            if (j == 0u) {
+                const u64 e = episodes[g];
+                acc += (double)(e - mark_episodes[g]);
+                mark_episodes[g] = e;
+            } else {
+                const size_t i = (size_t)g * (LEAGUE_COLS - 1u) + (j - 1u);
+                const double s = stat_sums[i];
+                acc += s - mark_sums[i];
+                mark_sums[i] = s;
+            }
+        }
+        *cell = acc;
+    }
 }

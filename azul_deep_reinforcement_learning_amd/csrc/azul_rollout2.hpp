@@ -183,9 +183,15 @@ __device__ __forceinline__ void pr2_opp_layer1(const __amdgpu_buffer_rsrc_t rso,
 
 // OPP: 0 the policy moves for both players, 1 GameRunner with the RandomAgent opponent, 2 GameRunner with a NETWORK opponent (a.Wopp),
 // 3 GameRunner with the one-ply GREEDY opponent (az2::greedy_pick2: no weights, no matrix phase, no draw)
-template <bool LID, int OPP>
-__global__ void __launch_bounds__(64 * PR2_WAVES) azul_policy_rollout2_kernel(BatchDev b, PolicyWeights W, RolloutArgs a)
+// ARENA (OPP 2 only; azul_batch_policy_rollout_arena): the kernel's weights are a stacked pool too and a.agent_member picks the workgroup's
+// agent from it -- a base offset per array chosen once, wave-uniform; everything the agent side reads goes through W below.  A template
+// flag, so that every other instantiation compiles exactly as before.
+template <bool LID, int OPP, bool ARENA = false>
+__global__ void __launch_bounds__(64 * PR2_WAVES) azul_policy_rollout2_kernel(BatchDev b, PolicyWeights Wk, RolloutArgs a)
 {
+    static_assert(!ARENA || OPP == 2, "the arena is the network-opponent kernel with a pool behind the agent seat");
+    PolicyWeights W = Wk;
+    if constexpr (ARENA) W = league_member<(u32)PF_IN, (u32)PF_ACT>(Wk, arena_agent_of_block(a));
     __shared__ float obsS[PF_GAMES * PF_OBS_STRIDE];
     __shared__ float hidS[PF_GAMES * PF_HID_STRIDE];
     __shared__ float lgS[PF_GAMES * PF_LOG_STRIDE];
@@ -708,8 +714,9 @@ AZ_FN void px_chain(const float *ap, const float *const (&bp)[NT], u32 bstride, 
 // two-player kernel: the null check in the one instantiation moved the register allocation of the existing azul_x_policy_rollout_vs_kernel
 // (private segment +8 bytes for <2, 5>, or +4 for <4, 9> with only the member index kept live), so the single-opponent kernels compile
 // exactly as before and the league has its own.
-template <u32 P, u32 D, int OPP, bool LEAGUE = false>
-AZ_FN void x_policy_rollout_body(const azx::XBatchDev &b, const PolicyWeights &W, const RolloutArgs &a, u32 id_base, PXShared<P, D> &S,
+// ARENA (with LEAGUE): a.agent_member picks the agent seat's member of the pool behind W in the same way; its own instantiations.
+template <u32 P, u32 D, int OPP, bool LEAGUE = false, bool ARENA = false>
+AZ_FN void x_policy_rollout_body(const azx::XBatchDev &b, const PolicyWeights &Wk, const RolloutArgs &a, u32 id_base, PXShared<P, D> &S,
                                  PXOpp<D> *O = nullptr, u32 max_replies = 0)
 {
     using Sh = PXShape<P, D>;
@@ -721,6 +728,10 @@ AZ_FN void x_policy_rollout_body(const azx::XBatchDev &b, const PolicyWeights &W
     const u32 gic = live ? gi : n - 1u;
     u64 counter = a.counter;
     if (a.counter_dev) counter += a.counter_dev[0];
+    static_assert(!ARENA || (OPP == 2 && LEAGUE), "the arena is the league kernel with a pool behind the agent seat");
+    PolicyWeights Wm = Wk;                               // (ARENA: the workgroup's agent, a base offset per array chosen once, wave-uniform)
+    if constexpr (ARENA) Wm = league_member<IN, NA>(Wk, arena_agent_of_block(a));
+    const PolicyWeights &W = ARENA ? Wm : Wk;
     for (u32 i = tid; i < (u32)PF_HID; i += 64u * PR2_WAVES) S.w2c[i] = W.w2c[i];
     for (u32 i = tid; i < (u32)PF_H2; i += 64u * PR2_WAVES) S.b1[i] = W.b1[i];
     for (u32 i = tid; i < NA; i += 64u * PR2_WAVES) S.b2a[i] = W.b2a[i];
@@ -1110,11 +1121,12 @@ __global__ void __launch_bounds__(64 * PR2_WAVES) azul_x_policy_rollout_kernel(a
 // ... with a NETWORK opponent (azul_batch_mp_policy_rollout_vs; OPP 2 of x_policy_rollout_body): the reply rounds inside the window, the
 // opponent's biases and the games' reply-loop state in LDS next to PXShared.  LEAGUE (azul_batch_mp_policy_rollout_league): a pool of opponents
 // behind a.Wopp, one member per workgroup (RolloutArgs::opp_member)
-template <u32 P, u32 D, bool LEAGUE = false>
+// ARENA (azul_batch_mp_policy_rollout_arena, <P, D, true, true>): the agent seat is a member of the pool behind W too (RolloutArgs::agent_member)
+template <u32 P, u32 D, bool LEAGUE = false, bool ARENA = false>
 __global__ void __launch_bounds__(64 * PR2_WAVES) azul_x_policy_rollout_vs_kernel(azx::XBatchDev b, PolicyWeights W, RolloutArgs a, u32 id_base,
                                                                                    u32 max_replies)
 {
     __shared__ PXShared<P, D> S;
     __shared__ PXOpp<D> O;
-    x_policy_rollout_body<P, D, 2, LEAGUE>(b, W, a, id_base, S, &O, max_replies);
+    x_policy_rollout_body<P, D, 2, LEAGUE, ARENA>(b, W, a, id_base, S, &O, max_replies);
 }

@@ -532,6 +532,32 @@ int azul_batch_mp_policy_rollout_league(azul_batch_t *b, int n_steps, const azul
  * copies back.  AZUL_ERR_INVALID: a NULL pointer, n_games < 1, pool_size outside 1..255. */
 int azul_league_tally(const uint64_t *episodes_dev, const double *stat_sums_dev, uint64_t *mark_episodes_dev, double *mark_sums_dev,
                       const uint8_t *member_dev, int n_games, int pool_size, double *results_dev, void *stream);
+/* ---- an ARENA: round-robin matches of a pool of nets inside the window kernels ---------------------------------------------------------
+ * The league entries with a pool member in the AGENT seat too: group i (games 16 i .. 16 i + 15, the last group may be ragged) is played
+ * by agent = member agent_member_dev[i] against opponent = member opp_member_dev[i] of ONE pool, stacked as the league's pool is.  All six
+ * arrays of every member must be non-NULL here: the agent's critic (w2c, b2c) is read.  Both arrays are uint8 [ceil(N / 16)] on the
+ * device, read once per workgroup at launch; a value >= pool_size is read as pool_size - 1, so the kernel never reads outside the pool.
+ * Contract: for the games of a group assigned (a, o), every output, record, MT19937 stream, counter and trace is bit-identical to
+ * azul_batch_policy_rollout_vs / azul_batch_mp_policy_rollout_vs with agent = member a and opponent = member o on the same batch, keys
+ * and counters -- a game's trajectory is keyed by its global id and does not depend on what its neighbours play.  No allocation and no
+ * host synchronisation.  AZUL_ERR_INVALID before any launch: everything _vs refuses (a wide batch for the two-player entry and the reverse
+ * included), pool_size outside 1..255, a NULL pool, agent_member_dev or opp_member_dev. */
+int azul_batch_policy_rollout_arena(azul_batch_t *b, int n_steps, const azul_net_weights_t *pool, int pool_size, const uint8_t *agent_member_dev,
+                                    const uint8_t *opp_member_dev, int num_inputs, int hidden_size, int num_actions, uint64_t seed,
+                                    uint64_t opponent_seed, uint64_t counter, uint64_t *counter_dev, const azul_rollout_buffers_t *out, float gamma,
+                                    void *stream);
+int azul_batch_mp_policy_rollout_arena(azul_batch_t *b, int n_steps, const azul_net_weights_t *pool, int pool_size, const uint8_t *agent_member_dev,
+                                       const uint8_t *opp_member_dev, int num_inputs, int hidden_size, int num_actions, uint64_t seed,
+                                       uint64_t opponent_seed, uint64_t counter, uint64_t *counter_dev, int max_replies,
+                                       const azul_rollout_buffers_t *out, float gamma, void *stream);
+/* azul_league_tally for ORDERED PAIRS: results_dev is double [pool_size][pool_size][11]; cell [a][o] gains episodes - mark_episodes and
+ * the ten stat_sums - mark_sums of the games whose group is assigned agent a, opponent o (both bytes clamped as above).  Within a cell
+ * the games are added in ascending order -- plain fp64 additions in one fixed order, no atomics: the same bits on every run
+ * (percent_first_player is not a whole number, so the order is part of the result) -- and then the marks move up.  A cell whose pair has
+ * no group is not written.  No host synchronisation.  AZUL_ERR_INVALID: a NULL pointer, n_games < 1, pool_size outside 1..255. */
+int azul_arena_tally(const uint64_t *episodes_dev, const double *stat_sums_dev, uint64_t *mark_episodes_dev, double *mark_sums_dev,
+                     const uint8_t *agent_member_dev, const uint8_t *opp_member_dev, int n_games, int pool_size, double *results_dev,
+                     void *stream);
 /* The same protocol one launch per cut, for opponents evaluated OUTSIDE the library (any network as PyTorch modules, or azul_policy_forward
  * on a second weight set): GameRunner.step / reset are cut at their opponent_move() calls.  pending_dev (uint8 [N], in / out) holds per
  * game 0 = nothing owed (the agent's next decision), 1 = an opponent_move() is owed inside GameRunner.step's loop (game_runner.py:46-47),
