@@ -12,19 +12,18 @@ cut-off abandons in a slot tends to be a long one (a renewal-reward argument: th
 than into a short one).  Only finished episodes are booked, so wins / episodes of a cell converges to the per-episode win rate only as
 the episodes per slot grow; with few episodes per slot it leans towards the outcomes of short episodes.
 """
-import ctypes as C
-
 import numpy as np
 import torch
 
 from . import _lib as L
 from .batch import batch_shape, parse_ext_rules
+from .pool import checked_seats
 from .records import STAT_KEYS
-from .rollout import PolicyRollout, _layer_sizes, _p
+from .rollout import PolicyRollout, _layer_sizes
 
 GROUP = L.LEAGUE_GROUP_GAMES
 _WIN = STAT_KEYS.index("win_percent")
-_ENTRIES = {False: "azul_batch_policy_rollout_arena", True: "azul_batch_mp_policy_rollout_arena"}
+_PAIRS = ("pairs are", "[parts][ceil(h / 16)][2]", "pairs name")        # checked_seats' words for an arena's seats
 
 
 def round_robin_pairs(K, groups, round, mirror=False):
@@ -92,8 +91,8 @@ class Arena(PolicyRollout):
         Arena(nets, n_games=4096, parts=1, rules=..., players=2, window=32, seed_base=0, sample_seed=0x5EED, opponent_seed=None,
               selection="Distribution" | "Max", mirror=False, move_limit=0, device=None, pairs=None)
 
-    Built on PolicyRollout's league: the stacked pool (all six arrays of every member; it serves both seats), the openings at construction
-    on the per-cut path, the trajectory buffers, the parts and their streams.  Window kernels only: two-player batches need
+    Built on PolicyRollout's league: the stacked pool (pool.NetPool: all six arrays of every member; it serves both seats), the openings at
+    construction on the per-cut path, the trajectory buffers, the window launch, the parts and their streams.  Window kernels only: two-player batches need
     ActorCritic(136, 180, hidden 180), wide batches (`players` = 3 / 4 or extended rules) ActorCritic(obs_size, num_actions, hidden 180)
     of the batch; anything else raises ValueError before anything is allocated.  `selection` applies to both seats.  `pairs`: the first
     pairing, an int array [parts][G][2] (default: round 0 of round_robin_pairs over the parts' groups, G = ceil(n_games / parts / 16)).
@@ -122,66 +121,25 @@ class Arena(PolicyRollout):
         K, G = len(nets), (int(n_games) // int(parts) + GROUP - 1) // GROUP
         self.mirror = bool(mirror)
         first = round_robin_pairs(K, int(parts) * G, 0, self.mirror).reshape(int(parts), G, 2) if pairs is None else \
-            self._checked_pairs(pairs, (int(parts), G, 2), K)
-        self._pairs_host = np.ascontiguousarray(first, dtype=np.uint8)
+            checked_seats(pairs, (int(parts), G, 2), K, *_PAIRS)
         self.schedule_round = 0                                # the next round play_schedule plays
         sw = dict(fused_wide=True, fused_opponent=True) if wide else dict(persistent=True)
         super().__init__(nets[0], n_games=int(n_games), parts=int(parts), rules=rules, seed_base=seed_base, device=device, window=window,
                          use_graph=False, sample_seed=sample_seed, opponent=nets, action_selection=selection, opponent_selection=selection,
-                         opponent_seed=opponent_seed, move_limit=move_limit, players=int(players), **sw)
-        assert self.window_entry in ("azul_batch_policy_rollout_league", "azul_batch_mp_policy_rollout_league")
-        self.arena_entry = _ENTRIES[self.wide]
+                         opponent_seed=opponent_seed, move_limit=move_limit, players=int(players), _pairs=first, **sw)
+        self.arena_entry = self.window_entry                   # azul_batch_policy_rollout_arena / azul_batch_mp_policy_rollout_arena
 
-    @staticmethod
-    def _checked_pairs(pairs, shape, K):
-        a = np.asarray(pairs)
-        if a.shape != shape or a.dtype.kind not in "iu":
-            raise ValueError("the pairs are an int array of shape [parts][ceil(h / 16)][2] = %s, got %s %s" % (shape, a.dtype, a.shape))
-        if a.size and (int(a.min()) < 0 or int(a.max()) >= K):
-            raise ValueError("the pairs name pool members 0..%d, got values in %d..%d" % (K - 1, int(a.min()), int(a.max())))
-        return a
-
-    # ---- PolicyRollout's pieces --------------------------------------------------------------------------------------------------------
-    def _stage_weights(self, kweights):
-        """The league's stacked pool, then the first pairing in place of the league's default assignment -- before the parts open their
-        games, so that the openings at construction are the first opponents' -- and the per-pair results."""
-        super()._stage_weights(None)
-        K = self._pool_size
-        self._assign_host = np.ascontiguousarray(self._pairs_host[:, :, 1])
-        self._assign = torch.from_numpy(self._assign_host.copy()).to(self.device)
-        self._agent_assign = torch.from_numpy(np.ascontiguousarray(self._pairs_host[:, :, 0])).to(self.device)
-        self._ar_results = torch.zeros(self.parts, K, K, 1 + L.NUM_STATS, dtype=torch.float64, device=self.device)
-
-    def _window_kernel(self, p, gamma):
-        """The whole window of part p in one launch of the arena entry: the pool serves both seats, a pair of bytes per group."""
-        env, w, tr = self.envs[p], self.work[p], self.traj[p]
-        out = self._buffers(tr, w, tr["returns"].data_ptr())
-        pool = L.NetWeights(*[getattr(self, "o" + k).data_ptr() for k in self._OPP_ARRAYS])
-        args = [env._h, self.T, C.byref(pool), self._pool_size, _p(self._agent_assign[p]), _p(self._assign[p]), self.obs_size, self.H,
-                self.num_actions, self.sample_seed, self.opponent_seed, 0, _p(w["counter"])]
-        if self.wide:
-            args.append(int(self.MAX_REPLY_ROUNDS))
-        L.check(getattr(L.lib, self.arena_entry)(*args, C.byref(out), C.c_float(gamma),
-                                                 C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
-
-    def _not_here(self, *a, **k):
+    def _need_league(self):      # PolicyRollout's league methods and set_opponent open with this: an arena's seats are pairs, its results per pair
         raise ValueError("this is an arena: pairs() / set_pairs(), set_member() and results() are its methods")
-
-    set_assignment = set_opponent = league_results = reset_member_results = _not_here
 
     # ---- the arena ---------------------------------------------------------------------------------------------------------------------
     def pairs(self):
         """The (agent, opponent) pair of every 16-game group: an int array [parts][G][2] (a host copy)."""
-        return self._pairs_host.astype(np.int64)
+        return self.pool.seats_host.astype(np.int64)
 
     def set_member(self, i, net_or_state_dict):
         """Install the weights of pool member i in place (both seats read the one pool)."""
-        self.set_pool_member(i, net_or_state_dict)
-
-    def _install_pairs(self, p):
-        self._agent_assign[p].copy_(torch.from_numpy(np.ascontiguousarray(self._pairs_host[p, :, 0])).to(self.device))
-        self._assign[p].copy_(torch.from_numpy(self._assign_host[p]).to(self.device))
-        self.work[p]["game_member"].copy_(self._assign[p].to(torch.int64).repeat_interleave(GROUP)[:self.h])
+        self.pool.set_member(i, net_or_state_dict)
 
     def set_pairs(self, pairs):
         """Pair the groups anew: an int array [parts][G][2] of pool members (agent, opponent), refused on the host for a wrong shape or a
@@ -189,15 +147,12 @@ class Arena(PolicyRollout):
         are installed in place on the parts' streams and EVERY game is restarted -- GameRunner.reset() and the new opponents' openings, on
         the per-cut path of the construction.  Every booked episode is therefore played from its first move to its last by one pair; the
         episodes abandoned in flight are never booked and the restart does not count as an episode."""
-        a = self._checked_pairs(pairs, self._pairs_host.shape, self._pool_size)
-        self._arena_tally()
-        self._pairs_host = np.ascontiguousarray(a, dtype=np.uint8)
-        self._assign_host = np.ascontiguousarray(self._pairs_host[:, :, 1])
-        cur = torch.cuda.current_stream(self.device)
+        a = checked_seats(pairs, self.pool.seats_host.shape, self.pool.size, *_PAIRS)
+        for s in self.streams:
+            s.wait_stream(torch.cuda.current_stream(self.device))
+        self.pool.install(a)
         for p in range(self.parts):
-            self.streams[p].wait_stream(cur)
             with torch.cuda.stream(self.streams[p]):
-                self._install_pairs(p)
                 self._net_reset(p)
                 t = self.traj[p]
                 self.envs[p].observe_all(0, t["obs"][self.T], t["mask"][self.T], t["player"][self.T])
@@ -211,33 +166,20 @@ class Arena(PolicyRollout):
     def play_schedule(self, windows_per_round, rounds=None):
         """Round after round: set_pairs(round_robin_pairs(K, groups, r, mirror)) for the next schedule round r, then `windows_per_round`
         windows.  `rounds` defaults to one full cycle (every pair played)."""
-        G = self._pairs_host.shape[1]
+        K, G = self.pool.size, self.pool.seats_host.shape[1]
         total = self.parts * G
-        n = rounds_per_cycle(self._pool_size, total, self.mirror) if rounds is None else int(rounds)
+        n = rounds_per_cycle(K, total, self.mirror) if rounds is None else int(rounds)
         for i in range(n):
-            self.set_pairs(round_robin_pairs(self._pool_size, total, self.schedule_round, self.mirror).reshape(self.parts, G, 2))
+            self.set_pairs(round_robin_pairs(K, total, self.schedule_round, self.mirror).reshape(self.parts, G, 2))
             self.schedule_round += 1
             self.play(windows_per_round)
-
-    def _arena_tally(self):
-        """azul_arena_tally for every part on its stream: what each pair's groups finished since the marks goes to the part's results."""
-        for p, env in enumerate(self.envs):
-            with torch.cuda.stream(self.streams[p]):
-                c, mk = env.counters_dev(), self._lg_marks[p]
-                L.check(L.lib.azul_arena_tally(_p(c["episodes"]), _p(c["stat_sums"]), _p(mk["episodes"]), _p(mk["stat_sums"]),
-                                               _p(self._agent_assign[p]), _p(self._assign[p]), self.h, self._pool_size,
-                                               _p(self._ar_results[p]), C.c_void_p(self.streams[p].cuda_stream)))
 
     def results(self, reset=False):
         """Per ordered pair what its groups finished since construction (or the last reset): {"episodes": int [K][K], "wins": [K][K] (the
         win_percent sums: episodes the agent seat won), "mean": {key: [K][K]} for the ten STAT_KEYS}; wins and means of a cell without
         episodes are NaN.  Reduced on the device in a fixed order: K x K x 11 doubles per part cross to the host (parts added in part
         order).  reset=True zeroes the results behind the read."""
-        self._arena_tally()
-        self.synchronize()
-        tot = self._ar_results.cpu().numpy().sum(axis=0)
-        if reset:
-            self._ar_results.zero_()
+        tot = self.pool.totals(reset)
         ep = tot[:, :, 0]
         has = ep > 0
         div = np.where(has, ep, 1.0)
@@ -251,27 +193,15 @@ class Arena(PolicyRollout):
 
     def state(self):
         """What a checkpoint carries of the arena besides the members' weights (host copies): the pairs, the per-pair results, the marks and
-        the per-game counters they refer to (league_state's reasons), the schedule round, and per part the games -- records, MT19937
+        the per-game counters they refer to (NetPool.state's reasons), the schedule round, and per part the games -- records, MT19937
         streams, the Philox step counter."""
-        st = self.league_state()
-        st.update(pairs=self._pairs_host.copy(), arena_results=self._ar_results.cpu(), schedule_round=self.schedule_round,
-                  windows_played=self.windows_played, games=[])
-        for p, env in enumerate(self.envs):
-            mt, pos = env.get_rng_range()
-            st["games"].append({"records": np.asarray(env.get_records()).copy(), "mt": np.asarray(mt).copy(), "pos": np.asarray(pos).copy(),
-                                "counter": self.work[p]["counter"].cpu().numpy().copy()})
-        return st
+        st = self.pool.state()
+        return dict(st, pairs=self.pool.seats_host.copy(), arena_results=st.pop("results"), schedule_round=self.schedule_round,
+                    windows_played=self.windows_played, games=self.games_state())
 
     def load_state(self, st):
-        self._checked_pairs(st["pairs"], self._pairs_host.shape, self._pool_size)
-        self._pairs_host = np.ascontiguousarray(st["pairs"], dtype=np.uint8)
-        self.load_league_state(st)
-        self._agent_assign.copy_(torch.from_numpy(np.ascontiguousarray(self._pairs_host[:, :, 0])))
-        self._ar_results.copy_(st["arena_results"])
+        a = checked_seats(st["pairs"], self.pool.seats_host.shape, self.pool.size, *_PAIRS)
+        self.pool.load_state(a, st["arena_results"], st["marks"], st["counters"])
         self.schedule_round, self.windows_played = int(st["schedule_round"]), int(st["windows_played"])
-        for p, env in enumerate(self.envs):
-            g = st["games"][p]
-            env.set_records(g["records"])
-            env.set_rng_range(g["mt"], g["pos"])
-            self.work[p]["counter"].copy_(torch.from_numpy(g["counter"]))
+        self.load_games_state(st["games"])
         torch.cuda.synchronize(self.device)

@@ -471,57 +471,30 @@ __device__ __forceinline__ u32 arena_agent_of_block(const RolloutArgs &a)
     return (u32)__builtin_amdgcn_readfirstlane((int)(m < top ? m : top));
 }
 
-// ---- league book-keeping: per pool member, what its groups' games finished since the marks (azul_league_tally) -------------------------
-// One workgroup (one wave) per member m, lane j < 11 owns column j of results[m] (0: episodes, 1..10: the ten statistic sums).  The lane
-// walks the 16-game groups in ascending order and, for the groups assigned to m (values >= K read as K - 1, as the rollout kernels read
-// them), adds counter - mark game by game in ascending order: plain fp64 additions in one fixed order, no atomics -- the same bits on every
-// run.  Then it moves the mark up.  Every game belongs to exactly one member, so no two workgroups touch the same mark.
+// ---- pool book-keeping: what the games of the 16-game groups finished since the marks (azul_league_tally, azul_arena_tally) -------------
+// One body for both: a ROW is a pool member -- the opponent's for the league (results [K][11]: one cell per row), the agent's for the
+// arena (results [K][K][11]: cell [a][o], `col_member` the opponents' bytes).  One workgroup (one wave) per row, lane j < 11 owns column
+// j of the row's cells (0: episodes, 1..10: the ten statistic sums).  The lane walks the groups in ascending order; for a group of its
+// row (bytes >= K read as K - 1, as the rollout kernels read them) it takes the cell's value, adds counter - mark game by game in
+// ascending order and puts the value back -- so within a cell the games are added in ascending order, plain fp64 additions in one fixed
+// order, no atomics: the same bits on every run.  Then the mark moves up.  A cell without a group is not written; every game belongs to
+// exactly one row, so no two workgroups touch the same mark.
 constexpr u32 LEAGUE_COLS = 11;
-__global__ void __launch_bounds__(64) azul_league_tally_kernel(const u64 *episodes, const double *stat_sums, u64 *mark_episodes, double *mark_sums,
-                                                               const uint8_t *opp_member, u32 n, u32 K, double *results)
+__device__ __forceinline__ void pool_tally_row(const u64 *episodes, const double *stat_sums, u64 *mark_episodes, double *mark_sums,
+                                               const uint8_t *row_member, const uint8_t *col_member, u32 n, u32 K, double *results)
 {
-    const u32 m = blockIdx.x, j = threadIdx.x;
-    if (m >= K || j >= LEAGUE_COLS) return;
+    const u32 row = blockIdx.x, j = threadIdx.x;
+    if (row >= K || j >= LEAGUE_COLS) return;
     const u32 groups = (n + (u32)PF_GAMES - 1u) / (u32)PF_GAMES;
-    double acc = results[(size_t)m * LEAGUE_COLS + j];
-    bool any = false;
     for (u32 grp = 0; grp < groups; grp++) {
-        const u32 mg = (u32)opp_member[grp];
-        if ((mg < K - 1u ? mg : K - 1u) != m) continue;
-        any = true;
-        const u32 g1 = (grp + 1u) * (u32)PF_GAMES < n ? (grp + 1u) * (u32)PF_GAMES : n;
-        for (u32 g = grp * (u32)PF_GAMES; g < g1; g++) {
-            if (j == 0u) {
-                const u64 e = episodes[g];
-                acc += (double)(e - mark_episodes[g]);
-                mark_episodes[g] = e;
-            } else {
-                const size_t i = (size_t)g * (LEAGUE_COLS - 1u) + (j - 1u);
-                const double s = stat_sums[i];
-                acc += s - mark_sums[i];
-                mark_sums[i] = s;
-            }
+        const u32 rg = (u32)row_member[grp];
+        if ((rg < K - 1u ? rg : K - 1u) != row) continue;
+        size_t c = row;                                          // the cell: the row itself, or [row][the group's opponent]
+        if (col_member) {
+            const u32 cg = (u32)col_member[grp];
+            c = (size_t)row * K + (cg < K - 1u ? cg : K - 1u);
         }
-    }
-    if (any) results[(size_t)m * LEAGUE_COLS + j] = acc;      // (a member without a group: its row is not written)
-}
-
-// ---- arena book-keeping: azul_league_tally_kernel for ORDERED PAIRS (azul_arena_tally) ---------------------------------------------------
-// results [K][K][11]: cell [a][o] gains what the games of the groups assigned agent a, opponent o finished since the marks.  One workgroup
-// (one wave) per agent member a, lane j < 11 owns column j of every cell of row a.  The lane walks the groups in ascending order; for a
-// group of its row it takes the cell's value, adds counter - mark game by game in ascending order and puts the value back -- so within a
-// cell the games are added in ascending order, plain fp64 additions, no atomics: the same bits on every run.  Then the mark moves up.
-// Both bytes are clamped as the rollout kernels clamp them.  A cell whose pair has no group is not written; every game belongs to one row.
-__global__ void __launch_bounds__(64) azul_arena_tally_kernel(const u64 *episodes, const double *stat_sums, u64 *mark_episodes, double *mark_sums,
-                                                              const uint8_t *agent_member, const uint8_t *opp_member, u32 n, u32 K, double *results)
-{
-    const u32 am = blockIdx.x, j = threadIdx.x;
-    if (am >= K || j >= LEAGUE_COLS) return;
-    const u32 groups = (n + (u32)PF_GAMES - 1u) / (u32)PF_GAMES;
-    for (u32 grp = 0; grp < groups; grp++) {
-        const u32 ag = (u32)agent_member[grp], og = (u32)opp_member[grp];
-        if ((ag < K - 1u ? ag : K - 1u) != am) continue;
-        double *cell = results + ((size_t)am * K + (og < K - 1u ? og : K - 1u)) * LEAGUE_COLS + j;
+        double *cell = results + c * LEAGUE_COLS + j;
         double acc = *cell;
         const u32 g1 = (grp + 1u) * (u32)PF_GAMES < n ? (grp + 1u) * (u32)PF_GAMES : n;
         for (u32 g = grp * (u32)PF_GAMES; g < g1; g++) {
@@ -538,4 +511,16 @@ __global__ void __launch_bounds__(64) azul_arena_tally_kernel(const u64 *episode
         }
         *cell = acc;
     }
+}
+
+__global__ void __launch_bounds__(64) azul_league_tally_kernel(const u64 *episodes, const double *stat_sums, u64 *mark_episodes, double *mark_sums,
+                                                               const uint8_t *opp_member, u32 n, u32 K, double *results)
+{
+    pool_tally_row(episodes, stat_sums, mark_episodes, mark_sums, opp_member, nullptr, n, K, results);
+}
+
+__global__ void __launch_bounds__(64) azul_arena_tally_kernel(const u64 *episodes, const double *stat_sums, u64 *mark_episodes, double *mark_sums,
+                                                              const uint8_t *agent_member, const uint8_t *opp_member, u32 n, u32 K, double *results)
+{
+    pool_tally_row(episodes, stat_sums, mark_episodes, mark_sums, agent_member, opp_member, n, K, results);
 }

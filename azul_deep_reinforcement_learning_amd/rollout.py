@@ -28,10 +28,7 @@ import torch
 from . import _lib as L
 from .batch import BatchedAzul, batch_shape, parse_ext_rules
 from .multiplayer import MultiplayerAzul
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr())
+from .pool import NetPool, _OPP_ARRAYS, _kmajor, _p, checked_seats
 
 
 # azul_batch_policy_rollout_returns takes what the two launch structs hold one by one: all weights, and the buffers obs .. returns
@@ -72,7 +69,7 @@ class PolicyRollout:
                  device=None, window=32, use_graph=True, fused_head=True, sample_seed=0x5EED, opponent=None, fused_mlp=True, persistent=False,
                  action_selection="Distribution", kweights=None, game_id_base=None, ring=1, opponent_selection="Distribution",
                  opponent_seed=None, opponent_trace=0, move_limit=0, players=2, fused_wide=False, fused_opponent=False, wide_ring=1,
-                 fused_seats=False, gae_lambda=None, bootstrap_tail=False):
+                 fused_seats=False, gae_lambda=None, bootstrap_tail=False, _pairs=None):
         """Who answers GameRunner's opponent_move(), and what plays a window.  "window kernel": ONE launch per window and part (_WINDOW_KERNELS),
         asked for by the switch in brackets; "per move" / "per cut": the launches of _window_moves.  Two-player reference batches (players=2, no
         extended-rule key in `rules`) and wide batches (`players` = 3 / 4 or extended rules) admit:
@@ -194,8 +191,10 @@ class PolicyRollout:
         self.game_id_base = int(seed_base if game_id_base is None else game_id_base) & 0xFFFFFFFF
         self.opponent_seed = L.POLICY_ARGMAX if opponent_selection == "Max" else \
             (int(opponent_seed) if opponent_seed is not None else (int(sample_seed) ^ 0x4F50504F4E454E54)) & 0xFFFFFFFFFFFFFFFF
-        self._stage_weights(kweights)
+        if _pairs is not None:       # arena.Arena's first seats, checked there: the league's row decided, its entry's _arena twin is launched
+            self.window_entry = self.window_entry.replace("_league", "_arena")
         self.envs, self.streams, self.work, self.traj, self.graphs, self.rings = [], [], [], [], [], []
+        self._stage_weights(kweights, _pairs)
         for p in range(parts):
             self._alloc_part(p, rules, seed_base, move_limit)
         torch.cuda.synchronize(self.device)
@@ -334,9 +333,10 @@ class PolicyRollout:
         # one launch per window needs no graph; reply rounds are data-dependent (a capture that fails clears the flag again)
         self.use_graph = bool(use_graph and self.window_entry is None and not self.cut)
 
-    def _stage_weights(self, kweights):
+    def _stage_weights(self, kweights, seats=None):
         """The k-major weight copies the kernels and GEMMs read.  kweights: tensors owned by someone else (A2CLearner.kweights(): views of
-        its flat master copy, kept current by the optimiser kernel) -- then nothing is copied here and refresh_weights() has nothing to do."""
+        its flat master copy, kept current by the optimiser kernel) -- then nothing is copied here and refresh_weights() has nothing to do.
+        A network opponent's pool is seated here, before the parts open their games (`seats`: an arena's first pairs; a league: the default)."""
         if self.wide and self.window_entry is None:
             kweights = None                                # (the PyTorch-GEMM path keeps its own copies)
         self._external_kweights = kweights is not None
@@ -347,20 +347,13 @@ class PolicyRollout:
         self.refresh_weights()
         if self.opponent == "net":
             self.opp_policy = self.opp_policy.to(self.device).eval()
-            self.set_opponent(self.opp_policy)
+            self.pool = NetPool([self.opp_policy], self.device, self.envs, self.streams)
         elif self.league:
-            # the pool STACKED array by array ([K][...] each, member m at m * size: include/azul_hip.h), the default assignment group i ->
-            # member i % K for every part, and the per-member results with their per-game marks (azul_league_tally)
-            K, G = len(self.opp_pool), (self.h + L.LEAGUE_GROUP_GAMES - 1) // L.LEAGUE_GROUP_GAMES
-            staged = [dict(self._kmajor(m.state_dict().__getitem__, self._OPP_ARRAYS)) for m in self.opp_pool]
-            for k in self._OPP_ARRAYS:
-                setattr(self, "o" + k, torch.stack([st[k] for st in staged]).contiguous())
+            if seats is None:                                  # the default assignment: group i -> member i % K, for every part
+                G = (self.h + L.LEAGUE_GROUP_GAMES - 1) // L.LEAGUE_GROUP_GAMES
+                seats = (torch.arange(G, dtype=torch.int64) % len(self.opp_pool)).repeat(self.parts, 1).numpy()
+            self.pool = NetPool(self.opp_pool, self.device, self.envs, self.streams, seats, self.h)
             self.opp_pool = None                               # (the weights are copied: the modules are not kept)
-            self._pool_size = K
-            self._assign_host = (torch.arange(G, dtype=torch.int64) % K).to(torch.uint8).repeat(self.parts, 1).numpy()
-            self._assign = torch.from_numpy(self._assign_host.copy()).to(self.device)
-            self._lg_results = torch.zeros(self.parts, K, 1 + L.NUM_STATS, dtype=torch.float64, device=self.device)
-            self._lg_marks = []
 
     def _alloc_part(self, p, rules, seed_base, move_limit):
         """Part p: its games (opened as GameRunner opens them), its stream, its trajectory ring and work buffers."""
@@ -401,16 +394,14 @@ class PolicyRollout:
             if self.wide and self.netopp:                      # the opponent's actor half as PyTorch GEMMs (its own hidden size)
                 w["opp_hidden"] = torch.zeros(h, self.ob1.shape[-1] // 2, device=d)
                 w["opp_logits"] = torch.zeros(h, env.num_actions, device=d)
-            if self.league:                                    # per game its group's member; one member's answers before they are taken
-                w["game_member"] = self._assign[p].to(torch.int64).repeat_interleave(L.LEAGUE_GROUP_GAMES)[:h].contiguous()
+            if self.league:                                    # one member's answers before they are taken
                 w["lg_action"], w["lg_logp"] = torch.zeros(h, dtype=torch.int32, device=d), torch.zeros(h, device=d)
-                c = env.counters_dev()
-                self._lg_marks.append({"episodes": c["episodes"].clone(), "stat_sums": c["stat_sums"].clone()})
         if self.bootstrap_tail:                                # the critic's value of slot T, and the hidden layer it is formed from
             w["tail_hidden"], w["tail_value"] = torch.zeros(h, self.H, device=d), torch.zeros(h, 1, device=d)
             t["tail_value"] = w["tail_value"].view(h)
         self.traj.append(t)
         self.work.append(w)
+        self.streams[p].wait_stream(torch.cuda.current_stream(d))      # (the buffers above and the pool's seats were written there)
         with torch.cuda.stream(self.streams[p]):
             if self.cut:
                 self._net_reset(p)                             # GameRunner.reset(): the network / greedy opponent opens when it starts
@@ -428,43 +419,30 @@ class PolicyRollout:
     def _persp(self):
         return 0 if self.opponent is not None else L.PERSP_CURRENT     # with any opponent NNRunner observes with perspective 0 (game_runner.py:56)
 
-    _OPP_ARRAYS = ("w1t", "b1", "w2c", "b2c", "w2a_t", "b2a")       # azul_net_weights_t, in its order
+    _OPP_ARRAYS, _kmajor = _OPP_ARRAYS, staticmethod(_kmajor)      # (pool.py's; the opponent's arrays are the attributes o + name, below the class)
 
-    def _kmajor(self, get, names):
-        """[(name, tensor)]: the k-major copies `names` of the reference's four layers (`get`: parameter name -> tensor), contiguous."""
-        with torch.no_grad():
-            g = lambda k: get(k).detach().to(self.device, torch.float32)
-            build = {"w1t": lambda: torch.cat([g("critic_linear1.weight"), g("actor_linear1.weight")], dim=0).t(),
-                     "b1": lambda: torch.cat([g("critic_linear1.bias"), g("actor_linear1.bias")]),
-                     "w2c": lambda: g("critic_linear2.weight").reshape(-1), "w2c_t": lambda: g("critic_linear2.weight").t(),
-                     "b2c": lambda: g("critic_linear2.bias").reshape(-1),
-                     "w2a_t": lambda: g("actor_linear2.weight").t(), "b2a": lambda: g("actor_linear2.bias")}
-            return [(k, build[k]().contiguous()) for k in names]
-
-    def _stage(self, get, prefix, names):
-        """The k-major copies `names` as attributes prefix + name, updated IN PLACE once they exist: captured HIP graphs and whoever shares
+    def _stage(self, get, names):
+        """The policy's k-major copies `names` as attributes, updated IN PLACE once they exist: captured HIP graphs and whoever shares
         kweights() keep reading the same addresses."""
         with torch.no_grad():
-            for k, v in self._kmajor(get, names):
-                name = prefix + k
-                if hasattr(self, name):
-                    getattr(self, name).copy_(v)
+            for k, v in _kmajor(get, names, self.device):
+                if hasattr(self, k):
+                    getattr(self, k).copy_(v)
                 else:
-                    setattr(self, name, v.clone())
+                    setattr(self, k, v.clone())
 
     def set_opponent(self, policy_or_state_dict):
         """Install the network opponent's weights (k-major copies, updated IN PLACE): a module with the reference's four layers or its
         state_dict -- e.g. `ro.set_opponent(policy)` every so many updates trains against a frozen past self."""
-        sd = policy_or_state_dict.state_dict() if hasattr(policy_or_state_dict, "state_dict") else policy_or_state_dict
         if self.league:
+            self._need_league()                                # (an arena's own refusal)
             raise ValueError("this rollout plays a league: set_pool_member(i, ...) installs the weights of one member")
-        self._stage(sd.__getitem__, "o", self._OPP_ARRAYS)
+        if not self.netopp:
+            raise ValueError("this rollout has no network opponent (opponent=<module>)")
+        self.pool.set_member(0, policy_or_state_dict)
 
-    # ---- the league (opponent=[net0, net1, ...]) --------------------------------------------------------------------------------
-    @property
-    def pool_size(self):
-        """Members of the league's pool (0 without a league)."""
-        return self._pool_size if self.league else 0
+    # ---- the league (opponent=[net0, net1, ...]): a few lines each over the pool, whose seats are the assignment -----------------------
+    pool_size = property(lambda self: self.pool.size if self.league else 0, doc="Members of the league's pool (0 without a league).")
 
     def _need_league(self):
         if not self.league:
@@ -474,44 +452,19 @@ class PolicyRollout:
         """Install the weights of pool member i (its slice of the stacked k-major copies, updated IN PLACE like set_opponent): a module
         with the reference's four layers, of the pool's shape, or its state_dict."""
         self._need_league()
-        if not 0 <= int(i) < self._pool_size:
-            raise ValueError("pool member %r outside 0..%d" % (i, self._pool_size - 1))
-        sd = policy_or_state_dict.state_dict() if hasattr(policy_or_state_dict, "state_dict") else policy_or_state_dict
-        with torch.no_grad():
-            for k, v in self._kmajor(sd.__getitem__, self._OPP_ARRAYS):
-                getattr(self, "o" + k)[int(i)].copy_(v)
+        self.pool.set_member(i, policy_or_state_dict)
 
     def assignment(self):
         """The pool member of every 16-game group: a uint8 array [parts][ceil(h / 16)] (a host copy)."""
         self._need_league()
-        return self._assign_host.copy()
+        return self.pool.seats_host.copy()
 
     def set_assignment(self, members):
         """Assign the groups anew: an int array [parts][ceil(h / 16)] of pool members, refused if any value is >= pool_size.  The tally runs
         first, so that the episodes finished so far are booked to the members they were played against; then the array is copied IN PLACE
         on the parts' streams, behind the windows in flight."""
-        import numpy as np
         self._need_league()
-        a = np.asarray(members)
-        if a.shape != self._assign_host.shape or a.dtype.kind not in "iu":
-            raise ValueError("the assignment is an int array of shape [parts][ceil(h / 16)] = %s, got %s %s"
-                             % (self._assign_host.shape, a.dtype, a.shape))
-        if a.size and (int(a.min()) < 0 or int(a.max()) >= self._pool_size):
-            raise ValueError("the assignment names pool members 0..%d, got values in %d..%d" % (self._pool_size - 1, int(a.min()), int(a.max())))
-        self._league_tally()
-        self._assign_host = np.ascontiguousarray(a, dtype=np.uint8)
-        for p in range(self.parts):
-            with torch.cuda.stream(self.streams[p]):
-                self._assign[p].copy_(torch.from_numpy(self._assign_host[p]).to(self.device))
-                self.work[p]["game_member"].copy_(self._assign[p].to(torch.int64).repeat_interleave(L.LEAGUE_GROUP_GAMES)[:self.h])
-
-    def _league_tally(self):
-        """azul_league_tally for every part on its stream: what each member's groups finished since the marks goes to the part's results."""
-        for p, env in enumerate(self.envs):
-            with torch.cuda.stream(self.streams[p]):
-                c, mk = env.counters_dev(), self._lg_marks[p]
-                L.check(L.lib.azul_league_tally(_p(c["episodes"]), _p(c["stat_sums"]), _p(mk["episodes"]), _p(mk["stat_sums"]), _p(self._assign[p]),
-                                                self.h, self._pool_size, _p(self._lg_results[p]), C.c_void_p(self.streams[p].cuda_stream)))
+        self.pool.install(checked_seats(members, self.pool.seats_host.shape, self.pool.size, "assignment is", "[parts][ceil(h / 16)]", "assignment names"))
 
     def league_results(self, reset=False):
         """Per pool member what the games assigned to it finished since construction (or the last reset): a list of pool_size dicts with
@@ -519,68 +472,57 @@ class PolicyRollout:
         in a fixed order: pool_size x 11 doubles per part cross to the host.  reset=True zeroes the results behind the read."""
         from .records import STAT_KEYS
         self._need_league()
-        self._league_tally()
-        self.synchronize()
-        tot = self._lg_results.cpu().numpy().sum(axis=0)       # (parts added in part order)
-        if reset:
-            self._lg_results.zero_()
-        return [dict([("episodes", int(tot[m, 0]))] + [(k, float(tot[m, 1 + i]) / tot[m, 0] if tot[m, 0] else float("nan"))
-                                                       for i, k in enumerate(STAT_KEYS)]) for m in range(self._pool_size)]
+        return [dict([("episodes", int(row[0]))] + [(k, float(row[1 + i]) / row[0] if row[0] else float("nan")) for i, k in enumerate(STAT_KEYS)])
+                for row in self.pool.totals(reset)]
 
     def reset_member_results(self, i):
         """Zero the results of pool member i (what it finished so far is booked first and dropped with the rest)."""
         self._need_league()
-        self._league_tally()
+        self.pool.tally()
         for p in range(self.parts):
             with torch.cuda.stream(self.streams[p]):
-                self._lg_results[p, int(i)].zero_()
+                self.pool.results[p, int(i)].zero_()
 
     def league_state(self):
-        """What a checkpoint carries of the league besides the stacked weights: the assignment, the results, their marks and the per-game
-        counters the marks refer to (host copies).  The counters travel because one of the statistics (percent_first_player) is not a
-        whole number: the results are sums of counter - mark, and only the same counters give the same sums bit for bit."""
-        self._need_league()
-        self.synchronize()
-        return {"assignment": self._assign_host.copy(), "results": self._lg_results.cpu(),
-                "marks": [{k: v.cpu() for k, v in mk.items()} for mk in self._lg_marks],
-                "counters": [{k: v.cpu() for k, v in env.counters_dev().items() if k != "keys"} for env in self.envs]}
+        """What a checkpoint carries of the league besides the stacked weights (host copies): the assignment and NetPool.state()."""
+        return dict(assignment=self.assignment(), **self.pool.state())
 
     def load_league_state(self, st):
         self._need_league()
-        self.synchronize()
-        self._assign_host = st["assignment"].copy()
-        self._assign.copy_(torch.from_numpy(self._assign_host))
-        for p in range(self.parts):
-            self.work[p]["game_member"].copy_(self._assign[p].to(torch.int64).repeat_interleave(L.LEAGUE_GROUP_GAMES)[:self.h])
-            c = self.envs[p].counters_dev()                     # (zero-copy views of the batch's per-game counters)
-            for k, v in st["counters"][p].items():
-                c[k].copy_(v)
-            for k, v in st["marks"][p].items():
-                self._lg_marks[p][k].copy_(v)
-        self._lg_results.copy_(st["results"])
-        torch.cuda.synchronize(self.device)
+        self.pool.load_state(st["assignment"], st["results"], st["marks"], st["counters"])
+
+    def games_state(self):
+        """Per part the games as a checkpoint carries them (host copies): records, MT19937 streams (`mt`, `pos`), the Philox step counter."""
+        return [dict(zip(("mt", "pos"), env.get_rng_range()), records=env.get_records(), counter=w["counter"].cpu().numpy().copy())
+                for env, w in zip(self.envs, self.work)]
+
+    def load_games_state(self, games):
+        for env, w, g in zip(self.envs, self.work, games):
+            env.set_records(g["records"])
+            env.set_rng_range(g["mt"], g["pos"])
+            w["counter"].copy_(torch.from_numpy(g["counter"]))
 
     def _opp_forward(self, p, j, logp_out):
         """The opponent's get_a_output (agent.py:73-81) for the games of part p that owe an opponent_move(): forward_actor of its net on
         what net_step_* left in work["net"], reply j of the step sampled with Philox key opponent_seed + j at the step's counter."""
         w = self.work[p]
-        net, sc = w["net"], w["scratch_f"]
+        net = w["net"]
         if self.scripted:
             # the scripted opponent: the best move of every game that owes one, from the mover's perspective (azul_batch_score_moves /
             # azul_batch_mp_score_moves)
             self.envs[p].greedy_action(active=net["pending"], out=net["action"])
             return
         key = self.opponent_seed if self.opponent_seed == L.POLICY_ARGMAX else (self.opponent_seed + j) & 0xFFFFFFFFFFFFFFFF
-        if self.league:
-            # the forward once per member present in the part's assignment (all of the part's games through that member's weights), then per
-            # game the answer of its group's member: exact, because the head draws per row by the game's global id
-            for m in sorted(set(int(x) for x in self._assign_host[p])):
-                self._opp_forward_net(p, key, [getattr(self, "o" + k)[m] for k in self._OPP_ARRAYS], w["lg_action"], w["lg_logp"])
-                mine = w["game_member"] == m
-                torch.where(mine, w["lg_action"], net["action"], out=net["action"])
-                torch.where(mine, w["lg_logp"], logp_out, out=logp_out)
-            return
-        self._opp_forward_net(p, key, [getattr(self, "o" + k) for k in self._OPP_ARRAYS], net["action"], logp_out)
+        present = self.pool.present(p)
+        if len(present) == 1:                                  # a single opponent, or one member for the whole part: its answers are the answers
+            return self._opp_forward_net(p, key, self.pool.member(present[0]), net["action"], logp_out)
+        # the forward once per member present in the part's seats (all of the part's games through that member's weights), then per game
+        # the answer of its group's member: exact, because the head draws per row by the game's global id
+        for m in present:
+            self._opp_forward_net(p, key, self.pool.member(m), w["lg_action"], w["lg_logp"])
+            mine = self.pool.game_member[p] == m
+            torch.where(mine, w["lg_action"], net["action"], out=net["action"])
+            torch.where(mine, w["lg_logp"], logp_out, out=logp_out)
 
     def _opp_forward_net(self, p, key, weights, action_out, logp_out):
         """forward_actor + the sampling head of ONE opponent net (`weights`: its six k-major arrays) for all games of part p."""
@@ -645,18 +587,11 @@ class PolicyRollout:
         """(Re)build the fused first-layer weights from the policy's parameters -- call after every optimiser step.  The
         staging tensors are updated IN PLACE: a captured HIP graph keeps reading the same addresses."""
         if not self._external_kweights:
-            self._stage(self.policy.get_parameter, "", ("w1t", "b1", "w2c_t", "w2a_t", "w2c"))      # (the biases of layer 2 are read in place)
+            self._stage(self.policy.get_parameter, ("w1t", "b1", "w2c_t", "w2a_t", "w2c"))      # (the biases of layer 2 are read in place)
 
     def kweights(self):
         """The k-major weight copies (refresh_weights keeps them current): the learner's gradient kernel reads the same layouts."""
         return {"w1t": self.w1t, "b1": self.b1, "w2c": self.w2c, "w2a_t": self.w2a_t}
-
-    def _net_weights(self, opponent=False):
-        """azul_net_weights_t of the agent (the second layer's biases straight from the module) or of the network opponent."""
-        pol = self.policy
-        w = (self.ow1t, self.ob1, self.ow2c, self.ob2c, self.ow2a_t, self.ob2a) if opponent else \
-            (self.w1t, self.b1, self.w2c, pol.critic_linear2.bias, self.w2a_t, pol.actor_linear2.bias)
-        return L.NetWeights(*[x.data_ptr() for x in w])
 
     def _buffers(self, tr, w, returns):
         """azul_rollout_buffers_t of a window's views; the opponent fields only with a network / greedy opponent (the trace only when asked for)."""
@@ -742,15 +677,19 @@ class PolicyRollout:
         # (a ring, or a lambda-return: the scan below writes the returns)
         out = self._buffers(tr, w, tr["returns"].data_ptr() if self.ring == 1 and self.gae_lambda is None else None)
         vs, flat = self.netopp, self.window_entry == "azul_batch_policy_rollout_returns"
-        wa, wo = self._net_weights(), self._net_weights(opponent=True) if vs else None
+        seats = self.pool.seat_ptrs[p] if self.league else []                         # none: a single opponent; the opponent's: a league; both: an arena
         args = [env._h, T]
         if not self.cut:
             args.append(1 if self.opponent == "random" else 0)                  # opponent_random: the entries without reply rounds play both
-        args += _WEIGHT_FIELDS(wa) if flat else [C.byref(wa)]                   # (_returns takes the structs' pointers one by one)
+        if len(seats) < 2:                                                      # (an arena's agent is a pool member: no weights of its own)
+            pol = self.policy                                                   # (the second layer's biases straight from the module)
+            wa = L.NetWeights(*[x.data_ptr() for x in (self.w1t, self.b1, self.w2c, pol.critic_linear2.bias, self.w2a_t, pol.actor_linear2.bias)])
+            args += _WEIGHT_FIELDS(wa) if flat else [C.byref(wa)]               # (_returns takes the structs' pointers one by one)
         if vs:
+            wo = self.pool.weights()
             args.append(C.byref(wo))                                            # the reply rounds run on the opponent's weights
-        if self.league:
-            args += [self._pool_size, _p(self._assign[p])]                      # ... of the pool member each 16-game group is assigned
+        if seats:
+            args += [self.pool.size] + seats                                    # ... of the pool member each 16-game group is seated with
         args += [self.obs_size, self.H, self.num_actions, self.sample_seed]
         if vs:
             args.append(self.opponent_seed)
@@ -845,3 +784,7 @@ class PolicyRollout:
     def counters(self):
         c = [e.counters() for e in self.envs]
         return {"episodes": sum(int(x["episodes"].sum()) for x in c), "stuck": sum(int(x["stuck"].sum()) for x in c)}
+
+
+for _k in _OPP_ARRAYS:       # ow1t .. ob2a, array k of the network opponent: member 0's view for a single opponent, the stack [K][...] for a league
+    setattr(PolicyRollout, "o" + _k, property(lambda self, k=_k: self.pool.stacks[k] if self.league else self.pool.stacks[k][0]))

@@ -326,20 +326,16 @@ class BatchedTrainer:
         ro = self.rollout
         ro.synchronize()
         torch.cuda.synchronize(ro.device)
-        envs = []
-        for p, env in enumerate(ro.envs):
-            mt, pos = env.get_rng_range()
-            envs.append({"records": env.get_records(), "mt": mt, "pos": pos,
-                         "counter": ro.work[p]["counter"].cpu().numpy().copy(),
-                         "next_obs": ro.traj[p]["obs"][ro.T].cpu(), "next_mask": ro.traj[p]["mask"][ro.T].cpu(),
-                         "next_player": ro.traj[p]["player"][ro.T].cpu()})
+        envs = ro.games_state()                          # records, MT19937 streams, Philox step counters
+        for p, e in enumerate(envs):
+            e.update({"next_" + k: ro.traj[p][k][ro.T].cpu() for k in ("obs", "mask", "player")})
         ck = {"policy": ro.policy.state_dict(), "optimizer": self.learner.optimizer_state(), "envs": envs,
               "batch": self.batch, "n_games": ro.n, "parts": ro.parts, "window": ro.T, "game_id_base": ro.game_id_base,
               "windows_played": ro.windows_played, "ring": ro.ring, "ring_saved": bool(save_ring and ro.ring > 1)}
         if ro.league:                                    # the assignment, the results and their marks, the snapshot and redraw counts
             ck["league"] = dict(ro.league_state(), snapshots=getattr(self, "snapshots", 0), redraws=getattr(self, "redraws", 0))
         if ro.netopp:                                    # the network opponent's (frozen) weights, a league's stacked: a resumed run plays the same nets
-            ck["opponent"] = {k: getattr(ro, k).cpu() for k in ("ow1t", "ob1", "ow2c", "ob2c", "ow2a_t", "ob2a")}
+            ck["opponent"] = {"o" + k: getattr(ro, "o" + k).cpu() for k in ro._OPP_ARRAYS}
         if save_ring and ro.ring > 1:
             ck["ring_buffers"] = [{k: v.cpu() for k, v in rg.items()} for rg in ro.rings]
             ck["learner_ring"] = self.learner.ring_state()
@@ -361,14 +357,11 @@ class BatchedTrainer:
             if ro.use_graph:                                                # the id base is a launch argument baked into the captured graphs
                 ro.graphs = []
                 ro._capture(getattr(ro, "gamma", self.gamma))               # (its warm-up window advances the games: they are restored below)
-        for p, (env, e) in enumerate(zip(ro.envs, ck["envs"])):
-            env.set_id_base(ro.game_id_base + p * ro.h)
-            env.set_records(e["records"])
-            env.set_rng_range(e["mt"], e["pos"])
-            ro.work[p]["counter"].copy_(torch.from_numpy(e["counter"]))
-            ro.traj[p]["obs"][ro.T].copy_(e["next_obs"])
-            ro.traj[p]["mask"][ro.T].copy_(e["next_mask"])
-            ro.traj[p]["player"][ro.T].copy_(e["next_player"])
+        ro.load_games_state(ck["envs"])
+        for p, e in enumerate(ck["envs"]):
+            ro.envs[p].set_id_base(ro.game_id_base + p * ro.h)
+            for k in ("obs", "mask", "player"):
+                ro.traj[p][k][ro.T].copy_(e["next_" + k])
         # the trajectory ring and the books of the ring selection: restored when the file has them (the run then equals the
         # uninterrupted one), otherwise the learner's books restart with the next window (nothing recorded before this call -- by the
         # checkpointed run or by this trainer -- is ever selected: `pending` starts at the next window, whose selection only reads
