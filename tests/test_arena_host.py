@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from tests.hostcheck import hostcheck
+from tests.pool_tally_ref import arena_tally_ref as tally_ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRIES = ("azul_batch_policy_rollout_arena", "azul_batch_mp_policy_rollout_arena", "azul_arena_tally")
@@ -53,18 +54,6 @@ def load_tally():
 
 def ptr(a):
     return a.ctypes.data_as(C.c_void_p)
-
-
-def tally_ref(ep, ss, mark_ep, mark_ss, agent, opp, K, results):
-    """The stated order: per cell [a][o] the games of its groups in ascending order, one fp64 addition per game and column."""
-    results = results.copy()
-    for grp in range(len(agent)):
-        a, o = min(int(agent[grp]), K - 1), min(int(opp[grp]), K - 1)
-        for g in range(grp * GROUP, min(len(ep), (grp + 1) * GROUP)):
-            results[a, o, 0] = results[a, o, 0] + np.float64(int(ep[g]) - int(mark_ep[g]))
-            for j in range(10):
-                results[a, o, 1 + j] = results[a, o, 1 + j] + (ss[g, j] - mark_ss[g, j])
-    return results
 
 
 def test_arena_tally_kernel_matches_the_numpy_recount_bit_for_bit():

@@ -18,7 +18,7 @@ from azul_deep_reinforcement_learning_amd.multiplayer import MultiplayerAzul
 from azul_deep_reinforcement_learning_amd.policy import BatchedActorCritic
 from azul_deep_reinforcement_learning_amd.records import STAT_KEYS
 from azul_deep_reinforcement_learning_amd.rollout import PolicyRollout
-from tests.test_gpu_league import GROUP, RULES2, _eq_games, _eq_state, _net2, _play
+from tests.test_gpu_league import GROUP, RULES2, _eq_games, _eq_state, _net2, _play, _wide
 from tests.test_gpu_mp_fused_rollout import SHAPES, _dims, _eq, _state
 
 pytestmark = pytest.mark.gpu
@@ -30,7 +30,7 @@ def _arena(nets, n, T, pairs, players=2, rules=RULES2, selection="Distribution")
 
 
 def _single(agent, opponent, n, T, players=2, rules=RULES2, selection="Distribution"):
-    sw = dict(fused_wide=True, fused_opponent=True) if players != 2 else dict(persistent=True)
+    sw = dict(fused_wide=True, fused_opponent=True) if _wide(players, rules) else dict(persistent=True)
     return PolicyRollout(agent, n_games=n, rules=rules, seed_base=11, window=T, opponent=opponent, players=players, action_selection=selection,
                          opponent_selection=selection, sample_seed=0x1234, use_graph=False, **sw)
 

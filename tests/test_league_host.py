@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from tests.hostcheck import hostcheck
+from tests.pool_tally_ref import league_tally_ref as tally_ref
 from tests.test_mp_score_moves_model import _modes
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -27,22 +28,6 @@ def load_tally():
 
 def ptr(a):
     return a.ctypes.data_as(C.c_void_p)
-
-
-def tally_ref(ep, ss, mark_ep, mark_ss, member, K, results):
-    """The kernel restated: per member, games in ascending order, one fp64 addition per game and column; then the marks move up."""
-    results, mark_ep, mark_ss = results.copy(), mark_ep.copy(), mark_ss.copy()
-    for m in range(K):
-        for grp, mg in enumerate(member):
-            if min(int(mg), K - 1) != m:
-                continue
-            for g in range(grp * GROUP, min(len(ep), (grp + 1) * GROUP)):
-                results[m, 0] = results[m, 0] + np.float64(int(ep[g]) - int(mark_ep[g]))
-                for j in range(10):
-                    results[m, 1 + j] = results[m, 1 + j] + (ss[g, j] - mark_ss[g, j])
-                mark_ep[g] = ep[g]
-                mark_ss[g] = ss[g]
-    return results, mark_ep, mark_ss
 
 
 @pytest.mark.parametrize("n", [1, 16, 17, 35])
