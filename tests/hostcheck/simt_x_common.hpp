@@ -1,5 +1,5 @@
-// simt_x_common.hpp -- TEST-ONLY: what the five shims of the WIDE kernels share (simt_rules_x.cpp, simt_runner_x.cpp, simt_net_x.cpp,
-// simt_x_rollout.cpp, simt_x_rollout_vs.cpp): the pick among the five compiled (players, displays) shapes, the RandomAgent table of a
+// simt_x_common.hpp -- TEST-ONLY: what the shims of the WIDE kernels share (simt_rules_x.cpp, simt_runner_x.cpp, simt_net_x.cpp,
+// simt_mp_score_moves.cpp, simt_x_rollout.cpp): the pick among the five compiled (players, displays) shapes, the RandomAgent table of a
 // display count, the azx::XBatchDev every entry builds from its arguments, and the launch loop.  The shims call the product's
 // __global__ functions (csrc/azul_x_kernels.hpp, csrc/azul_rollout2.hpp) and declare no LDS of their own.  Included after those headers.
 #pragma once
@@ -22,7 +22,7 @@ static const double2 *table_for(int displays)
     return (const double2 *)tabs[i];
 }
 
-// the arguments every shx_* / sxr_* / sxv_* entry takes -> the batch as the kernels see it (margin 0: the library's default)
+// the arguments every shx_* / sxr_* entry takes -> the batch as the kernels see it (margin 0: the library's default)
 static azx::XBatchDev x_batch(int n_games, uint8_t *state, u32 *mt, u32 *mtpos, u64 *episodes, u32 *stuck, double *stat_sum, int first_player, int pool,
                               int end_bonus, int short_deal, const double2 *tab, unsigned long long margin = 0)
 {

@@ -9,46 +9,14 @@ run_workgroup, s_barrier, MFMA and buffer-load emulation).  Checked per move and
     final records, MT19937 words and counters (game_runner.py:43-97, nn_runner.py:17-47);
   * the returns scan (nn_runner.py:70-76) and that no buffer load ever left its resource.
 Under ASan / UBSan (tests/hostcheck/run_sanitizers.sh) every LDS and global index the kernel forms is checked as well."""
-import ctypes as C
-import os
-
 import numpy as np
 import pytest
 
 from oracle import oracle as oz
-from tests.test_hostcheck_env2 import RULES, oracle_play, ptr, start_batch
-from tests.hostcheck import hostcheck
-
-
-
-def load(name=None):
-    name = name or os.environ.get("AZUL_SIMT_ROLLOUT_LIB", "libsimt_rollout2.so")
-    L = C.CDLL(hostcheck.build(name))
-    L.sr2_rollout.restype = C.c_longlong
-    L.sr2_rollout.argtypes = ([C.c_int] + [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_int, C.c_uint] + [C.c_void_p] * 6 + [C.c_int] + [C.c_void_p] * 11
-                              + [C.c_float, C.c_ulonglong, C.c_ulonglong])
-    L.sr2_buffer_oob.restype = C.c_ulonglong
-    return L
-
-
-def weights(seed):
-    rs = np.random.RandomState(seed)
-    w = {"w1t": rs.randn(136, 360) * 0.08, "b1": rs.randn(360) * 0.05, "w2c": rs.randn(180) * 0.1, "b2c": rs.randn(1) * 0.1,
-         "w2a_t": rs.randn(180, 180) * 0.12, "b2a": rs.randn(180) * 0.05}
-    return {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in w.items()}
-
-
-def forward(w, obs, mask):
-    """model.py:22-41 on one observation, fp32; masked log-softmax and the entropy term of agent.py:64-72 / nn_runner.py:32-40."""
-    h = np.maximum(obs.astype(np.float32) @ w["w1t"] + w["b1"], np.float32(0))
-    value = np.float32(h[:180] @ w["w2c"] + w["b2c"][0])
-    logits = (h[180:] @ w["w2a_t"] + w["b2a"]).astype(np.float64)
-    legal = mask.astype(bool)
-    z = logits[legal]
-    lse = z.max() + np.log(np.exp(z - z.max()).sum())
-    logp = np.full(180, -np.inf)
-    logp[legal] = z - lse
-    return float(value), logp, float(-logp[legal].mean())
+from tests.hostcheck import window
+from tests.hostcheck.window import forward, games_fields, to_agent_decision
+from tests.hostcheck.window import load2 as load, weights2 as weights
+from tests.test_hostcheck_env2 import RULES, oracle_play, start_batch
 
 
 def run(L, first, pool, opponent, n, T, seed0, warm=0, gamma=0.9, with_returns=True):
@@ -62,11 +30,8 @@ def run(L, first, pool, opponent, n, T, seed0, warm=0, gamma=0.9, with_returns=T
          "entropy": np.full((T, n), np.nan, np.float32), "status": np.full(n, 99, np.uint8),
          "returns": np.full((T, n), np.nan, np.float32)}
     oob0 = L.sr2_buffer_oob()
-    ops = L.sr2_rollout(n, ptr(state), ptr(mt), ptr(pos), ptr(ep), ptr(stuck), ptr(ss), first, pool, int(opponent), 1000,
-                        ptr(w["w1t"]), ptr(w["b1"]), ptr(w["w2c"]), ptr(w["b2c"]), ptr(w["w2a_t"]), ptr(w["b2a"]), T,
-                        ptr(o["obs"]), ptr(o["mask"]), ptr(o["player"]), ptr(o["action"]), ptr(o["reward"]), ptr(o["done"]),
-                        ptr(o["value"]), ptr(o["logp"]), ptr(o["entropy"]), ptr(o["status"]), ptr(o["returns"]) if with_returns else None,
-                        gamma, 4242, 17)
+    ops = window.run(L, **games_fields(n, state, mt, pos, ep, stuck, ss, first, pool), opp=int(opponent), agent=w, n_steps=T,
+                     **dict(o, returns=o["returns"] if with_returns else None), gamma=gamma, seed=4242, counter=17)
     assert ops > 0
     assert L.sr2_buffer_oob() == oob0                       # no weight fragment was ever requested outside its matrix
     episodes = 0
@@ -117,33 +82,6 @@ def test_random_agent_opponent_and_a_ragged_last_workgroup():
 
 
 # ---- the NETWORK opponent (azul_policy_rollout2_kernel<LID, 2>; game_runner.py:27-30 GameRunner(opponent=Agent(...))) ----------------------
-def load_vs():
-    L = load()
-    L.sr2_rollout_vs.restype = C.c_longlong
-    L.sr2_rollout_vs.argtypes = ([C.c_int] + [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_uint, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 11
-                                 + [C.c_float, C.c_ulonglong, C.c_ulonglong, C.c_ulonglong] + [C.c_void_p] * 3 + [C.c_int])
-    return L
-
-
-def to_agent_decision(rec, mt, pos, first, pool, rng):
-    """Bring a flat self-play state to a point where GameRunner hands the turn to the agent (game_runner.py:46: player 1 to move with at
-    least two legal moves, game not over) by letting a stand-in opponent play random legal moves."""
-    run = oz.NetRunner(lambda s, m: int(rng.choice(np.flatnonzero(m))), first if first else oz.FIRST_RANDOM, pool, rec=rec, mt=mt, pos=pos)
-    Lz = oz.lib()
-    for _ in range(200):
-        legal = int(run.get_valid_moves().sum())
-        over = bool(Lz.oz_is_end_of_game(C.byref(run.q.game)))
-        if over:
-            assert run.reset() == 0
-            continue
-        if run.q.game.current_player == 1 and legal >= 2:
-            break
-        assert Lz.oz_runner_opponent_move_with(C.byref(run.q), C.byref(run.r), run._cb, None) == 0
-    run.q.player_score = int(Lz.oz_potential(C.byref(run.q.game)))          # GameRunner.player_score follows the potential (game_runner.py:52)
-    m, p = run.rng_state()
-    return np.frombuffer(run.record().tobytes(), np.uint8).copy(), m, p
-
-
 def actor_forward(w, obs, mask):
     h = np.maximum(obs.astype(np.float32) @ w["w1t"][:, 180:] + w["b1"][180:], np.float32(0))
     logits = (h @ w["w2a_t"] + w["b2a"]).astype(np.float64)
@@ -163,9 +101,6 @@ def run_vs(L, first, pool, n, T, seed0, warm, slots=8, argmax=False, move_limit=
     state0, mt0, pos0 = state.copy(), mt.copy(), pos.copy()
     ep, stuck, ss = np.zeros(n, np.uint64), np.zeros(n, np.uint32), np.zeros((n, 10))
     wa, wo = weights(seed0), weights(seed0 + 1)
-    keys = ("w1t", "b1", "w2c", "b2c", "w2a_t", "b2a")
-    pa = (C.c_void_p * 6)(*[wa[k].ctypes.data for k in keys])
-    po = (C.c_void_p * 6)(*[wo[k].ctypes.data for k in keys])
     o = {"obs": np.full((T + 1, n, 136), -99, np.float32), "mask": np.full((T + 1, n, 180), 0xEE, np.uint8),
          "player": np.full((T + 1, n), 9, np.uint8), "action": np.full((T, n), -7, np.int32), "reward": np.full((T, n), -7777, np.int32),
          "done": np.full((T, n), 9, np.uint8), "value": np.full((T, n), np.nan, np.float32), "logp": np.full((T, n), np.nan, np.float32),
@@ -173,14 +108,8 @@ def run_vs(L, first, pool, n, T, seed0, warm, slots=8, argmax=False, move_limit=
          "opp_action": np.full((T, slots, n), -9, np.int32), "opp_logp": np.full((T, slots, n), np.nan, np.float32),
          "opp_replies": np.full((T, n), 200, np.uint8)}
     oob0 = L.sr2_buffer_oob()
-    AM = 0xFFFFFFFFFFFFFFFF
-    L.sr2_set_move_limit.argtypes = [C.c_uint]
-    L.sr2_set_move_limit(move_limit)
-    ops = L.sr2_rollout_vs(n, ptr(state), ptr(mt), ptr(pos), ptr(ep), ptr(stuck), ptr(ss), first, pool, 1000, C.cast(pa, C.c_void_p), C.cast(po, C.c_void_p), T,
-                           ptr(o["obs"]), ptr(o["mask"]), ptr(o["player"]), ptr(o["action"]), ptr(o["reward"]), ptr(o["done"]), ptr(o["value"]),
-                           ptr(o["logp"]), ptr(o["entropy"]), ptr(o["status"]), ptr(o["returns"]), 0.9, 4242, AM if argmax else 777, 17,
-                           ptr(o["opp_action"]), ptr(o["opp_logp"]), ptr(o["opp_replies"]), slots)
-    L.sr2_set_move_limit(0)
+    ops = window.run(L, **games_fields(n, state, mt, pos, ep, stuck, ss, first, pool), move_limit=move_limit, opp=2, agent=wa, opponent=wo,
+                     n_steps=T, **o, gamma=0.9, seed=4242, opp_seed=window.ARGMAX if argmax else 777, counter=17, opp_slots=slots)
     assert ops > 0 and L.sr2_buffer_oob() == oob0
     episodes = forced = opening = cuts = 0
     for g in range(n):
@@ -243,7 +172,7 @@ def run_vs(L, first, pool, n, T, seed0, warm, slots=8, argmax=False, move_limit=
 def test_network_opponent_with_a_move_limit():
     """The move limit (beyond the reference, off by default) on the network-opponent protocol: a move of either side that ends a round
     without ending the game once the episode has played `limit` moves cuts the episode (done = 3, reward 0, slot restarted and opened)."""
-    L = load_vs()
+    L = load()
     first, pool = RULES["lid_randomfirst"]
     ops, episodes, forced, opening, cuts = run_vs(L, first, pool, n=16, T=24, seed0=900, warm=20, move_limit=22)
     assert cuts >= 6
@@ -252,7 +181,7 @@ def test_network_opponent_with_a_move_limit():
 def test_network_opponent_in_the_rollout_kernel_replays_through_the_oracle():
     """GameRunner(opponent=Agent(...)) inside the kernel: the agent's records as with the RandomAgent opponent, every opponent_move() --
     replies, player 1's forced moves, the opening moves after an episode end -- answered by the second net on the mover's perspective."""
-    L = load_vs()
+    L = load()
     first, pool = RULES["lid_randomfirst"]
     ops, episodes, forced, opening = run_vs(L, first, pool, n=19, T=6, seed0=300, warm=40)        # (a ragged last workgroup)
     assert ops > 5000 and episodes >= 1 and forced >= 1
@@ -264,7 +193,7 @@ def test_network_opponent_window_ending_on_an_episode_end_reports_no_status():
     """The launch status is the LAST step's.  A window whose last step ends an episode also opens the next one (the opponent's opening
     moves while player 1 is not to move, game_runner.py:84-85): the opening loop that ends with player 1 to move leaves no status --
     AZUL_STUCK is for an opening in which the seat to move has no legal action.  (run_vs asserts the status of every game.)"""
-    L = load_vs()
+    L = load()
     first, pool = RULES["lid_randomfirst"]
     run_vs(L, first, pool, n=16, T=30, seed0=500, warm=50)
     ends = [t for t in range(30) if (run_vs.last_done[t] == 1).any()]
@@ -275,6 +204,6 @@ def test_network_opponent_window_ending_on_an_episode_end_reports_no_status():
 
 
 def test_network_opponent_argmax_and_the_random_pool():
-    L = load_vs()
+    L = load()
     first, pool = RULES["random_first1"]
     run_vs(L, first, pool, n=16, T=5, seed0=410, warm=30, argmax=True)

@@ -1,73 +1,48 @@
 """The ARENA inside the two-player window kernel on CPU: azul_policy_rollout2_kernel<LID, 2, true> (csrc/azul_rollout2.hpp, compiled
-UNMODIFIED by g++ and run as workgroups of eight emulated wavefronts: tests/hostcheck/simt_rollout2_arena.cpp) against the single-opponent
-kernel (simt_rollout2.cpp: sr2_rollout_vs) run once per ordered pair with that pair's weights.  35 games -- two full 16-game groups and a
+UNMODIFIED by g++ and run as workgroups of eight emulated wavefronts: tests/hostcheck/simt_rollout2.cpp, sr2_window with opp 2 and both member
+arrays) against the single-opponent kernel (the same entry without the arrays) run once per ordered pair with that pair's weights.  35 games -- two full 16-game groups and a
 ragged group of three -- five steps, general weights, a pool of two, pairs (agent, opponent) [(1, 0), (0, 1), (1, 1)]: every output buffer,
 record, MT19937 state, counter and trace of the games of a group must equal its pair's single-opponent run BYTE FOR BYTE.  Also: a pool of
 one equals the single-opponent kernel on all games; a member named by no group is never read (poisoned with NaN in all six arrays, nothing
 changes); an agent member past the pool is read as the last member and no weight fragment is requested outside its matrix."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
-from tests.hostcheck import hostcheck
-from tests.test_hostcheck_env2 import RULES, ptr
-from tests.test_hostcheck_rollout2 import load_vs
-from tests.test_hostcheck_rollout2_league import ARGMAX, CASES, GROUP, KEYS, N, SLOTS, T, fresh, games, member_weights, pointers
+from tests.hostcheck import window
+from tests.hostcheck.window import ARGMAX, CASES2 as CASES, GROUP, KEYS, N2 as N, SLOTS2 as SLOTS, games
+from tests.hostcheck.window import fresh2 as fresh, load2 as load, member_weights2 as member_weights, window_fields2
 
 PAIRS = [(1, 0), (0, 1), (1, 1)]
-
-
-def load_arena():
-    L = C.CDLL(hostcheck.build("libsimt_rollout2_arena.so"))
-    L.sr2a_rollout_arena.restype = C.c_longlong
-    L.sr2a_rollout_arena.argtypes = ([C.c_int] + [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_uint, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
-                                     + [C.c_void_p] * 11 + [C.c_float, C.c_ulonglong, C.c_ulonglong, C.c_ulonglong] + [C.c_void_p] * 3 + [C.c_int])
-    L.sr2a_buffer_oob.restype = C.c_ulonglong
-    return L
-
-
 _VS = {}
 
 
 def vs_reference(case, a, o):
     """The single-opponent run of agent = member a against opponent = member o: computed once per case and pair, shared, never modified."""
     if (case, a, o) not in _VS:
-        L = load_vs()
+        L = load()
         ruleset, argmax = CASES[case]
-        first, pool = RULES[ruleset]
         r = fresh(ruleset)
-        wa, wo = member_weights(a), member_weights(o)       # (kept alive: pointers() holds addresses only)
-        pa, po = pointers(wa), pointers(wo)
         oob0 = L.sr2_buffer_oob()
-        ops = L.sr2_rollout_vs(N, ptr(r["state"]), ptr(r["mt"]), ptr(r["pos"]), ptr(r["ep"]), ptr(r["stuck"]), ptr(r["ss"]), first, pool, 1000,
-                               C.cast(pa, C.c_void_p), C.cast(po, C.c_void_p), T, ptr(r["obs"]), ptr(r["mask"]), ptr(r["player"]), ptr(r["action"]),
-                               ptr(r["reward"]), ptr(r["done"]), ptr(r["value"]), ptr(r["logp"]), ptr(r["entropy"]), ptr(r["status"]),
-                               ptr(r["returns"]), 0.9, ARGMAX if argmax else 4242, ARGMAX if argmax else 777, 17, ptr(r["opp_action"]),
-                               ptr(r["opp_logp"]), ptr(r["opp_replies"]), SLOTS)
+        ops = window.run(L, **window_fields2(r, ruleset, ARGMAX if argmax else 4242, argmax), opp=2, agent=member_weights(a),
+                         opponent=member_weights(o))
         assert ops > 0 and L.sr2_buffer_oob() == oob0
         _VS[case, a, o] = r
     return _VS[case, a, o]
 
 
 def run_arena(case, pool_weights, pairs):
-    L = load_arena()
+    L = load()
     ruleset, argmax = CASES[case]
-    first, pool = RULES[ruleset]
     r = fresh(ruleset)
     stacked = {k: np.ascontiguousarray(np.stack([w[k] for w in pool_weights])) for k in KEYS}
-    pp = pointers(stacked)
     am = np.asarray([p[0] for p in pairs], np.uint8)
     om = np.asarray([p[1] for p in pairs], np.uint8)
     assert am.size == (N + GROUP - 1) // GROUP
-    oob0 = L.sr2a_buffer_oob()
-    ops = L.sr2a_rollout_arena(N, ptr(r["state"]), ptr(r["mt"]), ptr(r["pos"]), ptr(r["ep"]), ptr(r["stuck"]), ptr(r["ss"]), first, pool, 1000,
-                               C.cast(pp, C.c_void_p), len(pool_weights), ptr(am), ptr(om), T, ptr(r["obs"]), ptr(r["mask"]), ptr(r["player"]),
-                               ptr(r["action"]), ptr(r["reward"]), ptr(r["done"]), ptr(r["value"]), ptr(r["logp"]), ptr(r["entropy"]),
-                               ptr(r["status"]), ptr(r["returns"]), 0.9, ARGMAX if argmax else 4242, ARGMAX if argmax else 777, 17,
-                               ptr(r["opp_action"]), ptr(r["opp_logp"]), ptr(r["opp_replies"]), SLOTS)
+    oob0 = L.sr2_buffer_oob()
+    ops = window.run(L, **window_fields2(r, ruleset, ARGMAX if argmax else 4242, argmax), opp=2, agent=stacked, pool_size=len(pool_weights),
+                     agent_member=am, opp_member=om)
     assert ops > 0
-    assert L.sr2a_buffer_oob() == oob0                      # no weight fragment was requested outside its member's matrix
+    assert L.sr2_buffer_oob() == oob0                       # no weight fragment was requested outside its member's matrix
     return r
 
 

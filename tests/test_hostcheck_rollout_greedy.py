@@ -1,31 +1,20 @@
 """The greedy opponent INSIDE the persistent policy rollout kernel, on CPU: azul_policy_rollout2_kernel<LID, 3> (csrc/azul_rollout2.hpp: the
 agent's move, then az2::greedy_pick2's answers while either half of the wave owes an opponent_move(), csrc/azul_env2.hpp) compiled
-UNMODIFIED by g++ and run as workgroups of eight emulated wavefronts (tests/hostcheck/simt_rollout2_greedy.cpp).  Every game is replayed
+UNMODIFIED by g++ and run as workgroups of eight emulated wavefronts (tests/hostcheck/simt_rollout2.cpp: sr2_window, opp 3).  Every game is replayed
 through the oracle's callback GameRunner with the host model's greedy choice (tests/score_moves_model.py) as the opponent, fed the
 kernel's own agent actions: observation, mask, player, reward, done, the number of opponent moves and every traced answer per step; the
 final record bytes, all 624 MT19937 words and the index, the episode / stuck counters, the returns scan; opp_logp untouched; the agent's
 value / log-prob / entropy against a numpy forward.  Both rule sets, a ragged last workgroup with an odd game count, a trace shorter
 than a step's replies, and the move limit.  Reference: azulnet/game_runner.py:37-55, 76-85; azulnet/nn_runner.py:17-47."""
-import ctypes as C
-import os
-
 import numpy as np
 import pytest
 
 from oracle import oracle as oz
 from tests import greedy_rollout_cases as gc
-from tests.hostcheck import hostcheck
-from tests.test_hostcheck_env2 import RULES, ptr, start_batch
-from tests.test_hostcheck_rollout2 import forward, to_agent_decision, weights
-
-
-def load():
-    L = C.CDLL(hostcheck.build(os.environ.get("AZUL_SIMT_ROLLOUT_GREEDY_LIB", "libsimt_rollout2_greedy.so")))
-    L.srg_rollout.restype = C.c_longlong
-    L.srg_rollout.argtypes = ([C.c_int] + [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_uint, C.c_uint, C.c_void_p, C.c_int] + [C.c_void_p] * 11
-                              + [C.c_float, C.c_ulonglong, C.c_ulonglong] + [C.c_void_p] * 3 + [C.c_int])
-    L.srg_buffer_oob.restype = C.c_ulonglong
-    return L
+from tests.hostcheck import window
+from tests.hostcheck.window import forward, games_fields, to_agent_decision
+from tests.hostcheck.window import load2 as load, weights2 as weights
+from tests.test_hostcheck_env2 import RULES, start_batch
 
 
 def run_greedy(L, first, pool, n, T, seed0, warm, slots=4, move_limit=0, gamma=0.9):
@@ -36,19 +25,16 @@ def run_greedy(L, first, pool, n, T, seed0, warm, slots=4, move_limit=0, gamma=0
     state0, mt0, pos0 = state.copy(), mt.copy(), pos.copy()
     ep, stuck, ss = np.zeros(n, np.uint64), np.zeros(n, np.uint32), np.zeros((n, 10))
     w = weights(seed0)
-    pa = (C.c_void_p * 6)(*[w[k].ctypes.data for k in ("w1t", "b1", "w2c", "b2c", "w2a_t", "b2a")])
     o = {"obs": np.full((T + 1, n, 136), -99, np.float32), "mask": np.full((T + 1, n, 180), 0xEE, np.uint8),
          "player": np.full((T + 1, n), 9, np.uint8), "action": np.full((T, n), -7, np.int32), "reward": np.full((T, n), -7777, np.int32),
          "done": np.full((T, n), 9, np.uint8), "value": np.full((T, n), np.nan, np.float32), "logp": np.full((T, n), np.nan, np.float32),
          "entropy": np.full((T, n), np.nan, np.float32), "status": np.full(n, 99, np.uint8), "returns": np.full((T, n), np.nan, np.float32),
          "opp_action": np.full((T, slots, n), -9, np.int32), "opp_logp": np.full((T, slots, n), 123.5, np.float32),
          "opp_replies": np.full((T, n), 200, np.uint8)}
-    oob0 = L.srg_buffer_oob()
-    ops = L.srg_rollout(n, ptr(state), ptr(mt), ptr(pos), ptr(ep), ptr(stuck), ptr(ss), first, pool, 1000, move_limit, C.cast(pa, C.c_void_p), T,
-                        ptr(o["obs"]), ptr(o["mask"]), ptr(o["player"]), ptr(o["action"]), ptr(o["reward"]), ptr(o["done"]), ptr(o["value"]),
-                        ptr(o["logp"]), ptr(o["entropy"]), ptr(o["status"]), ptr(o["returns"]), gamma, 4242, 17,
-                        ptr(o["opp_action"]), ptr(o["opp_logp"]), ptr(o["opp_replies"]), slots)
-    assert ops > 0 and L.srg_buffer_oob() == oob0
+    oob0 = L.sr2_buffer_oob()
+    ops = window.run(L, **games_fields(n, state, mt, pos, ep, stuck, ss, first, pool), move_limit=move_limit, opp=3, agent=w, n_steps=T, **o,
+                     gamma=gamma, seed=4242, counter=17, opp_slots=slots)
+    assert ops > 0 and L.sr2_buffer_oob() == oob0
     assert (o["opp_logp"] == 123.5).all()                   # the greedy player has no log-probability: never written
     fp = first if first else oz.FIRST_RANDOM
     tot = {"calls": 0, "forced": 0, "opening": 0, "ties": 0, "cuts": 0, "episodes": 0, "untraced": 0, "zero": 0, "siblings": 0}

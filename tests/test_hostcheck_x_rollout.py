@@ -11,7 +11,6 @@ workgroup).  Every move of every game is checked against references that share n
   * the trajectory arrays are written exactly where they belong: guard cells around every output stay untouched.
 The games start part-way through their episodes (random legal moves on the models first), so that episodes end and restart inside the
 window; the batch of 37 games leaves the last workgroup ragged."""
-import ctypes as C
 import random
 
 import numpy as np
@@ -20,36 +19,9 @@ import pytest
 from oracle import oracle as oz
 from tests import policy_draw_ref as pdr
 from tests.mp_runner_model import MPRunner
-from tests.hostcheck import hostcheck
-
-GUARD = 7                      # guard cells past the end of every output array
-
-
-def load():
-    L = C.CDLL(hostcheck.build("libsimt_x_rollout.so"))
-    L.sxr_rollout.restype = C.c_longlong
-    L.sxr_rollout.argtypes = ([C.c_int] * 4 + [C.c_void_p] * 6 + [C.c_int] * 4 + [C.c_uint, C.c_void_p, C.c_int] + [C.c_void_p] * 10
-                              + [C.c_ulonglong, C.c_ulonglong])
-    L.sxr_buffer_oob.restype = C.c_ulonglong
-    return L
-
-
-def ptr(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
-
-
-def weights(n_obs, n_act, seed):
-    rs = np.random.RandomState(seed)
-    w = {"w1t": rs.randn(n_obs, 360) * 0.06, "b1": rs.randn(360) * 0.05, "w2c": rs.randn(180) * 0.1, "b2c": rs.randn(1) * 0.1,
-         "w2a_t": rs.randn(180, n_act) * 0.12, "b2a": rs.randn(n_act) * 0.05}
-    return {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in w.items()}
-
-
-def buf(shape, dtype, fill):
-    """An output array with GUARD cells behind it: (the whole allocation, the view the kernel writes)."""
-    n = int(np.prod(shape))
-    whole = np.full(n + GUARD, fill, dtype)
-    return whole, whole[:n].reshape(shape)
+from tests.hostcheck import window
+from tests.hostcheck.window import GUARD, buf, games_fields_x
+from tests.hostcheck.window import load_x as load, weights_x as weights
 
 
 CASES = [  # (P, first, pool, ext, opp)
@@ -83,20 +55,15 @@ def test_window_kernel_matches_numpy_forward_draw_reference_and_runner_model(P, 
     stuck = np.array([m.stuck for m in models], np.uint32)
     ss = np.stack([m.stat_sum for m in models]).astype(np.float64)
     w = weights(OBS, NA, seed)
-    wl = [w[k] for k in ("w1t", "b1", "w2c", "b2c", "w2a_t", "b2a")]
-    wp = (C.c_void_p * 6)(*[x.ctypes.data for x in wl])
     o, whole = {}, {}
     for k, shape, dt, fill in (("obs", (T + 1, n, OBS), np.float32, -99), ("mask", (T + 1, n, NA), np.uint8, 0xEE), ("player", (T + 1, n), np.uint8, 9),
                                ("action", (T, n), np.int32, -7), ("reward", (T, n), np.int32, -7777), ("done", (T, n), np.uint8, 9),
                                ("value", (T, n), np.float32, np.nan), ("logp", (T, n), np.float32, np.nan), ("entropy", (T, n), np.float32, np.nan),
                                ("status", (n,), np.uint8, 99)):
         whole[k], o[k] = buf(shape, dt, fill)
-    xpool = 2 if ext & oz.EXT_FINITE_BAG else (1 if pool == oz.POOL_LID else 0)
     oob0 = L.sxr_buffer_oob()
-    ops = L.sxr_rollout(n, P, D, opp, ptr(state), ptr(mt), ptr(pos), ptr(ep), ptr(stuck), ptr(ss), first, xpool, int(bool(ext & oz.EXT_END_BONUS)),
-                        int(bool(ext & oz.EXT_SHORT_DEAL)), id_base, wp, T, *[ptr(o[k]) for k in ("obs", "mask", "player", "action", "reward", "done",
-                                                                                                 "value", "logp", "entropy", "status")],
-                        seed, counter)
+    ops = window.run(L, **games_fields_x(n, P, D, state, mt, pos, ep, stuck, ss, first, pool, ext, id_base), opp=opp, agent=w, n_steps=T, **o,
+                     seed=seed, counter=counter)
     assert ops > 0
     assert L.sxr_buffer_oob() == oob0
     for k in whole:                                    # nothing written past any array

@@ -1,60 +1,44 @@
 """The ARENA inside the wide window kernel on CPU: azul_x_policy_rollout_vs_kernel<3, 5, true, true> (csrc/azul_rollout2.hpp, compiled
-UNMODIFIED by g++ and run as workgroups of eight emulated wavefronts: tests/hostcheck/simt_x_rollout_arena.cpp) against the single-opponent
-kernel (simt_x_rollout_vs.cpp: sxv_rollout) run once per ordered pair with that pair's weights.  Three players on five displays, 19 games -- a
+UNMODIFIED by g++ and run as workgroups of eight emulated wavefronts: tests/hostcheck/simt_x_rollout.cpp, sxr_window with opp 2 and both
+member arrays) against the single-opponent kernel (the same entry without the arrays) run once per ordered pair with that pair's weights.  Three players on five displays, 19 games -- a
 full 16-game group and a ragged group of three -- five steps, general weights, a pool of two, pairs (agent, opponent) [(1, 0), (0, 1)]: every
 output buffer, record, MT19937 state, counter and trace of the games of a group must equal its pair's single-opponent run BYTE FOR BYTE.
 Also: a pool of one equals the single-opponent kernel on all games; a member named by no group is never read (NaN poison); a member past the
 pool is read as the last one."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
-from tests.hostcheck import hostcheck
-from tests.test_hostcheck_x_rollout import ptr
-from tests.test_hostcheck_x_rollout_league import (CASES, GROUP, KEYS, N, fresh, games, head_args, load_vs, member_weights, pointers,
-                                                   tail_args)
+from tests.hostcheck import window
+from tests.hostcheck.window import CASES_X as CASES, GROUP, KEYS, NX as N, games, head_fields, tail_fields
+from tests.hostcheck.window import fresh_x as fresh, load_x as load, member_weights_x as member_weights
 
 PAIRS = [(1, 0), (0, 1)]
-
-
-def load_arena():
-    L = C.CDLL(hostcheck.build("libsimt_x_rollout_arena.so"))
-    L.sxa_rollout_arena.restype = C.c_longlong
-    L.sxa_rollout_arena.argtypes = ([C.c_int] * 3 + [C.c_void_p] * 6 + [C.c_int] * 4 + [C.c_uint, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
-                                    + [C.c_void_p] * 13 + [C.c_int, C.c_ulonglong, C.c_ulonglong, C.c_ulonglong, C.c_int])
-    L.sxa_buffer_oob.restype = C.c_ulonglong
-    return L
-
-
 _VS = {}
 
 
 def vs_reference(case, a, o):
     """The single-opponent run of agent = member a against opponent = member o: computed once per case and pair, shared, never modified."""
     if (case, a, o) not in _VS:
-        L = load_vs()
+        L = load()
         pool, argmax = CASES[case]
         r = fresh(pool)
-        wa, wo = member_weights(a), member_weights(o)       # (kept alive: pointers() holds addresses only)
-        wp, wop = pointers(wa), pointers(wo)
-        assert L.sxv_rollout(*head_args(r, pool), wp, wop, *tail_args(r, argmax)) > 0
+        assert window.run(L, **head_fields(r, pool), opp=2, agent=member_weights(a), opponent=member_weights(o), **tail_fields(r, argmax)) > 0
         _VS[case, a, o] = r
     return _VS[case, a, o]
 
 
 def run_arena(case, pool_weights, pairs):
-    L = load_arena()
+    L = load()
     pool, argmax = CASES[case]
     r = fresh(pool)
     stacked = {k: np.ascontiguousarray(np.stack([x[k] for x in pool_weights])) for k in KEYS}
-    pp = pointers(stacked)
     am = np.asarray([p[0] for p in pairs], np.uint8)
     om = np.asarray([p[1] for p in pairs], np.uint8)
     assert am.size == (N + GROUP - 1) // GROUP
-    oob0 = L.sxa_buffer_oob()
-    assert L.sxa_rollout_arena(*head_args(r, pool), pp, len(pool_weights), ptr(am), ptr(om), *tail_args(r, argmax)) > 0
-    assert L.sxa_buffer_oob() == oob0
+    oob0 = L.sxr_buffer_oob()
+    assert window.run(L, **head_fields(r, pool), opp=2, agent=stacked, pool_size=len(pool_weights), agent_member=am, opp_member=om,
+                      **tail_fields(r, argmax)) > 0
+    assert L.sxr_buffer_oob() == oob0
     return r
 
 

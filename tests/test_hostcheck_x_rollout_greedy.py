@@ -14,7 +14,6 @@ against references that share no code with the kernel:
 them a few steps before their end.  The census -- sibling halves owing different numbers of replies, a step without a reply, an episode
 ending inside a step, an opening played inside reply rounds, a tie resolved to the lowest action -- is computed from the replay, never from
 the kernel's counters, and every class has to occur over the cases."""
-import ctypes as C
 import functools
 import random
 
@@ -25,20 +24,12 @@ from oracle import oracle as oz
 from tests import mp_score_moves_model as mm
 from tests import policy_draw_ref as pdr
 from tests.mp_net_model import READY, MPNetRunner
-from tests.test_hostcheck_x_rollout import GUARD, buf, ptr, weights
-from tests.hostcheck import hostcheck
+from tests.hostcheck import window
+from tests.hostcheck.window import GUARD, buf, games_fields_x
+from tests.hostcheck.window import load_x as load, weights_x as weights
 
 N, T = 19, 6
 CLASSES = ("siblings_differ", "zero_replies", "episode_ends_in_step", "opening_in_reply_rounds", "tie_to_lowest")
-
-
-def load():
-    L = C.CDLL(hostcheck.build("libsimt_x_rollout_greedy.so"))
-    L.sxg_rollout.restype = C.c_longlong
-    L.sxg_rollout.argtypes = ([C.c_int] * 3 + [C.c_void_p] * 6 + [C.c_int] * 4 + [C.c_uint, C.c_void_p, C.c_int] + [C.c_void_p] * 13
-                              + [C.c_int, C.c_ulonglong, C.c_ulonglong, C.c_int])
-    L.sxg_buffer_oob.restype = C.c_ulonglong
-    return L
 
 
 CASES = [  # (P, first, pool, ext, trace slots)
@@ -103,7 +94,6 @@ def run_case(i):
     stuck = np.array([m.stuck for m in models], np.uint32)
     ss = np.stack([m.stat_sum for m in models]).astype(np.float64)
     w = weights(OBS, NA, seed)
-    wp = (C.c_void_p * 6)(*[w[k].ctypes.data for k in ("w1t", "b1", "w2c", "b2c", "w2a_t", "b2a")])
     o, whole = {}, {}
     for k, shape, dt, fill in (("obs", (T + 1, n, OBS), np.float32, -99), ("mask", (T + 1, n, NA), np.uint8, 0xEE), ("player", (T + 1, n), np.uint8, 9),
                                ("action", (T, n), np.int32, -7), ("reward", (T, n), np.int32, -7777), ("done", (T, n), np.uint8, 9),
@@ -111,15 +101,11 @@ def run_case(i):
                                ("status", (n,), np.uint8, 99), ("opp_action", (T, slots, n), np.int32, -5), ("opp_logp", (T, slots, n), np.float32, 55.0),
                                ("opp_replies", (T, n), np.uint8, 201)):
         whole[k], o[k] = buf(shape, dt, fill)
-    xpool = 2 if ext & oz.EXT_FINITE_BAG else (1 if pool == oz.POOL_LID else 0)
-    oob0 = L.sxg_buffer_oob()
-    ops = L.sxg_rollout(n, P, D, ptr(state), ptr(mt), ptr(pos), ptr(ep), ptr(stuck), ptr(ss), first, xpool, int(bool(ext & oz.EXT_END_BONUS)),
-                        int(bool(ext & oz.EXT_SHORT_DEAL)), id_base, wp, T,
-                        *[ptr(o[k]) for k in ("obs", "mask", "player", "action", "reward", "done", "value", "logp", "entropy", "status",
-                                              "opp_action", "opp_logp", "opp_replies")],
-                        slots, seed, counter, 512)
+    oob0 = L.sxr_buffer_oob()
+    ops = window.run(L, **games_fields_x(n, P, D, state, mt, pos, ep, stuck, ss, first, pool, ext, id_base), opp=3, agent=w, n_steps=T, **o,
+                     opp_slots=slots, seed=seed, counter=counter, max_replies=512)
     assert ops > 0
-    assert L.sxg_buffer_oob() == oob0
+    assert L.sxr_buffer_oob() == oob0
     for k in whole:                                    # nothing written past any array
         tail = whole[k][-GUARD:]
         assert (np.isnan(tail).all() if k in ("value", "logp", "entropy") else (tail == whole[k][-1]).all()), k

@@ -13,7 +13,6 @@ game is checked against references that share no code with the kernel:
   * the trace is written exactly for the rounds a game owed, and nothing is written past any output array (guard cells).
 The games start part-way through their episodes, so that episodes end, and the next episodes' openings are played, inside reply rounds; the
 batch of 37 games leaves the last workgroup ragged."""
-import ctypes as C
 import random
 
 import numpy as np
@@ -22,19 +21,11 @@ import pytest
 from oracle import oracle as oz
 from tests import policy_draw_ref as pdr
 from tests.mp_net_model import READY, MPNetRunner
-from tests.test_hostcheck_x_rollout import GUARD, buf, ptr, weights
-from tests.hostcheck import hostcheck
+from tests.hostcheck import window
+from tests.hostcheck.window import GUARD, buf, games_fields_x
+from tests.hostcheck.window import load_x as load, weights_x as weights
 
 SLOTS = 64                     # trace slots per step: more than any step's reply rounds with legal answers
-
-
-def load():
-    L = C.CDLL(hostcheck.build("libsimt_x_rollout_vs.so"))
-    L.sxv_rollout.restype = C.c_longlong
-    L.sxv_rollout.argtypes = ([C.c_int] * 3 + [C.c_void_p] * 6 + [C.c_int] * 4 + [C.c_uint, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 13
-                              + [C.c_int, C.c_ulonglong, C.c_ulonglong, C.c_ulonglong, C.c_int])
-    L.sxv_buffer_oob.restype = C.c_ulonglong
-    return L
 
 
 CASES = [  # (P, first, pool, ext, opponent selection)
@@ -72,9 +63,6 @@ def test_window_kernel_vs_network_matches_numpy_forwards_draw_reference_and_net_
     stuck = np.array([m.stuck for m in models], np.uint32)
     ss = np.stack([m.stat_sum for m in models]).astype(np.float64)
     w, wo = weights(OBS, NA, seed), weights(OBS, NA, seed + 1)
-    keys = ("w1t", "b1", "w2c", "b2c", "w2a_t", "b2a")
-    wp = (C.c_void_p * 6)(*[w[k].ctypes.data for k in keys])
-    wop = (C.c_void_p * 6)(*[wo[k].ctypes.data for k in keys])
     o, whole = {}, {}
     for k, shape, dt, fill in (("obs", (T + 1, n, OBS), np.float32, -99), ("mask", (T + 1, n, NA), np.uint8, 0xEE), ("player", (T + 1, n), np.uint8, 9),
                                ("action", (T, n), np.int32, -7), ("reward", (T, n), np.int32, -7777), ("done", (T, n), np.uint8, 9),
@@ -82,15 +70,11 @@ def test_window_kernel_vs_network_matches_numpy_forwards_draw_reference_and_net_
                                ("status", (n,), np.uint8, 99), ("opp_action", (T, SLOTS, n), np.int32, -5), ("opp_logp", (T, SLOTS, n), np.float32, 55.0),
                                ("opp_replies", (T, n), np.uint8, 201)):
         whole[k], o[k] = buf(shape, dt, fill)
-    xpool = 2 if ext & oz.EXT_FINITE_BAG else (1 if pool == oz.POOL_LID else 0)
-    oob0 = L.sxv_buffer_oob()
-    ops = L.sxv_rollout(n, P, D, ptr(state), ptr(mt), ptr(pos), ptr(ep), ptr(stuck), ptr(ss), first, xpool, int(bool(ext & oz.EXT_END_BONUS)),
-                        int(bool(ext & oz.EXT_SHORT_DEAL)), id_base, wp, wop, T,
-                        *[ptr(o[k]) for k in ("obs", "mask", "player", "action", "reward", "done", "value", "logp", "entropy", "status",
-                                              "opp_action", "opp_logp", "opp_replies")],
-                        SLOTS, seed, opp_seed, counter, 512)
+    oob0 = L.sxr_buffer_oob()
+    ops = window.run(L, **games_fields_x(n, P, D, state, mt, pos, ep, stuck, ss, first, pool, ext, id_base), opp=2, agent=w, opponent=wo,
+                     n_steps=T, **o, opp_slots=SLOTS, seed=seed, opp_seed=opp_seed, counter=counter, max_replies=512)
     assert ops > 0
-    assert L.sxv_buffer_oob() == oob0
+    assert L.sxr_buffer_oob() == oob0
     for k in whole:                                    # nothing written past any array
         tail = whole[k][-GUARD:]
         assert (np.isnan(tail).all() if tail.dtype == np.float32 and k in ("value", "logp", "entropy") else (tail == whole[k][-1]).all()), k
