@@ -164,4 +164,18 @@ AZ_FN void seed_stream(u32 *mt, u64 seed)
     mt[0] = 0x80000000u;
 }
 
+// ---- flat self-play (host side): which trajectory streams a launch writes -> the <OUT, PAD, BITS> of the kernel that writes them, for
+// both record families (the selectors: selfplay2_kernel in azul_selfplay_kernels.hpp, x_selfplay_kernel in azul_x_kernels.hpp).
+// none: no stream at all; core: mask, action, reward, done and packed without the records; full: core + the mask bits; pad: mask rows
+// that take the one-store-per-row path.  OUT 2 is the run-time subset.
+struct SelfplayVariant { int out; bool pad, bits; };
+static SelfplayVariant selfplay_variant(bool none, bool core, bool full, bool pad)
+{
+    if (none) return {0, false, false};
+    if (full && pad) return {1, true, true};
+    if (core && pad) return {1, true, false};
+    if (full) return {1, false, true};
+    return {2, false, false};
+}
+
 } // namespace az

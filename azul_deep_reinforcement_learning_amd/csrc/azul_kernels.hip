@@ -383,14 +383,7 @@ static azx::XBatchDev xdev(const azul_batch_t *b)
     return x;
 }
 
-// (players, displays) -> the instantiation; `call` is a macro body that uses PP / DD
-#define AZ_X_DISPATCH(b, call) do { \
-        const int pd_ = (b)->players * 16 + (b)->displays; \
-        if (pd_ == 2 * 16 + 5) { constexpr u32 PP = 2, DD = 5; call; } \
-        else if (pd_ == 3 * 16 + 5) { constexpr u32 PP = 3, DD = 5; call; } \
-        else if (pd_ == 3 * 16 + 7) { constexpr u32 PP = 3, DD = 7; call; } \
-        else if (pd_ == 4 * 16 + 5) { constexpr u32 PP = 4, DD = 5; call; } \
-        else { constexpr u32 PP = 4, DD = 9; call; } } while (0)
+static int fail_shape() { return fail(AZUL_ERR_INVALID, "no kernel is compiled for the batch's (players, displays)"); }      // (azul_batch_create_rules admits none such)
 
 static int launch_op_x(azul_batch_t *b, const OpArgs &a, void *stream, int count)
 {
@@ -419,7 +412,9 @@ static int launch_op_x(azul_batch_t *b, const OpArgs &a, void *stream, int count
     x.first = a.first; x.count = count < 0 ? b->d.n : (u32)count;
     const dim3 grid((x.count + 1u) / 2u), block(64);
     const azx::XBatchDev xb = xdev(b);
-    AZ_X_DISPATCH(b, hipLaunchKernelGGL((azul_x_op_kernel<PP, DD>), grid, block, 0, (hipStream_t)stream, xb, x));
+    const auto k = x_for_shape(b->players, b->displays, [](auto s) { return azul_x_op_kernel<s.P, s.D>; });
+    if (!k) return fail_shape();
+    hipLaunchKernelGGL(k, grid, block, 0, (hipStream_t)stream, xb, x);
     HIP_TRY(hipGetLastError());
     return AZUL_SUCCESS;
 }
@@ -701,34 +696,7 @@ int azul_policy_forward(const float *obs_dev, const uint8_t *mask_dev, const flo
     return AZUL_SUCCESS;
 }
 
-static int launch_rollout(azul_batch_t *b, const PolicyWeights &W, const RolloutArgs &a, int opp, void *stream, bool arena = false)
-{
-    const hipStream_t st = (hipStream_t)stream;
-    const bool lid = b->d.rules.tile_pool == POOL_LID;
-    const dim3 grid2((b->d.n + PF_GAMES - 1) / PF_GAMES), block2(64 * PR2_WAVES);
-    if (arena) {                                             // (opp == 2: W is the stacked pool, a.agent_member picks from it)
-        if (lid) hipLaunchKernelGGL((azul_policy_rollout2_kernel<true, 2, true>), grid2, block2, 0, st, b->d, W, a);
-        else hipLaunchKernelGGL((azul_policy_rollout2_kernel<false, 2, true>), grid2, block2, 0, st, b->d, W, a);
-    } else if (lid) {
-        if (opp == 3) hipLaunchKernelGGL((azul_policy_rollout2_kernel<true, 3>), grid2, block2, 0, st, b->d, W, a);
-        else if (opp == 2) hipLaunchKernelGGL((azul_policy_rollout2_kernel<true, 2>), grid2, block2, 0, st, b->d, W, a);
-        else if (opp == 1) hipLaunchKernelGGL((azul_policy_rollout2_kernel<true, 1>), grid2, block2, 0, st, b->d, W, a);
-        else hipLaunchKernelGGL((azul_policy_rollout2_kernel<true, 0>), grid2, block2, 0, st, b->d, W, a);
-    } else {
-        if (opp == 3) hipLaunchKernelGGL((azul_policy_rollout2_kernel<false, 3>), grid2, block2, 0, st, b->d, W, a);
-        else if (opp == 2) hipLaunchKernelGGL((azul_policy_rollout2_kernel<false, 2>), grid2, block2, 0, st, b->d, W, a);
-        else if (opp == 1) hipLaunchKernelGGL((azul_policy_rollout2_kernel<false, 1>), grid2, block2, 0, st, b->d, W, a);
-        else hipLaunchKernelGGL((azul_policy_rollout2_kernel<false, 0>), grid2, block2, 0, st, b->d, W, a);
-    }
-    HIP_TRY(hipGetLastError());
-    return AZUL_SUCCESS;
-}
-
 struct NetShape { int inputs, hidden, actions; };
-struct DrawKeys { uint64_t seed, opp_seed, counter; uint64_t *counter_dev; };
-// azul_batch_[mp_]policy_rollout_league: the pool behind `opponent`.  agent_member_dev (azul_batch_[mp_]policy_rollout_arena): the same pool is
-// behind `agent` too, one member per group for the agent seat
-struct League { int pool_size; const uint8_t *member_dev; const uint8_t *agent_member_dev; bool arena; };
 static_assert(AZUL_LEAGUE_GROUP_GAMES == PF_GAMES, "a league group is the 16 games of one workgroup of the window kernels");
 
 static int fail_in(const char *who, const char *what)
@@ -791,39 +759,21 @@ static int rollout_window(azul_batch_t *b, const char *who, bool wide, int n_ste
     }
     if ((net || opp == 3) && (out->opp_action || out->opp_logp) && out->opp_slots <= 0) return fail_in(who, "opp_slots must be positive with a trace");
     if (wide && n_steps == 0) return AZUL_SUCCESS;           // (the two-player kernel is launched with an empty window too: it writes slot 0)
-    const PolicyWeights W = {agent->w1t, agent->b1, agent->w2c, agent->b2c, agent->w2a_t, agent->b2a};
-    // returns: the two-player kernel writes a window of up to 32 steps itself (it keeps the rewards in 32 lanes); the wide kernels never do
-    RolloutArgs a = {n_steps, out->obs, out->mask, out->player, out->action, out->reward, out->done, out->value, out->logp, out->entropy, out->status,
-                     wide ? nullptr : out->returns, gamma, (u64)keys.seed, (u64)keys.counter, (u64 *)keys.counter_dev};
-    if (net) {                                               // (without a network opponent the opponent fields of `out` are ignored)
-        a.Wopp = {opponent->w1t, opponent->b1, opponent->w2c, opponent->b2c, opponent->w2a_t, opponent->b2a};
-        a.opp_seed = (u64)keys.opp_seed;
-        a.opp_action = out->opp_action; a.opp_logp = out->opp_logp; a.opp_replies = out->opp_replies; a.opp_slots = out->opp_slots;
-        if (league) { a.opp_member = league->member_dev; a.opp_pool = (u32)league->pool_size; }      // a base offset per workgroup, nothing else
-        if (arena) { a.agent_member = league->agent_member_dev; a.agent_pool = (u32)league->pool_size; }
-    }
-    if (opp == 3) {                                          // the greedy player's trace: its answers and their number (opp_logp is never written)
-        a.opp_action = out->opp_action; a.opp_replies = out->opp_replies; a.opp_slots = out->opp_slots;
-    }
+    PolicyWeights W;
+    RolloutArgs a;
+    window_pack(wide, n_steps, opp, agent, opponent, keys, out, gamma, league, W, a);
+    // which instantiation runs is azul_rollout2.hpp's statement (rollout2_kernel / x_rollout_kernel); both families run 16 games per workgroup
+    const dim3 grid((b->d.n + PF_GAMES - 1) / PF_GAMES), block(64 * PR2_WAVES);
     if (!wide) {
-        const int rc = launch_rollout(b, W, a, opp, stream, arena);
-        if (rc != AZUL_SUCCESS) return rc;
+        const rollout2_kernel_t k = rollout2_kernel(b->d.rules.tile_pool == POOL_LID, opp, arena);
+        if (!k) return fail_in(who, "unknown kind of opponent");
+        hipLaunchKernelGGL(k, grid, block, 0, (hipStream_t)stream, b->d, W, a);
     } else {
-        const dim3 grid((b->d.n + PF_GAMES - 1) / PF_GAMES), block(64 * PR2_WAVES);
-        const hipStream_t st = (hipStream_t)stream;
-        const azx::XBatchDev xb = xdev(b);
-        const u32 id_base = b->d.id_base;
-        if (net && arena)
-            AZ_X_DISPATCH(b, hipLaunchKernelGGL((azul_x_policy_rollout_vs_kernel<PP, DD, true, true>), grid, block, 0, st, xb, W, a, id_base, (u32)max_replies));
-        else if (net && league)
-            AZ_X_DISPATCH(b, hipLaunchKernelGGL((azul_x_policy_rollout_vs_kernel<PP, DD, true>), grid, block, 0, st, xb, W, a, id_base, (u32)max_replies));
-        else if (net) AZ_X_DISPATCH(b, hipLaunchKernelGGL((azul_x_policy_rollout_vs_kernel<PP, DD>), grid, block, 0, st, xb, W, a, id_base, (u32)max_replies));
-        else if (opp == 3)
-            AZ_X_DISPATCH(b, hipLaunchKernelGGL((azul_x_policy_rollout_kernel<PP, DD, 3>), grid, block, 0, st, xb, W, a, id_base, (u32)max_replies));
-        else if (opp) AZ_X_DISPATCH(b, hipLaunchKernelGGL((azul_x_policy_rollout_kernel<PP, DD, 1>), grid, block, 0, st, xb, W, a, id_base));
-        else AZ_X_DISPATCH(b, hipLaunchKernelGGL((azul_x_policy_rollout_kernel<PP, DD, 0>), grid, block, 0, st, xb, W, a, id_base));
-        HIP_TRY(hipGetLastError());
+        const x_rollout_kernel_t k = x_rollout_kernel(b->players, b->displays, opp, league != nullptr, arena);
+        if (!k) return fail_in(who, "unknown kind of opponent, or no kernel for the batch's (players, displays)");
+        hipLaunchKernelGGL(k, grid, block, 0, (hipStream_t)stream, xdev(b), W, a, b->d.id_base, (net || opp == 3) ? (u32)max_replies : 0u);
     }
+    HIP_TRY(hipGetLastError());
     if (out->returns && (wide || n_steps > 32))              // the window's discounted returns behind the kernel: the per-move path's own scan
         return azul_discounted_returns(out->reward, out->done, out->returns, nullptr, gamma, n_steps, (int)b->d.n, stream);
     return AZUL_SUCCESS;
@@ -981,24 +931,17 @@ int azul_batch_mp_policy_rollout_greedy(azul_batch_t *b, int n_steps, const azul
                           {seed, 0, counter, counter_dev}, out, gamma, max_replies, stream);
 }
 
-/* the wide shapes of azul_learner.hpp: (obs_size, num_actions) of p3_d5, p4_d5, p3_d7, p4_d9; hidden 180 */
+/* the shapes a2c_grad (azul_learner.hpp) has a kernel for; hidden 180 */
 int azul_a2c_flat_size(int num_inputs, int hidden_size, int num_actions)
 {
-    if (hidden_size != PF_HID) return AZUL_ERR_INVALID;
-    if ((num_inputs == PF_IN && num_actions == PF_ACT) || (num_inputs == 188 && num_actions == 180) || (num_inputs == 240 && num_actions == 180) ||
-        (num_inputs == 198 && num_actions == 240) || (num_inputs == 260 && num_actions == 300))
-        return (int)a2c_shape_n((u32)num_inputs, (u32)num_actions).params;
-    return AZUL_ERR_INVALID;
+    if (hidden_size != PF_HID || !a2c_grad(num_inputs, num_actions, 0).kernel) return AZUL_ERR_INVALID;
+    return (int)a2c_shape_n((u32)num_inputs, (u32)num_actions).params;
 }
-
-#define AZ_LN_DISPATCH(IN_, A_, launch) \
-    if (num_inputs == IN_ && num_actions == A_) { constexpr int LN_IN = IN_, LN_A = A_; launch; }
 
 // the one host body behind azul_a2c_gradients (obj 0) and azul_ppo_gradients (obj 1: LearnerArgs' PPO fields are read); `who`: the entry called
 static int a2c_gradients(const char *who, int obj, LearnerArgs a, const PolicyWeights &W, int n_samples, int num_inputs, int hidden_size,
                          int num_actions, int workspace_parts, float *grad_dev, void *stream)
 {
-    const bool reference = num_inputs == PF_IN && hidden_size == PF_HID && num_actions == PF_ACT;
     if (azul_a2c_flat_size(num_inputs, hidden_size, num_actions) < 0)
         return fail_in(who, "compiled shapes are ActorCritic(136, 180), (188, 180), (240, 180), (198, 240) and (260, 300), hidden 180");
     if (!W.w1t || !W.b1 || !W.w2c || !W.b2c || !W.w2a_t || !W.b2a || !a.w2a || !a.partial || !grad_dev || n_samples < 0 ||
@@ -1010,32 +953,19 @@ static int a2c_gradients(const char *who, int obj, LearnerArgs a, const PolicyWe
         if (!(a.value_coeff >= 0.f) || std::isinf(a.value_coeff) || !(a.entropy_coeff >= 0.f) || std::isinf(a.entropy_coeff))
             return fail_in(who, "value_coeff / entropy_coeff must be finite and >= 0");
     }
-    if (reference && (((uintptr_t)W.w2a_t & 7u) != 0 || ((uintptr_t)a.w2a & 7u) != 0 || ((uintptr_t)a.mask & 3u) != 0))
+    const A2CShapeN S = a2c_shape_n((u32)num_inputs, (u32)num_actions);
+    if (a2c_reference_layout(S) && (((uintptr_t)W.w2a_t & 7u) != 0 || ((uintptr_t)a.w2a & 7u) != 0 || ((uintptr_t)a.mask & 3u) != 0))
         return fail_in(who, "weights must be 8-byte aligned, mask_dev 4-byte aligned");
     STREAM_GUARD(stream);
     const hipStream_t st = (hipStream_t)stream;
-    const u32 total = a2c_shape_n((u32)num_inputs, (u32)num_actions).params + 4u;
-    const u32 per_pass = reference ? LG_M : LN_M;            // samples per pass of the shape's gradient kernel (azul_learner.hpp)
-    const u32 tiles = ((u32)n_samples + per_pass - 1) / per_pass;
+    const u32 total = S.params + 4u;
+    const A2CGrad g = a2c_grad(num_inputs, num_actions, obj);      // the shape's gradient kernel with its grid and block (azul_learner.hpp)
+    const u32 tiles = ((u32)n_samples + g.per_pass - 1) / g.per_pass;
     const u32 parts = tiles < (u32)workspace_parts ? tiles : (u32)workspace_parts;
     if (parts == 0) { HIP_TRY(hipMemsetAsync(grad_dev, 0, sizeof(float) * total, st)); return AZUL_SUCCESS; }
-    const dim3 grid(parts, 3), block(64 * LN_WAVES);      // the wide shapes: three workgroup roles per part (azul_learner.hpp)
-    if (obj == 0) {
-        if (reference) hipLaunchKernelGGL(azul_a2c_grad_kernel<0>, dim3(parts), dim3(64 * LG_WAVES), 0, st, W, a);
-        AZ_LN_DISPATCH(188, 180, hipLaunchKernelGGL((azul_a2c_grad_n_kernel<LN_IN, LN_A, 0>), grid, block, 0, st, W, a))
-        AZ_LN_DISPATCH(240, 180, hipLaunchKernelGGL((azul_a2c_grad_n_kernel<LN_IN, LN_A, 0>), grid, block, 0, st, W, a))
-        AZ_LN_DISPATCH(198, 240, hipLaunchKernelGGL((azul_a2c_grad_n_kernel<LN_IN, LN_A, 0>), grid, block, 0, st, W, a))
-        AZ_LN_DISPATCH(260, 300, hipLaunchKernelGGL((azul_a2c_grad_n_kernel<LN_IN, LN_A, 0>), grid, block, 0, st, W, a))
-    } else {
-        if (reference) hipLaunchKernelGGL(azul_a2c_grad_kernel<1>, dim3(parts), dim3(64 * LG_WAVES), 0, st, W, a);
-        AZ_LN_DISPATCH(188, 180, hipLaunchKernelGGL((azul_a2c_grad_n_kernel<LN_IN, LN_A, 1>), grid, block, 0, st, W, a))
-        AZ_LN_DISPATCH(240, 180, hipLaunchKernelGGL((azul_a2c_grad_n_kernel<LN_IN, LN_A, 1>), grid, block, 0, st, W, a))
-        AZ_LN_DISPATCH(198, 240, hipLaunchKernelGGL((azul_a2c_grad_n_kernel<LN_IN, LN_A, 1>), grid, block, 0, st, W, a))
-        AZ_LN_DISPATCH(260, 300, hipLaunchKernelGGL((azul_a2c_grad_n_kernel<LN_IN, LN_A, 1>), grid, block, 0, st, W, a))
-    }
+    hipLaunchKernelGGL(g.kernel, dim3(parts, g.roles), dim3(64 * g.waves), 0, st, W, a);
     const dim3 rgrid((total + 255) / 256), rblock(256);
-    if (reference) hipLaunchKernelGGL(azul_a2c_reduce_kernel, rgrid, rblock, 0, st, (const float *)a.partial, parts, grad_dev);
-    else hipLaunchKernelGGL(azul_a2c_reduce_n_kernel, rgrid, rblock, 0, st, (const float *)a.partial, parts, total, grad_dev);
+    a2c_reduce_launch(S, [&](auto k, auto... x) { hipLaunchKernelGGL(k, rgrid, rblock, 0, st, x...); }, (const float *)a.partial, parts, grad_dev);
     HIP_TRY(hipGetLastError());
     return AZUL_SUCCESS;
 }
@@ -1091,12 +1021,8 @@ static int a2c_apply_adam(const char *who, const float *grad_dev, float *flat_de
     const dim3 grid((S.params + 255) / 256), block(256);
     const float c1 = (float)bc1, c2s = (float)sqrt(bc2);
     if (step_dev) hipLaunchKernelGGL(azul_a2c_step_kernel, dim3(1), dim3(64), 0, hs, step_dev, n_total_dev);
-    if (num_inputs == PF_IN && num_actions == PF_ACT)        // the reference shape: its layout is a compile-time constant of the kernel
-        hipLaunchKernelGGL(azul_a2c_apply_kernel, grid, block, 0, hs, grad_dev, flat_dev, exp_avg_dev, exp_avg_sq_dev, lr, beta1, beta2, eps, c1, c2s, P,
-                           (const i32 *)step_dev, n_total_dev, n_total_host, stats_out_dev);
-    else
-        hipLaunchKernelGGL(azul_a2c_apply_n_kernel, grid, block, 0, hs, S, grad_dev, flat_dev, exp_avg_dev, exp_avg_sq_dev, lr, beta1, beta2, eps, c1, c2s,
-                           P, (const i32 *)step_dev, n_total_dev, n_total_host, stats_out_dev);
+    a2c_apply_launch(S, [&](auto k, auto... x) { hipLaunchKernelGGL(k, grid, block, 0, hs, x...); }, grad_dev, flat_dev, exp_avg_dev, exp_avg_sq_dev, lr,
+                     beta1, beta2, eps, c1, c2s, P, (const i32 *)step_dev, n_total_dev, n_total_host, stats_out_dev);
     HIP_TRY(hipGetLastError());
     return AZUL_SUCCESS;
 }
@@ -1203,7 +1129,9 @@ static int launch_runner_x(azul_batch_t *b, const azx::XRun &a0, const char *who
     a.count = b->d.n;
     const dim3 grid((a.count + 1u) / 2u), block(64);
     const azx::XBatchDev xb = xdev(b);
-    AZ_X_DISPATCH(b, hipLaunchKernelGGL((azul_x_runner_kernel<PP, DD>), grid, block, 0, (hipStream_t)stream, xb, a));
+    const auto k = x_for_shape(b->players, b->displays, [](auto s) { return azul_x_runner_kernel<s.P, s.D>; });
+    if (!k) return fail_shape();
+    hipLaunchKernelGGL(k, grid, block, 0, (hipStream_t)stream, xb, a);
     HIP_TRY(hipGetLastError());
     return AZUL_SUCCESS;
 }
@@ -1295,7 +1223,9 @@ static int mp_net(azul_batch_t *b, int op, const int32_t *actions_dev, const uin
     if (owing_dev) HIP_TRY(hipMemsetAsync(owing_dev, 0, sizeof(uint32_t), (hipStream_t)stream));
     const dim3 grid((a.count + 1u) / 2u), block(64);
     const azx::XBatchDev xb = xdev(b);
-    AZ_X_DISPATCH(b, hipLaunchKernelGGL((azul_x_net_kernel<PP, DD>), grid, block, 0, (hipStream_t)stream, xb, a));
+    const auto k = x_for_shape(b->players, b->displays, [](auto s) { return azul_x_net_kernel<s.P, s.D>; });
+    if (!k) return fail_shape();
+    hipLaunchKernelGGL(k, grid, block, 0, (hipStream_t)stream, xb, a);
     HIP_TRY(hipGetLastError());
     return AZUL_SUCCESS;
 }
@@ -1338,7 +1268,9 @@ int azul_batch_mp_score_moves(azul_batch_t *b, int perspective, const uint8_t *a
     a.active = active_dev; a.scores = scores_dev; a.best = best_dev; a.persp = perspective;
     const dim3 grid((b->d.n + 1u) / 2u), block(64);
     const azx::XBatchDev xb = xdev(b);
-    AZ_X_DISPATCH(b, hipLaunchKernelGGL((azul_x_score_moves_kernel<PP, DD>), grid, block, 0, (hipStream_t)stream, xb, a));
+    const auto k = x_for_shape(b->players, b->displays, [](auto s) { return azul_x_score_moves_kernel<s.P, s.D>; });
+    if (!k) return fail_shape();
+    hipLaunchKernelGGL(k, grid, block, 0, (hipStream_t)stream, xb, a);
     HIP_TRY(hipGetLastError());
     return AZUL_SUCCESS;
 }
@@ -1466,6 +1398,27 @@ int azul_game_call(azul_batch_t *b, azul_call_t *c, void *stream)
     return AZUL_SUCCESS;
 }
 
+// A batch with a move limit runs the self-play instantiation that carries the limit's code (azul_batch_set_move_limit); so does a batch whose
+// records the host has written -- only a handed-in state can stop on a rule error, and that instantiation marks and counts the slots a
+// stopped game no longer plays (move_limit == 0 is "no limit" there too).  The launch and the resource query both ask here.
+static bool marks_stopped_games(const azul_batch_t *b) { return b->d.move_limit || b->handed_in; }
+
+// Inside a timed region the first AZ_TIMED_PAIRS self-play launches are bracketed by their own event pair (the kernel's duration, not the
+// distance between launches): _begin before the launch, _end behind it.
+static int timed_launch_begin(azul_batch_t *b, hipStream_t st)
+{
+    if (!b->timing || b->timed_pairs >= AZ_TIMED_PAIRS) return AZUL_SUCCESS;
+    while ((int)b->lev.size() < 2 * (b->timed_pairs + 1)) { hipEvent_t e; HIP_TRY(hipEventCreate(&e)); b->lev.push_back(e); }
+    HIP_TRY(hipEventRecord(b->lev[2 * b->timed_pairs], st));
+    return AZUL_SUCCESS;
+}
+static int timed_launch_end(azul_batch_t *b, hipStream_t st)
+{
+    if (b->timing && b->timed_pairs < AZ_TIMED_PAIRS) { HIP_TRY(hipEventRecord(b->lev[2 * b->timed_pairs + 1], st)); b->timed_pairs++; }
+    if (b->timing) b->timed_launches++;
+    return AZUL_SUCCESS;
+}
+
 int azul_batch_selfplay_strided(azul_batch_t *b, int n_steps, uint8_t *mask_dev, int mask_row_bytes, uint64_t *maskbits_dev, int32_t *action_dev,
                                 int32_t *reward_dev, uint8_t *done_dev, uint32_t *packed_dev, uint8_t *rec_dev, void *stream)
 {
@@ -1473,6 +1426,11 @@ int azul_batch_selfplay_strided(azul_batch_t *b, int n_steps, uint8_t *mask_dev,
     if (!b || n_steps < 0) return fail(AZUL_ERR_INVALID, "azul_batch_selfplay: bad arguments");
     if (mask_row_bytes < AZUL_NUM_ACTIONS) return fail(AZUL_ERR_INVALID, "azul_batch_selfplay: mask rows hold 180 bytes, mask_row_bytes >= 180");
     if (n_steps == 0) return AZUL_SUCCESS;
+    const bool none = !mask_dev && !maskbits_dev && !action_dev && !reward_dev && !done_dev && !rec_dev && !packed_dev;
+    const bool core = mask_dev && action_dev && reward_dev && done_dev && packed_dev && !rec_dev;     // + maskbits_dev or not
+    const bool full = core && maskbits_dev;
+    const dim3 grid((b->d.n + 1u) / 2u), block(64);
+    const hipStream_t st = (hipStream_t)stream;
     if (b->x) {
         // three / four players and extended-rule batches (row N4): the flat loop mask -> RandomAgent -> Azul.step with a fresh Azul + new_round()
         // at each game end; two games per wavefront on the wide record (azul_rules_x.hpp); `reward` all zero (the shaped reward is
@@ -1481,64 +1439,29 @@ int azul_batch_selfplay_strided(azul_batch_t *b, int n_steps, uint8_t *mask_dev,
         if (mask_row_bytes < NA) return fail(AZUL_ERR_INVALID, "azul_batch_selfplay: mask rows hold azul_batch_num_actions bytes, mask_row_bytes must not be smaller");
         if ((u64)n_steps * b->d.n * (u64)(rec_dev && mask_row_bytes < AZUL_RECORD_BYTES_WIDE ? AZUL_RECORD_BYTES_WIDE : mask_row_bytes) >= (1ull << 32))
             return fail(AZUL_ERR_INVALID, "azul_batch_selfplay: a trajectory stream of one launch must stay below 4 GiB (use fewer moves per launch)");
-        const azx::XBatchDev xb = xdev(b);
         const azx::XTraj t = {n_steps, mask_dev, (u64 *)maskbits_dev, action_dev, reward_dev, done_dev, rec_dev, packed_dev, (u32)mask_row_bytes};
-        const bool none = !mask_dev && !maskbits_dev && !action_dev && !reward_dev && !done_dev && !rec_dev && !packed_dev;
-        const bool core = mask_dev && action_dev && reward_dev && done_dev && packed_dev && !rec_dev;     // + maskbits_dev or not
         // padded rows (8-byte aligned, room for ceil(NA / 8) 8-byte chunks; five displays: >= 192 like the two-player kernel) take the
         // one-store-per-row path
         const bool pad = mask_row_bytes % 8 == 0 && mask_row_bytes >= (b->displays == 5 ? 192 : NAP) && ((uintptr_t)mask_dev & 7u) == 0u;
-        const dim3 grid((b->d.n + 1u) / 2u), block(64);
-        const hipStream_t st = (hipStream_t)stream;
-        const bool pair = b->timing && b->timed_pairs < AZ_TIMED_PAIRS;       // per-launch event pair inside a timed region (as below)
-        if (pair) {
-            while ((int)b->lev.size() < 2 * (b->timed_pairs + 1)) { hipEvent_t e; HIP_TRY(hipEventCreate(&e)); b->lev.push_back(e); }
-            HIP_TRY(hipEventRecord(b->lev[2 * b->timed_pairs], st));
-        }
-        if (none) AZ_X_DISPATCH(b, hipLaunchKernelGGL((azul_x_selfplay_kernel<PP, DD, 0, false, false>), grid, block, 0, st, xb, t));
-        else if (core && pad && maskbits_dev) AZ_X_DISPATCH(b, hipLaunchKernelGGL((azul_x_selfplay_kernel<PP, DD, 1, true, true>), grid, block, 0, st, xb, t));
-        else if (core && pad) AZ_X_DISPATCH(b, hipLaunchKernelGGL((azul_x_selfplay_kernel<PP, DD, 1, true, false>), grid, block, 0, st, xb, t));
-        else AZ_X_DISPATCH(b, hipLaunchKernelGGL((azul_x_selfplay_kernel<PP, DD, 2, false, false>), grid, block, 0, st, xb, t));
+        const x_selfplay_kernel_t k = x_selfplay_kernel(b->players, b->displays, selfplay_variant(none, core, full, pad));
+        if (!k) return fail_shape();
+        if (int rc = timed_launch_begin(b, st)) return rc;
+        hipLaunchKernelGGL(k, grid, block, 0, st, xdev(b), t);
         HIP_TRY(hipGetLastError());
-        if (pair) { HIP_TRY(hipEventRecord(b->lev[2 * b->timed_pairs + 1], st)); b->timed_pairs++; }
-        if (b->timing) b->timed_launches++;
-        return AZUL_SUCCESS;
+        return timed_launch_end(b, st);
     }
     if ((u64)n_steps * b->d.n * (u64)(rec_dev && mask_row_bytes < AZUL_RECORD_BYTES ? AZUL_RECORD_BYTES : mask_row_bytes) >= (1ull << 32))
         return fail(AZUL_ERR_INVALID, "azul_batch_selfplay: a trajectory stream of one launch must stay below 4 GiB (use fewer moves per launch)");
     TrajArgs t = {n_steps, mask_dev, (u64 *)maskbits_dev, action_dev, reward_dev, done_dev, rec_dev, packed_dev};
-    const bool none = !mask_dev && !maskbits_dev && !action_dev && !reward_dev && !done_dev && !rec_dev && !packed_dev;
-    const bool core = mask_dev && action_dev && reward_dev && done_dev && packed_dev && !rec_dev;     // + maskbits_dev or not
-    const bool full = core && maskbits_dev;
-    const dim3 grid((b->d.n + 1u) / 2u), block(64);
-    const hipStream_t st = (hipStream_t)stream;
     const u32 ms = (u32)mask_row_bytes;
     // padded rows (>= 192 bytes, 8-byte aligned: alloc_trajectory(mask_pitch = 192)) take the one-store-per-row path
     const bool pad = ms >= 192u && ms % 8u == 0u && ((uintptr_t)mask_dev & 7u) == 0u;
-#define AZ_LAUNCH(LID, LIM) do { \
-        if (none) hipLaunchKernelGGL((azul_selfplay2_kernel<LID, 0, false, false, LIM>), grid, block, 0, st, b->d, t, ms); \
-        else if (full && pad) hipLaunchKernelGGL((azul_selfplay2_kernel<LID, 1, true, true, LIM>), grid, block, 0, st, b->d, t, ms); \
-        else if (core && pad) hipLaunchKernelGGL((azul_selfplay2_kernel<LID, 1, true, false, LIM>), grid, block, 0, st, b->d, t, ms); \
-        else if (full) hipLaunchKernelGGL((azul_selfplay2_kernel<LID, 1, false, true, LIM>), grid, block, 0, st, b->d, t, ms); \
-        else hipLaunchKernelGGL((azul_selfplay2_kernel<LID, 2, false, false, LIM>), grid, block, 0, st, b->d, t, ms); \
-    } while (0)
-    // inside a timed region the first AZ_TIMED_PAIRS launches are bracketed by their own event pair (the kernel's duration,
-    // not the distance between launches)
-    const bool pair = b->timing && b->timed_pairs < AZ_TIMED_PAIRS;
-    if (pair) {
-        while ((int)b->lev.size() < 2 * (b->timed_pairs + 1)) { hipEvent_t e; HIP_TRY(hipEventCreate(&e)); b->lev.push_back(e); }
-        HIP_TRY(hipEventRecord(b->lev[2 * b->timed_pairs], st));
-    }
-    // (a batch with a move limit runs the instantiation that carries the limit's code: azul_batch_set_move_limit; so does a batch whose
-    // records the host has written -- only a handed-in state can stop on a rule error, and that instantiation marks and counts the slots a
-    // stopped game no longer plays; move_limit == 0 is "no limit" there too)
-    if (b->d.move_limit || b->handed_in) { if (b->d.rules.tile_pool == POOL_LID) AZ_LAUNCH(true, true); else AZ_LAUNCH(false, true); }
-    else { if (b->d.rules.tile_pool == POOL_LID) AZ_LAUNCH(true, false); else AZ_LAUNCH(false, false); }
-#undef AZ_LAUNCH
+    const selfplay2_kernel_t k = selfplay2_kernel(b->d.rules.tile_pool == POOL_LID, marks_stopped_games(b), selfplay_variant(none, core, full, pad));
+    if (!k) return fail(AZUL_ERR_INVALID, "azul_batch_selfplay: no kernel is compiled for these trajectory streams");
+    if (int rc = timed_launch_begin(b, st)) return rc;
+    hipLaunchKernelGGL(k, grid, block, 0, st, b->d, t, ms);
     HIP_TRY(hipGetLastError());
-    if (pair) { HIP_TRY(hipEventRecord(b->lev[2 * b->timed_pairs + 1], st)); b->timed_pairs++; }
-    if (b->timing) b->timed_launches++;
-    return AZUL_SUCCESS;
+    return timed_launch_end(b, st);
 }
 
 int azul_batch_selfplay(azul_batch_t *b, int n_steps, uint8_t *mask_dev, uint64_t *maskbits_dev, int32_t *action_dev,
@@ -1633,13 +1556,9 @@ int azul_selfplay_kernel_resources(azul_batch_t *b, int padded_rows, int mask_bi
 {
     BATCH_GUARD(b, nullptr);
     if (!b || b->x) return fail(AZUL_ERR_INVALID, "azul_selfplay_kernel_resources: two-player reference batches");
-    const bool lid = b->d.rules.tile_pool == POOL_LID, lim = b->d.move_limit != 0 || b->handed_in;
-    const void *fn;
-#define AZ_PICK(LID, LIM) (padded_rows ? (mask_bits ? (const void *)azul_selfplay2_kernel<LID, 1, true, true, LIM> : (const void *)azul_selfplay2_kernel<LID, 1, true, false, LIM>) \
-                                       : (mask_bits ? (const void *)azul_selfplay2_kernel<LID, 1, false, true, LIM> : (const void *)azul_selfplay2_kernel<LID, 2, false, false, LIM>))
-    if (lim) fn = lid ? AZ_PICK(true, true) : AZ_PICK(false, true);
-    else fn = lid ? AZ_PICK(true, false) : AZ_PICK(false, false);
-#undef AZ_PICK
+    // the launch's own selector, asked for the core streams with or without the mask bits / padded rows
+    const void *fn = (const void *)selfplay2_kernel(b->d.rules.tile_pool == POOL_LID, marks_stopped_games(b),
+                                                    selfplay_variant(false, true, mask_bits != 0, padded_rows != 0));
     hipFuncAttributes at;
     HIP_TRY(hipFuncGetAttributes(&at, fn));
     int blocks = 0;

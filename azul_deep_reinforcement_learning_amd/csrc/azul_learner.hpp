@@ -1140,3 +1140,43 @@ __global__ void __launch_bounds__(64 * LN_WAVES) azul_a2c_grad_n_kernel(PolicyWe
 }
 
 #undef LN_LANE
+
+// ---- which kernels an update runs, stated ONCE (host side): a2c_gradients / a2c_apply_adam of azul_kernels.hip and the lockstep
+// emulation (tests/hostcheck/simt_a2c_launch.hpp) launch what these name ----------------------------------------------------------------
+// The gradient kernel of a compiled shape (hidden 180; the one list of them) for the objective obj (0 A2C, otherwise PPO): grid
+// (parts, roles) x 64 * waves threads, per_pass samples per pass.  kernel == nullptr: the shape is not compiled in.
+struct A2CGrad { void (*kernel)(PolicyWeights, LearnerArgs); u32 roles, waves, per_pass; };
+template <int IN, int A>
+static A2CGrad a2c_grad_n(int obj)                       // the wide shapes: three workgroup roles per part
+{
+    return {obj == 0 ? azul_a2c_grad_n_kernel<IN, A, 0> : azul_a2c_grad_n_kernel<IN, A, 1>, 3u, (u32)LN_WAVES, (u32)LN_M};
+}
+static A2CGrad a2c_grad(int num_inputs, int num_actions, int obj)
+{
+    if (num_inputs == PF_IN && num_actions == PF_ACT) return {obj == 0 ? azul_a2c_grad_kernel<0> : azul_a2c_grad_kernel<1>, 1u, LG_WAVES, (u32)LG_M};
+    if (num_inputs == 188 && num_actions == 180) return a2c_grad_n<188, 180>(obj);
+    if (num_inputs == 240 && num_actions == 180) return a2c_grad_n<240, 180>(obj);
+    if (num_inputs == 198 && num_actions == 240) return a2c_grad_n<198, 240>(obj);
+    if (num_inputs == 260 && num_actions == 300) return a2c_grad_n<260, 300>(obj);
+    return {nullptr, 0u, 0u, 0u};
+}
+
+// The reduce and the Adam step: the reference shape's layout is a compile-time constant of its kernels, every other shape hands its
+// layout to the _n form.  run(kernel, its arguments...) performs the launch.
+static bool a2c_reference_layout(const A2CShapeN &S) { return S.in == (u32)PF_IN && S.act == (u32)PF_ACT; }
+template <class Run>
+static void a2c_reduce_launch(const A2CShapeN &S, Run &&run, const float *partial, u32 parts, float *grad)
+{
+    if (a2c_reference_layout(S)) run(azul_a2c_reduce_kernel, partial, parts, grad);
+    else run(azul_a2c_reduce_n_kernel, partial, parts, S.params + 4u, grad);
+}
+template <class Run>
+static void a2c_apply_launch(const A2CShapeN &S, Run &&run, const float *grad, float *flat, float *m, float *v, float lr, float beta1, float beta2,
+                             float eps, float bias_c1, float bias_c2_sqrt, const ModuleParams &P, const i32 *step_dev, const float *n_total_dev,
+                             float n_total_host, float *stats_out)
+{
+    if (a2c_reference_layout(S))
+        run(azul_a2c_apply_kernel, grad, flat, m, v, lr, beta1, beta2, eps, bias_c1, bias_c2_sqrt, P, step_dev, n_total_dev, n_total_host, stats_out);
+    else
+        run(azul_a2c_apply_n_kernel, S, grad, flat, m, v, lr, beta1, beta2, eps, bias_c1, bias_c2_sqrt, P, step_dev, n_total_dev, n_total_host, stats_out);
+}

@@ -20,7 +20,7 @@
 #pragma once
 
 #include "azul_env2.hpp"
-#include "azul_rules_x.hpp"     // the wide-record rules of x_policy_rollout_body below
+#include "azul_x_kernels.hpp"   // the wide-record rules of x_policy_rollout_body below (azul_rules_x.hpp) and the list of compiled shapes
 
 constexpr u32 PR2_WAVES = 8;
 constexpr u32 PR2_AHEAD = 6;       // k-steps of layer-1 weights in flight (3..6 measured alike, 8 and 12 slower: profiles/round3_policy_rollout_phases.txt)
@@ -1129,4 +1129,66 @@ __global__ void __launch_bounds__(64 * PR2_WAVES) azul_x_policy_rollout_vs_kerne
     __shared__ PXShared<P, D> S;
     __shared__ PXOpp<D> O;
     x_policy_rollout_body<P, D, 2, LEAGUE, ARENA>(b, W, a, id_base, S, &O, max_replies);
+}
+
+// ---- the host side of a window launch, stated ONCE: which instantiation runs and what it is handed.  rollout_window (azul_kernels.hip)
+// and the lockstep emulation (tests/hostcheck/simt_rollout2.cpp, simt_x_rollout.cpp) launch what these return -------------------------
+// opp = 0 the policy on every seat, 1 RandomAgent seats, 2 a network, 3 greedy; any other: nullptr.  A two-player league is <LID, 2>.
+typedef void (*rollout2_kernel_t)(BatchDev, PolicyWeights, RolloutArgs);
+template <bool LID>
+static rollout2_kernel_t rollout2_kernel_of(int opp, bool arena)
+{
+    if (opp == 2 && arena) return azul_policy_rollout2_kernel<LID, 2, true>;
+    if (opp == 3) return azul_policy_rollout2_kernel<LID, 3>;
+    if (opp == 2) return azul_policy_rollout2_kernel<LID, 2>;
+    if (opp == 1) return azul_policy_rollout2_kernel<LID, 1>;
+    if (opp == 0) return azul_policy_rollout2_kernel<LID, 0>;
+    return nullptr;
+}
+static rollout2_kernel_t rollout2_kernel(bool lid, int opp, bool arena)
+{
+    return lid ? rollout2_kernel_of<true>(opp, arena) : rollout2_kernel_of<false>(opp, arena);
+}
+
+// ... of a wide batch: six kinds over the shapes of x_for_shape.  opp 0 / 1 do not read the last argument, max_replies: pass 0
+typedef void (*x_rollout_kernel_t)(azx::XBatchDev, PolicyWeights, RolloutArgs, u32, u32);
+template <u32 P, u32 D>
+static x_rollout_kernel_t x_rollout_kernel_of(int opp, bool league, bool arena)
+{
+    if (opp == 2 && arena) return azul_x_policy_rollout_vs_kernel<P, D, true, true>;
+    if (opp == 2 && league) return azul_x_policy_rollout_vs_kernel<P, D, true>;
+    if (opp == 2) return azul_x_policy_rollout_vs_kernel<P, D>;
+    if (opp == 3) return azul_x_policy_rollout_kernel<P, D, 3>;
+    if (opp == 1) return azul_x_policy_rollout_kernel<P, D, 1>;
+    if (opp == 0) return azul_x_policy_rollout_kernel<P, D, 0>;
+    return nullptr;
+}
+static x_rollout_kernel_t x_rollout_kernel(int players, int displays, int opp, bool league, bool arena)
+{
+    return x_for_shape(players, displays, [&](auto s) { return x_rollout_kernel_of<s.P, s.D>(opp, league, arena); });
+}
+
+// What a window kernel is handed, from the public structs (include/azul_hip.h) once rollout_window has checked them
+struct DrawKeys { uint64_t seed, opp_seed, counter; uint64_t *counter_dev; };
+// azul_batch_[mp_]policy_rollout_league: the pool behind `opponent`.  agent_member_dev (azul_batch_[mp_]policy_rollout_arena): the same pool is
+// behind `agent` too, one member per group for the agent seat
+struct League { int pool_size; const uint8_t *member_dev; const uint8_t *agent_member_dev; bool arena; };
+
+static void window_pack(bool wide, int n_steps, int opp, const azul_net_weights_t *agent, const azul_net_weights_t *opponent, DrawKeys keys,
+                        const azul_rollout_buffers_t *out, float gamma, const League *league, PolicyWeights &W, RolloutArgs &a)
+{
+    W = {agent->w1t, agent->b1, agent->w2c, agent->b2c, agent->w2a_t, agent->b2a};
+    // returns: the two-player kernel writes a window of up to 32 steps itself (it keeps the rewards in 32 lanes); the wide kernels never do
+    a = RolloutArgs{n_steps, out->obs, out->mask, out->player, out->action, out->reward, out->done, out->value, out->logp, out->entropy, out->status,
+                    wide ? nullptr : out->returns, gamma, (u64)keys.seed, (u64)keys.counter, (u64 *)keys.counter_dev};
+    if (opp == 2) {                                          // (without a network opponent the opponent fields of `out` are ignored)
+        a.Wopp = {opponent->w1t, opponent->b1, opponent->w2c, opponent->b2c, opponent->w2a_t, opponent->b2a};
+        a.opp_seed = (u64)keys.opp_seed;
+        a.opp_action = out->opp_action; a.opp_logp = out->opp_logp; a.opp_replies = out->opp_replies; a.opp_slots = out->opp_slots;
+        if (league) { a.opp_member = league->member_dev; a.opp_pool = (u32)league->pool_size; }      // a base offset per workgroup, nothing else
+        if (league && league->arena) { a.agent_member = league->agent_member_dev; a.agent_pool = (u32)league->pool_size; }
+    }
+    if (opp == 3) {                                          // the greedy player's trace: its answers and their number (opp_logp is never written)
+        a.opp_action = out->opp_action; a.opp_replies = out->opp_replies; a.opp_slots = out->opp_slots;
+    }
 }

@@ -300,3 +300,25 @@ __global__ void __launch_bounds__(64) azul_selfplay2_kernel(BatchDev b, TrajArgs
     az2::wave_record(b.wave_prof, wstamps, wave_id, wave_id * 2u + 1u < b.n, prof, r.regens, lane);
 #endif
 }
+
+// Which instantiation a launch runs (host side): azul_batch_selfplay_strided launches what this returns, azul_selfplay_kernel_resources
+// reports its registers.  v: selfplay_variant (azul_common.hpp); lim: the instantiation with the move limit's code.  nullptr: not compiled.
+typedef void (*selfplay2_kernel_t)(BatchDev, TrajArgs, u32);
+template <bool LID, bool LIM>
+static selfplay2_kernel_t selfplay2_kernel_of(SelfplayVariant v)
+{
+    if (v.out == 0) return azul_selfplay2_kernel<LID, 0, false, false, LIM>;
+    if (v.out == 1 && v.pad) return v.bits ? azul_selfplay2_kernel<LID, 1, true, true, LIM> : azul_selfplay2_kernel<LID, 1, true, false, LIM>;
+    if (v.out == 1 && v.bits) return azul_selfplay2_kernel<LID, 1, false, true, LIM>;
+    if (v.out == 2) return azul_selfplay2_kernel<LID, 2, false, false, LIM>;
+    return nullptr;
+}
+// (A template only for WHERE its kernels land in the code object: they are instantiated at the first call, in the self-play entry at the end
+// of azul_kernels.hip, behind every other kernel -- the benchmarked one page-aligned at 0x554000, as in every build before.  Chosen in this
+// header they came first, the same code at 0x8e800, and bench.py ran 0.3-0.7 % slower: LABNOTES.md.)
+template <class V>
+static selfplay2_kernel_t selfplay2_kernel(bool lid, bool lim, V v)
+{
+    if (lim) return lid ? selfplay2_kernel_of<true, true>(v) : selfplay2_kernel_of<false, true>(v);
+    return lid ? selfplay2_kernel_of<true, false>(v) : selfplay2_kernel_of<false, false>(v);
+}

@@ -57,3 +57,37 @@ __global__ void __launch_bounds__(64) azul_x_score_moves_kernel(azx::XBatchDev b
 {
     azx::score_moves_body_x<P, D>(b, a, blockIdx.x);
 }
+
+// ---- host side: the five compiled (players, displays) shapes, the ONE list of them for the library (azul_kernels.hip) and the lockstep
+// emulation (tests/hostcheck): f(XShape<P, D>()) -- a kernel of that shape, s.P and s.D being constants -- for a batch's shape, nullptr
+// for any other (azul_batch_create_rules admits only these five)
+template <u32 P_, u32 D_>
+struct XShape { static constexpr u32 P = P_, D = D_; };
+
+template <class F>
+static auto x_for_shape(int players, int displays, F f) -> decltype(f(XShape<2, 5>()))
+{
+    const int pd = players * 16 + displays;
+    if (pd == 2 * 16 + 5) return f(XShape<2, 5>());
+    if (pd == 3 * 16 + 5) return f(XShape<3, 5>());
+    if (pd == 3 * 16 + 7) return f(XShape<3, 7>());
+    if (pd == 4 * 16 + 5) return f(XShape<4, 5>());
+    if (pd == 4 * 16 + 9) return f(XShape<4, 9>());
+    return nullptr;
+}
+
+// The flat self-play kernel of a shape for the trajectory streams `v` (azul_common.hpp: selfplay_variant).  The wide kernels have no
+// unpadded OUT 1 form: such rows go through OUT 2's run-time subset.
+typedef void (*x_selfplay_kernel_t)(azx::XBatchDev, azx::XTraj);
+template <u32 P, u32 D>
+static x_selfplay_kernel_t x_selfplay_kernel_of(SelfplayVariant v)
+{
+    if (v.out == 0) return azul_x_selfplay_kernel<P, D, 0, false, false>;
+    if (v.out == 1 && v.pad && v.bits) return azul_x_selfplay_kernel<P, D, 1, true, true>;
+    if (v.out == 1 && v.pad) return azul_x_selfplay_kernel<P, D, 1, true, false>;
+    return azul_x_selfplay_kernel<P, D, 2, false, false>;
+}
+static x_selfplay_kernel_t x_selfplay_kernel(int players, int displays, SelfplayVariant v)
+{
+    return x_for_shape(players, displays, [&](auto s) { return x_selfplay_kernel_of<s.P, s.D>(v); });
+}

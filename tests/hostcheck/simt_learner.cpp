@@ -14,9 +14,6 @@ using namespace az;
 #include "azul_learner.hpp"
 #include "simt_a2c_launch.hpp"
 
-struct GradJob { PolicyWeights W; LearnerArgs a; };
-static void grad_lane(void *arg) { GradJob *j = (GradJob *)arg; azul_a2c_grad_kernel(j->W, j->a); }
-
 struct FwdJob { const float *obs; const uint8_t *mask; PolicyWeights W; u64 seed, counter; u32 n; float *value; i32 *action; float *logp, *entropy, *logits; u32 id_base; };
 static void fwd_lane(void *arg)
 {
@@ -44,18 +41,11 @@ long long sl_gradients_dev(int n, int parts, const float *obs, const uint8_t *ma
                            const i32 *n_dev, const float *inv_n_dev, const float *w1t, const float *b1, const float *w2c, const float *b2c,
                            const float *w2a_t, const float *b2a, const float *w2a, float *partial /* [parts][LG_P_TOTAL] */, float *grad)
 {
-    GradJob j;
-    memset(&j, 0, sizeof(j));
-    j.W = {w1t, b1, w2c, b2c, w2a_t, b2a};
-    j.a.obs = obs; j.a.mask = mask; j.a.action = action; j.a.qvals = qvals; j.a.n = (u32)n; j.a.inv_n = inv_n; j.a.w2a = w2a;
-    j.a.partial = partial; j.a.index = index; j.a.n_dev = n_dev; j.a.inv_n_dev = inv_n_dev;
-    simt::g_grid_dim = {(unsigned)parts, 1, 1};
-    long long ops = 0;
-    for (int blk = 0; blk < parts; blk++) {
-        simt::g_block_idx = {(unsigned)blk, 0, 0};
-        ops += (long long)simt::run_workgroup(grad_lane, &j, (int)LG_WAVES, 512u << 10);
-    }
-    return ops + run_reduce(LG_SHAPE, partial, parts, grad);
+    LearnerArgs a;
+    memset(&a, 0, sizeof(a));
+    a.obs = obs; a.mask = mask; a.action = action; a.qvals = qvals; a.n = (u32)n; a.inv_n = inv_n; a.w2a = w2a;
+    a.partial = partial; a.index = index; a.n_dev = n_dev; a.inv_n_dev = inv_n_dev;
+    return run_gradients(PF_IN, PF_ACT, 0, {w1t, b1, w2c, b2c, w2a_t, b2a}, a, parts) + run_reduce(LG_SHAPE, partial, parts, grad);
 }
 
 long long sl_gradients(int n, int parts, const float *obs, const uint8_t *mask, const i32 *action, const float *qvals, const i32 *index, float inv_n,

@@ -28,7 +28,7 @@ extern "C" {
 long long shx_score_moves(int n_games, int players, int displays, uint8_t *state, u32 *mt, u32 *mtpos, u64 *episodes, u32 *stuck, double *stat_sum,
                           int first_player, int pool, int end_bonus, int short_deal, int persp, const uint8_t *active, i32 *scores, i32 *best)
 {
-    lane_fn fn = SIMT_X_PICK(lane_run, players, displays);
+    lane_fn fn = x_for_shape(players, displays, [](auto s) { return (lane_fn)lane_run<s.P, s.D>; });
     if (!fn || n_games <= 0) return -1;
     SJob j;
     memset(&j, 0, sizeof(j));

@@ -26,7 +26,7 @@ long long shx_net(int n_games, int players, int displays, uint8_t *state, u32 *m
                   int first_player, int pool, int end_bonus, int short_deal, int op, const i32 *actions, const uint8_t *active, uint8_t *pending,
                   uint8_t *replies, i32 *reward, uint8_t *done, uint8_t *status, float *obs, uint8_t *mask, u32 *owing)
 {
-    lane_fn fn = SIMT_X_PICK(lane_run, players, displays);
+    lane_fn fn = x_for_shape(players, displays, [](auto s) { return (lane_fn)lane_run<s.P, s.D>; });
     if (!fn || n_games <= 0) return -1;
     NJob j;
     memset(&j, 0, sizeof(j));

@@ -40,7 +40,7 @@ long long shx_selfplay(int n_games, int players, int displays, uint8_t *state, u
                        int first_player, int pool, int end_bonus, int short_deal, unsigned long long margin, int n_steps, int variant,
                        uint8_t *mask, int pitch, u64 *maskbits, i32 *action, i32 *reward, uint8_t *done, u32 *packed, uint8_t *rec)
 {
-    lane_fn fn = SIMT_X_PICK(lane_play, players, displays);
+    lane_fn fn = x_for_shape(players, displays, [](auto s) { return (lane_fn)lane_play<s.P, s.D>; });
     const double2 *tab = table_for(displays);
     if (!fn || !tab || n_games <= 0 || n_steps < 0) return -1;
     XJob j;
@@ -56,7 +56,7 @@ int shx_op(uint8_t *rec, int players, int displays, int first_player, int pool, 
            int action, u32 *mt, u32 *pos, const uint8_t *mask_in, uint8_t *mask_out, float *obs, int persp, int *flags, double *stats10,
            int *action_out, int *player, int *rng_dirty, int *next_action /* NULL: not asked for */, unsigned pos_set /* 0, or 1 + index */)
 {
-    lane_fn fn = SIMT_X_PICK(lane_op, players, displays);
+    lane_fn fn = x_for_shape(players, displays, [](auto s) { return (lane_fn)lane_op<s.P, s.D>; });
     const double2 *tab = table_for(displays);
     if (!fn || !tab) return -1;
     u64 episodes = 0; u32 stuck = 0; double stat_sum[10] = {0};

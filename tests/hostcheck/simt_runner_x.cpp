@@ -26,7 +26,7 @@ long long shx_runner(int n_games, int players, int displays, uint8_t *state, u32
                      int first_player, int pool, int end_bonus, int short_deal, int op, const i32 *actions, const uint8_t *active, i32 *reward,
                      uint8_t *done, uint8_t *status, i32 *potential, int persp, float *obs, uint8_t *mask, uint8_t *player)
 {
-    lane_fn fn = SIMT_X_PICK(lane_run, players, displays);
+    lane_fn fn = x_for_shape(players, displays, [](auto s) { return (lane_fn)lane_run<s.P, s.D>; });
     const double2 *tab = table_for(displays);
     if (!fn || !tab || n_games <= 0) return -1;
     RJob j;

@@ -37,27 +37,27 @@ struct SimtWindowCall {
     int32_t opp_slots;
 };
 
-#ifdef __HIPCC__               // ---- the shims' side; they include this after csrc/azul_policy.hpp
-// The call -> the agent's weights and the RolloutArgs of its kind, as rollout_window fills them; `league` / `arena` = what the member
-// arrays say.  Returns -1 where a call is refused: an unknown opp, no games, a league / arena with a missing member array or a pool_size
-// outside 1..255.
+#ifdef __HIPCC__               // ---- the shims' side; they include this after csrc/azul_rollout2.hpp
+// The call -> the public structs -> the agent's weights and the RolloutArgs of its kind, filled by the library's own window_pack
+// (csrc/azul_rollout2.hpp; rollout_window calls the same); `league` / `arena` = what the member arrays say.  Returns -1 where a call cannot be
+// emulated: no games, a league / arena with a missing member array or a pool_size outside 1..255.  (An unknown opp is the kernel
+// selectors' refusal.)
 static int window_args(const SimtWindowCall &c, bool wide, PolicyWeights &W, RolloutArgs &a, bool &league, bool &arena)
 {
-    const bool net = c.opp == 2;
-    league = net && (c.opp_member || c.agent_member);
+    league = c.opp == 2 && (c.opp_member || c.agent_member);
     arena = league && c.agent_member;
-    if (c.opp < 0 || c.opp > 3 || c.n_games <= 0) return -1;
+    if (c.n_games <= 0) return -1;
     if (league && (!c.opp_member || c.pool_size < 1 || c.pool_size > 255)) return -1;
-    W = {c.agent[0], c.agent[1], c.agent[2], c.agent[3], c.agent[4], c.agent[5]};
-    a = RolloutArgs{c.n_steps, c.obs, c.mask, c.player, c.action, c.reward, c.done, c.value, c.logp, c.entropy, c.status,
-                    wide ? nullptr : c.returns, c.gamma, c.seed, c.counter, nullptr};
-    if (net) {
-        a.Wopp = arena ? W : PolicyWeights{c.opponent[0], c.opponent[1], c.opponent[2], c.opponent[3], c.opponent[4], c.opponent[5]};
-        a.opp_seed = c.opp_seed;
-        if (league) { a.opp_member = c.opp_member; a.opp_pool = (u32)c.pool_size; }
-        if (arena) { a.agent_member = c.agent_member; a.agent_pool = (u32)c.pool_size; }
-    }
-    if (net || c.opp == 3) { a.opp_action = c.opp_action; a.opp_logp = c.opp_logp; a.opp_replies = c.opp_replies; a.opp_slots = c.opp_slots; }
+    const azul_net_weights_t agent = {c.agent[0], c.agent[1], c.agent[2], c.agent[3], c.agent[4], c.agent[5]};
+    const azul_net_weights_t opponent = {c.opponent[0], c.opponent[1], c.opponent[2], c.opponent[3], c.opponent[4], c.opponent[5]};
+    const azul_rollout_buffers_t out = {c.obs, c.mask, c.player, c.action, c.reward, c.done, c.value, c.logp, c.entropy, c.status, c.returns,
+                                        c.opp_action, c.opp_logp, c.opp_replies, c.opp_slots};
+    const League lg = {c.pool_size, c.opp_member, c.agent_member, arena};
+    window_pack(wide, c.n_steps, c.opp, &agent, arena ? &agent : &opponent, {c.seed, c.opp_seed, c.counter, nullptr}, &out, c.gamma,
+                league ? &lg : nullptr, W, a);
+    // the one difference from the library, which passes the greedy kernels no opp_logp: here they get it, so that the tests can show it is
+    // never written
+    if (c.opp == 3) a.opp_logp = c.opp_logp;
     return 0;
 }
 #endif

@@ -1,16 +1,11 @@
 // simt_x_common.hpp -- TEST-ONLY: what the shims of the WIDE kernels share (simt_rules_x.cpp, simt_runner_x.cpp, simt_net_x.cpp,
-// simt_mp_score_moves.cpp, simt_x_rollout.cpp): the pick among the five compiled (players, displays) shapes, the RandomAgent table of a
-// display count, the azx::XBatchDev every entry builds from its arguments, and the launch loop.  The shims call the product's
-// __global__ functions (csrc/azul_x_kernels.hpp, csrc/azul_rollout2.hpp) and declare no LDS of their own.  Included after those headers.
+// simt_mp_score_moves.cpp, simt_x_rollout.cpp): the RandomAgent table of a display count, the azx::XBatchDev every entry builds from its
+// arguments, and the launch loop.  The shims call the product's __global__ functions (csrc/azul_x_kernels.hpp, csrc/azul_rollout2.hpp),
+// picked for a (players, displays) by the product's own selectors over its one list of shapes (csrc/azul_x_kernels.hpp: x_for_shape),
+// and declare no LDS of their own.  Included after those headers.
 #pragma once
 
 typedef void (*lane_fn)(void *);
-
-// FN<P, D> for the shape (players, displays) of AZ_X_DISPATCH (csrc/azul_kernels.hip), or nullptr
-#define SIMT_X_PICK(FN, players, displays)                                                                                              \
-    ((players) == 2 && (displays) == 5 ? (lane_fn)FN<2, 5> : (players) == 3 && (displays) == 5 ? (lane_fn)FN<3, 5>                        \
-     : (players) == 3 && (displays) == 7 ? (lane_fn)FN<3, 7> : (players) == 4 && (displays) == 5 ? (lane_fn)FN<4, 5>                      \
-     : (players) == 4 && (displays) == 9 ? (lane_fn)FN<4, 9> : (lane_fn)nullptr)
 
 // the sampling table of a batch with `displays` displays (azul_batch_create builds the same: 5 (displays + 1) + 1 rows), or nullptr
 static const double2 *table_for(int displays)

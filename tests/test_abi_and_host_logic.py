@@ -191,6 +191,59 @@ def test_the_benchmark_never_hands_records_into_the_batch_it_measures():
     records, so bench.py must not call set_records on it (its never-ending-games A/B copies records on the device: BatchedAzul.records_dev)."""
     bench = open(os.path.join(ROOT, "bench.py")).read()
     assert "set_records(" not in bench and "set_state" not in bench
-    host = open(os.path.join(ROOT, "azul_deep_reinforcement_learning_amd", "csrc", "azul_kernels.hip")).read()
+    host = _code(os.path.join(ROOT, "azul_deep_reinforcement_learning_amd", "csrc", "azul_kernels.hip"))
     assert host.count("b->handed_in = true;") == 2                      # the two entries that write a caller's record into the batch
-    assert "if (b->d.move_limit || b->handed_in)" in host               # ... and the launch that follows them
+    # ... the one statement of "this batch runs the marking instantiation", which nothing else in the file restates ...
+    assert "static bool marks_stopped_games(const azul_batch_t *b) { return b->d.move_limit || b->handed_in; }" in host
+    assert host.count("b->handed_in") == 3 and host.count("move_limit ||") == 1
+    # ... and its two callers: the launch that follows those entries, and the resource query bench.py reports the launch's registers from
+    launch = host[host.index("int azul_batch_selfplay_strided("):host.index("int azul_batch_selfplay(")]
+    query = host[host.index("int azul_selfplay_kernel_resources("):host.index("int azul_pack_c1(")]
+    for body in (launch, query):
+        assert body.count("selfplay2_kernel(b->d.rules.tile_pool == POOL_LID, marks_stopped_games(b),") == 1 and body.count("selfplay2_kernel(") == 1
+
+
+def _code(path):
+    """A source file without its comments: /* ... */ blocks, comment lines and the trailing comment of a code line."""
+    lines = [re.sub(r"\s*//.*$", "", ln) for ln in re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S).splitlines()]
+    return "\n".join(ln for ln in lines if ln.strip())
+
+
+def test_every_kernel_instantiation_is_chosen_in_one_place_per_family():
+    """Which template instantiation of a __global__ kernel a launch runs is stated once, by a host function next to the kernels in the csrc
+    headers; azul_kernels.hip (the launch and the resource query) and the lockstep emulation's shims call it.  So neither spells a
+    template-id of those kernels, and the old per-file dispatch macros are gone."""
+    import glob
+    csrc = os.path.join(ROOT, "azul_deep_reinforcement_learning_amd", "csrc")
+    host = _code(os.path.join(csrc, "azul_kernels.hip"))
+    shims = {os.path.basename(f): _code(f) for pat in ("*.cpp", "*.hpp") for f in glob.glob(os.path.join(ROOT, "tests", "hostcheck", pat))}
+    assert len(shims) >= 19
+    for kernel in ("azul_policy_rollout2_kernel", "azul_x_policy_rollout_kernel", "azul_x_policy_rollout_vs_kernel", "azul_a2c_grad_n_kernel"):
+        assert not re.search(kernel + r"\s*<", host), kernel
+        for name, text in shims.items():
+            assert not re.search(kernel + r"\s*<", text), (kernel, name)
+    # self-play: no product host code names an instantiation (the shims' explicit variants name one on purpose)
+    for kernel in ("azul_selfplay2_kernel", "azul_x_selfplay_kernel"):
+        assert not re.search(kernel + r"\s*<", host), kernel
+    everything = [host] + list(shims.values()) + [_code(f) for f in glob.glob(os.path.join(csrc, "*.hpp"))]
+    for macro in ("SIMT_X_PICK", "AZ_LAUNCH", "AZ_PICK", "AZ_LN_DISPATCH", "AZ_X_DISPATCH"):
+        for text in everything:
+            assert macro not in text, macro
+    # the selectors are where the kernels are, and the library launches through them
+    for header, names in (("azul_rollout2.hpp", ("rollout2_kernel(", "x_rollout_kernel(", "window_pack(")),
+                          ("azul_x_kernels.hpp", ("x_for_shape(", "x_selfplay_kernel(")),
+                          ("azul_selfplay_kernels.hpp", ("selfplay2_kernel(",)),
+                          ("azul_learner.hpp", ("a2c_grad(", "a2c_reduce_launch(", "a2c_apply_launch("))):
+        text = _code(os.path.join(csrc, header))
+        for n in names:
+            assert "static " in text and re.search(r"\b" + re.escape(n), text), (header, n)
+            assert re.search(r"\b" + re.escape(n), host), n
+
+
+def test_the_window_shims_refuse_what_the_librarys_selectors_have_no_kernel_for():
+    """An unknown kind of opponent (two-player shim) and an unknown (players, displays) (wide shim) are refused by rollout2_kernel /
+    x_rollout_kernel of csrc/azul_rollout2.hpp returning no kernel: the shims have no list of their own."""
+    from tests.hostcheck import window
+    assert window.run(window.load2(), n_games=1, opp=4) < 0
+    assert window.run(window.load_x(), n_games=1, players=2, displays=7, opp=0) < 0
+    assert window.run(window.load_x(), n_games=1, players=3, displays=5, opp=4) < 0
