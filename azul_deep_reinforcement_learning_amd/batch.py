@@ -354,6 +354,32 @@ class BatchedAzul:
         L.check(self._gr.score_moves(self._h, self.PERSP_TO_MOVE, _ptr(self._dev(active, torch.uint8)), None, _ptr(best), self._stream()))
         return best
 
+    def playout_moves(self, playouts=8, seed=0, call=0, perspective=None, active=None, sums=None, best=None):
+        """The flat Monte-Carlo table in one launch, the games untouched: sums [N][180] int32, for every legal action the sum over
+        `playouts` (1 .. L.PLAYOUTS_MAX) random playouts of score[p] - score[1 - p] at the END OF THE ROUND -- the move, then both seats
+        play uniformly over their legal pattern-line moves (floor moves only when nothing else is legal) until the round ends, then
+        count_score (include/azul_hip.h: azul_batch_playout_moves has the playout, step by step) -- L.SCORE_ILLEGAL elsewhere; best [N] int32,
+        the first legal action with the maximal sum (-1: nothing is legal).  The draws are Philox4x32-10 words keyed by `seed` (64 bits) at
+        counters of (action, ply, playout, the game's GLOBAL id, `call` (32 bits)): the same arguments give the same table wherever a game
+        sits in a batch; nothing is drawn from the games' MT19937 streams.  `perspective`, `active`, `sums` / `best` as score_moves' arguments.
+        Two-player reference batches only (a wide batch is refused by the library).  Returns (sums, best)."""
+        if sums is None:
+            sums = torch.full((self.n, L.NUM_ACTIONS), L.SCORE_ILLEGAL, dtype=torch.int32, device=self.device)
+        if best is None:
+            best = torch.full((self.n,), -1, dtype=torch.int32, device=self.device)
+        L.check(L.lib.azul_batch_playout_moves(self._h, int(L.PERSP_CURRENT if perspective is None else perspective), int(playouts),
+                                               int(seed) & 0xFFFFFFFFFFFFFFFF, int(call) & 0xFFFFFFFF, _ptr(self._dev(active, torch.uint8)),
+                                               _ptr(sums), _ptr(best), self._stream()))
+        return sums, best
+
+    def playout_action(self, playouts=8, seed=0, call=0, active=None, out=None):
+        """The flat Monte-Carlo player: for every game the move with the maximal playout_moves sum from the mover's perspective (-1: nothing
+        is legal).  `out`: a preallocated int32 [N]; games whose `active` is 0 keep what it held."""
+        best = torch.full((self.n,), -1, dtype=torch.int32, device=self.device) if out is None else out
+        L.check(L.lib.azul_batch_playout_moves(self._h, L.PERSP_CURRENT, int(playouts), int(seed) & 0xFFFFFFFFFFFFFFFF, int(call) & 0xFFFFFFFF,
+                                               _ptr(self._dev(active, torch.uint8)), None, _ptr(best), self._stream()))
+        return best
+
     # -- policy-driven self-play (config 3) ----------------------------------------------------------
     def observe_all(self, perspective=L.PERSP_CURRENT, obs=None, mask=None, player=None):
         obs = self._new((self.n, self.obs_size), torch.float32) if obs is None else obs

@@ -60,6 +60,25 @@ AZ_FN void observe2(const G2 &g, u32 persp, float *lds_row, float *glob, u32 l)
     }
 }
 
+// ---- the legal action of ordinal `want` (counted from 0, ascending action order) as a move code: p1 .. p5 are the counts of legal actions
+// below mask words 1 .. 5.  The one statement of the step for random_agent2 and playout_agent2 below.
+AZ_FN u32 ordinal_code2(const Mask2 &m, u32 want, u32 p1, u32 p2, u32 p3, u32 p4, u32 p5, const K2 &k)
+{
+    const u32 l = k.l;
+    const bool g1 = want >= p1, g2 = want >= p2, g3 = want >= p3, g4 = want >= p4, g5 = want >= p5;
+    // (the selects as a tree of depth three -- the g's are monotone, g5 => g4 => .. => g1 -- instead of a chain of five: -0.45 % on the headline kernel)
+    const u32 w01 = g1 ? m.m[1] : m.m[0], w23 = g3 ? m.m[3] : m.m[2], w45 = g5 ? m.m[5] : m.m[4];
+    const u32 b01 = g1 ? p1 : 0u, b23 = g3 ? p3 : p2, b45 = g5 ? p5 : p4;
+    const u32 mword = g4 ? w45 : (g2 ? w23 : w01);
+    const u32 base = g4 ? b45 : (g2 ? b23 : b01);
+    const u32 prow_ = (u32)g1 + (u32)g2 + (u32)g3 + (u32)g4 + (u32)g5;
+    // my bit is set AND its rank among the word's set bits is the wanted one, as ONE compare (a ballot of an and of two compares goes
+    // through a 0 / 1 register): 2 (rank - wanted) + bit == 1
+    const bool hit = (((u32)__popc(mword & ((1u << l) - 1u)) - (want - base)) << 1) + ((mword >> l) & 1u) == 1u;
+    const u32 ln = (u32)__builtin_ctz(hb(hit) | 0x80000000u);
+    return hbcast(k.lcode, ln) | (prow_ << 13) | ((30u * prow_ + ln) << 17);
+}
+
 // ---- RandomAgent.get_a_output (game_runner.py:87-97): selfplay_step2's decision as a function --------------------------------------
 // Returns false when nothing is legal (ValueError in the reference, raised BEFORE random() is called: no words consumed).
 AZ_FN bool random_agent2(const Mask2 &m, Rng2 &r, const Tab2 &T, const K2 &k, u32 &code)
@@ -87,20 +106,19 @@ AZ_FN bool random_agent2(const Mask2 &m, Rng2 &r, const Tab2 &T, const K2 &k, u3
         const double sT = M ? sJ : T.fs[9u * Jc].y;      // the boundary search works on CPython's own x = random() * (S[J] + 0.0)
         kg = sample_slow2(T, M ? x : u * (sT + 0.0), sT, J, M, L);
     }
-    const u32 want = kg - 1u;
-    const bool g1 = want >= p1, g2 = want >= p2, g3 = want >= p3, g4 = want >= p4, g5 = want >= p5;
-    // (the selects as a tree of depth three -- the g's are monotone, g5 => g4 => .. => g1 -- instead of a chain of five: -0.45 % on the headline kernel)
-    const u32 w01 = g1 ? m.m[1] : m.m[0], w23 = g3 ? m.m[3] : m.m[2], w45 = g5 ? m.m[5] : m.m[4];
-    const u32 b01 = g1 ? p1 : 0u, b23 = g3 ? p3 : p2, b45 = g5 ? p5 : p4;
-    const u32 mword = g4 ? w45 : (g2 ? w23 : w01);
-    const u32 base = g4 ? b45 : (g2 ? b23 : b01);
-    const u32 prow_ = (u32)g1 + (u32)g2 + (u32)g3 + (u32)g4 + (u32)g5;
-    // my bit is set AND its rank among the word's set bits is the wanted one, as ONE compare (a ballot of an and of two compares goes
-    // through a 0 / 1 register): 2 (rank - wanted) + bit == 1
-    const bool hit = (((u32)__popc(mword & ((1u << l) - 1u)) - (want - base)) << 1) + ((mword >> l) & 1u) == 1u;
-    const u32 ln = (u32)__builtin_ctz(hb(hit) | 0x80000000u);
-    code = hbcast(k.lcode, ln) | (prow_ << 13) | ((30u * prow_ + ln) << 17);
+    code = ordinal_code2(m, kg - 1u, p1, p2, p3, p4, p5, k);
     return true;
+}
+
+// ---- the flat Monte-Carlo playout's move (azul_ops2.hpp: playout_moves_body2): uniform over the legal pattern-line moves, the floor moves
+// only when nothing else is legal; `w` is the 32-bit word that decides.  False (nothing played) when nothing is legal.
+AZ_FN bool playout_agent2(const Mask2 &m, u32 w, const K2 &k, u32 &code)
+{
+    const u32 c0 = __popc(m.m[0]), c1 = __popc(m.m[1]), c2 = __popc(m.m[2]), c3 = __popc(m.m[3]), c4 = __popc(m.m[4]), c5 = __popc(m.m[5]);
+    const u32 p1 = c0, p2 = p1 + c1, p3 = p2 + c2, p4 = p3 + c3, p5 = p4 + c4, L = p5 + c5;
+    const u32 M = L - c0, n = M ? M : c0, base = M ? c0 : 0u;
+    code = ordinal_code2(m, base + __umulhi(w, n), p1, p2, p3, p4, p5, k);      // (L == 0: ordinal 0 of an empty mask, a code nobody plays)
+    return L != 0u;
 }
 
 // the same packing for an action given by number

@@ -11,6 +11,8 @@
 // Kernels
 //   azul_seed_kernel            one THREAD per game: CPython init_by_array is a strictly sequential 1247-step recurrence
 //   azul_op_kernel              every single-call rule / runner entry point of the ABI for two-player batches (azul_ops2.hpp)
+//   azul_score_moves_kernel, azul_playout_moves_kernel    every legal move of every game priced on a copy: one ply exactly / by random
+//                               playouts to the end of the round (azul_ops2.hpp); the games are only read
 //   azul_x_op_kernel            the rule entries for batches of 3- / 4-player games and for extended-rule batches (row N4;
 //                               azul_x_kernels.hpp on azul_rules_x.hpp: 256-byte wide records)
 //   azul_selfplay2_kernel       state register-resident across n_steps env moves (the hot path); azul_x_selfplay_kernel: row N4's
@@ -1116,6 +1118,8 @@ int azul_batch_score_moves(azul_batch_t *b, int perspective, const uint8_t *acti
     return AZUL_SUCCESS;
 }
 
+// (azul_batch_playout_moves, the table by random playouts, is the LAST entry of this file: see there)
+
 // ---- GameRunner for P seats (azul_rules_x.hpp: runner_body_x): the azul_batch_mp_* entries ------------------------------------------------------
 // One launch over the whole batch, no host synchronisation, no allocation: capturable in a HIP graph.  Wide batches only; a two-player
 // reference batch is refused with the name of its own entry (`twin`).
@@ -1636,6 +1640,34 @@ int azul_timing_launch_ms(azul_batch_t *b, float *launch_ms, int cap, int *n)
     if (!b || b->timing || cap < 0 || (cap > 0 && !launch_ms)) return fail(AZUL_ERR_INVALID, "azul_timing_launch_ms: after azul_timing_end, with room for `cap` values");
     for (int i = 0; i < b->timed_pairs && i < cap; i++) HIP_TRY(hipEventElapsedTime(launch_ms + i, b->lev[2 * i], b->lev[2 * i + 1]));
     if (n) *n = b->timed_pairs;
+    return AZUL_SUCCESS;
+}
+
+// ---- the flat Monte-Carlo table -------------------------------------------------------------------------------------------------------------
+// The last entry of the file on purpose: playout_moves_kernel is a template that instantiates azul_playout_moves_kernel at its first call,
+// here, so the two kernels land BEHIND the self-play kernels in the code object and no older kernel moves relative to another (the
+// code starts 0x600 later: the two kernels' descriptors and metadata precede it).  Instantiated in the middle of the file they sat in
+// front of the benchmarked kernel and pushed it 0x2c00 along (csrc/azul_selfplay_kernels.hpp: selfplay2_kernel; LABNOTES.md).
+// every legal move's sum over `playouts` random playouts to the end of the round and the move with the maximal sum (azul_ops2.hpp:
+// playout_moves_body2): one launch, the games are only read
+int azul_batch_playout_moves(azul_batch_t *b, int perspective, int playouts, uint64_t seed, uint32_t call, const uint8_t *active_dev,
+                             int32_t *sums_dev, int32_t *best_dev, void *stream)
+{
+    BATCH_GUARD(b, stream);
+    if (!b) return fail(AZUL_ERR_INVALID, "batch is NULL");
+    if (b->x) return fail(AZUL_ERR_INVALID, "azul_batch_playout_moves: a wide batch (three / four players or extended rules): the playouts run on "
+                                            "the two-player rule book, two-player reference batches only");
+    if (playouts < 1 || playouts > AZUL_PLAYOUTS_MAX)
+        return fail(AZUL_ERR_INVALID, "azul_batch_playout_moves: playouts must be in 1 .. AZUL_PLAYOUTS_MAX (256)");
+    if (!sums_dev && !best_dev) return fail(AZUL_ERR_INVALID, "azul_batch_playout_moves: sums_dev and best_dev are both NULL");
+    if (perspective != AZUL_PERSP_PLAYER0 && perspective != AZUL_PERSP_PLAYER1 && perspective != AZUL_PERSP_CURRENT)
+        return fail(AZUL_ERR_INVALID, "azul_batch_playout_moves: perspective must be 0, 1 or AZUL_PERSP_CURRENT");
+    PlayoutMovesArgs a;
+    a.active = active_dev; a.sums = sums_dev; a.best = best_dev; a.persp = perspective;
+    a.playouts = (u32)playouts; a.call = call; a.seed = seed;
+    const dim3 grid((b->d.n + 1u) / 2u), block(64);
+    hipLaunchKernelGGL(playout_moves_kernel(b->d.rules.tile_pool == POOL_LID), grid, block, 0, (hipStream_t)stream, b->d, a);
+    HIP_TRY(hipGetLastError());
     return AZUL_SUCCESS;
 }
 

@@ -345,3 +345,111 @@ AZ_FN void score_moves_body2(const BatchDev &b, const ScoreMovesArgs &a, u32 pai
 }
 
 } // namespace az2
+
+// ---- azul_playout_moves_kernel's body: THE FLAT MONTE-CARLO TABLE -- every legal move priced by random playouts to the end of the round ------
+// For every legal action a of every game the SUM over k < playouts of score[p] - score[1 - p] after: a copy of the game, the unchecked
+// move(*nn_deserialize(a)) (azul.py:118-161), then while the round lasts (is_end_of_round :182-183) next_player (:177-181) and one move of
+// the playout policy -- uniform over the legal pattern-line moves of check_all_valid (game_runner.py:113-117), floor moves only when
+// nothing else is legal (playout_agent2, azul_env2.hpp) -- and count_score() (:192-295) on the state the playout stopped in: the end of
+// the round, a player with nothing legal (the token alone in the centre), or PLAYOUT_MAX_PLIES moves (a guard: a round holds at most 20
+// source groups, and the centre grows by at most three colours per emptied display).  A playout deals no tiles and reads no MT19937 word:
+// ply `ply` of playout k of candidate a of global game G draws word 0 of Philox4x32-10 at counter (a | ply << 16, k, G, call) under key
+// `seed`, so a game's row does not depend on where the game sits in a batch.  The games are only read; no LDS, no sampler table.
+struct PlayoutMovesArgs {
+    const uint8_t *active;   // [n] in, optional: games with 0 are not looked at and their rows are not written
+    i32 *sums;               // [n][180] out, optional: the table; AZUL_SCORE_ILLEGAL where the legal mask holds 0
+    i32 *best;               // [n] out, optional: first legal action with the maximal sum, -1 when nothing is legal
+    int persp;               // 0, 1 or AZUL_PERSP_CURRENT (the player to move)
+    u32 playouts;            // K, 1 .. AZUL_PLAYOUTS_MAX: |sum| <= K * 2^16 fits an i32
+    u32 call;                // counter word 3
+    u64 seed;                // the Philox key
+};
+
+__device__ __forceinline__ u32 philox_u32_words(u32 c0, u32 c1, u32 c2, u32 c3, u64 seed);      // azul_policy.hpp, beside philox_u32
+
+namespace az2 {
+
+constexpr u32 PLAYOUT_MAX_PLIES = 64;
+
+// The table of games 2 pair and 2 pair + 1: score_moves_body2's wave-uniform candidate loop and its six named result registers per lane;
+// per candidate, `playouts` playouts on a register copy of the game.  The two halves of a wave finish a playout at different plies: a half
+// that has stopped (`live` false -- also the half whose mask lacks the candidate) moves no more, under a per-half `if` behind a wave_any
+// as apply_step2 scores a round end, and is scored with the other half on the state it stopped in once neither moves.
+// The maximum is taken in two half-wave steps (a sum of 256 score differences does not fit score_key's 17 bits): every lane keeps the
+// first of its own candidates with its maximal sum, the half's maximal sum is found, then the lowest action among the lanes that hold it.
+template <bool LID>
+AZ_FN void playout_moves_body2(const BatchDev &b, const PlayoutMovesArgs &a, u32 pair)
+{
+    const u32 lane = wv::lane(), l = lane & 31u, half = lane >> 5;
+    const u32 gi = 2u * pair + half;
+    if (gi >= b.n) return;                           // odd batch: the last wave serves one game
+    if (a.active && a.active[gi] == 0) return;
+    K2 k;
+    k2_init(k);
+    G2 g;
+    g2_load(g, b.state + (size_t)gi * AZUL_RECORD_BYTES, l);
+    prime2(g, k);
+    Mask2 m;
+    legal_mask2(g, k, m);
+    const u32 me = me2(g);
+    const u32 p = a.persp == AZUL_PERSP_CURRENT ? me : (u32)a.persp;
+    const u32 G = b.id_base + gi;                    // the global game id
+    i32 s0 = SCORE_ILLEGAL, s1 = SCORE_ILLEGAL, s2 = SCORE_ILLEGAL, s3 = SCORE_ILLEGAL, s4 = SCORE_ILLEGAL, s5 = SCORE_ILLEGAL;
+    i32 top = SCORE_ILLEGAL;                         // my candidates' maximal sum so far and the first action that reached it
+    u32 top_act = 0;
+#pragma unroll 1
+    for (u32 row = 0; row < 6u; row++) {
+        const u32 word = row == 0u ? m.m[0] : row == 1u ? m.m[1] : row == 2u ? m.m[2] : row == 3u ? m.m[3] : row == 4u ? m.m[4] : m.m[5];
+#pragma unroll 1
+        for (u32 ln = 0; ln < 30u; ln++) {
+            const bool legal = ((word >> ln) & 1u) != 0u;
+            if (!wave_any(legal)) continue;
+            const u32 act = 30u * row + ln;
+            const u32 first = action_code2(act, k);
+            i32 sum = 0;
+#pragma unroll 1
+            for (u32 kk = 0; kk < a.playouts; kk++) {
+                G2 t = g;
+                do_move2<LID>(t, first, g.B, k);                                   // azul.py:118-161 (total for every action number: whatif_after2)
+                t.B = hb(t.cs != 0u) & 0x7fffffffu;
+                bool live = legal;
+#pragma unroll 1
+                for (u32 ply = 0; ply < PLAYOUT_MAX_PLIES; ply++) {
+                    live = live & (t.B != 0u);                                     // :182-183
+                    t.cur = live ? ((t.cur < 2u) ? t.cur + 1u : 1u) : t.cur;       // :177-181
+                    Mask2 pm;
+                    legal_mask2(t, k, pm);
+                    u32 code;
+                    live = playout_agent2(pm, philox_u32_words(act | (ply << 16), kk, G, a.call, a.seed), k, code) & live;
+                    if (!wave_any(live)) break;
+                    if (live) {
+                        do_move2<LID>(t, code, t.B, k);
+                        t.B = hb(t.cs != 0u) & 0x7fffffffu;
+                    }
+                }
+                count_score2<LID>(t, k);                                           // :192-295
+                sum += t.score0 - t.score1;
+            }
+            const i32 v = p == 0u ? sum : -sum;
+            const bool mine = legal & (l == ln);
+            s0 = (mine & (row == 0u)) ? v : s0; s1 = (mine & (row == 1u)) ? v : s1; s2 = (mine & (row == 2u)) ? v : s2;
+            s3 = (mine & (row == 3u)) ? v : s3; s4 = (mine & (row == 4u)) ? v : s4; s5 = (mine & (row == 5u)) ? v : s5;
+            const bool better = mine & (v > top);                                  // (ascending action order: the first of equal sums stays)
+            top = better ? v : top;
+            top_act = better ? act : top_act;
+        }
+    }
+    if (a.sums && l < 30u) {
+        i32 *out = a.sums + (size_t)gi * AZUL_NUM_ACTIONS + l;
+        out[0] = s0; out[30] = s1; out[60] = s2; out[90] = s3; out[120] = s4; out[150] = s5;
+    }
+    if (a.best) {
+        // |sum| <= 256 * 2^16 = 2^24: sum + 2^30 is a positive number, 0 = no legal action of mine (lanes 30, 31 hold 0)
+        const u32 vkey = top != SCORE_ILLEGAL ? (u32)(top + (1 << 30)) : 0u;
+        const u32 vmax = hmax(vkey);
+        const u32 amax = hmax(((vkey == vmax) & (vmax != 0u)) ? 256u - top_act : 0u);
+        if (l == 0u) a.best[gi] = vmax ? (i32)(256u - amax) : -1;
+    }
+}
+
+} // namespace az2

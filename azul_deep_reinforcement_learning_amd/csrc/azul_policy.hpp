@@ -30,6 +30,14 @@ __device__ __forceinline__ u32 philox_u32(u64 seed, u64 counter, u32 game)
     return c0;
 }
 
+// the same block for a caller that lays out the four counter words itself (azul_ops2.hpp: playout_moves_body2, which declares it ahead)
+__device__ __forceinline__ u32 philox_u32_words(u32 c0, u32 c1, u32 c2, u32 c3, u64 seed)
+{
+    u32 k0 = (u32)seed, k1 = (u32)(seed >> 32);
+    for (int i = 0; i < 10; i++) { philox_round(c0, c1, c2, c3, k0, k1); k0 += 0x9E3779B9u; k1 += 0xBB67AE85u; }
+    return c0;
+}
+
 __device__ __forceinline__ float policy_uniform(u64 seed, u64 counter, u32 game)      // [0, 1), 24 bits
 {
     return (float)(philox_u32(seed, counter, game) >> 8) * (1.0f / 16777216.0f);

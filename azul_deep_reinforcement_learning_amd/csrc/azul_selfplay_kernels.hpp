@@ -33,6 +33,23 @@ __global__ void __launch_bounds__(64) azul_score_moves_kernel(BatchDev b, ScoreM
     az2::score_moves_body2<LID>(b, a, blockIdx.x);
 }
 
+// Every legal move's sum over random playouts to the end of the round and the move with the maximal sum (azul_ops2.hpp:
+// playout_moves_body2), the games untouched: the same grid, ceil(n / 2) one-wave workgroups, two games per wavefront
+template <bool LID>
+__global__ void __launch_bounds__(64) azul_playout_moves_kernel(BatchDev b, PlayoutMovesArgs a)
+{
+    az2::playout_moves_body2<LID>(b, a, blockIdx.x);
+}
+// Which instantiation a launch runs (host side): azul_batch_playout_moves and the lockstep emulation's shim launch what this returns.
+// (A template, like selfplay2_kernel below: the kernels are instantiated where the selector is first called, so a file that includes this
+// header without azul_policy.hpp's Philox block -- the other shims -- instantiates nothing that needs it.)
+typedef void (*playout_moves_kernel_t)(BatchDev, PlayoutMovesArgs);
+template <class B>
+static playout_moves_kernel_t playout_moves_kernel(B lid)
+{
+    return lid ? azul_playout_moves_kernel<true> : azul_playout_moves_kernel<false>;
+}
+
 // Discounted returns over the time-major trajectory of one launch window (reference loop: nn_runner.py:70-76,
 // qval = reward + gamma * qval backwards within an episode).  One thread per game walks its column backwards;
 // `done[t][g] != 0` ends an episode at move t; `carry[g]` holds the return flowing in from the NEXT window

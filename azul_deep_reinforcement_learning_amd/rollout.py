@@ -69,7 +69,7 @@ class PolicyRollout:
                  device=None, window=32, use_graph=True, fused_head=True, sample_seed=0x5EED, opponent=None, fused_mlp=True, persistent=False,
                  action_selection="Distribution", kweights=None, game_id_base=None, ring=1, opponent_selection="Distribution",
                  opponent_seed=None, opponent_trace=0, move_limit=0, players=2, fused_wide=False, fused_opponent=False, wide_ring=1,
-                 fused_seats=False, gae_lambda=None, bootstrap_tail=False, _pairs=None):
+                 fused_seats=False, gae_lambda=None, bootstrap_tail=False, opponent_playouts=8, _pairs=None):
         """Who answers GameRunner's opponent_move(), and what plays a window.  "window kernel": ONE launch per window and part (_WINDOW_KERNELS),
         asked for by the switch in brackets; "per move" / "per cut": the launches of _window_moves.  Two-player reference batches (players=2, no
         extended-rule key in `rules`) and wide batches (`players` = 3 / 4 or extended rules) admit:
@@ -85,6 +85,7 @@ class PolicyRollout:
                                azul_batch_policy_rollout_greedy [fused_opponent]
             "greedy_margin"    ValueError                                           per cut
                                                                                     azul_batch_mp_policy_rollout_greedy [fused_wide, fused_seats]
+            "playout"          per cut (no window kernel)                           ValueError
 
         Every other combination of an opponent with fused_wide / fused_opponent / fused_seats raises ValueError, before anything is allocated.
         A window kernel computes what the per-move / per-cut path computes: the same trajectories, records, streams and counters (wide
@@ -123,6 +124,14 @@ class PolicyRollout:
         (game_runner.py:48-50), one launch per reply round in place of the network's forward; records as with "random"; persistent and
         use_graph resolve to False, ring to 1; at most MAX_REPLY_ROUNDS reply rounds per step or opening (a game with nothing legal would owe
         its move for ever: RuntimeError).
+        opponent="playout" (`opponent_playouts` = K in 1 .. L.PLAYOUTS_MAX, default 8): the scripted flat Monte-Carlo player on the same
+        per-cut protocol -- every opponent_move() is BatchedAzul.playout_action's answer, the move with the maximal sum of score differences
+        over K random playouts to the end of the round (azul_batch_playout_moves), one launch per reply round; reply round j of agent step t
+        draws with seed = opponent_seed + j and call = (counter + t) & 0xffffffff, counter the Philox step counter at the start of the
+        window (an opening at construction: the counter before the first step, 0xffffffff), so a run restored from games_state() replays bit
+        for bit; records, trace, persistent / use_graph / ring and MAX_REPLY_ROUNDS as with "greedy".  It answers per cut only: a wide batch,
+        fused_opponent=True and fused_wide=True raise ValueError, and so does opponent_selection="Max" (the player has no distribution to
+        take the maximum of).
         opponent="greedy_margin": the same scripted player for three / four seats and extended rules -- every other seat answers with
         MultiplayerAzul.greedy_action, the move that maximises the MOVER's margin over the best other seat after move + count_score
         (azul_batch_mp_score_moves; beyond the reference for P > 2, like the wide reward), through MultiplayerAzul.net_* exactly as a network
@@ -183,7 +192,7 @@ class PolicyRollout:
         there: ValueError."""
         self._check_modes(policy, n_games, parts, rules, window, use_graph, fused_head, opponent, fused_mlp, persistent, action_selection, ring,
                           opponent_selection, opponent_trace, move_limit, players, fused_wide, fused_opponent, wide_ring, fused_seats,
-                          gae_lambda, bootstrap_tail)
+                          gae_lambda, bootstrap_tail, opponent_playouts)
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         self.policy = policy.to(self.device).eval()
         self.windows_played = 0
@@ -210,7 +219,7 @@ class PolicyRollout:
 
     def _check_modes(self, policy, n_games, parts, rules, window, use_graph, fused_head, opponent, fused_mlp, persistent, action_selection, ring,
                      opponent_selection, opponent_trace, move_limit, players, fused_wide, fused_opponent, wide_ring, fused_seats=False,
-                     gae_lambda=None, bootstrap_tail=False):
+                     gae_lambda=None, bootstrap_tail=False, opponent_playouts=8):
         """Every refusal of the constructor, then the resolution of the modes -- from the arguments and the modules' shapes alone: no device
         and no library call, so nothing is allocated before a refusal.  Three facts come out: the record family (`wide`), who answers
         opponent_move() (`opponent`, one of the kinds below) and what plays a window (`window_entry`: a row of _WINDOW_KERNELS, or None for
@@ -219,7 +228,7 @@ class PolicyRollout:
         self.n, self.parts, self.h, self.T = n_games, parts, n_games // parts, window
         self.players = int(players)
         self.wide = self.players != 2 or parse_ext_rules(rules, self.players) != 0
-        # None | "random" | "net" | "league" | "greedy" | "greedy_margin"
+        # None | "random" | "net" | "league" | "greedy" | "greedy_margin" | "playout"
         kind = opponent if opponent is None or isinstance(opponent, str) else ("league" if isinstance(opponent, (list, tuple)) else "net")
         members = list(opponent) if kind == "league" else ([opponent] if kind == "net" else [])      # the network opponents, one or a pool
         netopp = kind in ("net", "league")
@@ -248,6 +257,16 @@ class PolicyRollout:
         if kind == "greedy_margin" and not self.wide:
             raise ValueError("opponent=\"greedy_margin\" maximises the margin over the best other seat on batches of three / four players or "
                              "extended rules; a two-player reference batch has opponent=\"greedy\"")
+        if kind == "playout":
+            if self.wide or fused_wide or fused_opponent:
+                raise ValueError("opponent=\"playout\" answers per cut (one azul_batch_playout_moves launch per reply round) on two-player "
+                                 "reference batches: no wide batch (%d players / extended rules), no fused_wide=True, no fused_opponent=True -- "
+                                 "no window kernel plays it" % self.players)
+            if opponent_selection == "Max":
+                raise ValueError("opponent_selection=\"Max\" has no meaning for opponent=\"playout\": the player takes the maximal playout sum, "
+                                 "there is no distribution")
+            if not 1 <= int(opponent_playouts) <= L.PLAYOUTS_MAX:
+                raise ValueError("opponent_playouts must be in 1 .. %d, got %r" % (L.PLAYOUTS_MAX, opponent_playouts))
         if fused_seats:
             if kind != "greedy_margin":
                 raise ValueError("fused_seats=True plays the greedy_margin seats of a wide batch inside its window kernel: it needs "
@@ -299,19 +318,21 @@ class PolicyRollout:
         if kind is None and (bootstrap_tail or (lam is not None and lam < 1.0)):
             raise ValueError("gae_lambda < 1 and bootstrap_tail need the records of ONE seat (any opponent but None): consecutive records of "
                              "flat self-play belong to different seats observed with PERSP_CURRENT, so V(s_{t+1}) is another seat's value")
-        assert kind in (None, "random", "net", "league", "greedy", "greedy_margin")
+        assert kind in (None, "random", "net", "league", "greedy", "greedy_margin", "playout")
         # -- the resolution
         self.opponent, self.opp_policy = kind, (members[0] if kind == "net" else None)
         self.netopp, self.league = netopp, kind == "league"    # a network answers (one net, or a pool of them: opp_pool)
         self.opp_pool = members if self.league else None
-        self.scripted = kind in ("greedy", "greedy_margin")    # answers are env.greedy_action's: no weights, no log-probabilities
+        self.scripted = kind in ("greedy", "greedy_margin", "playout")     # answers are env.greedy_action's / playout_action's: no weights, no log-probabilities
+        self.opponent_playouts = int(opponent_playouts) if kind == "playout" else 0
         self.cut = netopp or self.scripted                     # GameRunner.step cut at its opponent_move() calls (BatchedAzul.net_*)
         self.fused_head = fused_head
         # the one-launch forward (azul_policy_forward) is compiled for the reference's ActorCritic(136, 180, hidden 180)
         self.fused_mlp = bool(fused_mlp and fused_head and not self.wide and policy.critic_linear1.in_features == L.OBS_SIZE and
                               policy.critic_linear1.out_features == 180 and policy.actor_linear2.out_features == L.NUM_ACTIONS)
         asked = {"persistent": persistent and self.fused_mlp, "fused_wide": fused_wide, "fused_opponent": fused_opponent, "fused_seats": fused_seats}
-        self.window_entry = row.entry if asked[row.switch] else None          # the whole window in ONE launch per part; same results
+        # the whole window in ONE launch per part; same results (no window kernel plays the playout opponent)
+        self.window_entry = row.entry if asked[row.switch] and kind != "playout" else None
         self.fused_wide, self.fused_opponent, self.fused_seats = bool(fused_wide), bool(fused_opponent), bool(fused_seats)
         self.fused_greedy = self.fused_opponent and kind == "greedy"
         self.persistent = self.window_entry is not None and not self.wide
@@ -507,6 +528,11 @@ class PolicyRollout:
         what net_step_* left in work["net"], reply j of the step sampled with Philox key opponent_seed + j at the step's counter."""
         w = self.work[p]
         net = w["net"]
+        if self.opponent == "playout":
+            # the flat Monte-Carlo player: reply j of a step draws with seed opponent_seed + j at the step's call (_env_step / _net_reset)
+            self.envs[p].playout_action(self.opponent_playouts, (self.opponent_seed + j) & 0xFFFFFFFFFFFFFFFF, w["playout_call"],
+                                        active=net["pending"], out=net["action"])
+            return
         if self.scripted:
             # the scripted opponent: the best move of every game that owes one, from the mover's perspective (azul_batch_score_moves /
             # azul_batch_mp_score_moves)
@@ -553,6 +579,8 @@ class PolicyRollout:
         """GameRunner.reset() with the network opponent for every game of part p (game_runner.py:76-85); its opening moves draw at the
         counter before the first step."""
         w = self.work[p]
+        if self.opponent == "playout":
+            w["playout_call"] = (int(w["counter"][0].item()) - 1) & 0xFFFFFFFF
         self.envs[p].net_reset_begin(w["net"], w["status"])
         self._reply_rounds(p, "the opening of reset()", None, None)
 
@@ -581,7 +609,7 @@ class PolicyRollout:
         raise RuntimeError("%s opponent: games %s (global ids) still owe an opponent_move() after %d reply rounds of %s (round %d); "
                            "statuses %s -- the opponent keeps answering with moves that are not legal (a forward that is not finite, or a "
                            "state with nothing legal, answers -1)"
-                           % ("greedy" if self.scripted else "network", ids[:16], rounds, where, rounds, [int(st[i]) for i in owing[:16]]))
+                           % (("playout" if self.opponent == "playout" else "greedy") if self.scripted else "network", ids[:16], rounds, where, rounds, [int(st[i]) for i in owing[:16]]))
 
     def refresh_weights(self):
         """(Re)build the fused first-layer weights from the policy's parameters -- call after every optimiser step.  The
@@ -650,6 +678,8 @@ class PolicyRollout:
             # GameRunner.step cut at its opponent_move() calls: the agent's move, then reply rounds while any game owes one (one host
             # synchronisation per round: this is the per-move reference structure, the window kernel is the fast path)
             net = w["net"]
+            if self.opponent == "playout":
+                w["playout_call"] = (w["playout_counter"] + t) & 0xFFFFFFFF
             env.net_step_begin(tr["action"][t], net, tr["reward"][t], tr["done"][t], w["status"])
             self._reply_rounds(p, "agent step %d of the window" % t, tr["reward"][t], tr["done"][t],
                                (tr["opp_action"][t], tr["opp_logp"][t]) if self.opp_slots else None)
@@ -728,6 +758,8 @@ class PolicyRollout:
     def _window_moves(self, p, gamma):
         """The window of part p move by move (what a HIP graph captures): slot T of the last window becomes slot 0, T moves, the returns scan."""
         T, tr = self.T, self.traj[p]
+        if self.opponent == "playout":                   # the Philox step counter at the start of the window (one read: this path synchronises per reply round)
+            self.work[p]["playout_counter"] = int(self.work[p]["counter"][0].item())
         tr["obs"][0].copy_(tr["obs"][T])
         tr["mask"][0].copy_(tr["mask"][T])
         tr["player"][0].copy_(tr["player"][T])

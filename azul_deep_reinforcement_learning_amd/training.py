@@ -79,7 +79,7 @@ class BatchedTrainer:
                  ring=3, opponent="random", opponent_refresh=0, move_limit=0, players=2, fused_wide=False,
                  fused_opponent=False, fused_learner=False, fused_seats=False, gae_lambda=None, bootstrap_tail=False, algorithm="a2c",
                  clip_eps=0.2, value_coeff=0.5, entropy_coeff=0.01, epochs=4, minibatches=4, normalize_advantage=True, league_size=4,
-                 league_sampling="uniform", pfsp_power=2.0):
+                 league_sampling="uniform", pfsp_power=2.0, opponent_playouts=8):
         """ring: trajectory windows kept (persistent rollout with one part): with ring >= 2 every step of every episode is trained
         exactly once (episodes straddle windows; an episode may span ring - 1 window boundaries), like NNRunner.train.
         opponent: "random" (GameRunner's default RandomAgent, the reference's scripts/training.py), a module (GameRunner(opponent=Agent(...)),
@@ -95,6 +95,11 @@ class BatchedTrainer:
         fused_wide=True and fused_seats=True (hidden 180), inside the wide window kernel (PolicyRollout(fused_seats=True)): one launch per
         window, the learner as for any fused_wide rollout (fused_learner=True trains whole episodes from the ring), still nothing in the
         checkpoint for the opponent.
+        opponent="playout" (two-player reference batches; opponent_playouts=K in 1..256): PolicyRollout's scripted flat Monte-Carlo player -- the
+        move with the maximal sum of score differences over K random playouts to the end of the round -- on the per-cut path exactly as
+        "greedy" without fused_opponent (no window kernel: fused_opponent / fused_wide raise ValueError; ring 1, update_from_windows).  The
+        opponent has no state: its draws are keyed by the Philox step counter a checkpoint already carries; checkpoints carry
+        `opponent_playouts` and a file written with another K is refused, so a resumed run replays bit for bit.
         opponent="league" (league_size=K in 1..255, opponent_refresh=k, league_sampling="uniform" | "pfsp", pfsp_power): a POOL of K frozen past
         selves (PolicyRollout(opponent=[...]): every 16-game group plays one member, inside the window kernels where a single network opponent
         plays there).  The pool starts as K copies of the initial policy; every k updates the current policy is written into slot
@@ -183,7 +188,8 @@ class BatchedTrainer:
                                      ring=ring if (persistent and parts == 1) else 1,
                                      move_limit=move_limit, players=players, fused_wide=fused_wide,
                                      fused_opponent=fused_opponent, wide_ring=ring if (wide_fused and parts == 1) else 1,
-                                     fused_seats=fused_seats, gae_lambda=gae_lambda, bootstrap_tail=bootstrap_tail)
+                                     fused_seats=fused_seats, gae_lambda=gae_lambda, bootstrap_tail=bootstrap_tail,
+                                     opponent_playouts=opponent_playouts)
         self.gamma = gamma
         self.results_dir = results_dir
         self.batch = 0
@@ -332,6 +338,8 @@ class BatchedTrainer:
         ck = {"policy": ro.policy.state_dict(), "optimizer": self.learner.optimizer_state(), "envs": envs,
               "batch": self.batch, "n_games": ro.n, "parts": ro.parts, "window": ro.T, "game_id_base": ro.game_id_base,
               "windows_played": ro.windows_played, "ring": ro.ring, "ring_saved": bool(save_ring and ro.ring > 1)}
+        if ro.opponent == "playout":                     # the scripted player's one setting (its draws follow the Philox step counter in `envs`)
+            ck["opponent_playouts"] = ro.opponent_playouts
         if ro.league:                                    # the assignment, the results and their marks, the snapshot and redraw counts
             ck["league"] = dict(ro.league_state(), snapshots=getattr(self, "snapshots", 0), redraws=getattr(self, "redraws", 0))
         if ro.netopp:                                    # the network opponent's (frozen) weights, a league's stacked: a resumed run plays the same nets
@@ -347,6 +355,9 @@ class BatchedTrainer:
         ck = torch.load(path, map_location="cpu", weights_only=False)
         if (ck["n_games"], ck["parts"], ck["window"]) != (ro.n, ro.parts, ro.T):
             raise ValueError("checkpoint was written for n_games=%d parts=%d window=%d" % (ck["n_games"], ck["parts"], ck["window"]))
+        if ro.opponent == "playout" and ck.get("opponent_playouts", ro.opponent_playouts) != ro.opponent_playouts:
+            raise ValueError("checkpoint was written for opponent_playouts=%d, this trainer plays %d"
+                             % (ck["opponent_playouts"], ro.opponent_playouts))
         ro.synchronize()
         ro.policy.load_state_dict(ck["policy"])
         self.learner.load_optimizer_state(ck["optimizer"])          # also rebuilds the flat master copy from the module

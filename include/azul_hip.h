@@ -218,6 +218,24 @@ int azul_batch_score_preview(azul_batch_t *b, int32_t *potential_dev /*[N]*/, vo
 #define AZUL_SCORE_ILLEGAL INT32_MIN
 int azul_batch_score_moves(azul_batch_t *b, int perspective, const uint8_t *active_dev, int32_t *scores_dev /*[N][180], optional*/,
                            int32_t *best_dev /*[N], optional*/, void *stream);
+/* The flat Monte-Carlo table: every legal move of every game priced by `playouts` random playouts to the END OF THE ROUND, in ONE launch,
+ * the games untouched (records, MT19937 words and index, counters).  With p = `perspective` as above, G = the game's global id
+ * (azul_batch_set_id_base + index) and a a legal action: sums[g][a] = the sum over k < playouts of score[p] - score[1 - p] after playout
+ * (a, k): a copy of game g, move(*nn_deserialize(a)) (azul.py:118-161, the unchecked move), ply = 0, then repeat { stop if is_end_of_round()
+ * (:182-183); next_player() (:177-181); mask = check_all_valid (game_runner.py:113-117), L its count: stop if L == 0 (the token alone in
+ * the centre); stop if ply == 64 (a guard: a round ends far sooner); with J the legal floor moves (actions 0..29) and M = L - J take
+ * (n, base) = (M, J) if M > 0, else (J, 0) -- uniform over the pattern-line moves, floor moves only when nothing else is legal; w = word 0
+ * of Philox4x32-10 at counter (a | ply << 16, k, G, call) under key (seed lo, seed hi); play the legal action of ordinal
+ * base + ((w * n) >> 32) in ascending action order; ply += 1 }, then count_score() (:192-295).  A playout stops at the end of the round:
+ * it deals no tiles and draws nothing from the game's MT19937 stream, and its draws depend on (seed, call, G, a, k, ply) only -- a game's
+ * row is the same wherever it sits in a batch.  Any other a: AZUL_SCORE_ILLEGAL.  best[g]: the first legal action, in action order, with
+ * the maximal sum; -1 when nothing is legal.  active_dev (optional): rows of games with 0 are not written at all.  sums_dev and best_dev
+ * are each optional, not both.  AZUL_ERR_INVALID before any launch: a wide batch (three / four players or extended rules), playouts
+ * outside 1 .. AZUL_PLAYOUTS_MAX (the bound of a launch's length; 256 * 2^16 fits an int32), both outputs NULL, a perspective outside
+ * {0, 1, AZUL_PERSP_CURRENT}.  BEYOND THE REFERENCE, which has no such player: the rules it plays by are the reference's. */
+#define AZUL_PLAYOUTS_MAX 256
+int azul_batch_playout_moves(azul_batch_t *b, int perspective, int playouts, uint64_t seed, uint32_t call, const uint8_t *active_dev,
+                             int32_t *sums_dev /*[N][180], optional*/, int32_t *best_dev /*[N], optional*/, void *stream);
 
 /* ---- GameRunner for P players: batches of 3 / 4 players and extended-rule batches (wide records) ------------------------------
  * The reference's GameRunner (game_runner.py:23-97) on an Azul(players = P): the agent is seat 0 ("player 1"), every other seat answers

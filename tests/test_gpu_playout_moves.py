@@ -1,0 +1,284 @@
+"""azul_batch_playout_moves on the MI355X: the table and `best` of the shared states of three oracle streams against the host model
+(tests/playout_moves_model.py) at batch sizes 1, 2, 3 and 33, both rule sets of tests/test_gpu_score_moves.py, the three perspectives,
+K = 1 and 3 playouts per move, with the games untouched; the optional outputs and the refusals; a row that follows the game's global id;
+`seed` and `call`; K = 256; PolicyRollout(opponent="playout") replayed game by game through the oracle's GameRunner with the model's
+answer as the opponent; a BatchedTrainer run and the replay of its checkpoint; the constructor's ValueErrors.  The CPU suite runs the same kernel under the lockstep
+emulation (tests/test_hostcheck_playout_moves.py)."""
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+
+from oracle import oracle as oz
+from tests import playout_moves_model as pm
+from tests import score_moves_model as sm
+from tests.test_gpu_score_moves import RULESETS, _batch, _snapshot
+
+pytestmark = pytest.mark.gpu
+CANARY = 0x5EED5EED
+
+
+def _env(sl, rules):
+    env = _batch(sm.stream_states()[0][sl], rules)
+    env.set_id_base(pm.GBASE + sl.start)               # shared state i is global game GBASE + i wherever it sits
+    return env
+
+
+@pytest.mark.parametrize("n", [1, 2, 3, 33])
+@pytest.mark.parametrize("ruleset", ["lid_randomfirst", "random_first1"])
+def test_table_and_best_equal_the_model_and_the_games_are_untouched(ruleset, n):
+    from azul_deep_reinforcement_learning_amd import _lib as L
+    rules = RULESETS[ruleset][0]
+    lo = {1: 119, 2: 57, 3: 200, 33: 0}[n]
+    chunks = [slice(lo, lo + n)] if n < 33 else [slice(i, i + 33) for i in range(0, 330, 33)] + [slice(327, 360)]
+    for sl in chunks:
+        env = _env(sl, rules)
+        before = _snapshot(env)
+        for K in (1, 3):
+            for persp in (0, 1, L.PERSP_CURRENT):
+                tabs, best = pm.stream_tables(K, persp)
+                s, b = env.playout_moves(K, pm.SEED, pm.CALL, persp)
+                assert s.dtype == torch.int32 and tuple(s.shape) == (n, 180) and b.dtype == torch.int32 and tuple(b.shape) == (n,)
+                assert np.array_equal(s.cpu().numpy().astype(np.int64), tabs[sl]), (sl, K, persp)
+                assert np.array_equal(b.cpu().numpy(), best[sl]), (sl, K, persp)
+            assert np.array_equal(env.playout_action(K, pm.SEED, pm.CALL).cpu().numpy(), pm.stream_tables(K)[1][sl]), (sl, K)
+        # an active mask with holes: the rows of the other games keep what they held
+        active = torch.tensor([(i % 3) != 1 for i in range(n)], dtype=torch.uint8, device="cuda")
+        s = torch.full((n, 180), CANARY, dtype=torch.int32, device="cuda")
+        b = torch.full((n,), CANARY, dtype=torch.int32, device="cuda")
+        env.playout_moves(3, pm.SEED, pm.CALL, active=active, sums=s, best=b)
+        g = torch.full((n,), CANARY, dtype=torch.int32, device="cuda")
+        env.playout_action(3, pm.SEED, pm.CALL, active=active, out=g)
+        on = active.cpu().numpy() != 0
+        tabs, best = pm.stream_tables(3)
+        s, b, g = s.cpu().numpy(), b.cpu().numpy(), g.cpu().numpy()
+        assert np.array_equal(s[on].astype(np.int64), tabs[sl][on]) and (s[~on] == CANARY).all()
+        assert np.array_equal(b[on], best[sl][on]) and (b[~on] == CANARY).all()
+        assert np.array_equal(g, b)
+        assert _snapshot(env) == before, "playout_moves changed records, MT19937 state or counters"
+
+
+def test_the_stuck_record_beside_a_game_that_plays_on():
+    other = sm.stream_states()[0][3]
+    env = _batch(np.stack([pm.stuck_record(), other, pm.last_move_record()]), RULESETS["lid_randomfirst"][0])
+    env.set_id_base(pm.GBASE + 2)                      # row 1 is shared state 3
+    s, b = env.playout_moves(3, pm.SEED, pm.CALL)
+    s, b = s.cpu().numpy().astype(np.int64), b.cpu().numpy()
+    for row, (acts, best) in ((0, (pm.STUCK_ACTIONS, pm.STUCK_BEST)), (2, (pm.LAST_MOVE_ACTIONS, pm.LAST_MOVE_BEST))):
+        want = np.full(180, pm.ILLEGAL, np.int64)
+        for a, v in acts.items():
+            want[a] = 3 * v                            # (player 1 moves in both: the mover's values are score[0] - score[1])
+        assert np.array_equal(s[row], want) and b[row] == best, row
+    assert np.array_equal(s[1], pm.stream_tables(3)[0][3]) and b[1] == pm.stream_tables(3)[1][3]
+
+
+def test_optional_outputs_and_refusals():
+    from azul_deep_reinforcement_learning_amd import BatchedAzul, _lib as L
+    sl = slice(30, 37)
+    tabs, best = pm.stream_tables(1)
+    env = _env(sl, RULESETS["lid_randomfirst"][0])
+    n = 7
+    ptr = lambda t: C.c_void_p(t.data_ptr())
+    call = lambda h, persp, K, s, b: L.lib.azul_batch_playout_moves(h, persp, K, pm.SEED, pm.CALL, None, s, b, None)
+    s = torch.full((n, 180), CANARY, dtype=torch.int32, device="cuda")
+    b = torch.full((n,), CANARY, dtype=torch.int32, device="cuda")
+    assert call(env._h, L.PERSP_CURRENT, 1, ptr(s), None) == L.SUCCESS                 # sums only
+    torch.cuda.synchronize()
+    assert np.array_equal(s.cpu().numpy().astype(np.int64), tabs[sl]) and (b.cpu().numpy() == CANARY).all()
+    s.fill_(CANARY)
+    assert call(env._h, L.PERSP_CURRENT, 1, None, ptr(b)) == L.SUCCESS                 # best only
+    torch.cuda.synchronize()
+    assert np.array_equal(b.cpu().numpy(), best[sl]) and (s.cpu().numpy() == CANARY).all()
+    # refusals, before any launch
+    b.fill_(CANARY)
+    assert call(env._h, L.PERSP_CURRENT, 1, None, None) == L.ERR_INVALID
+    assert b"both NULL" in L.lib.azul_last_error_string()
+    for bad in (-1, 3, L.PERSP_MOVER):
+        assert call(env._h, bad, 1, ptr(s), ptr(b)) == L.ERR_INVALID
+        assert b"perspective" in L.lib.azul_last_error_string()
+    for bad in (0, -1, 257, 1 << 20):
+        assert call(env._h, L.PERSP_CURRENT, bad, ptr(s), ptr(b)) == L.ERR_INVALID
+        assert b"playouts" in L.lib.azul_last_error_string()
+    with pytest.raises(L.AzulHipError, match="playouts"):
+        env.playout_moves(0)
+    wide = BatchedAzul(4, players=3, device="cuda", seed=1)
+    wide.init()
+    ws = torch.full((4, 180), CANARY, dtype=torch.int32, device="cuda")
+    wb = torch.full((4,), CANARY, dtype=torch.int32, device="cuda")
+    assert call(wide._h, 0, 1, ptr(ws), ptr(wb)) == L.ERR_INVALID
+    assert b"wide batch" in L.lib.azul_last_error_string()
+    with pytest.raises(L.AzulHipError, match="wide batch"):
+        wide.playout_moves(2)
+    with pytest.raises(L.AzulHipError, match="wide batch"):
+        wide.playout_action(2)
+    from azul_deep_reinforcement_learning_amd import MultiplayerAzul
+    mp = MultiplayerAzul(4, players=3, device="cuda")
+    with pytest.raises(L.AzulHipError, match="wide batch"):
+        mp.playout_moves(2)
+    torch.cuda.synchronize()
+    for t in (s, b, ws, wb):
+        assert (t.cpu().numpy() == CANARY).all()
+
+
+def test_a_row_follows_the_global_id_and_seed_and_call_each_change_a_table():
+    recs = sm.stream_states()[0]
+    rules = RULESETS["lid_randomfirst"][0]
+    i = 150
+    tabs, best = pm.stream_tables(3)
+    a = _batch(recs[[i, 10, 11]], rules)
+    a.set_id_base(pm.GBASE + i)
+    b = _batch(recs[[20, 21, 22, 23, i, 24, 25]], rules)
+    b.set_id_base(pm.GBASE + i - 4)
+    sa, ba = (t.cpu().numpy() for t in a.playout_moves(3, pm.SEED, pm.CALL))
+    sb, bb = (t.cpu().numpy() for t in b.playout_moves(3, pm.SEED, pm.CALL))
+    assert np.array_equal(sa[0], sb[4]) and ba[0] == bb[4]
+    assert np.array_equal(sa[0].astype(np.int64), tabs[i]) and ba[0] == best[i]
+    # another seed / another call: the model's table of state i under it, and it differs from the shared one
+    for seed, call in ((pm.SEED + 1, pm.CALL), (pm.SEED, pm.CALL + 1), (pm.SEED ^ (1 << 40), pm.CALL), (pm.SEED, pm.CALL ^ (1 << 31))):
+        want, wbest = pm.table(recs[i], pm.GBASE + i, 3, seed=seed, call=call)
+        s, bst = (t.cpu().numpy() for t in a.playout_moves(3, seed, call))
+        assert np.array_equal(s[0].astype(np.int64), want) and bst[0] == wbest, (seed, call)
+        assert not np.array_equal(want, tabs[i]), (seed, call)
+
+
+def test_256_playouts_on_two_games():
+    recs = sm.stream_states()[0]
+    sl = slice(44, 46)
+    env = _env(sl, RULESETS["lid_randomfirst"][0])
+    s, b = (t.cpu().numpy() for t in env.playout_moves(256, pm.SEED, pm.CALL))
+    for row, i in enumerate(range(sl.start, sl.stop)):
+        want, wbest = pm.table(recs[i], pm.GBASE + i, 256)
+        assert np.array_equal(s[row].astype(np.int64), want) and b[row] == wbest, i
+
+
+def _replay_with_the_playout_model(G, K, seed, calls, rec0, mt0, pos0, first, pool, action, opp_action, opp_replies, obs, mask, player, reward, done):
+    """tests/test_gpu_score_moves.py's replay with the MODEL's playout answer as the opponent: the oracle's GameRunner fed the recorded
+    agent actions; reply j of step t is answered at (seed + j, calls[t]); every env-side record and traced answer must equal the rollout's."""
+    S, R = len(action), opp_action.shape[1]
+    assert int(opp_replies.max(initial=0)) <= R, "a step had more replies than the trace holds: raise opponent_trace"
+    cur = {"t": 0, "j": 0, "calls": 0}
+
+    def opponent(s, m):
+        a = pm.action_of_game(run.q.game, G, K, (seed + cur["j"]) & 0xFFFFFFFFFFFFFFFF, calls[cur["t"]])
+        assert a >= 0 and m[a], ("playout answer not legal", cur["t"], cur["j"], a)
+        assert a == int(opp_action[cur["t"], cur["j"]]), ("traced opp_action", cur["t"], cur["j"], a, int(opp_action[cur["t"], cur["j"]]))
+        assert np.array_equal(s, oz.get_state(run.q.game, run.q.game.current_player - 1))
+        cur["j"] += 1
+        cur["calls"] += 1
+        return a
+
+    run = oz.NetRunner(opponent, first, pool, rec=rec0, mt=mt0, pos=pos0)
+    for t in range(S):
+        cur["t"], cur["j"] = t, 0
+        m = run.get_valid_moves()
+        assert np.array_equal(np.asarray(mask[t]).astype(bool), m), ("mask", t)
+        assert np.array_equal(np.asarray(obs[t]).astype(np.int64), run.get_state(0)), ("obs", t)
+        assert int(player[t]) == 1 == int(run.q.game.current_player) and int(m.sum()) >= 2, ("player", t)
+        a = int(action[t])
+        assert 0 <= a < 180 and m[a], ("agent action", t, a)
+        rc, rew, dn = run.step(a)
+        assert rc == 0 and rew == int(reward[t]) and dn == bool(done[t]), ("reward / done", t, rew, int(reward[t]), dn, int(done[t]))
+        if dn:
+            assert run.reset() == 0
+        assert cur["j"] == int(opp_replies[t]), ("replies", t, cur["j"], int(opp_replies[t]))
+    assert np.array_equal(np.asarray(mask[S]).astype(bool), run.get_valid_moves()) and np.array_equal(np.asarray(obs[S]).astype(np.int64), run.get_state(0))
+    return run, cur["calls"]
+
+
+@pytest.mark.parametrize("ruleset", ["lid_randomfirst", "random_first1"])
+def test_playout_rollout_replays_through_the_oracle(ruleset):
+    from azul_deep_reinforcement_learning_amd import PolicyRollout
+    from azul_deep_reinforcement_learning_amd.policy import BatchedActorCritic
+    rules, first, pool = RULESETS[ruleset]
+    torch.manual_seed(3)
+    net = BatchedActorCritic(136, 180, 180)
+    T, n, K = 8, 6, 2
+    ro = PolicyRollout(net, n_games=n, window=T, opponent="playout", opponent_playouts=K, opponent_trace=4, rules=rules, seed_base=900,
+                       opponent_seed=0xABCDEF0123456789)
+    assert ro.opponent == "playout" and ro.opponent_playouts == K and not ro.persistent and not ro.use_graph and ro.ring == 1
+    env = ro.envs[0]
+    start = env.get_records()
+    rng0 = [env.get_rng(g) for g in range(n)]
+    wins = []
+    for _ in range(2):
+        tr = ro.run_window()
+        ro.synchronize()
+        wins.append({k: v.cpu().numpy().copy() for k, v in tr[0].items()})
+    finals, (fmt, fpos) = env.get_records(), env.get_rng_range()
+    assert (np.concatenate([w["opp_logp"] for w in wins]) == 0).all()
+    cat = lambda key, sl: np.concatenate([w[key][sl] for w in wins])
+    calls = 0
+    for g in range(n):
+        slot = lambda key: np.concatenate([w[key][:T, g] for w in wins] + [wins[-1][key][T:T + 1, g]])
+        # agent step t of the run (the Philox step counter starts at 0 and moves one per step) draws at call t; the game's global id is 900 + g
+        run, c = _replay_with_the_playout_model(900 + g, K, ro.opponent_seed, list(range(2 * T)), start[g], rng0[g][0], rng0[g][1], first, pool,
+                                                cat("action", (slice(None), g)), cat("opp_action", (slice(None), slice(None), g)),
+                                                cat("opp_replies", (slice(None), g)), slot("obs"), slot("mask"), slot("player"),
+                                                cat("reward", (slice(None), g)), cat("done", (slice(None), g)))
+        calls += c
+        assert run.record().tobytes() == finals[g].tobytes(), g
+        m_e, idx = run.rng_state()
+        assert int(fpos[g]) == idx and np.array_equal(fmt[g], m_e), g
+    assert calls >= 2 * T * n // 2                       # the opponent really moved: about one reply per agent step
+
+
+def test_trainer_against_the_playout_opponent_and_its_checkpoint(tmp_path):
+    import os
+    from azul_deep_reinforcement_learning_amd.policy import BatchedActorCritic
+    from azul_deep_reinforcement_learning_amd.training import AGENT_STAT_KEYS, BatchedTrainer
+    kw = dict(opponent="playout", opponent_playouts=2, n_games=8, window=8, results_dir=str(tmp_path))
+    torch.manual_seed(4)
+    tr = BatchedTrainer(BatchedActorCritic(136, 180, 180), seed_base=11, **kw)
+    assert tr.rollout.opponent == "playout" and tr.rollout.ring == 1 and not tr.rollout.persistent and tr.rollout.opponent_playouts == 2
+    rows = [tr.run_batch() for _ in range(2)]
+    torch.cuda.synchronize()
+    assert tr.learner.updates == 2
+    for r in rows:
+        assert all(np.isfinite(r[k]) for k in AGENT_STAT_KEYS[1:]), r
+    # a resumed run replays bit for bit: the opponent's draws follow the Philox step counter the checkpoint carries
+    ck = os.path.join(str(tmp_path), "playout.pt")
+    tr.save_checkpoint(ck)
+    saved = torch.load(ck, map_location="cpu", weights_only=False)
+    assert saved["opponent_playouts"] == 2 and "opponent" not in saved
+    state = lambda t: ({k: v.detach().cpu().clone() for k, v in t.rollout.policy.state_dict().items()}, t.rollout.envs[0].get_records().tobytes(),
+                       t.rollout.envs[0].get_rng_range(), t.rollout.work[0]["counter"].tolist(),
+                       {k: v.cpu().clone() for k, v in t.rollout.traj[0].items()})
+    row_a = tr.run_batch()                                  # the third batch of the uninterrupted run
+    tr.rollout.synchronize()
+    want = state(tr)
+    torch.manual_seed(99)
+    tr2 = BatchedTrainer(BatchedActorCritic(136, 180, 180), seed_base=9000, **kw)
+    tr2.load_checkpoint(ck)
+    row_b = tr2.run_batch()
+    tr2.rollout.synchronize()
+    got = state(tr2)
+    assert tr2.batch == 3
+    for k in want[0]:
+        assert torch.equal(want[0][k], got[0][k]), k
+    assert want[1] == got[1] and np.array_equal(want[2][0], got[2][0]) and np.array_equal(want[2][1], got[2][1]) and want[3] == got[3]
+    for k in want[4]:
+        assert torch.equal(want[4][k], got[4][k]), k
+    assert int(want[4]["opp_replies"].sum()) > 0
+    for k in AGENT_STAT_KEYS[1:]:
+        assert row_a[k] == row_b[k], k
+    with pytest.raises(ValueError, match="opponent_playouts"):
+        BatchedTrainer(BatchedActorCritic(136, 180, 180), seed_base=11, **dict(kw, opponent_playouts=3)).load_checkpoint(ck)
+
+
+def test_the_constructor_refuses_what_the_playout_opponent_does_not_play():
+    from azul_deep_reinforcement_learning_amd import PolicyRollout
+    from azul_deep_reinforcement_learning_amd.policy import BatchedActorCritic
+    from azul_deep_reinforcement_learning_amd.training import BatchedTrainer
+    net = BatchedActorCritic(136, 180, 180)
+    for kw in (dict(fused_opponent=True), dict(players=3), dict(rules={"first_player": "Random", "tile_pool": "Lid", "short_deal": True})):
+        with pytest.raises(ValueError, match="answers per cut"):
+            PolicyRollout(net, n_games=4, window=4, opponent="playout", **kw)
+    with pytest.raises(ValueError, match="answers per cut"):
+        PolicyRollout(BatchedActorCritic(188, 180, 180), n_games=4, window=4, opponent="playout", players=3, fused_wide=True)
+    with pytest.raises(ValueError, match="Max"):
+        PolicyRollout(net, n_games=4, window=4, opponent="playout", opponent_selection="Max")
+    with pytest.raises(ValueError, match="opponent_playouts"):
+        PolicyRollout(net, n_games=4, window=4, opponent="playout", opponent_playouts=300)
+    with pytest.raises(ValueError, match="answers per cut"):
+        BatchedTrainer(BatchedActorCritic(136, 180, 180), opponent="playout", n_games=8, window=8, fused_opponent=True)

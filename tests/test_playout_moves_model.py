@@ -1,0 +1,115 @@
+"""The host model of azul_batch_playout_moves (tests/playout_moves_model.py: the playout of include/azul_hip.h statement by statement on the
+oracle, the draws from tests/policy_draw_ref.py's Philox4x32-10) on cases worked by hand, and the condition of the tests that run the
+kernel against it: the states they use hold every playout class.  Plus the refusals of the playout opponent that need no device."""
+import numpy as np
+import pytest
+
+from tests import playout_moves_model as pm
+from tests import score_moves_model as sm
+
+
+def _hand(rec, per_playout, best, K=3):
+    """`per_playout`: action -> the mover's (player 1's) value of ONE playout; every playout of these records gives the same."""
+    for persp, sign in ((0, 1), (1, -1), (pm.PERSP_CURRENT, 1)):
+        tab, b = pm.table(rec, G=77, K=K, perspective=persp)
+        want = np.full(180, pm.ILLEGAL, np.int64)
+        for a, v in per_playout.items():
+            want[a] = sign * K * v
+        assert np.array_equal(tab, want), persp
+        # the first maximum: from player 2's side every sign flips, and with it the choice
+        assert b == (best if sign == 1 else min(a for a, v in per_playout.items() if v == min(per_playout.values())))
+
+
+def test_a_state_one_move_from_the_end_of_the_round_by_hand():
+    rec = pm.last_move_record()
+    _hand(rec, pm.LAST_MOVE_ACTIONS, pm.LAST_MOVE_BEST)
+    _, _, facts = pm.state_values(rec, G=77, k_count=2)
+    assert len(facts) == 12 and all(f["candidate_ends_round"] and f["plies"] == 0 and not f["stuck"] for _, f in facts)
+    # no draw decides anything here: any seed, call and game id give the same table
+    assert np.array_equal(pm.table(rec, 1, 2, seed=5, call=9)[0], pm.table(rec, 77, 2)[0])
+
+
+def test_the_crafted_stuck_record_by_hand():
+    rec = pm.stuck_record()
+    _hand(rec, pm.STUCK_ACTIONS, pm.STUCK_BEST)
+    _, legal, facts = pm.state_values(rec, G=77, k_count=2)
+    assert sorted(np.flatnonzero(legal)) == sorted(pm.STUCK_ACTIONS)
+    assert len(facts) == 12 and all(f["stuck"] and f["plies"] == 0 and not f["candidate_ends_round"] for _, f in facts)
+
+
+def test_the_draws_are_the_host_philox_at_the_documented_counter():
+    from tests import policy_draw_ref as pr
+    d = pm._Draws(pm.SEED, pm.CALL, 4242, 3)
+    for a, ply, k in ((0, 0, 0), (179, 5, 2), (91, 23, 1), (17, 24, 0), (60, 63, 2)):
+        want = int(pr.philox4x32_10((a | ply << 16, k, 4242, pm.CALL), (pm.SEED & 0xFFFFFFFF, pm.SEED >> 32))[0])
+        assert d.word(a, ply, k) == want
+
+
+def test_tables_of_the_shared_states_are_consistent():
+    recs = sm.stream_states()[0]
+    t0, _ = pm.stream_tables(2, 0)
+    t1, _ = pm.stream_tables(2, 1)
+    tc, bc = pm.stream_tables(2, pm.PERSP_CURRENT)
+    legal = sm.stream_tables(0)[0] != sm.ILLEGAL                 # the one-ply table's legal actions are these
+    assert np.array_equal(t0 != pm.ILLEGAL, legal) and np.array_equal(t1[legal], -t0[legal])
+    mover1 = np.array([pm.mover_of(r) for r in recs]) == 1
+    assert mover1.any() and (~mover1).any()
+    assert np.array_equal(tc[~mover1], t0[~mover1]) and np.array_equal(tc[mover1], t1[mover1])
+    for i in range(len(recs)):
+        lg = np.flatnonzero(legal[i])
+        if len(lg) == 0:
+            assert bc[i] == -1
+        else:
+            assert legal[i, bc[i]] and tc[i, bc[i]] == tc[i, lg].max() and not (tc[i, lg[lg < bc[i]]] == tc[i, bc[i]]).any()
+    # K playouts are the first K of KMAX: the table of 3 is the table of 2 plus the third playout
+    vals, lg_all, movers, _ = pm.stream_values()
+    t3, _ = pm.stream_tables(3, 0)
+    assert np.array_equal(t3[legal], t0[legal] + vals[:, :, 2][legal])
+
+
+def test_the_states_the_kernel_tests_use_hold_every_class():
+    """Coverage is a CONDITION of the tests that run the kernel, not a measurement: the emulation test runs all 360 shared states (each once,
+    tests/playout_moves_model.emulation_chunks) and the crafted stuck record, the GPU test the same at K = 1 and 3."""
+    chunks = [c for combo in range(len(pm.EMULATION_COMBOS)) for c in pm.emulation_chunks(combo)]
+    assert sorted(i for lo, n in chunks for i in range(lo, lo + n)) == list(range(360))
+    for combo in range(len(pm.EMULATION_COMBOS)):
+        assert {n for _, n in pm.emulation_chunks(combo)} >= set(pm.EMULATION_SIZES), combo
+    total = pm.classify_states(range(360), K=2)
+    print(total)
+    assert total["playouts"] == 16324 and total["longest"] < pm.MAX_PLIES
+    for name in pm.PLAYOUT_CLASSES + pm.STATE_CLASSES:
+        if name != "stuck":
+            assert total[name] >= 1, (name, total)
+    assert total["stuck"] == 0                                   # play does not reach one: hence the crafted record
+    assert all(f["stuck"] for _, f in pm.state_values(pm.stuck_record(), G=1, k_count=1)[2])
+
+
+def _check(**over):
+    from azul_deep_reinforcement_learning_amd.rollout import PolicyRollout
+    ro = PolicyRollout.__new__(PolicyRollout)
+    args = dict(policy=None, n_games=4, parts=1, window=8, use_graph=True, fused_head=True, opponent="playout", fused_mlp=True, persistent=True,
+                action_selection="Distribution", ring=3, opponent_selection="Distribution", opponent_trace=0, move_limit=0, fused_wide=False,
+                fused_opponent=False, wide_ring=1, rules={"first_player": "Random", "tile_pool": "Lid"}, players=2)
+    args.update(over)
+    ro._check_modes(**args)
+    return ro
+
+
+def test_playout_opponent_refusals_need_no_device():
+    for over in (dict(players=3), dict(rules={"first_player": "Random", "tile_pool": "Lid", "short_deal": True}), dict(fused_opponent=True)):
+        with pytest.raises(ValueError, match="answers per cut"):
+            _check(**over)
+    with pytest.raises(ValueError, match="answers per cut"):
+        _check(players=3, fused_wide=True)
+    with pytest.raises(ValueError, match="Max"):
+        _check(opponent_selection="Max")
+    for k in (0, 257):
+        with pytest.raises(ValueError, match="opponent_playouts"):
+            _check(opponent_playouts=k)
+
+
+def test_playout_opponent_resolves_to_the_per_cut_path():
+    from azul_deep_reinforcement_learning_amd import BatchedActorCritic
+    ro = _check(policy=BatchedActorCritic(136, 180, 180), opponent_playouts=5, opponent_trace=2)
+    assert ro.opponent == "playout" and ro.scripted and ro.cut and not ro.netopp and ro.opponent_playouts == 5
+    assert ro.window_entry is None and not ro.persistent and not ro.use_graph and ro.ring == 1 and ro.opp_slots == 2
