@@ -12,7 +12,8 @@ Families (each generator call returns them in this order, `per` records each; FA
 Closure bound: box + lid + displays + xdisplays + centre colours + pattern lines of the P players <= 255 in every record -- the tiles that can
 still reach the bag: no refill (azul.py:81-83) can then find more than 255 tiles, whatever is played.  The exception is `overflow`: box = 0,
 lid = [51] * 5 (the most the documented domain accepts) on a round-ending table whose full lines return tiles, so that the refill finds more
-than 255.
+than 255.  `ended` is the other named generator outside the families: records at the ends of an episode (the ended flag set, an empty
+table, a complete wall row with the flag clear) for the kernels that run whole windows (tests/window_domain_cases.py).
 
 Every absent player's field and every unused xdisplays row is zero."""
 import ctypes as C
@@ -221,6 +222,27 @@ def overflow(n, P, D, seed, wide_record=True):
     rec["box"] = 0
     rec["lid"] = 51
     return rec
+
+
+def ended(n, P, D, seed, wide_record=True):
+    """The named records at the ends of an episode (NOT a family: batch() and the existing tests' records stay what they are), scattered
+    records in thirds: the record's ended flag (bit 6 of `flags`) set -- Azul.step answers GameEnded whatever is on the table; an empty
+    table without the token -- nothing is legal, the round is over and nobody can end it; a complete wall row with the flag still clear --
+    is_end_of_game() reads the walls (azul.py:184-191), step's GameEnded the flag (:298-299): any legal move ends the episode."""
+    rs = np.random.RandomState(seed)
+    rec = _scatter(rs, n, P, D, wide_record)
+    for i in range(n):
+        kind = i * 3 // n
+        if kind == 0:
+            rec["flags"][i] |= 1 << 6
+        elif kind == 1:
+            rec["displays"][i] = 0
+            rec["center"][i] = 0
+            if wide_record:
+                rec["xdisplays"][i] = 0
+        else:
+            rec["walls"][i, rs.randint(P)] |= np.uint32(0x1f << (5 * rs.randint(5)))
+    return _fit(rec, P)
 
 
 # ---- the oracle's side ---------------------------------------------------------------------------------------------------------------------------

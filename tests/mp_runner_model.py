@@ -17,6 +17,8 @@ GUARD = 4096          # replies per opponent loop before the slot counts as stuc
 class MPRunner:
     """One game slot of a wide batch: the game, its CPython stream, the runner's player_score / move_counter and the slot's counters."""
 
+    two = False            # record() packs the wide record
+
     def __init__(self, players, first_player, tile_pool, ext=0, seed=None, rng=None):
         self.P, self.first, self.pool, self.ext = players, first_player, tile_pool, ext
         self.g = oz.Game()
@@ -30,6 +32,25 @@ class MPRunner:
         self.episodes = 0
         self.stuck = 0
         self.stat_sum = np.zeros(10)
+
+    @classmethod
+    def from_record(cls, rec, cfg, rng, first_player=oz.FIRST_RANDOM):
+        """A slot that holds a handed-in record (tests/domain_records.py: cfg = (players, ext, tile_pool); rng: the slot's stream, e.g.
+        domain_records.stream_of) instead of a fresh game: the wide 256-byte record (oz.unpack_np; the runner tail from bytes 228..231) or,
+        at P = 2, the 128-byte record (oz.unpack(...).game; player_score / move_counter are its tail) -- record() then packs that record."""
+        P, ext, pool = cfg
+        m = cls(P, first_player, pool, ext, rng=rng)
+        raw = np.frombuffer(np.asarray(rec).tobytes(), np.uint8)
+        m.two = raw.size == 128
+        if m.two:
+            assert P == 2 and ext == 0
+            q = oz.unpack(raw, pool, first_player)
+            m.g = oz.Game.from_buffer_copy(bytes(q.game))
+            m.phi, m.moves = int(q.player_score), int(q.move_counter)
+        else:
+            m.g = oz.unpack_np(raw, pool, ext)
+            m.phi, m.moves = int(raw[228:230].view("<i2")[0]), int(raw[230:232].view("<u2")[0])
+        return m
 
     # -- primitives ------------------------------------------------------------------------------------------------
     @property
@@ -174,6 +195,11 @@ class MPRunner:
     # -- what the device holds ------------------------------------------------------------------------------------
     def record(self):
         """The 256-byte wide record + the runner's tail (bytes 228..229 i16 player_score, 230..231 u16 move_counter)."""
+        if self.two:       # (from_record on a 128-byte record: oz.pack of a Runner that carries the model's game and tail)
+            q = oz.Runner()
+            q.game = oz.Game.from_buffer_copy(bytes(self.g))
+            q.first_player, q.tile_pool, q.player_score, q.move_counter = self.first, self.pool, self.phi, self.moves & 0xFFFF
+            return np.frombuffer(oz.pack(q).tobytes(), np.uint8).copy()
         rec = np.zeros(256, np.uint8)
         assert self.L.oz_pack_np(C.byref(self.g), rec.ctypes.data_as(C.POINTER(C.c_uint8))) == 0
         rec[228:230] = np.array([self.phi], "<i2").view(np.uint8)

@@ -174,6 +174,49 @@ def classify_states(indices, K=2):
     return total
 
 
+# ---- arbitrary in-domain records (tests/domain_records.py) ------------------------------------------------------------------------------------
+DOMAIN_GBASE = 70000           # global id of domain record 0 of a config
+DOMAIN_ENDED = 9               # `ended` records behind the emulation's 160; the GPU batch: 254 of the 256 + 3 `ended` = 257
+DOMAIN_CLASSES = ("candidate_ends_round", "plies_8_or_more", "forced_floor", "token_in_playout", "ends_game", "none_legal", "tie")
+
+
+@functools.lru_cache(maxsize=None)
+def domain_values(cfg, n):
+    """(records uint8 [N][128], values int64 [N][180][KMAX], legal bool [N][180], movers int [N], facts [N]) of a two-player config's domain
+    records, computed once: n = dr.CPU_N -> the 160 records of dr.batch(cfg, n) and DOMAIN_ENDED of dr.ended; n = dr.GPU_N -> the first 254
+    of dr.batch(cfg, n) and 3 of dr.ended (257: the last wave holds one game).  Record i is global game DOMAIN_GBASE + i at (SEED, CALL)."""
+    from tests import domain_records as dr
+    pool = cfg[2]
+    recs, n_ended = dr.batch(cfg, n)[0], (DOMAIN_ENDED if n == dr.CPU_N else 3)
+    recs = np.concatenate([recs if n == dr.CPU_N else recs[:n - 2], dr.ended(n_ended, 2, 5, 8800 + pool, False)])
+    raw = np.ascontiguousarray(recs).view(np.uint8).reshape(len(recs), -1).copy()
+    vals, legal, facts = zip(*[state_values(r, DOMAIN_GBASE + i, pool=pool) for i, r in enumerate(raw)])
+    return raw, np.stack(vals), np.stack(legal), np.array([mover_of(r) for r in raw]), list(facts)
+
+
+def domain_tables(cfg, n, K, perspective=PERSP_CURRENT):
+    """(tables int64 [N][180], best int32 [N]) of domain_values(cfg, n) for K <= KMAX playouts."""
+    _, vals, legal, movers, _ = domain_values(cfg, n)
+    tabs = np.stack([table_of(vals[i], legal[i], K, int(movers[i]), perspective) for i in range(len(vals))])
+    return tabs, np.array([best_of(t) for t in tabs], np.int32)
+
+
+def domain_census(cfg, n, K):
+    """{class of DOMAIN_CLASSES: count} of domain_values(cfg, n) at K playouts: the playout classes count playouts, none_legal and tie records."""
+    _, _, legal, _, facts = domain_values(cfg, n)
+    tabs, _ = domain_tables(cfg, n, K)
+    total = dict.fromkeys(DOMAIN_CLASSES, 0)
+    for i, fs in enumerate(facts):
+        for k, f in fs:
+            if k < K:
+                for name in DOMAIN_CLASSES[:5]:
+                    total[name] += int(f[name])
+        lg = np.flatnonzero(legal[i])
+        total["none_legal"] += int(len(lg) == 0)
+        total["tie"] += int(len(lg) >= 2 and int((tabs[i][lg] == tabs[i][lg].max()).sum()) >= 2)
+    return total
+
+
 # ---- crafted records ----------------------------------------------------------------------------------------------------------------------
 def _blank(current_player=1):
     rec = np.zeros((), oz.RECORD_DTYPE)

@@ -1,6 +1,7 @@
 """azul_batch_playout_moves on the MI355X: the table and `best` of the shared states of three oracle streams against the host model
 (tests/playout_moves_model.py) at batch sizes 1, 2, 3 and 33, both rule sets of tests/test_gpu_score_moves.py, the three perspectives,
-K = 1 and 3 playouts per move, with the games untouched; the optional outputs and the refusals; a row that follows the game's global id;
+K = 1 and 3 playouts per move, with the games untouched; 257 arbitrary in-domain records per pool (tests/domain_records.py, `ended` records
+included), global ids that cross 2^32 and call = 0xFFFFFFFF; the optional outputs and the refusals; a row that follows the game's global id;
 `seed` and `call`; K = 256; PolicyRollout(opponent="playout") replayed game by game through the oracle's GameRunner with the model's
 answer as the opponent; a BatchedTrainer run and the replay of its checkpoint; the constructor's ValueErrors.  The CPU suite runs the same kernel under the lockstep
 emulation (tests/test_hostcheck_playout_moves.py)."""
@@ -11,6 +12,7 @@ import pytest
 import torch
 
 from oracle import oracle as oz
+from tests import domain_records as dr
 from tests import playout_moves_model as pm
 from tests import score_moves_model as sm
 from tests.test_gpu_score_moves import RULESETS, _batch, _snapshot
@@ -57,6 +59,53 @@ def test_table_and_best_equal_the_model_and_the_games_are_untouched(ruleset, n):
         assert np.array_equal(b[on], best[sl][on]) and (b[~on] == CANARY).all()
         assert np.array_equal(g, b)
         assert _snapshot(env) == before, "playout_moves changed records, MT19937 state or counters"
+
+
+def _domain_env(cfg, rows, id_base):
+    from tests.test_gpu_domain_records import make_env
+    raw = pm.domain_values(cfg, dr.GPU_N)[0][rows]
+    env = make_env(cfg, len(raw))
+    env.set_records(raw.view(oz.RECORD_DTYPE).reshape(-1))                    # (set_state validates every record against the domain)
+    env.set_id_base(id_base)
+    return env, raw
+
+
+@pytest.mark.parametrize("cfg", dr.TWO_CONFIGS, ids=dr.config_id)
+def test_table_and_best_on_257_arbitrary_in_domain_records_equal_the_model(cfg):
+    """azul_playout_moves_kernel on tests/domain_records.py's records (states no game reaches) and three `ended` records -- 257: the last
+    wave holds one game -- at K = 1 and 3 from the three perspectives; tests/test_playout_moves_model.py asserts that they hold every
+    playout class, a record with nothing legal and a tie."""
+    from azul_deep_reinforcement_learning_amd import _lib as L
+    n = 257
+    env, raw = _domain_env(cfg, slice(0, n), pm.DOMAIN_GBASE)
+    assert len(raw) == n
+    for K in (1, 3):
+        for persp in (0, 1, L.PERSP_CURRENT):
+            tabs, best = pm.domain_tables(cfg, dr.GPU_N, K, persp)
+            s, b = env.playout_moves(K, pm.SEED, pm.CALL, persp)
+            s, b = s.cpu().numpy().astype(np.int64), b.cpu().numpy()
+            for g in range(n):
+                assert np.array_equal(s[g], tabs[g]), (K, persp, g)
+            assert np.array_equal(b, best), (K, persp)
+    assert (best == -1).any()
+    assert env.get_records().tobytes() == raw.tobytes()
+
+
+def test_global_ids_that_cross_2_to_the_32_and_the_last_call_number():
+    """Five domain records as global games 2^32 - 2 .. 2^32 + 2: the id is a 32-bit Philox counter word, so rows 2, 3, 4 draw as games 0, 1, 2;
+    and one call with call = 0xFFFFFFFF, the counter word's last value."""
+    cfg = dr.TWO_CONFIGS[0]
+    rows = [0, 70, 140, 200, 256]                            # one record of every family and an `ended` one
+    id_base = (1 << 32) - 2
+    env, raw = _domain_env(cfg, rows, id_base)
+    for call in (pm.CALL, 0xFFFFFFFF):
+        s, b = env.playout_moves(3, pm.SEED, call)
+        s, b = s.cpu().numpy().astype(np.int64), b.cpu().numpy()
+        for j, r in enumerate(raw):
+            G = (id_base + j) & 0xFFFFFFFF
+            want, wbest = pm.table(r, G, 3, seed=pm.SEED, call=call, pool=cfg[2])
+            assert np.array_equal(s[j], want) and b[j] == wbest, (call, j, G)
+    assert env.get_records().tobytes() == raw.tobytes()
 
 
 def test_the_stuck_record_beside_a_game_that_plays_on():

@@ -5,7 +5,8 @@ azul_policy.hpp's Philox block, all UNMODIFIED) compiled by g++ and run under th
 The states: ALL 360 shared states of three oracle streams, each run once -- cut into consecutive batches of 1, 2, 3 and 7 records (odd
 counts leave the last wave one game), every run of four batches given to one of the six (pool, perspective) combinations in turn
 (playout_moves_model.emulation_chunks; tests/test_playout_moves_model.py asserts that they hold every playout class) -- plus the crafted
-stuck record; then an `active` mask with holes and a canary, each output optional, record bytes unchanged, and the same record at two
+stuck record; the 160 arbitrary in-domain records of tests/domain_records.py per pool and nine `ended` records, in the same batch sizes
+(states no game reaches: an error of the rule book on one of them inside a playout shows only here); then an `active` mask with holes and a canary, each output optional, record bytes unchanged, and the same record at two
 batch positions with id_base chosen so that its global id is the same.  The `-m gpu` tests repeat it on the real kernel
 (tests/test_gpu_playout_moves.py)."""
 import ctypes as C
@@ -13,6 +14,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from tests import domain_records as dr
 from tests import playout_moves_model as pm
 from tests import score_moves_model as sm
 from tests.hostcheck import hostcheck as hc
@@ -54,6 +56,25 @@ def test_table_and_best_equal_the_model(combo):
         s, b = run(recs[lo:lo + n], pool, persp, pm.GBASE + lo)
         assert np.array_equal(s.astype(np.int64), tabs[lo:lo + n]), (lo, n)
         assert np.array_equal(b, best[lo:lo + n]), (lo, n)
+
+
+@pytest.mark.parametrize("cfg", dr.TWO_CONFIGS, ids=dr.config_id)
+def test_table_and_best_on_arbitrary_in_domain_records_equal_the_model(cfg):
+    """The 160 records of tests/domain_records.py (mixed and overfull lines, floors at 7, dense walls, round-ending tables, box / lid edges:
+    states no game reaches) and 9 `ended` records, in consecutive batches of 1, 2, 3 and 7: the kernel runs do_move2, legal_mask2 and
+    count_score2 on a register copy for up to 13 plies from each.  The census is a condition on the oracle's side."""
+    raw = pm.domain_values(cfg, dr.CPU_N)[0]
+    census = pm.domain_census(cfg, dr.CPU_N, K)
+    assert all(census[c] >= 1 for c in pm.DOMAIN_CLASSES), census
+    tabs, best = pm.domain_tables(cfg, dr.CPU_N, K)
+    assert len(raw) == dr.CPU_N + pm.DOMAIN_ENDED and (best[dr.CPU_N:] == -1).any()
+    lo, j = 0, 0
+    while lo < len(raw):
+        n = min(pm.EMULATION_SIZES[j % 4], len(raw) - lo)
+        s, b = run(raw[lo:lo + n], cfg[2], pm.PERSP_CURRENT, pm.DOMAIN_GBASE + lo)          # (run asserts that the records are unchanged)
+        assert np.array_equal(s.astype(np.int64), tabs[lo:lo + n]), (lo, n, [dr.family_of(i, dr.CPU_N) for i in range(lo, min(lo + n, dr.CPU_N))])
+        assert np.array_equal(b, best[lo:lo + n]), (lo, n)
+        lo, j = lo + n, j + 1
 
 
 @pytest.mark.parametrize("n,holes", [(1, [0]), (2, [1]), (3, [0, 2]), (7, [1, 2, 6])])

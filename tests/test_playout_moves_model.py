@@ -4,6 +4,7 @@ kernel against it: the states they use hold every playout class.  Plus the refus
 import numpy as np
 import pytest
 
+from tests import domain_records as dr
 from tests import playout_moves_model as pm
 from tests import score_moves_model as sm
 
@@ -82,6 +83,21 @@ def test_the_states_the_kernel_tests_use_hold_every_class():
             assert total[name] >= 1, (name, total)
     assert total["stuck"] == 0                                   # play does not reach one: hence the crafted record
     assert all(f["stuck"] for _, f in pm.state_values(pm.stuck_record(), G=1, k_count=1)[2])
+
+
+@pytest.mark.parametrize("n,Ks", [(dr.CPU_N, (2,)), (dr.GPU_N, (1, 3))], ids=["emulation", "gpu"])
+@pytest.mark.parametrize("cfg", dr.TWO_CONFIGS, ids=dr.config_id)
+def test_the_domain_records_the_kernel_tests_use_hold_every_class(cfg, n, Ks):
+    """The same condition for the arbitrary in-domain records (pm.domain_values): every class of pm.DOMAIN_CLASSES at every K the kernel
+    tests use, a record with nothing legal among the `ended` records, and no playout that the ply bound cuts."""
+    raw, _, legal, _, facts = pm.domain_values(cfg, n)
+    assert len(raw) == (dr.CPU_N + pm.DOMAIN_ENDED if n == dr.CPU_N else 257)
+    assert (~legal[-(pm.DOMAIN_ENDED if n == dr.CPU_N else 3):].any(axis=1)).any()
+    assert max(f["plies"] for fs in facts for _, f in fs) < pm.MAX_PLIES
+    for K in Ks:
+        census = pm.domain_census(cfg, n, K)
+        print(dr.config_id(cfg), n, K, census)
+        assert all(census[c] >= 1 for c in pm.DOMAIN_CLASSES), (K, census)
 
 
 def _check(**over):
