@@ -22,6 +22,8 @@ PERSP_PLAYER0, PERSP_PLAYER1, PERSP_CURRENT = 0, 1, 2
 PERSP_MOVER = 7
 SCORE_ILLEGAL = -2 ** 31              # AZUL_SCORE_ILLEGAL: azul_batch_score_moves' entry of an action that is not legal
 PLAYOUTS_MAX = 256                    # AZUL_PLAYOUTS_MAX: azul_batch_playout_moves' bound on the playouts per move
+PLAYOUT_UNIFORM, PLAYOUT_GREEDY = 0, 1                # AZUL_PLAYOUT_*: azul_batch_playout_moves_policy's playout policies
+PLAYOUT_POLICIES = {"uniform": PLAYOUT_UNIFORM, "greedy": PLAYOUT_GREEDY}
 FLAG_END_OF_ROUND, FLAG_END_OF_GAME, FLAG_ENDED_FLAG = 1, 2, 4
 A2C_FLAT_SIZE = 82082          # k-major flat layout of the parameters / gradient / Adam moments (82081 + 1 pad)
 LEAGUE_GROUP_GAMES = 16                   # AZUL_LEAGUE_GROUP_GAMES: the games of one workgroup of the window kernels play one pool member
@@ -138,6 +140,7 @@ SIGNATURES = {
     "azul_batch_score_preview": (_i, [_vp, _vp, _vp]),
     "azul_batch_score_moves": (_i, [_vp, _i, _vp, _vp, _vp, _vp]),
     "azul_batch_playout_moves": (_i, [_vp, _i, _i, _u64, _u32, _vp, _vp, _vp, _vp]),
+    "azul_batch_playout_moves_policy": (_i, [_vp, _i, _i, _i, _i, _u64, _u32, _vp, _vp, _vp, _vp]),
     "azul_batch_mp_runner_init": (_i, [_vp, _vp, _vp, _vp]),
     "azul_batch_mp_runner_reset": (_i, [_vp, _vp, _vp, _vp]),
     "azul_batch_mp_runner_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -354,7 +354,17 @@ class BatchedAzul:
         L.check(self._gr.score_moves(self._h, self.PERSP_TO_MOVE, _ptr(self._dev(active, torch.uint8)), None, _ptr(best), self._stream()))
         return best
 
-    def playout_moves(self, playouts=8, seed=0, call=0, perspective=None, active=None, sums=None, best=None):
+    @staticmethod
+    def _playout_policy(policy, explore):
+        """(AZUL_PLAYOUT_* number, explore) of playout_moves' / playout_action's `policy` ("uniform" | "greedy", or the number) and `explore`;
+        the library refuses what lies outside its ranges."""
+        if isinstance(policy, str):
+            if policy not in L.PLAYOUT_POLICIES:
+                raise ValueError("policy must be \"uniform\" or \"greedy\", got %r" % (policy,))
+            policy = L.PLAYOUT_POLICIES[policy]
+        return int(policy), int(explore)
+
+    def playout_moves(self, playouts=8, seed=0, call=0, perspective=None, active=None, sums=None, best=None, policy="uniform", explore=0):
         """The flat Monte-Carlo table in one launch, the games untouched: sums [N][180] int32, for every legal action the sum over
         `playouts` (1 .. L.PLAYOUTS_MAX) random playouts of score[p] - score[1 - p] at the END OF THE ROUND -- the move, then both seats
         play uniformly over their legal pattern-line moves (floor moves only when nothing else is legal) until the round ends, then
@@ -362,22 +372,29 @@ class BatchedAzul:
         the first legal action with the maximal sum (-1: nothing is legal).  The draws are Philox4x32-10 words keyed by `seed` (64 bits) at
         counters of (action, ply, playout, the game's GLOBAL id, `call` (32 bits)): the same arguments give the same table wherever a game
         sits in a batch; nothing is drawn from the games' MT19937 streams.  `perspective`, `active`, `sums` / `best` as score_moves' arguments.
-        Two-player reference batches only (a wide batch is refused by the library).  Returns (sums, best)."""
+        Two-player reference batches only (a wide batch is refused by the library).  Returns (sums, best).
+        policy="greedy" (azul_batch_playout_moves_policy): both seats of a playout play greedy_action's move -- the first legal action that
+        maximises the mover's score difference after move + count_score -- except on a ply whose draw's low byte is below `explore`
+        (0 .. 255), which plays the uniform move from the same draw.  explore=0 draws nothing: `seed` and `call` have no effect and the
+        table is `playouts` times the one deterministic playout's value.  policy="uniform" takes explore=0 only."""
+        pol, explore = self._playout_policy(policy, explore)
         if sums is None:
             sums = torch.full((self.n, L.NUM_ACTIONS), L.SCORE_ILLEGAL, dtype=torch.int32, device=self.device)
         if best is None:
             best = torch.full((self.n,), -1, dtype=torch.int32, device=self.device)
-        L.check(L.lib.azul_batch_playout_moves(self._h, int(L.PERSP_CURRENT if perspective is None else perspective), int(playouts),
-                                               int(seed) & 0xFFFFFFFFFFFFFFFF, int(call) & 0xFFFFFFFF, _ptr(self._dev(active, torch.uint8)),
-                                               _ptr(sums), _ptr(best), self._stream()))
+        L.check(L.lib.azul_batch_playout_moves_policy(self._h, int(L.PERSP_CURRENT if perspective is None else perspective), int(playouts),
+                                                      pol, explore, int(seed) & 0xFFFFFFFFFFFFFFFF, int(call) & 0xFFFFFFFF,
+                                                      _ptr(self._dev(active, torch.uint8)), _ptr(sums), _ptr(best), self._stream()))
         return sums, best
 
-    def playout_action(self, playouts=8, seed=0, call=0, active=None, out=None):
+    def playout_action(self, playouts=8, seed=0, call=0, active=None, out=None, policy="uniform", explore=0):
         """The flat Monte-Carlo player: for every game the move with the maximal playout_moves sum from the mover's perspective (-1: nothing
-        is legal).  `out`: a preallocated int32 [N]; games whose `active` is 0 keep what it held."""
+        is legal).  `out`: a preallocated int32 [N]; games whose `active` is 0 keep what it held.  `policy` / `explore`: playout_moves'."""
+        pol, explore = self._playout_policy(policy, explore)
         best = torch.full((self.n,), -1, dtype=torch.int32, device=self.device) if out is None else out
-        L.check(L.lib.azul_batch_playout_moves(self._h, L.PERSP_CURRENT, int(playouts), int(seed) & 0xFFFFFFFFFFFFFFFF, int(call) & 0xFFFFFFFF,
-                                               _ptr(self._dev(active, torch.uint8)), None, _ptr(best), self._stream()))
+        L.check(L.lib.azul_batch_playout_moves_policy(self._h, L.PERSP_CURRENT, int(playouts), pol, explore, int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                                      int(call) & 0xFFFFFFFF, _ptr(self._dev(active, torch.uint8)), None, _ptr(best),
+                                                      self._stream()))
         return best
 
     # -- policy-driven self-play (config 3) ----------------------------------------------------------

@@ -1648,10 +1648,10 @@ int azul_timing_launch_ms(azul_batch_t *b, float *launch_ms, int cap, int *n)
 // here, so the two kernels land BEHIND the self-play kernels in the code object and no older kernel moves relative to another (the
 // code starts 0x600 later: the two kernels' descriptors and metadata precede it).  Instantiated in the middle of the file they sat in
 // front of the benchmarked kernel and pushed it 0x2c00 along (csrc/azul_selfplay_kernels.hpp: selfplay2_kernel; LABNOTES.md).
-// every legal move's sum over `playouts` random playouts to the end of the round and the move with the maximal sum (azul_ops2.hpp:
-// playout_moves_body2): one launch, the games are only read
-int azul_batch_playout_moves(azul_batch_t *b, int perspective, int playouts, uint64_t seed, uint32_t call, const uint8_t *active_dev,
-                             int32_t *sums_dev, int32_t *best_dev, void *stream)
+// every legal move's sum over `playouts` playouts to the end of the round under the chosen playout policy and the move with the maximal sum
+// (azul_ops2.hpp: playout_moves_body2): one launch, the games are only read
+int azul_batch_playout_moves_policy(azul_batch_t *b, int perspective, int playouts, int policy, int explore, uint64_t seed, uint32_t call,
+                                    const uint8_t *active_dev, int32_t *sums_dev, int32_t *best_dev, void *stream)
 {
     BATCH_GUARD(b, stream);
     if (!b) return fail(AZUL_ERR_INVALID, "batch is NULL");
@@ -1662,13 +1662,25 @@ int azul_batch_playout_moves(azul_batch_t *b, int perspective, int playouts, uin
     if (!sums_dev && !best_dev) return fail(AZUL_ERR_INVALID, "azul_batch_playout_moves: sums_dev and best_dev are both NULL");
     if (perspective != AZUL_PERSP_PLAYER0 && perspective != AZUL_PERSP_PLAYER1 && perspective != AZUL_PERSP_CURRENT)
         return fail(AZUL_ERR_INVALID, "azul_batch_playout_moves: perspective must be 0, 1 or AZUL_PERSP_CURRENT");
+    if (policy != AZUL_PLAYOUT_UNIFORM && policy != AZUL_PLAYOUT_GREEDY)
+        return fail(AZUL_ERR_INVALID, "azul_batch_playout_moves_policy: policy must be AZUL_PLAYOUT_UNIFORM (0) or AZUL_PLAYOUT_GREEDY (1)");
+    if (explore < 0 || explore > 255) return fail(AZUL_ERR_INVALID, "azul_batch_playout_moves_policy: explore must be in 0 .. 255");
+    if (explore != 0 && policy == AZUL_PLAYOUT_UNIFORM)
+        return fail(AZUL_ERR_INVALID, "azul_batch_playout_moves_policy: explore must be 0 with AZUL_PLAYOUT_UNIFORM (every ply of it is uniform)");
     PlayoutMovesArgs a;
     a.active = active_dev; a.sums = sums_dev; a.best = best_dev; a.persp = perspective;
-    a.playouts = (u32)playouts; a.call = call; a.seed = seed;
+    a.playouts = (u32)playouts; a.call = call; a.seed = seed; a.policy = (uint16_t)policy; a.explore = (uint16_t)explore;
     const dim3 grid((b->d.n + 1u) / 2u), block(64);
-    hipLaunchKernelGGL(playout_moves_kernel(b->d.rules.tile_pool == POOL_LID), grid, block, 0, (hipStream_t)stream, b->d, a);
+    hipLaunchKernelGGL(playout_moves_kernel(b->d.rules.tile_pool == POOL_LID, policy), grid, block, 0, (hipStream_t)stream, b->d, a);
     HIP_TRY(hipGetLastError());
     return AZUL_SUCCESS;
+}
+
+// the uniform policy under its first name
+int azul_batch_playout_moves(azul_batch_t *b, int perspective, int playouts, uint64_t seed, uint32_t call, const uint8_t *active_dev,
+                             int32_t *sums_dev, int32_t *best_dev, void *stream)
+{
+    return azul_batch_playout_moves_policy(b, perspective, playouts, AZUL_PLAYOUT_UNIFORM, 0, seed, call, active_dev, sums_dev, best_dev, stream);
 }
 
 } // extern "C"

@@ -362,8 +362,13 @@ struct PlayoutMovesArgs {
     int persp;               // 0, 1 or AZUL_PERSP_CURRENT (the player to move)
     u32 playouts;            // K, 1 .. AZUL_PLAYOUTS_MAX: |sum| <= K * 2^16 fits an i32
     u32 call;                // counter word 3
+    // (two 16-bit fields in what was the padding in front of `seed`: the block keeps its size and every older field its offset, and the
+    // uniform kernel its instruction stream)
+    uint16_t policy;         // AZUL_PLAYOUT_UNIFORM (0: an all-zero block is the uniform playout) / AZUL_PLAYOUT_GREEDY: names the instantiation (playout_moves_kernel)
+    uint16_t explore;        // AZUL_PLAYOUT_GREEDY: a ply whose word's low byte is below this plays the uniform move (0 .. 255; 0: no word is read)
     u64 seed;                // the Philox key
 };
+static_assert(sizeof(PlayoutMovesArgs) == 48, "policy / explore fill the padding");
 
 __device__ __forceinline__ u32 philox_u32_words(u32 c0, u32 c1, u32 c2, u32 c3, u64 seed);      // azul_policy.hpp, beside philox_u32
 
@@ -377,7 +382,16 @@ constexpr u32 PLAYOUT_MAX_PLIES = 64;
 // as apply_step2 scores a round end, and is scored with the other half on the state it stopped in once neither moves.
 // The maximum is taken in two half-wave steps (a sum of 256 score differences does not fit score_key's 17 bits): every lane keeps the
 // first of its own candidates with its maximal sum, the half's maximal sum is found, then the lowest action among the lanes that hold it.
-template <bool LID>
+// POLICY == AZUL_PLAYOUT_GREEDY (azul_playout_policy_kernel): a ply plays greedy_pick2's move -- score_moves_body2's `best` for the playout's
+// state, the rule the window kernel's greedy opponent plays by -- unless the low byte of the ply's word is below a.explore: then the uniform
+// policy's move from the same word.  The two halves of a wave may differ on a ply: both codes are computed and each half takes its own;
+// greedy_pick2 runs wave-uniformly, outside the per-half `if (live)`, on a mask that is EMPTY for a half that does not play greedily on this
+// ply (stopped, or exploring), so its ballot skips that half's candidates.  The copy is advanced by do_move2 only: its what-if caches are
+// stale, and greedy_pick2 reads the opponent's only as an offset common to every candidate -- both are zeroed on the copy, so the key's score
+// is the mover's what-if score itself, in [0, 2^16 + 145), and score_key stays monotone (a stale offset could push it below -2^16);
+// whatif_after2 prices from the copy's own lines, floor, wall and score.  With a.explore == 0 nothing is drawn and the `playouts` playouts of a
+// candidate are equal: one is run and its value multiplied.
+template <bool LID, int POLICY = AZUL_PLAYOUT_UNIFORM>
 AZ_FN void playout_moves_body2(const BatchDev &b, const PlayoutMovesArgs &a, u32 pair)
 {
     const u32 lane = wv::lane(), l = lane & 31u, half = lane >> 5;
@@ -407,11 +421,13 @@ AZ_FN void playout_moves_body2(const BatchDev &b, const PlayoutMovesArgs &a, u32
             const u32 act = 30u * row + ln;
             const u32 first = action_code2(act, k);
             i32 sum = 0;
+            const u32 explore = POLICY == AZUL_PLAYOUT_GREEDY ? (u32)a.explore : 0u;
 #pragma unroll 1
-            for (u32 kk = 0; kk < a.playouts; kk++) {
+            for (u32 kk = 0; kk < ((POLICY == AZUL_PLAYOUT_GREEDY && explore == 0u) ? 1u : a.playouts); kk++) {
                 G2 t = g;
                 do_move2<LID>(t, first, g.B, k);                                   // azul.py:118-161 (total for every action number: whatif_after2)
                 t.B = hb(t.cs != 0u) & 0x7fffffffu;
+                if (POLICY == AZUL_PLAYOUT_GREEDY) t.wi0 = t.wi1 = 0;              // (stale from here on: a neutral offset for greedy_pick2)
                 bool live = legal;
 #pragma unroll 1
                 for (u32 ply = 0; ply < PLAYOUT_MAX_PLIES; ply++) {
@@ -420,8 +436,30 @@ AZ_FN void playout_moves_body2(const BatchDev &b, const PlayoutMovesArgs &a, u32
                     Mask2 pm;
                     legal_mask2(t, k, pm);
                     u32 code;
-                    live = playout_agent2(pm, philox_u32_words(act | (ply << 16), kk, G, a.call, a.seed), k, code) & live;
-                    if (!wave_any(live)) break;
+                    if (POLICY == AZUL_PLAYOUT_UNIFORM) {
+                        live = playout_agent2(pm, philox_u32_words(act | (ply << 16), kk, G, a.call, a.seed), k, code) & live;
+                        if (!wave_any(live)) break;
+                    } else {
+                        live = live & (mask_count2(pm) != 0u);
+                        if (!wave_any(live)) break;
+                        bool greedy = live;
+                        code = 0;
+                        if (explore != 0u) {
+                            const u32 w = philox_u32_words(act | (ply << 16), kk, G, a.call, a.seed);
+                            playout_agent2(pm, w, k, code);
+                            greedy = live & ((w & 0xffu) >= explore);            // the low byte decides the branch, the high bits the ordinal
+                        }
+                        if (wave_any(greedy)) {
+                            Mask2 gm = pm;
+#pragma unroll
+                            for (u32 r = 0; r < 6u; r++) gm.m[r] = greedy ? pm.m[r] : 0u;
+                            const i32 ga = greedy_pick2<LID>(t, gm, k);
+                            // (a half that plays greedily has a legal move: ga >= 0.  The mask makes the argument a number the compiler
+                            // can see is below 256, as at action_code2's other call sites: from the range it derives ACROSS them it divides
+                            // in 8 bits there, and an unbounded argument here changed the uniform kernel's code -- one instruction, one VGPR)
+                            code = greedy ? action_code2((u32)ga & 0xffu, k) : code;
+                        }
+                    }
                     if (live) {
                         do_move2<LID>(t, code, t.B, k);
                         t.B = hb(t.cs != 0u) & 0x7fffffffu;
@@ -430,6 +468,7 @@ AZ_FN void playout_moves_body2(const BatchDev &b, const PlayoutMovesArgs &a, u32
                 count_score2<LID>(t, k);                                           // :192-295
                 sum += t.score0 - t.score1;
             }
+            if (POLICY == AZUL_PLAYOUT_GREEDY && explore == 0u) sum *= (i32)a.playouts;
             const i32 v = p == 0u ? sum : -sum;
             const bool mine = legal & (l == ln);
             s0 = (mine & (row == 0u)) ? v : s0; s1 = (mine & (row == 1u)) ? v : s1; s2 = (mine & (row == 2u)) ? v : s2;

@@ -40,14 +40,23 @@ __global__ void __launch_bounds__(64) azul_playout_moves_kernel(BatchDev b, Play
 {
     az2::playout_moves_body2<LID>(b, a, blockIdx.x);
 }
-// Which instantiation a launch runs (host side): azul_batch_playout_moves and the lockstep emulation's shim launch what this returns.
+// The same table with the greedy playout policy (AZUL_PLAYOUT_GREEDY: playout_moves_body2's second parameter): a kernel of its own name,
+// so the uniform kernel above is the instantiation it was
+template <bool LID>
+__global__ void __launch_bounds__(64) azul_playout_policy_kernel(BatchDev b, PlayoutMovesArgs a)
+{
+    az2::playout_moves_body2<LID, AZUL_PLAYOUT_GREEDY>(b, a, blockIdx.x);
+}
+// Which instantiation a launch runs (host side): azul_batch_playout_moves_policy and the lockstep emulation's shims launch what this
+// returns; with one argument, the uniform policy's.
 // (A template, like selfplay2_kernel below: the kernels are instantiated where the selector is first called, so a file that includes this
 // header without azul_policy.hpp's Philox block -- the other shims -- instantiates nothing that needs it.)
 typedef void (*playout_moves_kernel_t)(BatchDev, PlayoutMovesArgs);
 template <class B>
-static playout_moves_kernel_t playout_moves_kernel(B lid)
+static playout_moves_kernel_t playout_moves_kernel(B lid, int policy = AZUL_PLAYOUT_UNIFORM)
 {
-    return lid ? azul_playout_moves_kernel<true> : azul_playout_moves_kernel<false>;
+    if (policy != AZUL_PLAYOUT_GREEDY) return lid ? azul_playout_moves_kernel<true> : azul_playout_moves_kernel<false>;
+    return lid ? azul_playout_policy_kernel<true> : azul_playout_policy_kernel<false>;
 }
 
 // Discounted returns over the time-major trajectory of one launch window (reference loop: nn_runner.py:70-76,

@@ -69,7 +69,8 @@ class PolicyRollout:
                  device=None, window=32, use_graph=True, fused_head=True, sample_seed=0x5EED, opponent=None, fused_mlp=True, persistent=False,
                  action_selection="Distribution", kweights=None, game_id_base=None, ring=1, opponent_selection="Distribution",
                  opponent_seed=None, opponent_trace=0, move_limit=0, players=2, fused_wide=False, fused_opponent=False, wide_ring=1,
-                 fused_seats=False, gae_lambda=None, bootstrap_tail=False, opponent_playouts=8, _pairs=None):
+                 fused_seats=False, gae_lambda=None, bootstrap_tail=False, opponent_playouts=8, opponent_playout_policy="uniform",
+                 opponent_playout_explore=0, _pairs=None):
         """Who answers GameRunner's opponent_move(), and what plays a window.  "window kernel": ONE launch per window and part (_WINDOW_KERNELS),
         asked for by the switch in brackets; "per move" / "per cut": the launches of _window_moves.  Two-player reference batches (players=2, no
         extended-rule key in `rules`) and wide batches (`players` = 3 / 4 or extended rules) admit:
@@ -131,7 +132,9 @@ class PolicyRollout:
         window (an opening at construction: the counter before the first step, 0xffffffff), so a run restored from games_state() replays bit
         for bit; records, trace, persistent / use_graph / ring and MAX_REPLY_ROUNDS as with "greedy".  It answers per cut only: a wide batch,
         fused_opponent=True and fused_wide=True raise ValueError, and so does opponent_selection="Max" (the player has no distribution to
-        take the maximum of).
+        take the maximum of).  `opponent_playout_policy` = "uniform" (default) | "greedy" and `opponent_playout_explore` (0 .. 255; 0 with
+        "uniform") choose the playout policy (BatchedAzul.playout_moves: with "greedy" both seats of a playout play greedy_action's move,
+        a ply in explore / 256 the uniform one); the protocol, the seeds and the calls are the same, and "greedy" with explore 0 draws nothing.
         opponent="greedy_margin": the same scripted player for three / four seats and extended rules -- every other seat answers with
         MultiplayerAzul.greedy_action, the move that maximises the MOVER's margin over the best other seat after move + count_score
         (azul_batch_mp_score_moves; beyond the reference for P > 2, like the wide reward), through MultiplayerAzul.net_* exactly as a network
@@ -192,7 +195,7 @@ class PolicyRollout:
         there: ValueError."""
         self._check_modes(policy, n_games, parts, rules, window, use_graph, fused_head, opponent, fused_mlp, persistent, action_selection, ring,
                           opponent_selection, opponent_trace, move_limit, players, fused_wide, fused_opponent, wide_ring, fused_seats,
-                          gae_lambda, bootstrap_tail, opponent_playouts)
+                          gae_lambda, bootstrap_tail, opponent_playouts, opponent_playout_policy, opponent_playout_explore)
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         self.policy = policy.to(self.device).eval()
         self.windows_played = 0
@@ -219,7 +222,7 @@ class PolicyRollout:
 
     def _check_modes(self, policy, n_games, parts, rules, window, use_graph, fused_head, opponent, fused_mlp, persistent, action_selection, ring,
                      opponent_selection, opponent_trace, move_limit, players, fused_wide, fused_opponent, wide_ring, fused_seats=False,
-                     gae_lambda=None, bootstrap_tail=False, opponent_playouts=8):
+                     gae_lambda=None, bootstrap_tail=False, opponent_playouts=8, opponent_playout_policy="uniform", opponent_playout_explore=0):
         """Every refusal of the constructor, then the resolution of the modes -- from the arguments and the modules' shapes alone: no device
         and no library call, so nothing is allocated before a refusal.  Three facts come out: the record family (`wide`), who answers
         opponent_move() (`opponent`, one of the kinds below) and what plays a window (`window_entry`: a row of _WINDOW_KERNELS, or None for
@@ -267,6 +270,13 @@ class PolicyRollout:
                                  "there is no distribution")
             if not 1 <= int(opponent_playouts) <= L.PLAYOUTS_MAX:
                 raise ValueError("opponent_playouts must be in 1 .. %d, got %r" % (L.PLAYOUTS_MAX, opponent_playouts))
+            if opponent_playout_policy not in L.PLAYOUT_POLICIES:
+                raise ValueError("opponent_playout_policy must be \"uniform\" or \"greedy\", got %r" % (opponent_playout_policy,))
+            if isinstance(opponent_playout_explore, bool) or not isinstance(opponent_playout_explore, int) or not 0 <= opponent_playout_explore <= 255:
+                raise ValueError("opponent_playout_explore must be an integer in 0 .. 255, got %r" % (opponent_playout_explore,))
+            if opponent_playout_explore and opponent_playout_policy == "uniform":
+                raise ValueError("opponent_playout_explore=%d has no meaning with opponent_playout_policy=\"uniform\" (every ply of it is "
+                                 "uniform): it must be 0" % opponent_playout_explore)
         if fused_seats:
             if kind != "greedy_margin":
                 raise ValueError("fused_seats=True plays the greedy_margin seats of a wide batch inside its window kernel: it needs "
@@ -325,6 +335,8 @@ class PolicyRollout:
         self.opp_pool = members if self.league else None
         self.scripted = kind in ("greedy", "greedy_margin", "playout")     # answers are env.greedy_action's / playout_action's: no weights, no log-probabilities
         self.opponent_playouts = int(opponent_playouts) if kind == "playout" else 0
+        self.opponent_playout_policy = opponent_playout_policy if kind == "playout" else "uniform"
+        self.opponent_playout_explore = int(opponent_playout_explore) if kind == "playout" else 0
         self.cut = netopp or self.scripted                     # GameRunner.step cut at its opponent_move() calls (BatchedAzul.net_*)
         self.fused_head = fused_head
         # the one-launch forward (azul_policy_forward) is compiled for the reference's ActorCritic(136, 180, hidden 180)
@@ -531,7 +543,8 @@ class PolicyRollout:
         if self.opponent == "playout":
             # the flat Monte-Carlo player: reply j of a step draws with seed opponent_seed + j at the step's call (_env_step / _net_reset)
             self.envs[p].playout_action(self.opponent_playouts, (self.opponent_seed + j) & 0xFFFFFFFFFFFFFFFF, w["playout_call"],
-                                        active=net["pending"], out=net["action"])
+                                        active=net["pending"], out=net["action"], policy=self.opponent_playout_policy,
+                                        explore=self.opponent_playout_explore)
             return
         if self.scripted:
             # the scripted opponent: the best move of every game that owes one, from the mover's perspective (azul_batch_score_moves /

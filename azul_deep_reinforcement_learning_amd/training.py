@@ -79,7 +79,7 @@ class BatchedTrainer:
                  ring=3, opponent="random", opponent_refresh=0, move_limit=0, players=2, fused_wide=False,
                  fused_opponent=False, fused_learner=False, fused_seats=False, gae_lambda=None, bootstrap_tail=False, algorithm="a2c",
                  clip_eps=0.2, value_coeff=0.5, entropy_coeff=0.01, epochs=4, minibatches=4, normalize_advantage=True, league_size=4,
-                 league_sampling="uniform", pfsp_power=2.0, opponent_playouts=8):
+                 league_sampling="uniform", pfsp_power=2.0, opponent_playouts=8, opponent_playout_policy="uniform", opponent_playout_explore=0):
         """ring: trajectory windows kept (persistent rollout with one part): with ring >= 2 every step of every episode is trained
         exactly once (episodes straddle windows; an episode may span ring - 1 window boundaries), like NNRunner.train.
         opponent: "random" (GameRunner's default RandomAgent, the reference's scripts/training.py), a module (GameRunner(opponent=Agent(...)),
@@ -100,6 +100,9 @@ class BatchedTrainer:
         "greedy" without fused_opponent (no window kernel: fused_opponent / fused_wide raise ValueError; ring 1, update_from_windows).  The
         opponent has no state: its draws are keyed by the Philox step counter a checkpoint already carries; checkpoints carry
         `opponent_playouts` and a file written with another K is refused, so a resumed run replays bit for bit.
+        opponent_playout_policy="uniform" | "greedy", opponent_playout_explore=0..255: the playout policy of that player (PolicyRollout has
+        the definition); checkpoints carry both, a file without them was written by the uniform player (uniform / 0), and a file written
+        with other values is refused like another K.
         opponent="league" (league_size=K in 1..255, opponent_refresh=k, league_sampling="uniform" | "pfsp", pfsp_power): a POOL of K frozen past
         selves (PolicyRollout(opponent=[...]): every 16-game group plays one member, inside the window kernels where a single network opponent
         plays there).  The pool starts as K copies of the initial policy; every k updates the current policy is written into slot
@@ -189,7 +192,8 @@ class BatchedTrainer:
                                      move_limit=move_limit, players=players, fused_wide=fused_wide,
                                      fused_opponent=fused_opponent, wide_ring=ring if (wide_fused and parts == 1) else 1,
                                      fused_seats=fused_seats, gae_lambda=gae_lambda, bootstrap_tail=bootstrap_tail,
-                                     opponent_playouts=opponent_playouts)
+                                     opponent_playouts=opponent_playouts, opponent_playout_policy=opponent_playout_policy,
+                                     opponent_playout_explore=opponent_playout_explore)
         self.gamma = gamma
         self.results_dir = results_dir
         self.batch = 0
@@ -340,6 +344,7 @@ class BatchedTrainer:
               "windows_played": ro.windows_played, "ring": ro.ring, "ring_saved": bool(save_ring and ro.ring > 1)}
         if ro.opponent == "playout":                     # the scripted player's one setting (its draws follow the Philox step counter in `envs`)
             ck["opponent_playouts"] = ro.opponent_playouts
+            ck["opponent_playout_policy"], ck["opponent_playout_explore"] = ro.opponent_playout_policy, ro.opponent_playout_explore
         if ro.league:                                    # the assignment, the results and their marks, the snapshot and redraw counts
             ck["league"] = dict(ro.league_state(), snapshots=getattr(self, "snapshots", 0), redraws=getattr(self, "redraws", 0))
         if ro.netopp:                                    # the network opponent's (frozen) weights, a league's stacked: a resumed run plays the same nets
@@ -358,6 +363,10 @@ class BatchedTrainer:
         if ro.opponent == "playout" and ck.get("opponent_playouts", ro.opponent_playouts) != ro.opponent_playouts:
             raise ValueError("checkpoint was written for opponent_playouts=%d, this trainer plays %d"
                              % (ck["opponent_playouts"], ro.opponent_playouts))
+        if ro.opponent == "playout":                     # (a file without the keys was written by the uniform player)
+            for key, absent in (("opponent_playout_policy", "uniform"), ("opponent_playout_explore", 0)):
+                if ck.get(key, absent) != getattr(ro, key):
+                    raise ValueError("checkpoint was written for %s=%r, this trainer plays %r" % (key, ck.get(key, absent), getattr(ro, key)))
         ro.synchronize()
         ro.policy.load_state_dict(ck["policy"])
         self.learner.load_optimizer_state(ck["optimizer"])          # also rebuilds the flat master copy from the module

@@ -236,6 +236,25 @@ int azul_batch_score_moves(azul_batch_t *b, int perspective, const uint8_t *acti
 #define AZUL_PLAYOUTS_MAX 256
 int azul_batch_playout_moves(azul_batch_t *b, int perspective, int playouts, uint64_t seed, uint32_t call, const uint8_t *active_dev,
                              int32_t *sums_dev /*[N][180], optional*/, int32_t *best_dev /*[N], optional*/, void *stream);
+/* The same table under a chosen PLAYOUT POLICY.  Everything not listed here is azul_batch_playout_moves' definition word for word: the copy,
+ * the candidate's unchecked move, the loop's stops (end of the round, L == 0, ply == 64), count_score(), the sum over k, best, active_dev,
+ * the optional outputs, the perspectives, the global id G and the Philox counter (a | ply << 16, k, G, call) under key `seed`.
+ *   policy == AZUL_PLAYOUT_UNIFORM: `explore` must be 0; the result is azul_batch_playout_moves', bit for bit.
+ *   policy == AZUL_PLAYOUT_GREEDY, explore in 0 .. 255: ply `ply` of playout k takes the same word w.  If (w & 0xFF) < explore the ply plays
+ *     the uniform policy's move from that same w -- the legal action of ordinal base + ((w * n) >> 32): the low byte decides the branch, the
+ *     high bits the ordinal.  Otherwise it plays the GREEDY MOVE: with q the ply's mover, the first legal action, in ascending action
+ *     order, that maximises score[q] - score[1 - q] after move(*nn_deserialize(.)) and count_score() on a copy -- what
+ *     azul_batch_score_moves(AZUL_PERSP_CURRENT) gives as `best` for that state.  With explore == 0 no word is read and the `playouts`
+ *     playouts of a candidate are equal by definition: one is run and its value multiplied by `playouts` -- the table is still the sum over
+ *     k, and |sum| <= 256 * 2^16 still holds.
+ * AZUL_ERR_INVALID before any launch: azul_batch_playout_moves' refusals (a wide batch, playouts outside 1 .. AZUL_PLAYOUTS_MAX, both
+ * outputs NULL, a perspective outside {0, 1, AZUL_PERSP_CURRENT}), a policy outside {0, 1}, explore outside 0 .. 255, explore != 0 with
+ * AZUL_PLAYOUT_UNIFORM.  BEYOND THE REFERENCE, as the entry above. */
+#define AZUL_PLAYOUT_UNIFORM 0
+#define AZUL_PLAYOUT_GREEDY  1
+int azul_batch_playout_moves_policy(azul_batch_t *b, int perspective, int playouts, int policy, int explore, uint64_t seed, uint32_t call,
+                                    const uint8_t *active_dev, int32_t *sums_dev /*[N][180], optional*/, int32_t *best_dev /*[N], optional*/,
+                                    void *stream);
 
 /* ---- GameRunner for P players: batches of 3 / 4 players and extended-rule batches (wide records) ------------------------------
  * The reference's GameRunner (game_runner.py:23-97) on an Azul(players = P): the agent is seat 0 ("player 1"), every other seat answers
